@@ -9,6 +9,9 @@ A step = forward + CrossEntropy + zero_grad + backward (+ gradient all-reduce wh
 Adam.step on one synthetic batch that is already resident in HBM (train.py:31-40 of the
 reference).  Weak scaling: the per-GPU batch is fixed, value = N * batch * K / t.
 
+With --dump-outputs DIR rank 0 also writes what the last timed step computed (dump_outputs below) as float32 .npy files; the
+inputs and the initial weights are seeded, so two builds run with the same arguments can be compared output for output.
+
 Rank 0 prints ONE JSON line.  Besides the driver's contract it carries
   roofline      the dominant hand-written kernel: algorithmic flops divided
                 by its average launch time measured live with events on the launch stream
@@ -192,6 +195,28 @@ def roofline_report(kern, steps, workload, batch):
     return res
 
 
+DUMP_SAMPLE = 1 << 22        # elements per sampled array: 16 MB of float32 each, well inside the 64 MB budget of a dump
+
+
+def dump_outputs(out_dir, model, logits, loss):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files, so that two builds can be compared
+    output for output.  logits.npy and loss.npy are whole; grads.npy and params.npy (the weights after the Adam update) are the
+    trainable parameters flattened in named_parameters() order, whole when they fit in DUMP_SAMPLE elements and otherwise the
+    same DUMP_SAMPLE sorted positions drawn by a fixed seed (they depend only on the parameter count, so on the workload)."""
+    import numpy as np
+    params = [p for p in model.parameters() if p.requires_grad]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    if flat_p.numel() > DUMP_SAMPLE:
+        idx = torch.randint(0, flat_p.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        idx = idx.to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"logits": logits, "loss": loss.reshape(1), "grads": flat_g, "params": flat_p}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -214,7 +239,12 @@ def main():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="(test hook) bring the process group up, all-reduce one number, print a stub line and exit: exercises the "
                          "self-launch / relay path without a GPU (KANVIT_DIST_BACKEND=gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (logits, loss, sampled gradients and updated "
+                         "weights) as DIR/<name>.npy; rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(self_launch(args.gpus))                    # plain `python bench.py --gpus N`: spawn the ranks, relay the line
@@ -277,10 +307,14 @@ def main():
     y = torch.randint(0, wl["out_d"], (wl["batch"],), device=dev, generator=g)
 
     amp_on = [args.amp == "bf16"]
+    last = {}       # the last step's logits for --dump-outputs, detached: a kept autograd graph would carry its AccumulateGrad
+                    # nodes, bound to the stream of that step, into the next step (the side-stream warm-up, the graph capture)
 
     def step():
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp_on[0]):
-            loss = crit(model(x), y)
+            logits = model(x)
+            loss = crit(logits, y)
+        last["logits"] = logits.detach()
         if reducer is not None:
             reducer.zero_grad()
             reducer.scale_loss(loss).backward()        # sums over ranks become means inside the collective / the loss: no pass over the buckets
@@ -320,6 +354,7 @@ def main():
         torch.cuda.current_stream().wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         opt.zero_grad(set_to_none=True)
+        last.clear()                                        # freed here, not inside the capture
         with torch.cuda.graph(graph):
             static_loss = step()
         fence()
@@ -347,6 +382,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax)
     final_loss = float(loss.detach())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, last["logits"], loss)
 
     if rank == 0:
         ms = 1e3 * dt / args.steps

@@ -109,9 +109,12 @@ def test_structural_known_answers():
 def test_msa(t, loop):
     blob = load_npz("msa.npz")
     p = t + "."
-    sd = state_dict_from(blob, p)
-    params = {k: v.clone().requires_grad_(not ko.is_buffer_key(k)) for k, v in sd.items()}
-    x = T(blob[p + "x"]).clone().requires_grad_(True)
+    # float64: the key-bias gradient is zero in exact arithmetic (softmax is shift invariant), so in float32 both sides of its
+    # comparison are rounding noise, and ours changes with the host's vector ISA (AVX2 vs AVX-512 kernels).  In float64 only
+    # the golden's own, fixed float32 noise is left.
+    sd = {k: v.double() for k, v in state_dict_from(blob, p).items()}
+    params = {k: v.requires_grad_(not ko.is_buffer_key(k)) for k, v in sd.items()}
+    x = T(blob[p + "x"]).double().requires_grad_(True)
     y = ko.msa_forward(params, "", x, 2, faithful_loop=loop)
     (y * torch.linspace(-1, 1, y.numel()).reshape(y.shape)).sum().backward()
     assert max_err(y, T(blob[p + "y"])) < 1e-5

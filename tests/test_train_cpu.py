@@ -113,3 +113,37 @@ def test_bench_self_launches_its_ranks(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rendezvous-only"],
                        env=dict(env, KANVIT_DIST_BACKEND="no-such-backend"), capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "launching" in r.stderr and not r.stdout.strip()
+
+
+def test_bench_dump_outputs_are_float_fixed_and_bounded(tmp_path):
+    """bench.py --dump-outputs: float .npy files under 64 MB in all, and the sampled positions of a model larger than the
+    sample (ViT-S here) are the same from run to run, so two builds can be compared output for output."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    from model import VisionTransformer
+    wl = bench.WORKLOADS["vits16-224-cheby"]
+    torch.manual_seed(0)
+    m = VisionTransformer(wl["chw"], wl["n_patches"], wl["n_blocks"], wl["d"], wl["heads"], wl["out_d"], type=wl["type"])
+    params = [p for p in m.parameters() if p.requires_grad]
+    n = sum(p.numel() for p in params)
+    assert n > bench.DUMP_SAMPLE
+    for i, p in enumerate(params):
+        p.grad = torch.full_like(p, float(i))                     # the gradient names the parameter it belongs to
+    logits = torch.randn(wl["batch"], wl["out_d"])
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), m, logits, torch.tensor(1.5))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["grads.npy", "logits.npy", "loss.npy", "params.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    for k, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{k}.npy"))
+    assert np.array_equal(got["logits"], logits.numpy()) and got["loss"].tolist() == [1.5]
+    assert got["grads"].shape == got["params"].shape == (bench.DUMP_SAMPLE,)
+    # sorted positions over the flattened parameters: the parameter indices they fall in never decrease, and span the model
+    g = got["grads"]
+    assert np.all(np.diff(g) >= 0) and g[0] == 0 and g[-1] == len(params) - 1
+    flat = torch.cat([p.detach().reshape(-1) for p in params]).numpy()
+    assert np.isin(got["params"], flat).all()
