@@ -1,4 +1,5 @@
 """Fixture loading helpers shared by the CPU and GPU tests."""
+import contextlib
 import os
 
 import numpy as np
@@ -51,3 +52,42 @@ def close(a, b, rtol=1e-4, atol=2e-6):
     """max|a-b| <= atol + rtol*max|b| -- for tensors that may be mathematically zero."""
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return float((a - b).abs().max()) <= atol + rtol * float(b.abs().max())
+
+
+def kernel_name(raw):
+    """A device kernel's profiler name as `name<args>`: no `void`, no namespace, no parameter list
+    ('void (anonymous namespace)::kan_fwd_reg_kernel<1, 2, 3, 4, 5, true>(LayerArgs)' -> 'kan_fwd_reg_kernel<1, 2, 3, 4, 5, true>')."""
+    s = raw.strip()
+    if s.startswith("void "):
+        s = s[5:]
+    s = s.replace("(anonymous namespace)::", "")
+    depth, cut, ns = 0, len(s), 0
+    for i, c in enumerate(s):
+        if c == "<":
+            depth += 1
+        elif c == ">":
+            depth -= 1
+        elif c == "(" and depth == 0:
+            cut = i
+            break
+        elif c == ":" and depth == 0 and s[i + 1:i + 2] == ":":
+            ns = i + 2
+    return s[ns:cut].strip()
+
+
+@contextlib.contextmanager
+def record_kernels():
+    """with record_kernels() as names: ...  -- `names` becomes the set of device kernels launched inside the block, normalised by
+    kernel_name().  torch.profiler (device activity) sees every launch on the device, the library's hipLaunchKernelGGL ones included.
+    A block that records no device kernel at all raises: the recorder is not working, and a form assertion built on it would
+    be meaningless."""
+    from torch.profiler import ProfilerActivity, profile
+    names = set()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA], acc_events=True) as prof:
+        yield names
+        torch.cuda.synchronize()
+    for e in prof.events():
+        if e.device_type != torch.autograd.DeviceType.CPU:
+            names.add(kernel_name(e.name))
+    assert names, "torch.profiler recorded no device kernel"
