@@ -17,10 +17,18 @@ namespace {
 // SINE (GP = 5): d loss / d freq is summed per lane over the features of a step, wave-reduced into per-wave LDS slots and
 // written as this row tile's partials to dparam (same protocol as the LDS-tile kernel).
 // =============================================================================================
+constexpr int kv_bwi_g0(int fam) { return fam == KV_CHEBY ? 1 : 0; }
+constexpr int kv_bwi_kt(int fam, int gp, int kt) { return ((16 * kt) / gp * (gp - kv_bwi_g0(fam)) + 15) / 16; }
+
+// CHEBY: dT0/dx = 0, so the T0 slots are left out of the permutation -- slot q <-> (feature q / (GP-1), basis index q % (GP-1) + 1) --
+// and KT = 5 accumulators become kv_bwi_kt = 4 (the template keeps KT = 5: FPH = 16 features per half either way).  Every dPhi value
+// is the same contraction as before, only in another accumulator slot: dx is bitwise unchanged.
 template <int FAM, int GP, int KT, bool SHARED>
 __global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2) void kan_bwd_input_reg_kernel(const LayerArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int KCT = 32 * KT;
+    constexpr int G0 = kv_bwi_g0(FAM), GPE = GP - G0;
+    constexpr int KTE = kv_bwi_kt(FAM, GP, KT);   // accumulators actually contracted
+    constexpr int KCT = 32 * KTE;
     // W^T image: element (n = h*16 + s, k) at s*WS2 + h*HOFF + k.  HOFF = 32 (mod 64) puts the two lane halves of a fragment
     // read on disjoint bank halves (with the old [2s+h][KCT+1] rows the halves were 33 banks apart: one bank shared, every
     // ds_read2_b32 took 3 cycles instead of 2 -- the 16.7 % LDS conflict rate of profiles/r02_sq_pmc_fp32.md); WS2 = 2 (mod 16)
@@ -28,6 +36,7 @@ __global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2)
     constexpr int HOFF = (KCT % 64 == 32) ? KCT : KCT + 32;
     constexpr int WS2 = ((HOFF + KCT + 13) / 16) * 16 + 2;
     constexpr int FPH = (16 * KT) / GP;           // features per lane half and chunk
+    static_assert(16 * KTE >= FPH * GPE, "the slots hold every contracted (feature, basis index)");
     constexpr int IC = 2 * FPH;
     constexpr bool RBF = (FAM == KV_RBF);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hf = lane >> 5;
@@ -72,7 +81,7 @@ __global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2)
         const int rho = kr & 31, kt = kr >> 5;
         const int h_ = (rho >> 2) & 1, r_ = (rho & 3) + 4 * (rho >> 3);
         const int slot = kt * 16 + r_;
-        const int jq = slot / GP, g_ = slot - jq * GP;
+        const int jq = slot / GPE, g_ = slot - jq * GPE + G0;
         kofs[q] = (v < NV && jq < FPH) ? ((h_ * FPH + jq) * GP + g_) * a.O : -1;
         nofs[q] = n4;
     }
@@ -107,7 +116,7 @@ __global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2)
 
     const int spc = nshare * ncn;                 // steps per feature chunk
     const int T = (ci1 - ci0) * spc;
-    f32x16 acc[KT];
+    f32x16 acc[KTE];
     float dxacc[FPH];
     float xv[FPH];
 
@@ -124,7 +133,7 @@ __global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2)
     for (int t = 0; t < T; ++t) {
         if (p == 0 && cn == 0) {                  // new feature chunk
 #pragma unroll
-            for (int kt = 0; kt < KT; ++kt)
+            for (int kt = 0; kt < KTE; ++kt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[kt][r] = 0.0f;
 #pragma unroll
@@ -178,18 +187,18 @@ __global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2)
         // W^T fragments are read ONE k-step ahead into a second register set (same reasoning as the forward kernel: an LDS
         // read -> wait -> MFMA chain on one register pair leaves the matrix pipe idle for the read latency on every pair)
         const float* wp = W_s + (t & 1) * WSZ + hf * HOFF + l31;
-        float wa[2][KT];
+        float wa[2][KTE];
 #pragma unroll
-        for (int kt = 0; kt < KT; ++kt) wa[0][kt] = wp[kt * 32];
+        for (int kt = 0; kt < KTE; ++kt) wa[0][kt] = wp[kt * 32];
 #pragma unroll
         for (int s2 = 0; s2 < 16; ++s2) {
             if (s2 + 1 < 16) {
 #pragma unroll
-                for (int kt = 0; kt < KT; ++kt) wa[(s2 + 1) & 1][kt] = wp[(s2 + 1) * WS2 + kt * 32];
+                for (int kt = 0; kt < KTE; ++kt) wa[(s2 + 1) & 1][kt] = wp[(s2 + 1) * WS2 + kt * 32];
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int kt = 0; kt < KT; ++kt)
+            for (int kt = 0; kt < KTE; ++kt)
                 acc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[s2 & 1][kt], dyv[s2], acc[kt], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -221,8 +230,9 @@ __global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2)
                 float dsum = 0.0f, usum = 0.0f;
 #pragma unroll
                 for (int g_ = 0; g_ < GP; ++g_) {
-                    const int slot = j * GP + g_;
                     const float d = gen.next(g_);
+                    if (g_ < G0) continue;            // CHEBY: dT0/dx = 0 (dsum + v * 0 = dsum for the finite v it had)
+                    const int slot = j * GPE + g_ - G0;
                     const float v = acc[slot / 16][slot % 16];
                     if (RBF && g_ < GP - 1) usum += v * d;       // RBF: the last column is the silu base path (has_base)
                     else dsum += v * d;
@@ -262,7 +272,7 @@ __global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2)
             }
             if (!SHARED || p == nshare - 1) {
 #pragma unroll
-                for (int kt = 0; kt < KT; ++kt)
+                for (int kt = 0; kt < KTE; ++kt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[kt][r] = 0.0f;
             }
@@ -292,7 +302,7 @@ int launch_bwd_input_reg(const LayerArgs& a0, hipStream_t st) {
         ((uintptr_t)a.dx & 15) || ((uintptr_t)a.dy & 15) || ((uintptr_t)a.w & 15))
         return 1;
     if ((long long)IC * GP * a.O >= (1LL << 30)) return 1;
-    constexpr int KCT_ = 32 * KT, HOFF_ = (KCT_ % 64 == 32) ? KCT_ : KCT_ + 32, WS2_ = ((HOFF_ + KCT_ + 13) / 16) * 16 + 2;
+    constexpr int KCT_ = 32 * kv_bwi_kt(FAM, GP, KT), HOFF_ = (KCT_ % 64 == 32) ? KCT_ : KCT_ + 32, WS2_ = ((HOFF_ + KCT_ + 13) / 16) * 16 + 2;
     const size_t lds = sizeof(float) * (2 * 16 * WS2_ + (FAM == KV_SINE ? (size_t)nshare * 4 * GP : 0));
     if (FAM == KV_SINE && !a.dparam) return 1;
     const bool shared = kv_shared_basis<FAM>() && kv_share_ok(FAM, a.flags) && nshare > 1;

@@ -161,13 +161,21 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_dma_kernel(const LayerArgs
         }
     };
 
-    f32x16 acc[GP][NOT];
+    // fp32 CHEBY: Phi_0 = T0 = 1, so dW[g][i*GP][o] = sum_m dY[m][o] for every feature i.  Those rows are not contracted on the matrix
+    // cores: each lane sums the dY values it reads (column l31 of every tile, the rows of its half) on the VALU, the two halves and the
+    // four waves are added in a fixed order, and the sum is written to the T0 row of all 32 features.
+    constexpr int G0 = (FAM == KV_CHEBY && !BF) ? 1 : 0;
+    constexpr int NJ = GP - G0;                         // basis values contracted on the matrix cores
+    f32x16 acc[NJ][NOT];
 #pragma unroll
-    for (int j = 0; j < GP; ++j)
+    for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int i = 0; i < NOT; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][i][r] = 0.0f;
+    float csum[NOT];
+#pragma unroll
+    for (int i = 0; i < NOT; ++i) csum[i] = 0.0f;
 
     // lane (l31, hf) reads row 2i + hf of the block, i = 0..7: x[row][l31] and dY[row][32 t + l31]
     const float* rdx = ring + hf * 32 + l31;
@@ -215,8 +223,13 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_dma_kernel(const LayerArgs
 #pragma unroll
                 for (int j = 0; j < GP; ++j) {
                     const float av = gen.next(j);
+                    if (j < G0) continue;
 #pragma unroll
-                    for (int t = 0; t < NOT; ++t) acc[j][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, cdy[i][t], acc[j][t], 0, 0, 0);
+                    for (int t = 0; t < NOT; ++t) acc[j - G0][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, cdy[i][t], acc[j - G0][t], 0, 0, 0);
+                }
+                if constexpr (G0 > 0) {
+#pragma unroll
+                    for (int t = 0; t < NOT; ++t) csum[t] += cdy[i][t];
                 }
             }
         } else {
@@ -261,24 +274,36 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_dma_kernel(const LayerArgs
     static_assert(KVD_NSLOT == 4 || KVD_NSLOT == 5, "the step sequence above is written out for four or five slots");
 
     // ---- the four partial sums of the work-group, through the LDS: images [accumulator register][lane], two at a time ----
-    constexpr int NREG = GP * NOT * 16;
+    constexpr int NREG = NJ * NOT * 16 + (G0 ? NOT : 0);      // the accumulators, then the column sums
     static_assert(2 * NREG * 64 <= 4 * KVD_NSLOT * SLOTF, "two accumulator images fit the rings");
     float* img = smem + (wave >> 1) * (NREG * 64) + lane;
+    if constexpr (G0 > 0) {           // the wave's column sums: rows of half 0, plus rows of half 1 (lane l31 + 32)
+#pragma unroll
+        for (int t = 0; t < NOT; ++t) csum[t] += __shfl_xor(csum[t], 32);      // (a + b == b + a: both halves hold the same bits)
+    }
     auto put = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < GP; ++j)
+        for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int t = 0; t < NOT; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) img[((j * NOT + t) * 16 + r) * 64] = acc[j][t][r];
+        if constexpr (G0 > 0) {
+#pragma unroll
+            for (int t = 0; t < NOT; ++t) img[(NJ * NOT * 16 + t) * 64] = csum[t];
+        }
     };
     auto add = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < GP; ++j)
+        for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int t = 0; t < NOT; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[j][t][r] += img[((j * NOT + t) * 16 + r) * 64];
+        if constexpr (G0 > 0) {
+#pragma unroll
+            for (int t = 0; t < NOT; ++t) csum[t] += img[(NJ * NOT * 16 + t) * 64];
+        }
     };
     __syncthreads();                  // every wave has left its ring
     if (wave & 1) put();              // waves 1, 3 -> images 0, 1
@@ -307,7 +332,7 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_dma_kernel(const LayerArgs
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int fr = fb * 32 + kv_acc_row(r, hf);
-                gb[((long long)fr * GP + j) * a.O] = acc[j][i][r];
+                gb[((long long)fr * GP + j) * a.O] = j < G0 ? csum[i] : acc[j - G0][i][r];
             }
     }
 }

@@ -107,13 +107,22 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs
 #pragma unroll
     for (int i = 0; i < NOT; ++i) dyo[i] = (int)tcol[i] + l31;
 
-    f32x16 acc[JC][NOT];
+    // fp32 CHEBY: Phi_0 = T0 = 1, so dW[g][i*GP][o] = sum_m dY[m][o] for every feature i.  Those rows are not contracted on the matrix
+    // cores: each lane sums the dY values it takes out of the ring (the rows of its half, in row order) on the VALU, the two halves are
+    // added at the end, and the sum is written to the T0 row of all 32 features.  The gather form visits the same rows in the same order.
+    constexpr int G0 = (FAM == KV_CHEBY && !BF) ? 1 : 0;
+    static_assert(!G0 || JC == GP, "the T0 column is the first of the only window");
+    constexpr int NJ = JC - G0;                   // basis values contracted on the matrix cores
+    f32x16 acc[NJ][NOT];
 #pragma unroll
-    for (int j = 0; j < JC; ++j)
+    for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int i = 0; i < NOT; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][i][r] = 0.0f;
+    float csum[NOT];
+#pragma unroll
+    for (int i = 0; i < NOT; ++i) csum[i] = 0.0f;
 
     // token of (block, step u, e): fp32: 2*(blk*UB + u) + hf ; bf16: 16*blk + 8*hf + e
     float rx[PD][NTOK], ru[RBF ? PD : 1][RBF ? NTOK : 1], rdy[PD][NTOK][NOT];
@@ -246,9 +255,14 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs
 #pragma unroll
                         for (int j = 0; j < JC; ++j) {
                             const float av = gen.next(j);
+                            if (j < G0) continue;
 #pragma unroll
                             for (int i = 0; i < NOT; ++i)
-                                acc[j][i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, cdy[t][i], acc[j][i], 0, 0, 0);
+                                acc[j - G0][i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, cdy[t][i], acc[j - G0][i], 0, 0, 0);
+                        }
+                        if constexpr (G0 > 0) {
+#pragma unroll
+                            for (int i = 0; i < NOT; ++i) csum[i] += cdy[t][i];
                         }
                     }
                 } else {
@@ -325,9 +339,14 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs
 #pragma unroll
                 for (int j = 0; j < JC; ++j) {
                     const float av = gen.next(j);
+                    if (j < G0) continue;
 #pragma unroll
                     for (int i = 0; i < NOT; ++i)
-                        acc[j][i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, cdy[t][i], acc[j][i], 0, 0, 0);
+                        acc[j - G0][i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, cdy[t][i], acc[j - G0][i], 0, 0, 0);
+                }
+                if constexpr (G0 > 0) {
+#pragma unroll
+                    for (int i = 0; i < NOT; ++i) csum[i] += cdy[t][i];
                 }
             }
         } else {
@@ -370,6 +389,10 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs
     }
 
     }
+    if constexpr (G0 > 0) {
+#pragma unroll
+        for (int i = 0; i < NOT; ++i) csum[i] += __shfl_xor(csum[i], 32);      // (a + b == b + a: both halves hold the same bits)
+    }
     // dW partial of this slab: row k = (fb*32 + acc row)*GP + j, 32 contiguous columns per row
     float* base = a.slab + (long long)slab * ((long long)a.groups * a.K * a.O);
 #pragma unroll
@@ -383,7 +406,7 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int fr = fb * 32 + kv_acc_row(r, hf);
-                if (GP % JC == 0 || j0 + j < GP) gb[((long long)fr * GP + j0 + j) * a.O] = acc[j][i][r];      // the last window of 9 = 5 + 4 carries one idle slot
+                if (GP % JC == 0 || j0 + j < GP) gb[((long long)fr * GP + j0 + j) * a.O] = j < G0 ? csum[i] : acc[j - G0][i][r];      // the last window of 9 = 5 + 4 carries one idle slot
             }
     }
     };

@@ -36,7 +36,10 @@ __device__ __forceinline__ void kan_fwd_reg_body(const LayerArgs& a, float* __re
     const int n0 = (bx - gs * ntn) * BN;
     const int nsets = a.groups / NSH;
     const long long m0 = (long long)by * BM;
-    const int GP = GPC > 0 ? GPC : a.GP, KC = IC * GP;      // k rows per chunk (even); compile-time in the GPC instantiations (host: a.GP == GPC)
+    // CHEBY: T0 = cos(0 * acos t) is the constant 1, so the g = 0 k rows only add the per-column constant b[o] = sum_i W[i*GP][o].
+    // The GPC instantiation contracts g >= 1 on the matrix cores and sums those rows on the VALU of the staging threads (below).
+    constexpr int G0 = (FAM == KV_CHEBY && GPC > 0) ? 1 : 0;
+    const int GP = GPC > 0 ? GPC : a.GP, GPE = GP - G0, KC = IC * GPE;      // k rows per chunk (even); compile-time in the GPC instantiations (host: a.GP == GPC)
     const int nch = a.I / IC;
     const int WSZ = KC * WROW;
     const int mrem = (m0 + BM <= a.M) ? BM : (int)(a.M - m0);
@@ -92,18 +95,32 @@ __device__ __forceinline__ void kan_fwd_reg_body(const LayerArgs& a, float* __re
     for (int q = 0; q < WQ; ++q) {
         const int lr = wr0 + q * WRS;             // LDS row = 2*s + h
         const int s_ = lr >> 1, h_ = lr & 1;
-        const int j_ = s_ / GP, g_ = s_ - j_ * GP;
+        const int j_ = s_ / GPE, g_ = s_ - j_ * GPE + G0;
         koff[q] = (lr < KC) ? ((h_ * ICH + j_) * GP + g_) * a.O : -1;
     }
+    // CHEBY T0 rows: thread tid < WROW sums the rows of features NB0*part .. NB0*part + NB0-1 of every chunk (part = tid / (WROW/4)) for
+    // the 4 columns cc of the work-group's WROW; the four parts are added in a fixed order after the loop.  The order of every column's
+    // sum does not depend on NSH, so the NSH = 1 tail pieces form the same bits as the shared launch.
+    constexpr int NB0 = G0 ? IC / 4 : 1;
+    static_assert(!G0 || (IC % 4 == 0 && WROW <= 256), "T0 sums: four parts of a chunk, one thread per part and 4 columns");
+    const int t0t = tid % WROW, t0part = t0t / (WROW / 4), t0cc = (t0t % (WROW / 4)) * 4;
+    const int t0g = (NSH == 1) ? gs : (t0cc / BN) * nsets + gs;
+    const float* t0src = a.w + (long long)t0g * a.K * a.O + (long long)(t0part * NB0) * GP * a.O + n0 + t0cc % BN;
+    f32x4 w0reg[NB0];
+    f32x4 bpart = {0.0f, 0.0f, 0.0f, 0.0f};
     auto load_w = [&](int c) {
 #pragma unroll
         for (int p = 0; p < NSH; ++p) {
             const int g = (NSH == 1) ? gs : p * nsets + gs;
-            const float* src = a.w + ((long long)g * a.K + (long long)c * KC) * a.O + n0 + wc;      // chunk base (natural k order)
+            const float* src = a.w + ((long long)g * a.K + (long long)c * IC * GP) * a.O + n0 + wc;      // chunk base (natural k order)
 #pragma unroll
             for (int q = 0; q < WQ; ++q)      // unconditional: a predicated load is a branch around it plus an s_waitcnt vmcnt(1) in front of every
                 if (q * WRS < KC)             // load (two in flight instead of all of them); rows past KC re-read row 0 and are never stored
                     wreg[p][q] = *reinterpret_cast<const f32x4*>(src + (koff[q] >= 0 ? koff[q] : 0));
+        }
+        if constexpr (G0 > 0) {                   // every thread loads (threads past WROW repeat a column and never add)
+#pragma unroll
+            for (int r = 0; r < NB0; ++r) w0reg[r] = *reinterpret_cast<const f32x4*>(t0src + ((long long)c * IC + r) * GP * a.O);
         }
     };
     auto store_w = [&](int buf) {
@@ -113,6 +130,10 @@ __device__ __forceinline__ void kan_fwd_reg_body(const LayerArgs& a, float* __re
 #pragma unroll
             for (int q = 0; q < WQ; ++q)
                 if (koff[q] >= 0) *reinterpret_cast<f32x4*>(dst + (wr0 + q * WRS) * WROW + p * BN) = wreg[p][q];
+        if constexpr (G0 > 0) {                   // the chunk's T0 rows of this part, in feature order
+#pragma unroll
+            for (int r = 0; r < NB0; ++r) bpart += w0reg[r];
+        }
     };
 
     f32x16 acc[NSH * NT];
@@ -205,7 +226,8 @@ __device__ __forceinline__ void kan_fwd_reg_body(const LayerArgs& a, float* __re
         }
         const float* wp = W_s + (c & 1) * WSZ + hf * WROW + l31;
         if constexpr (GPC > 0) {
-            constexpr int VH = ICH * GPC;               // k-steps of this chunk (one generated value per lane and step)
+            constexpr int GPCE = GPC - G0;
+            constexpr int VH = ICH * GPCE;              // k-steps of this chunk (one generated value per lane and step)
             constexpr int NTT = NSH * NT;
             float phi[VH];
 #pragma unroll
@@ -215,7 +237,10 @@ __device__ __forceinline__ void kan_fwd_reg_body(const LayerArgs& a, float* __re
 #pragma unroll
                 for (int g = 0; g < GPC; ++g) {
                     if constexpr (SINE_PH) phi[j * GPC + g] = kv_sin(__fadd_rn(__fmul_rn(xc[j], b.bp[g]), phc[j * GPC + g]));      // BasisGen<KV_SINE>::next with the phase from registers
-                    else phi[j * GPC + g] = gen.next(g);
+                    else {
+                        const float v = gen.next(g);      // (CHEBY: next(0) is the constant 1, folded away)
+                        if (g >= G0) phi[j * GPCE + g - G0] = v;
+                    }
                 }
             }
             float wa[2][NTT];
@@ -251,6 +276,19 @@ __device__ __forceinline__ void kan_fwd_reg_body(const LayerArgs& a, float* __re
         __syncthreads();
     }
 
+    // CHEBY: b = ((part 0 + part 1) + part 2) + part 3 per column, through the LDS (the W buffers are dead after the last barrier)
+    float* b_s = smem + 4 * WROW;                 // [WROW]; the parts at [4][WROW] in front of it
+    if constexpr (G0 > 0) {
+        if (tid < WROW) *reinterpret_cast<f32x4*>(smem + t0part * WROW + t0cc) = bpart;
+        __syncthreads();
+        if (tid < WROW / 4) {
+            const f32x4 s = ((*reinterpret_cast<const f32x4*>(smem + t0cc) + *reinterpret_cast<const f32x4*>(smem + WROW + t0cc)) +
+                             *reinterpret_cast<const f32x4*>(smem + 2 * WROW + t0cc)) + *reinterpret_cast<const f32x4*>(smem + 3 * WROW + t0cc);
+            *reinterpret_cast<f32x4*>(b_s + t0cc) = s;
+        }
+        __syncthreads();
+    }
+
     // epilogue: with the flipped product, accumulator registers 4q..4q+3 of a tile are 4 consecutive y columns of the lane's
     // OWN row (column 8q + 4hf + 0..3 of the tile): float4 stores straight from registers, no staging tile, no barrier
     if (row < mrem) {
@@ -264,6 +302,7 @@ __device__ __forceinline__ void kan_fwd_reg_body(const LayerArgs& a, float* __re
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 f32x4 v = {acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
+                if constexpr (G0 > 0) v += *reinterpret_cast<const f32x4*>(b_s + t * 32 + 8 * q + 4 * hf);
                 if (bp) v += *reinterpret_cast<const f32x4*>(bp + 8 * q);
                 if (posrow) v += *reinterpret_cast<const f32x4*>(posrow + col + 8 * q);
                 *reinterpret_cast<f32x4*>(yp + 8 * q) = v;
