@@ -247,7 +247,10 @@ int kanvit_attn_bwd(const kanvit_attn_desc* d, const float* q, const float* k, c
  * strides; lse [B][H][q_len]).  Exact fp32 (KANVIT_FLAG_BF16_MFMA is refused).  A query whose keys are all dead gets o = 0,
  * lse = -FLT_MAX, zero gradients.  Any q_len / k_len: the swept operand is walked in LDS chunks of 128 rows (running max / sum in
  * the forward, utils.py:199-221), so these entry points also serve self-attention heads too long for kanvit_attn_fwd's
- * one-head-per-work-group form (N > 224 at D = 64). */
+ * one-head-per-work-group form (N > 224 at D = 64).  Head size: D even and <= KANVIT_ATTN_X_MAX_D, wider than
+ * kanvit_attn_fwd's KANVIT_ATTN_MAX_D, so they also serve every head wider than 64 (ViT-H/14: D = 80; D = 128).  The domain
+ * grew from D <= 64 to D <= 128 without a change of struct, signature or ABI version. */
+#define KANVIT_ATTN_X_MAX_D 128
 typedef struct kanvit_attn_ext {
     int32_t Nk;              /* key / value length */
     int32_t reserved;

@@ -18,7 +18,11 @@
 // A position is dead when key >= k_len, or causal and key > query, or the mask says so.  A query whose keys are ALL
 // dead gets o = 0, lse = -FLT_MAX and zero gradients (the reference's clamp(min=EPSILON) row sum gives the same o = 0 and
 // lse = log(1e-10) - FLT_MAX for a fully MASKED row).
-// Limits (host-checked): D even and <= 64.
+// Head sizes: DT = ceil(D / 32) column tiles of 32 (x_load_tile zero-fills the columns >= D).  DT = 1, 2 (D <= 64) run eight waves,
+// two per SIMD, each with its own 32-row staging tile in LDS.  DT = 3, 4 (D <= 96, <= 128) run four waves, one per SIMD, so that a
+// lane may hold up to 512 registers (the dK/dV kernel keeps 4 x 16*DT values of K, V, dK, dV), and alias the staging tiles onto the
+// chunk buffers (they are used only before the sweep and after it, across a barrier) to fit the 160 KiB of LDS at 128-row chunks.
+// Limits (host-checked): D even and <= KANVIT_ATTN_X_MAX_D (128).
 #include "kanvit_common.h"
 
 #include <float.h>
@@ -26,8 +30,14 @@
 
 namespace {
 
-constexpr int XTHR = 512;        // 8 waves: two per SIMD (one LDS chunk of the swept operand serves eight 32-row tiles)
-constexpr int XW = XTHR / 64;
+// Work-group shape of the DT form: 8 waves, two per SIMD (one LDS chunk of the swept operand serves eight 32-row tiles) up to D = 64;
+// 4 waves, one per SIMD, with each wave's 32-row staging tile aliased onto the chunk buffers for D > 64.
+template <int DT>
+struct XShape {
+    static constexpr int THR = DT <= 2 ? 512 : 256;
+    static constexpr int W = THR / 64;
+    static constexpr bool ALIAS = DT > 2;
+};
 constexpr float LOG2E_X = 1.4426950408889634f;
 
 struct AttnXArgs {
@@ -115,19 +125,19 @@ __device__ __forceinline__ void x_store_tile(float* __restrict__ dstg, long long
 
 constexpr int XCH = 4;            // tiles of 32 rows per LDS chunk of the swept operand (128 rows)
 
-// forward: grid (B*H, ceil(q tiles / 8)); a wave owns a 32-query tile and sweeps the keys in chunks of XCH tiles with the running
+// forward: grid (B*H, ceil(q tiles / waves)); a wave owns a 32-query tile and sweeps the keys in chunks of XCH tiles with the running
 // (max, sum) rescale of utils.py:199-221 -- in this orientation (O^T[d][query]: the query is the lane) the rescale of the partial
 // output is one multiplication of the lane's accumulators by a lane-private factor
 template <int DT>
-__global__ __launch_bounds__(XTHR) void attn_x_fwd_kernel(const AttnXArgs a) {
+__global__ __launch_bounds__(XShape<DT>::THR) void attn_x_fwd_kernel(const AttnXArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int KS = 32 * DT + 1, CH = XCH * 32;
+    constexpr int KS = 32 * DT + 1, CH = XCH * 32, XTHR = XShape<DT>::THR, XW = XShape<DT>::W;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hf = lane >> 5;
     const int bh = blockIdx.x, bi = bh / a.H, hi = bh - bi * a.H;
     const int D = a.D, nkt = a.nkt;
     float* K_s = smem;
     float* V_s = K_s + CH * KS;
-    float* Q_w = V_s + CH * KS + wave * 32 * KS;
+    float* Q_w = (XShape<DT>::ALIAS ? smem : V_s + CH * KS) + wave * 32 * KS;      // aliased: read before the first chunk fill's barrier
 
     const float* qb = a.q + bi * a.qsb + hi * a.qsh;
     const float* kb = a.k + bi * a.ksb + hi * a.ksh;
@@ -243,12 +253,12 @@ __global__ __launch_bounds__(256) void attn_x_delta_kernel(const AttnXArgs a) {
     if (row < rows && sub == 0) a.delta[row] = s;
 }
 
-// dK, dV: key-stationary (utils.py:262-291).  grid (B*H, ceil(key tiles / 8)); a wave owns a 32-key tile (K, V fragments in registers,
+// dK, dV: key-stationary (utils.py:262-291).  grid (B*H, ceil(key tiles / waves)); a wave owns a 32-key tile (K, V fragments in registers,
 // dK^T / dV^T in accumulators) and sweeps the queries in LDS chunks of XCH tiles.
 template <int DT>
-__global__ __launch_bounds__(XTHR) void attn_x_bwd_kv_kernel(const AttnXArgs a) {
+__global__ __launch_bounds__(XShape<DT>::THR) void attn_x_bwd_kv_kernel(const AttnXArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int KS = 32 * DT + 1, CH = XCH * 32;
+    constexpr int KS = 32 * DT + 1, CH = XCH * 32, XTHR = XShape<DT>::THR, XW = XShape<DT>::W;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hf = lane >> 5;
     const int bh = blockIdx.x, bi = bh / a.H, hi = bh - bi * a.H;
     const int D = a.D;
@@ -256,7 +266,7 @@ __global__ __launch_bounds__(XTHR) void attn_x_bwd_kv_kernel(const AttnXArgs a) 
     float* dO_s = Q_s + CH * KS;
     float* lse_s = dO_s + CH * KS;
     float* dl_s = lse_s + CH;
-    float* T_w = dl_s + CH + wave * 32 * KS;
+    float* T_w = (XShape<DT>::ALIAS ? smem : dl_s + CH) + wave * 32 * KS;          // aliased: in Q_s, used only outside the sweep
 
     const float* qb = a.q + bi * a.qsb + hi * a.qsh;
     const float* kb = a.k + bi * a.ksb + hi * a.ksh;
@@ -348,17 +358,17 @@ __global__ __launch_bounds__(XTHR) void attn_x_bwd_kv_kernel(const AttnXArgs a) 
     if (jt < a.nkt) x_store_tile<DT>(dvb, a.vsn, jt * 32, a.Nk, D, T_w, lane);
 }
 
-// dQ: query-stationary mirror of the forward kernel (grid (B*H, ceil(q tiles / 8)); keys swept in LDS chunks of XCH tiles)
+// dQ: query-stationary mirror of the forward kernel (grid (B*H, ceil(q tiles / waves)); keys swept in LDS chunks of XCH tiles)
 template <int DT>
-__global__ __launch_bounds__(XTHR) void attn_x_bwd_q_kernel(const AttnXArgs a) {
+__global__ __launch_bounds__(XShape<DT>::THR) void attn_x_bwd_q_kernel(const AttnXArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int KS = 32 * DT + 1, CH = XCH * 32;
+    constexpr int KS = 32 * DT + 1, CH = XCH * 32, XTHR = XShape<DT>::THR, XW = XShape<DT>::W;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hf = lane >> 5;
     const int bh = blockIdx.x, bi = bh / a.H, hi = bh - bi * a.H;
     const int D = a.D, nkt = a.nkt;
     float* K_s = smem;
     float* V_s = K_s + CH * KS;
-    float* T_w = V_s + CH * KS + wave * 32 * KS;
+    float* T_w = (XShape<DT>::ALIAS ? smem : V_s + CH * KS) + wave * 32 * KS;      // aliased: in K_s, used only outside the sweep
 
     const float* qb = a.q + bi * a.qsb + hi * a.qsh;
     const float* kb = a.k + bi * a.ksb + hi * a.ksh;
@@ -435,7 +445,7 @@ __global__ __launch_bounds__(XTHR) void attn_x_bwd_q_kernel(const AttnXArgs a) {
 int x_check(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const char* who) {
     if (!d || !e) return kv_fail(KANVIT_EINVAL, "%s: null descriptor", who);
     if (d->B < 0 || d->H < 1 || d->N < 1 || e->Nk < 1 || d->D < 1) return kv_fail(KANVIT_EINVAL, "%s: bad sizes", who);
-    if (d->D > KANVIT_ATTN_MAX_D || (d->D & 1)) return kv_fail(KANVIT_EINVAL, "%s: D=%d must be even and <= %d", who, d->D, KANVIT_ATTN_MAX_D);
+    if (d->D > KANVIT_ATTN_X_MAX_D || (d->D & 1)) return kv_fail(KANVIT_EINVAL, "%s: D=%d must be even and <= %d", who, d->D, KANVIT_ATTN_X_MAX_D);
     if ((long long)d->B * d->H > 0x7fffffffLL) return kv_fail(KANVIT_EINVAL, "%s: B*H too large", who);
     if (!(d->scale > 0.0f)) return kv_fail(KANVIT_EINVAL, "%s: scale=%g must be positive (the running maximum is taken over the raw scores)", who, (double)d->scale);
     if (d->causal && e->Nk > d->N)
@@ -461,10 +471,18 @@ AttnXArgs x_args(const kanvit_attn_desc* d, const kanvit_attn_ext* e) {
     return a;
 }
 
+// LDS of a work-group: the two chunk buffers (CH rows each) and, unless aliased onto them, one 32-row staging tile per wave
+template <int DT>
+constexpr size_t x_stage_floats() {
+    static_assert(!XShape<DT>::ALIAS || XShape<DT>::W * 32 <= 2 * XCH * 32, "aliased staging tiles must lie inside the chunk buffers");
+    return XShape<DT>::ALIAS ? 0 : (size_t)XShape<DT>::W * 32 * (32 * DT + 1);
+}
+
 template <int DT>
 int x_launch_fwd(const AttnXArgs& a, hipStream_t st) {
-    constexpr int KS = 32 * DT + 1, CH = XCH * 32;
-    const size_t lds = sizeof(float) * ((size_t)2 * CH * KS + (size_t)XW * 32 * KS);
+    constexpr int KS = 32 * DT + 1, CH = XCH * 32, XTHR = XShape<DT>::THR, XW = XShape<DT>::W;
+    const size_t lds = sizeof(float) * ((size_t)2 * CH * KS + x_stage_floats<DT>());
+    static_assert(sizeof(float) * ((size_t)2 * CH * KS + x_stage_floats<DT>()) <= 160 * 1024, "forward LDS over 160 KiB");
     KV_ALLOW_LDS(160 * 1024, (attn_x_fwd_kernel<DT>));
     hipLaunchKernelGGL((attn_x_fwd_kernel<DT>), dim3((unsigned)(a.B * a.H), (unsigned)((a.nqt + XW - 1) / XW)), dim3(XTHR), lds, st, a);
     KV_LAUNCH_CHECK("attn_x_fwd_kernel");
@@ -473,9 +491,10 @@ int x_launch_fwd(const AttnXArgs& a, hipStream_t st) {
 
 template <int DT>
 int x_launch_bwd(const AttnXArgs& a, hipStream_t st) {
-    constexpr int KS = 32 * DT + 1, CH = XCH * 32;
-    const size_t lds_kv = sizeof(float) * ((size_t)2 * CH * KS + 2 * (size_t)CH + (size_t)XW * 32 * KS);
-    const size_t lds_q = sizeof(float) * ((size_t)2 * CH * KS + (size_t)XW * 32 * KS);
+    constexpr int KS = 32 * DT + 1, CH = XCH * 32, XTHR = XShape<DT>::THR, XW = XShape<DT>::W;
+    const size_t lds_kv = sizeof(float) * ((size_t)2 * CH * KS + 2 * (size_t)CH + x_stage_floats<DT>());
+    const size_t lds_q = sizeof(float) * ((size_t)2 * CH * KS + x_stage_floats<DT>());
+    static_assert(sizeof(float) * ((size_t)2 * CH * KS + 2 * (size_t)CH + x_stage_floats<DT>()) <= 160 * 1024, "dK/dV LDS over 160 KiB");
     KV_ALLOW_LDS(160 * 1024, (attn_x_bwd_kv_kernel<DT>));
     KV_ALLOW_LDS(160 * 1024, (attn_x_bwd_q_kernel<DT>));
     hipLaunchKernelGGL((attn_x_bwd_kv_kernel<DT>), dim3((unsigned)(a.B * a.H), (unsigned)((a.nkt + XW - 1) / XW)), dim3(XTHR), lds_kv, st, a);
@@ -498,7 +517,7 @@ int kanvit_attn_x_fwd(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const
     a.q = q; a.k = k; a.v = v; a.out = o; a.lse = lse;
     a.vec = a.vec && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0);
     hipStream_t st = (hipStream_t)stream;
-    return d->D <= 32 ? x_launch_fwd<1>(a, st) : x_launch_fwd<2>(a, st);
+    return d->D <= 32 ? x_launch_fwd<1>(a, st) : d->D <= 64 ? x_launch_fwd<2>(a, st) : d->D <= 96 ? x_launch_fwd<3>(a, st) : x_launch_fwd<4>(a, st);
 }
 
 size_t kanvit_attn_x_bwd_workspace(const kanvit_attn_desc* d, const kanvit_attn_ext* e) {
@@ -522,7 +541,7 @@ int kanvit_attn_x_bwd(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const
     const long long rows = (long long)d->B * d->H * d->N;
     hipLaunchKernelGGL(attn_x_delta_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, a);
     KV_LAUNCH_CHECK("attn_x_delta_kernel");
-    return d->D <= 32 ? x_launch_bwd<1>(a, st) : x_launch_bwd<2>(a, st);
+    return d->D <= 32 ? x_launch_bwd<1>(a, st) : d->D <= 64 ? x_launch_bwd<2>(a, st) : d->D <= 96 ? x_launch_bwd<3>(a, st) : x_launch_bwd<4>(a, st);
 }
 
 }  // extern "C"

@@ -449,7 +449,11 @@ def _attn_desc(q, k, v, o, causal: bool, scale: float, flags: int = 0) -> AttnDe
 
 def _attn_fits_one_workgroup(N: int, D: int) -> bool:
     """The ViT kernels of csrc/attention.hip hold one head in a work-group's LDS (check_desc's bound: N <= 224 at D = 64, 256 at
-    D <= 32); longer sequences (e.g. 384 x 384 images at patch 16: N = 577) take the chunked general kernels (csrc/attention_x.hip)."""
+    D <= 32) and take D <= 64 (KANVIT_ATTN_MAX_D); longer sequences (e.g. 384 x 384 images at patch 16: N = 577) and wider heads
+    (64 < D <= 128, e.g. ViT-H/14: D = 80) take the chunked general kernels (csrc/attention_x.hip).  The forward and the backward
+    both route by this one predicate."""
+    if D > 64:
+        return False
     ks, npad = (32 if D <= 32 else 64) + 1, (N + 31) // 32 * 32
     return N <= 256 and 4 * (2 * npad * ks + 2 * npad + 4 * 32 * ks) <= 160 * 1024
 
@@ -594,11 +598,15 @@ def _autocast_flags() -> int:
 
 
 def attention_packed(qkv: torch.Tensor, causal: bool = False, scale: Optional[float] = None) -> torch.Tensor:
+    """Self-attention on qkv[B, N, 3, H, D] -> o[B, N, H*D].  D even and <= 128.  Heads of D <= 64 that fit one work-group run the
+    ViT kernels (on the bf16 matrix cores under bf16 autocast); longer sequences and heads wider than 64 run the exact-fp32 general
+    kernels, with or without autocast (they take no KANVIT_FLAG_BF16_MFMA)."""
     return _AttnPackedFn.apply(qkv, causal, qkv.shape[-1] ** -0.5 if scale is None else scale, _autocast_flags())
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False,
               scale: Optional[float] = None) -> torch.Tensor:
+    """Self-attention on q, k, v of shape (B, H, N, D); routing and autocast behaviour as attention_packed()."""
     return _AttnFn.apply(q, k, v, causal, q.shape[-1] ** -0.5 if scale is None else scale, _autocast_flags())
 
 

@@ -26,8 +26,9 @@ def default(val, d):
 class FlashAttentionFunction(Function):
     """Same call signature as the reference (utils.py:137): apply(q, k, v, mask, causal,
     q_bucket_size, k_bucket_size) with q (b, h, q_len, d) and k, v (b, h, k_len, d).  The bucket sizes only chose
-    the tiling of the python implementation; on MI355X a whole head fits one workgroup, so they
-    do not change anything.  Self-attention without a mask (the ViT path) runs the kernels of csrc/attention.hip; a mask
+    the tiling of the python implementation; the kernels choose their own tiling, so they
+    do not change anything.  Head size d: even and <= 128.  Self-attention without a mask (the ViT path) runs the kernels of
+    csrc/attention.hip when the head fits one work-group (d <= 64, N <= 224), else the general kernels; a mask
     ((b, k_len) key padding or anything broadcastable to (b, h, q_len, k_len), True = attend; utils.py:156-164) or
     q_len != k_len (cross-attention) runs the general kernels of csrc/attention_x.hip (exact fp32).  `causal` together with
     k_len > q_len raises: the reference shifts the diagonal the wrong way there (utils.py:169: the first k_len - q_len

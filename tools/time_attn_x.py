@@ -1,6 +1,7 @@
 """Event-timed general attention kernels (csrc/attention_x.hip) next to the tuned ViT kernels: python tools/time_attn_x.py
 Prints ms and algorithmic TFLOP/s (forward 2 products, backward 5) for self-attention at N = 197 (both kernel families) and at lengths only
-the chunked kernels take (N = 577: ViT-B/16 at 384 x 384)."""
+the chunked kernels take (N = 577: ViT-B/16 at 384 x 384), then heads wider than 64, which only the general kernels take (ViT-H/14:
+D = 80 at N = 257; D = 128 at N = 197; N = 577 at D = 64 and at D = 128 side by side)."""
 import os
 import sys
 R = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
@@ -22,7 +23,9 @@ def run(fn, n_it=20):
     return s.elapsed_time(e) / n_it
 
 
-for (B, H, N, D, general) in ((128, 12, 197, 64, False), (128, 12, 197, 64, True), (32, 12, 577, 64, True), (8, 12, 1025, 64, True)):
+SHAPES = ((128, 12, 197, 64, False), (128, 12, 197, 64, True), (32, 12, 577, 64, True), (8, 12, 1025, 64, True),
+          (32, 16, 257, 80, True), (128, 6, 197, 128, True), (32, 12, 577, 128, True))
+for (B, H, N, D, general) in SHAPES:
     q, k, v = (torch.randn(B, H, N, D, device="cuda") for _ in range(3))
     o = torch.empty_like(q)
     do = torch.randn_like(q)
