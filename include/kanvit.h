@@ -78,8 +78,8 @@ extern "C" {
 /* basis families: phi_g(x) generated on the fly, never stored in HBM */
 #define KANVIT_LINEAR 0   /* phi = x                               nn.Linear in attention.py:136-142           */
 #define KANVIT_CHEBY 1    /* T_g(tanh x), g = 0..degree            models/cheby.py:36-48                       */
-#define KANVIT_BSPLINE 2  /* Cox-de Boor B-splines (+ silu base)   models/effkan.py:99-132,174-187             */
-#define KANVIT_RBF 3      /* exp(-((u-c_g)/h)^2) (+ silu base)     models/fastkan.py:29-30,66-76               */
+#define KANVIT_BSPLINE 2  /* Cox-de Boor B-splines (+ base act)    models/effkan.py:99-132,174-187             */
+#define KANVIT_RBF 3      /* exp(-((u-c_g)/h)^2) (+ base act)      models/fastkan.py:29-30,66-76               */
 #define KANVIT_SINE 4     /* sin(x f_g + p_ig)                     models/sinekan.py:81-91                     */
 #define KANVIT_FOURIER 5  /* cos(k x), sin(k x), k = 1..G          models/nfkan.py:36-52                       */
 
@@ -110,7 +110,7 @@ typedef struct kanvit_layer_desc {
     int32_t G;             /* cheby: degree+1; bspline: grid_size+spline_order; rbf: num_grids;
                               sine: grid_size; fourier: gridsize; linear: 1                 */
     int32_t spline_order;  /* BSPLINE only                                                  */
-    int32_t has_base;      /* BSPLINE / RBF: extra silu(x) column per input feature         */
+    int32_t has_base;      /* BSPLINE / RBF: extra base column act(x) per input feature     */
     float rbf_inv_h;       /* RBF: 1 / denominator                                          */
     int32_t flags;         /* KANVIT_FLAG_*                                                  */
     int64_t M;             /* rows                                                          */
@@ -119,8 +119,19 @@ typedef struct kanvit_layer_desc {
     int64_t ldy;           /* row stride of y and dy (group g uses columns [g*O, +O))       */
     int64_t bparam_stride; /* floats between consecutive groups in bparams                  */
     float ln_eps;          /* KANVIT_FLAG_FUSED_LN: epsilon of the fused LayerNorm          */
-    int32_t reserved;
+    int32_t base_act;      /* BSPLINE / RBF with has_base: KANVIT_BASE_* of the base column (0 = SiLU).  Nonzero for
+                              another family, with has_base = 0, or outside 0..5 is KANVIT_EINVAL  */
 } kanvit_layer_desc;
+
+/* base activations of the BSPLINE / RBF base column (kanvit_layer_desc.base_act): the reference's `base_activation`
+ * (models/effkan.py:38, models/fastkan.py:61), whose value the base weights multiply.  Every kernel form of the two families
+ * exists for each of them, so a descriptor takes the same kernels whatever its activation.                                */
+#define KANVIT_BASE_SILU 0        /* x * sigmoid(x)                                    nn.SiLU (the default)             */
+#define KANVIT_BASE_GELU 1        /* x/2 (1 + erf(x / sqrt 2))                         nn.GELU(), F.gelu                 */
+#define KANVIT_BASE_GELU_TANH 2   /* x/2 (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3)))     nn.GELU(approximate='tanh')       */
+#define KANVIT_BASE_RELU 3        /* max(x, 0), derivative 0 at x = 0                  nn.ReLU(), F.relu                 */
+#define KANVIT_BASE_TANH 4        /* tanh x                                            nn.Tanh(), torch.tanh             */
+#define KANVIT_BASE_IDENTITY 5    /* x                                                 nn.Identity()                     */
 
 /* 1 if KANVIT_FLAG_FUSED_LN may be set for this layer (register kernels cover forward and both gradients), else 0 */
 int kanvit_layer_ln_fusable(const kanvit_layer_desc* d);

@@ -7,7 +7,7 @@
 //   CHEBY   models/cheby.py:37-43     T_d(tanh x) = cos(d*acos(tanh x)); evaluated by the
 //                                     three-term recurrence ("Transcendental cost")
 //   BSPLINE models/effkan.py:99-132   Cox-de Boor recursion, half-open order-0 indicator
-//   RBF     models/fastkan.py:29-30   exp(-((u-c)/h)^2);  base path silu(x) fastkan.py:74
+//   RBF     models/fastkan.py:29-30   exp(-((u-c)/h)^2);  base path act(x) fastkan.py:74 (SiLU by default; kv_base)
 //   SINE    models/sinekan.py:86      sin(x*freq + phase)
 //   FOURIER models/nfkan.py:44-45     cos(k x), sin(k x), k = 1..G (rotation recurrence)
 #pragma once
@@ -32,6 +32,7 @@ struct BasisArgs {
     float inv_h;       // RBF
     const float* bp;   // this group's parameter table
     int uniform;       // BSPLINE: KANVIT_FLAG_UNIFORM_KNOTS (closed-form cubic)
+    int act;           // BSPLINE / RBF: base activation code (KANVIT_BASE_*), read by the KV_ACT_DYN generators only
 };
 
 // tanh(x) = 1 - 2/(exp(2x)+1): v_exp_f32 + v_rcp_f32, absolute error ~2e-7 over the whole range
@@ -144,6 +145,65 @@ __device__ __forceinline__ float kv_dsilu(float x) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Base activation of the BSPLINE / RBF base column (KANVIT_BASE_* of kanvit.h).  The kernels are instantiated twice: ACT =
+// KV_ACT_SILU is the SiLU code above, verbatim (the kernels with the historical names), and ACT = KV_ACT_DYN reads the code
+// from the launch arguments (wave-uniform: a scalar branch per evaluation, one per (row, feature)) and covers the others
+// (the *_act_* kernels).  Values and derivatives restate torch's: F.gelu (erf form and tanh form, its backward
+// formulas), relu with threshold_backward's derivative (0 at x = 0), tanh, identity.
+// ---------------------------------------------------------------------------------------------
+#define KV_ACT_SILU 0
+#define KV_ACT_DYN 1
+#define KV_BASE_GELU 1
+#define KV_BASE_GELU_TANH 2
+#define KV_BASE_RELU 3
+#define KV_BASE_TANH 4
+#define KV_BASE_IDENTITY 5
+
+__device__ __forceinline__ float kv_base_dyn(float x, int act) {
+    switch (act) {
+        case KV_BASE_GELU: return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
+        case KV_BASE_GELU_TANH: {
+            const float inner = 0.7978845608028654f * fmaf(0.044715f * x * x, x, x);
+            return 0.5f * x * (1.0f + kv_tanh(inner));
+        }
+        case KV_BASE_RELU: return x <= 0.0f ? 0.0f : x;      // a NaN stays a NaN (torch.relu)
+        case KV_BASE_TANH: return kv_tanh(x);
+        default: return x;                                     // KV_BASE_IDENTITY
+    }
+}
+__device__ __forceinline__ float kv_dbase_dyn(float x, int act) {
+    switch (act) {
+        case KV_BASE_GELU: {       // Phi(x) + x phi(x)
+            const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f));
+            const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
+            return fmaf(x, pdf, cdf);
+        }
+        case KV_BASE_GELU_TANH: {  // torch's GeluBackward, approximate = 'tanh'
+            const float x2 = x * x;
+            const float k = 0.7978845608028654f;
+            const float t = kv_tanh(k * fmaf(0.044715f * x2, x, x));
+            return fmaf(0.5f * x * (1.0f - t * t), k * fmaf(3.0f * 0.044715f, x2, 1.0f), 0.5f * (1.0f + t));
+        }
+        case KV_BASE_RELU: return x <= 0.0f ? 0.0f : 1.0f;
+        case KV_BASE_TANH: {
+            const float t = kv_tanh(x);
+            return 1.0f - t * t;
+        }
+        default: return 1.0f;
+    }
+}
+template <int ACT>
+__device__ __forceinline__ float kv_base(float x, int act) {
+    if constexpr (ACT == KV_ACT_SILU) return kv_silu(x);
+    else return kv_base_dyn(x, act);
+}
+template <int ACT>
+__device__ __forceinline__ float kv_dbase(float x, int act) {
+    if constexpr (ACT == KV_ACT_SILU) return kv_dsilu(x);
+    else return kv_dbase_dyn(x, act);
+}
+
+// ---------------------------------------------------------------------------------------------
 // B-spline helpers.  Both run the Cox-de Boor recursion up to order-1, then finish the last
 // level producing values and (optionally) derivatives in one pass:
 //   dB_{j,p}/dx = p*(B_{j,p-1}/(t_{j+p}-t_j) - B_{j+1,p-1}/(t_{j+p+1}-t_{j+1}))
@@ -248,7 +308,7 @@ __device__ __forceinline__ float kv_bsel4(int j0, int jg, const float (&v)[4]) {
 // ---------------------------------------------------------------------------------------------
 // forward: write GP values for feature i (value xv; RBF spline path uses uv) to dst[j*stride]
 // ---------------------------------------------------------------------------------------------
-template <int FAM>
+template <int FAM, int ACT = KV_ACT_SILU>
 __device__ __forceinline__ void basis_fwd(const BasisArgs& b, float xv, float uv, int i, float* __restrict__ dst,
                                           int stride) {
     if constexpr (FAM == KV_LINEAR) {
@@ -288,13 +348,13 @@ __device__ __forceinline__ void basis_fwd(const BasisArgs& b, float xv, float uv
             kv_bspline_rt(kn, b.nk, b.order, xv, val, nullptr);
             for (int j = 0; j < b.G; ++j) dst[j * stride] = val[j];
         }
-        if (b.has_base) dst[b.G * stride] = kv_silu(xv);
+        if (b.has_base) dst[b.G * stride] = kv_base<ACT>(xv, b.act);
     } else if constexpr (FAM == KV_RBF) {
         for (int g = 0; g < b.G; ++g) {
             const float d = (uv - b.bp[g]) * b.inv_h;
             dst[g * stride] = __expf(-d * d);
         }
-        if (b.has_base) dst[b.G * stride] = kv_silu(xv);
+        if (b.has_base) dst[b.G * stride] = kv_base<ACT>(xv, b.act);
     } else if constexpr (FAM == KV_SINE) {
         const float* fr = b.bp;
         const float* ph = b.bp + b.G + (long long)i * b.G;
@@ -324,7 +384,7 @@ __device__ __forceinline__ float kv_wave_sum(float v) {
     return v;
 }
 
-template <int FAM>
+template <int FAM, int ACT = KV_ACT_SILU>
 __device__ __forceinline__ void basis_bwd(const BasisArgs& b, float xv, float uv, int i, bool valid,
                                           const float* __restrict__ dA, int stride, float& dx, float& du,
                                           float* __restrict__ dfreq_wave) {
@@ -366,7 +426,7 @@ __device__ __forceinline__ void basis_bwd(const BasisArgs& b, float xv, float uv
             kv_bspline_rt(kn, b.nk, b.order, xv, val, der);
             for (int j = 0; j < b.G; ++j) acc += dA[j * stride] * der[j];
         }
-        if (b.has_base) acc += dA[b.G * stride] * kv_dsilu(xv);
+        if (b.has_base) acc += dA[b.G * stride] * kv_dbase<ACT>(xv, b.act);
         dx = acc;
     } else if constexpr (FAM == KV_RBF) {
         float acc = 0.0f;
@@ -375,7 +435,7 @@ __device__ __forceinline__ void basis_bwd(const BasisArgs& b, float xv, float uv
             acc += dA[g * stride] * (__expf(-d * d) * (-2.0f * d * b.inv_h));
         }
         du = acc;
-        if (b.has_base) dx = dA[b.G * stride] * kv_dsilu(xv);
+        if (b.has_base) dx = dA[b.G * stride] * kv_dbase<ACT>(xv, b.act);
     } else if constexpr (FAM == KV_SINE) {
         const float* fr = b.bp;
         const float* ph = b.bp + b.G + (long long)i * b.G;
@@ -411,7 +471,7 @@ __device__ __forceinline__ void basis_bwd(const BasisArgs& b, float xv, float uv
 // conditional, so the compiler cannot speculate the parameter loads (knots, centres, frequencies, phases) out of it; left
 // in the loop they put an L1 round trip on the critical path of every step.
 // ---------------------------------------------------------------------------------------------
-template <int FAM, int GP, int J0C = -1>      // J0C >= 0: the window start is a compile-time constant (B-spline / RBF windows)
+template <int FAM, int GP, int J0C = -1, int ACT = KV_ACT_SILU>      // J0C >= 0: the window start is a compile-time constant (B-spline / RBF windows)
 struct BasisGenP {
     static constexpr bool SINE_ = (FAM == KV_SINE || FAM == KV_SINE_DF);
     static constexpr int NC0 = SINE_ ? GP : 1;         // RBF: only the first centre (uniform grid, kv_rbf8)
@@ -430,8 +490,10 @@ struct BasisGenP {
     int j0w;
     float s1, c1r, sk, ck;
     bool sin_half;
+    int act;
     __device__ __forceinline__ void prepare(const BasisArgs& b, int feat, int j0 = 0) {
         G = b.G;
+        act = b.act;
         inv_h = b.inv_h;
         j0w = j0;
         if constexpr (SINE_) {
@@ -489,12 +551,12 @@ struct BasisGenP {
         } else if constexpr (FAM == KV_BSPLINE) {
             const int jg = (J0C >= 0 ? J0C : j0w) + j;
             if (J0C >= 0 && jg > 8) return 0.0f;                  // idle slot of the last window (9 = 5 + 4)
-            if (jg >= (J0C >= 0 ? 8 : G)) return kv_silu(x);      // compile-time windows: G = 8 (GP = 9 with the silu column; host-checked)
+            if (jg >= (J0C >= 0 ? 8 : G)) return kv_base<ACT>(x, act);      // compile-time windows: G = 8 (GP = 9 with the base column; host-checked)
             return kv_bsel4(j0, jg, bv);
         } else if constexpr (FAM == KV_RBF) {
             const int jg = (J0C >= 0 ? J0C : j0w) + j;
             if (J0C >= 0 && jg > 8) return 0.0f;
-            if (jg >= (J0C >= 0 ? 8 : G)) return kv_silu(x);
+            if (jg >= (J0C >= 0 ? 8 : G)) return kv_base<ACT>(x, act);
             return kv_sel8(pr, jg);            // compile-time jg: the unused Gaussians of a window are never computed (dead code)
         } else if constexpr (FAM == KV_FOURIER) {
             const float v = sin_half ? sk : ck;
@@ -543,7 +605,7 @@ __device__ __forceinline__ void basis_bwd_sine_reg(const BasisArgs& b, float xv,
 constexpr int kv_gc(int fam, int gp) {
     return gp <= 0 ? -1 : (fam == KV_RBF || fam == KV_BSPLINE) ? gp - 1 : (fam == KV_FOURIER ? gp / 2 : (fam == KV_SINE ? gp : -1));
 }
-template <int FAM, int GC = -1>
+template <int FAM, int GC = -1, int ACT = KV_ACT_SILU>
 struct BasisGen {
     __device__ __forceinline__ int gcount() const { return GC >= 0 ? GC : G; }
     float x, u, t, p0, p1, c1, s1, ck, sk;
@@ -553,12 +615,13 @@ struct BasisGen {
     bool in;
     const float* bp;
     float inv_h;
-    int has_base;
+    int has_base, act;
 
     __device__ __forceinline__ void init(const BasisArgs& b, float xv, float uv, int feat) {
         x = xv;
         u = uv;
         G = b.G;
+        act = b.act;
         i = feat;
         bp = b.bp;
         inv_h = b.inv_h;
@@ -589,10 +652,10 @@ struct BasisGen {
             p1 = p2;
             return p2;
         } else if constexpr (FAM == KV_BSPLINE) {
-            if (j >= gcount()) return kv_silu(x);
+            if (j >= gcount()) return kv_base<ACT>(x, act);
             return kv_bsel4(j0, j, bv);
         } else if constexpr (FAM == KV_RBF) {
-            if (j >= gcount()) return kv_silu(x);
+            if (j >= gcount()) return kv_base<ACT>(x, act);
             return kv_sel8(pr, j);
         } else if constexpr (FAM == KV_SINE) {
             return kv_sin(__fadd_rn(__fmul_rn(x, bp[j]), bp[gcount() + (long long)i * gcount() + j]));
@@ -612,20 +675,21 @@ struct BasisGen {
 };
 
 
-// Derivative generator: next(j) = d phi_j / d(input) for j = 0 .. GP-1 in order (RBF: d/du for j < G, d silu/dx for j = G).
-template <int FAM, int GC = -1>
+// Derivative generator: next(j) = d phi_j / d(input) for j = 0 .. GP-1 in order (RBF: d/du for j < G, d base/dx for j = G).
+template <int FAM, int GC = -1, int ACT = KV_ACT_SILU>
 struct BasisDGen {
     __device__ __forceinline__ int gcount() const { return GC >= 0 ? GC : G; }
     float x, u, t, sech2, u0, u1, c1, s1, ck, sk, inv_h;
     float pr[(FAM == KV_RBF) ? 8 : 1];
     float lastc;   // SINE: cos(x f_j + p_ij) of the last next() (the caller needs it for d loss / d freq)
     float dv[4];
-    int j0, G, i;
+    int j0, G, i, act;
     bool in;
     const float* bp;
 
     __device__ __forceinline__ void init(const BasisArgs& b, float xv, float uv, int feat) {
         i = feat;
+        act = b.act;
         x = xv;
         u = uv;
         G = b.G;
@@ -662,10 +726,10 @@ struct BasisDGen {
             u1 = u2;
             return r;
         } else if constexpr (FAM == KV_BSPLINE) {
-            if (j >= gcount()) return kv_dsilu(x);
+            if (j >= gcount()) return kv_dbase<ACT>(x, act);
             return kv_bsel4(j0, j, dv);
         } else if constexpr (FAM == KV_RBF) {
-            if (j >= gcount()) return kv_dsilu(x);
+            if (j >= gcount()) return kv_dbase<ACT>(x, act);
             return kv_sel8(pr, j) * (-2.0f * (t - (float)j) * inv_h);
         } else if constexpr (FAM == KV_SINE) {      // d sin(x f + p)/dx = f cos(x f + p)
             const float f = bp[j];
@@ -687,3 +751,29 @@ struct BasisDGen {
         }
     }
 };
+
+// ---------------------------------------------------------------------------------------------
+// Launch of a kernel K<TARGS> that exists in two instantiations of one body: the SiLU kernel K (the base column of every
+// family that has one is silu(x): KV_ACT_SILU) and, for BSPLINE / RBF with another base activation, its KV_ACT_DYN twin KA
+// (the *_act_* kernels, which read the activation code from the launch arguments).  The twin is instantiated for those two
+// families only; every launch of a BSPLINE / RBF kernel goes through these macros, so no route can run the SiLU code for a
+// descriptor that asks for another activation.
+// ---------------------------------------------------------------------------------------------
+constexpr bool kv_act_fam(int fam) { return fam == KV_BSPLINE || fam == KV_RBF; }
+#define KV_UNPAREN(...) __VA_ARGS__
+#define KV_ACT_LAUNCH(FAMX, ACTC, K, KA, TARGS, ...)                                    \
+    do {                                                                                \
+        if (kv_act_fam(FAMX) && (ACTC) != 0) {                                          \
+            if constexpr (kv_act_fam(FAMX)) hipLaunchKernelGGL((KA<KV_UNPAREN TARGS>), __VA_ARGS__); \
+        } else {                                                                        \
+            hipLaunchKernelGGL((K<KV_UNPAREN TARGS>), __VA_ARGS__);                     \
+        }                                                                               \
+    } while (0)
+#define KV_ACT_ALLOW_LDS(FAMX, ACTC, bytes, K, KA, TARGS)                               \
+    do {                                                                                \
+        if (kv_act_fam(FAMX) && (ACTC) != 0) {                                          \
+            if constexpr (kv_act_fam(FAMX)) KV_ALLOW_LDS(bytes, (KA<KV_UNPAREN TARGS>)); \
+        } else {                                                                        \
+            KV_ALLOW_LDS(bytes, (K<KV_UNPAREN TARGS>));                                 \
+        }                                                                               \
+    } while (0)

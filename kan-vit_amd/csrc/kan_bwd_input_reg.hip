@@ -23,8 +23,8 @@ constexpr int kv_bwi_kt(int fam, int gp, int kt) { return ((16 * kt) / gp * (gp 
 // CHEBY: dT0/dx = 0, so the T0 slots are left out of the permutation -- slot q <-> (feature q / (GP-1), basis index q % (GP-1) + 1) --
 // and KT = 5 accumulators become kv_bwi_kt = 4 (the template keeps KT = 5: FPH = 16 features per half either way).  Every dPhi value
 // is the same contraction as before, only in another accumulator slot: dx is bitwise unchanged.
-template <int FAM, int GP, int KT, bool SHARED>
-__global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2) void kan_bwd_input_reg_kernel(const LayerArgs a) {
+template <int FAM, int GP, int KT, bool SHARED, int ACT>
+__device__ __forceinline__ void kan_bwd_input_reg_kbody(const LayerArgs& a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int G0 = kv_bwi_g0(FAM), GPE = GP - G0;
     constexpr int KTE = kv_bwi_kt(FAM, GP, KT);   // accumulators actually contracted
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2)
             }
 #pragma unroll
             for (int j = 0; j < FPH; ++j) {
-                BasisDGen<FAM, kv_gc(FAM, GP)> gen;
+                BasisDGen<FAM, kv_gc(FAM, GP), ACT> gen;
                 gen.init(b, xv[j], RBF ? uvv[j] : 0.0f, ci * IC + hf * FPH + j);
                 float dsum = 0.0f, usum = 0.0f;
 #pragma unroll
@@ -290,6 +290,15 @@ __global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2)
         }
     }
 }
+template <int FAM, int GP, int KT, bool SHARED>
+__global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2) void kan_bwd_input_reg_kernel(const LayerArgs a) {
+    kan_bwd_input_reg_kbody<FAM, GP, KT, SHARED, KV_ACT_SILU>(a);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int GP, int KT, bool SHARED>
+__global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2) void kan_bwd_input_reg_act_kernel(const LayerArgs a) {
+    kan_bwd_input_reg_kbody<FAM, GP, KT, SHARED, KV_ACT_DYN>(a);
+}
 
 // ---- register-form input gradient (fp32 exact) ---------------------------------------------------
 template <int FAM, int GP, int KT>
@@ -313,12 +322,12 @@ int launch_bwd_input_reg(const LayerArgs& a0, hipStream_t st) {
     dim3 grid((unsigned)a.xmod, (unsigned)(t1 + nci * (tiles - t1)), 1);
     if (shared) {
         if constexpr (kv_shared_basis<FAM>()) {
-            hipLaunchKernelGGL((kan_bwd_input_reg_kernel<FAM, GP, KT, true>), grid, dim3(256), lds, st, a);
+            KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_kernel, kan_bwd_input_reg_act_kernel, (FAM, GP, KT, true), grid, dim3(256), lds, st, a);
             KV_LAUNCH_CHECK("kan_bwd_input_reg_kernel");
             return 0;
         }
     }
-    hipLaunchKernelGGL((kan_bwd_input_reg_kernel<FAM, GP, KT, false>), grid, dim3(256), lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_kernel, kan_bwd_input_reg_act_kernel, (FAM, GP, KT, false), grid, dim3(256), lds, st, a);
     KV_LAUNCH_CHECK("kan_bwd_input_reg_kernel");
     return 0;
 }

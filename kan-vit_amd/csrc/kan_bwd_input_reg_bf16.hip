@@ -39,8 +39,8 @@ __global__ __launch_bounds__(256) void kan_pack_w_bwd_reg_kernel(const float* __
     *reinterpret_cast<u32x4*>(wb2 + e * 8) = out;
 }
 
-template <int FAM, int GP, int KT, bool SHARED>
-__global__ __launch_bounds__(256, FAM == KV_SINE ? 1 : 2) void kan_bwd_input_reg_bf16_kernel(const LayerArgs a) {
+template <int FAM, int GP, int KT, bool SHARED, int ACT>
+__device__ __forceinline__ void kan_bwd_input_reg_bf16_kbody(const LayerArgs& a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int KCT = 32 * KT;
     constexpr int FPH = (16 * KT) / GP;
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256, FAM == KV_SINE ? 1 : 2) void kan_bwd_input_reg
             }
 #pragma unroll
             for (int j = 0; j < FPH; ++j) {
-                BasisDGen<FAM, kv_gc(FAM, GP)> gen;
+                BasisDGen<FAM, kv_gc(FAM, GP), ACT> gen;
                 gen.init(b, xv[j], RBF ? uvv[j] : 0.0f, ci * IC + hf * FPH + j);
                 float dsum = 0.0f, usum = 0.0f;
 #pragma unroll
@@ -260,6 +260,15 @@ __global__ __launch_bounds__(256, FAM == KV_SINE ? 1 : 2) void kan_bwd_input_reg
         }
     }
 }
+template <int FAM, int GP, int KT, bool SHARED>
+__global__ __launch_bounds__(256, FAM == KV_SINE ? 1 : 2) void kan_bwd_input_reg_bf16_kernel(const LayerArgs a) {
+    kan_bwd_input_reg_bf16_kbody<FAM, GP, KT, SHARED, KV_ACT_SILU>(a);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int GP, int KT, bool SHARED>
+__global__ __launch_bounds__(256, FAM == KV_SINE ? 1 : 2) void kan_bwd_input_reg_bf16_act_kernel(const LayerArgs a) {
+    kan_bwd_input_reg_bf16_kbody<FAM, GP, KT, SHARED, KV_ACT_DYN>(a);
+}
 
 // =============================================================================================
 // The same kernel with the dY of its row tile RESIDENT (round 4), for the per-head layers (O = 64, at most three groups sharing x).
@@ -270,8 +279,8 @@ __global__ __launch_bounds__(256, FAM == KV_SINE ? 1 : 2) void kan_bwd_input_reg
 // three step images, two steps ahead (no staging registers, no ds_write, one barrier per step); the next chunk's x a chunk ahead;
 // the other work-group of the CU covers the prologue.  Same operands, same roundings, same order of the sums as the kernel above: bitwise the same dx.
 // =============================================================================================
-template <int FAM, int GP, int KT, int NSH, bool SHARED>
-__global__ __launch_bounds__(256, 2) void kan_bwd_input_res_bf16_kernel(const LayerArgs a) {
+template <int FAM, int GP, int KT, int NSH, bool SHARED, int ACT>
+__device__ __forceinline__ void kan_bwd_input_res_bf16_kbody(const LayerArgs& a) {
     static_assert(FAM != KV_SINE, "SineKAN keeps the streaming kernel (its d freq partials)");
     static_assert(NSH == 1 || NSH == 3, "one group, or q|k|v");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -497,7 +506,7 @@ __global__ __launch_bounds__(256, 2) void kan_bwd_input_res_bf16_kernel(const La
                 }
 #pragma unroll
                 for (int j = 0; j < FPH; ++j) {
-                    BasisDGen<FAM, kv_gc(FAM, GP)> gen;
+                    BasisDGen<FAM, kv_gc(FAM, GP), ACT> gen;
                     gen.init(b, xv[j], RBF ? uvv[j] : 0.0f, ci * IC + hf * FPH + j);
                     float dsum = 0.0f, usum = 0.0f;
 #pragma unroll
@@ -542,6 +551,17 @@ __global__ __launch_bounds__(256, 2) void kan_bwd_input_res_bf16_kernel(const La
         }
     }
 }
+template <int FAM, int GP, int KT, int NSH, bool SHARED>
+__global__ __launch_bounds__(256, 2) void kan_bwd_input_res_bf16_kernel(const LayerArgs a) {
+    kan_bwd_input_res_bf16_kbody<FAM, GP, KT, NSH, SHARED, KV_ACT_SILU>(a);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments).  One work-group per CU:
+// the activation's derivative does not fit the 256-register budget of two, and this kernel's explicit vmcnt waits must not
+// share the counter with scratch spills
+template <int FAM, int GP, int KT, int NSH, bool SHARED>
+__global__ __launch_bounds__(256, 1) void kan_bwd_input_res_bf16_act_kernel(const LayerArgs a) {
+    kan_bwd_input_res_bf16_kbody<FAM, GP, KT, NSH, SHARED, KV_ACT_DYN>(a);
+}
 
 template <int FAM, int GP, int KT>
 int launch_bwd_input_reg_bf16(LayerArgs& a, const BwdRegBf16Plan& p, hipStream_t st) {
@@ -558,7 +578,7 @@ int launch_bwd_input_reg_bf16(LayerArgs& a, const BwdRegBf16Plan& p, hipStream_t
         v.O = 64;
         v.vcols = 1;
         dim3 vgrid(1, (unsigned)((a.M + BM - 1) / BM), 1);
-        hipLaunchKernelGGL((kan_bwd_input_reg_bf16_kernel<FAM, GP, KT, true>), vgrid, dim3(256), p.lds, st, v);
+        KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_bf16_kernel, kan_bwd_input_reg_bf16_act_kernel, (FAM, GP, KT, true), vgrid, dim3(256), p.lds, st, v);
         KV_LAUNCH_CHECK("kan_bwd_input_reg_bf16_kernel");
         return 0;
     }
@@ -577,21 +597,21 @@ int launch_bwd_input_reg_bf16(LayerArgs& a, const BwdRegBf16Plan& p, hipStream_t
             constexpr int IC_ = 2 * ((16 * KT) / GP);
             const size_t lds3 = (size_t)3 * 4 * 2 * 32 * KT * 16 + sizeof(float) * 4 * 32 * (IC_ + 4);      // a ring of three W step images + four store strips
             if (nshare == 1) {
-                KV_ALLOW_LDS(160 * 1024, (kan_bwd_input_res_bf16_kernel<FAM, GP, KT, 1, false>));
-                hipLaunchKernelGGL((kan_bwd_input_res_bf16_kernel<FAM, GP, KT, 1, false>), grid, dim3(256), lds3, st, a);
+                KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 1, false));
+                KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 1, false), grid, dim3(256), lds3, st, a);
                 KV_LAUNCH_CHECK("kan_bwd_input_res_bf16_kernel");
                 return 0;
             }
             if (shared) {
                 if constexpr (kv_shared_basis<FAM>()) {
-                    KV_ALLOW_LDS(160 * 1024, (kan_bwd_input_res_bf16_kernel<FAM, GP, KT, 3, true>));
-                    hipLaunchKernelGGL((kan_bwd_input_res_bf16_kernel<FAM, GP, KT, 3, true>), grid, dim3(256), lds3, st, a);
+                    KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 3, true));
+                    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 3, true), grid, dim3(256), lds3, st, a);
                     KV_LAUNCH_CHECK("kan_bwd_input_res_bf16_kernel");
                     return 0;
                 }
             } else {
-                KV_ALLOW_LDS(160 * 1024, (kan_bwd_input_res_bf16_kernel<FAM, GP, KT, 3, false>));
-                hipLaunchKernelGGL((kan_bwd_input_res_bf16_kernel<FAM, GP, KT, 3, false>), grid, dim3(256), lds3, st, a);
+                KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 3, false));
+                KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 3, false), grid, dim3(256), lds3, st, a);
                 KV_LAUNCH_CHECK("kan_bwd_input_res_bf16_kernel");
                 return 0;
             }
@@ -599,12 +619,12 @@ int launch_bwd_input_reg_bf16(LayerArgs& a, const BwdRegBf16Plan& p, hipStream_t
     }
     if (shared) {
         if constexpr (kv_shared_basis<FAM>()) {
-            hipLaunchKernelGGL((kan_bwd_input_reg_bf16_kernel<FAM, GP, KT, true>), grid, dim3(256), p.lds, st, a);
+            KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_bf16_kernel, kan_bwd_input_reg_bf16_act_kernel, (FAM, GP, KT, true), grid, dim3(256), p.lds, st, a);
             KV_LAUNCH_CHECK("kan_bwd_input_reg_bf16_kernel");
             return 0;
         }
     }
-    hipLaunchKernelGGL((kan_bwd_input_reg_bf16_kernel<FAM, GP, KT, false>), grid, dim3(256), p.lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_bf16_kernel, kan_bwd_input_reg_bf16_act_kernel, (FAM, GP, KT, false), grid, dim3(256), p.lds, st, a);
     KV_LAUNCH_CHECK("kan_bwd_input_reg_bf16_kernel");
     return 0;
 }

@@ -28,9 +28,8 @@ __device__ __forceinline__ void kv_static_for(F&& f) {
 // =============================================================================================
 // PG (kanvit_patch_embed_bwd_weight): the rows of x are patches of an NCHW image batch and dY carries the class-token rows
 // (PatchWalk, kan_layer_common.h) -- no transient [B*P, I] patch matrix, no copy of dY without its class-token rows.
-template <int FAM, int GP, int NOT, bool BF, int JC = GP, bool PG = false>
-__global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs a, int nfb, int nos, int tiles_per_bg,
-                                                                 int shared, int nbg) {
+template <int FAM, int GP, int NOT, bool BF, int JC, bool PG, int ACT>
+__device__ __forceinline__ void kan_bwd_weight_reg_kbody(const LayerArgs& a, int nfb, int nos, int tiles_per_bg, int shared, int nbg) {
     static_assert(!(PG && FAM == KV_RBF), "FastKAN's patch embedding reads u = LayerNorm(x): no gather form");
     static_assert(!(PG && BF), "the gather form is exact fp32 (bf16 MFMA phases are too short to hide the row walker: launch_bwd_weight_reg)");
     constexpr int NJC = (GP + JC - 1) / JC;       // wide bases (G = 28) are contracted in NJC windows of JC basis functions,
@@ -92,7 +91,7 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs
     constexpr int J0C = decltype(j0c)::value;
     const int g0 = bg;                 // basis parameters: identical for every group of a shared launch
     const BasisArgs b = make_basis(a, g0);
-    BasisGenP<FAM, JC, J0C> proto;          // knots / centres / frequencies / phases of this lane's feature, loaded once
+    BasisGenP<FAM, JC, J0C, ACT> proto;          // knots / centres / frequencies / phases of this lane's feature, loaded once
     proto.prepare(b, f, j0);
 
     // Addressing: wave-uniform 64-bit bases (start of this slab) + 32-bit per-lane offsets, so that a load costs one or two
@@ -250,7 +249,7 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs
                     for (int t = 0; t < NTOK; ++t) {
                         walk_fill(2 * t);                      // (patch gather) two rows of the next block per MFMA group
                         walk_fill(2 * t + 1);
-                        BasisGenP<FAM, JC, J0C> gen = proto;
+                        BasisGenP<FAM, JC, J0C, ACT> gen = proto;
                         gen.init(cx[t], RBF ? cu[t] : 0.0f);
 #pragma unroll
                         for (int j = 0; j < JC; ++j) {
@@ -269,7 +268,7 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs
                     unsigned af[JC][4];
 #pragma unroll
                     for (int ep = 0; ep < 4; ++ep) {
-                        BasisGenP<FAM, JC, J0C> g0_ = proto, g1_ = proto;
+                        BasisGenP<FAM, JC, J0C, ACT> g0_ = proto, g1_ = proto;
                         g0_.init(cx[2 * ep], RBF ? cu[2 * ep] : 0.0f);
                         g1_.init(cx[2 * ep + 1], RBF ? cu[2 * ep + 1] : 0.0f);
 #pragma unroll
@@ -334,7 +333,7 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs
         if constexpr (!BF) {
 #pragma unroll
             for (int t = 0; t < NTOK; ++t) {
-                BasisGenP<FAM, JC, J0C> gen = proto;
+                BasisGenP<FAM, JC, J0C, ACT> gen = proto;
                 gen.init(cx[t], RBF ? cu[t] : 0.0f);
 #pragma unroll
                 for (int j = 0; j < JC; ++j) {
@@ -353,7 +352,7 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs
             unsigned af[JC][4];
 #pragma unroll
             for (int ep = 0; ep < 4; ++ep) {
-                BasisGenP<FAM, JC, J0C> g0_ = proto, g1_ = proto;
+                BasisGenP<FAM, JC, J0C, ACT> g0_ = proto, g1_ = proto;
                 g0_.init(cx[2 * ep], RBF ? cu[2 * ep] : 0.0f);
                 g1_.init(cx[2 * ep + 1], RBF ? cu[2 * ep + 1] : 0.0f);
 #pragma unroll
@@ -425,6 +424,17 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs
         run(std::integral_constant<int, -1>{});
     }
 }
+template <int FAM, int GP, int NOT, bool BF, int JC = GP, bool PG = false>
+__global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs a, int nfb, int nos, int tiles_per_bg,
+                                                                 int shared, int nbg) {
+    kan_bwd_weight_reg_kbody<FAM, GP, NOT, BF, JC, PG, KV_ACT_SILU>(a, nfb, nos, tiles_per_bg, shared, nbg);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int GP, int NOT, bool BF, int JC = GP, bool PG = false>
+__global__ __launch_bounds__(256) void kan_bwd_weight_reg_act_kernel(const LayerArgs a, int nfb, int nos, int tiles_per_bg,
+                                                                 int shared, int nbg) {
+    kan_bwd_weight_reg_kbody<FAM, GP, NOT, BF, JC, PG, KV_ACT_DYN>(a, nfb, nos, tiles_per_bg, shared, nbg);
+}
 
 // =============================================================================================
 // The same streaming weight gradient on 16-ROW tiles (exact fp32, v_mfma_f32_16x16x4_f32), for the GP = 9 B-spline basis.
@@ -446,8 +456,8 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_reg_kernel(const LayerArgs
 // evaluation is a minority of them, and the twelve dY streams add more ring moves and selects than the halved evaluations remove.  Five
 // values x SIX tiles of 16 at two waves per SIMD -- the same work per evaluation as the 32-row form, a partner wave to cover the
 // latencies -- was measured too: 372-374 against 360-364 us, same box.)
-template <int FAM, int GP, int JC, int NC>
-__global__ __launch_bounds__(256, 2) void kan_bwd_weight_reg16_kernel(const LayerArgs a, int nfb, int nos, int tiles_per_bg, int shared, int nbg) {
+template <int FAM, int GP, int JC, int NC, int ACT>
+__device__ __forceinline__ void kan_bwd_weight_reg16_kbody(const LayerArgs& a, int nfb, int nos, int tiles_per_bg, int shared, int nbg) {
     constexpr int NJC = (GP + JC - 1) / JC;
     static_assert(GP % JC == 0 && (NJC == 3 || NJC == 1), "whole windows: three of three values (B-spline) or all nine (FastKAN)");
     constexpr bool RBF = (FAM == KV_RBF);
@@ -501,7 +511,7 @@ __global__ __launch_bounds__(256, 2) void kan_bwd_weight_reg16_kernel(const Laye
 
     auto run = [&](auto j0c) {
         constexpr int J0C = decltype(j0c)::value;
-        BasisGenP<FAM, JC, J0C> proto;
+        BasisGenP<FAM, JC, J0C, ACT> proto;
         proto.prepare(b, f, J0C);
         f32x4 acc[JC][NC];
 #pragma unroll
@@ -554,7 +564,7 @@ __global__ __launch_bounds__(256, 2) void kan_bwd_weight_reg16_kernel(const Laye
             if constexpr (REFILL) load_block(q, blk + PD);
 #pragma unroll
             for (int t = 0; t < UB; ++t) {
-                BasisGenP<FAM, JC, J0C> gen = proto;
+                BasisGenP<FAM, JC, J0C, ACT> gen = proto;
                 gen.init(cx[t], cu[t]);
 #pragma unroll
                 for (int j = 0; j < JC; ++j) {
@@ -587,6 +597,15 @@ __global__ __launch_bounds__(256, 2) void kan_bwd_weight_reg16_kernel(const Laye
         else run(std::integral_constant<int, 2 * JC>{});
     }
 }
+template <int FAM, int GP, int JC, int NC>
+__global__ __launch_bounds__(256, 2) void kan_bwd_weight_reg16_kernel(const LayerArgs a, int nfb, int nos, int tiles_per_bg, int shared, int nbg) {
+    kan_bwd_weight_reg16_kbody<FAM, GP, JC, NC, KV_ACT_SILU>(a, nfb, nos, tiles_per_bg, shared, nbg);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int GP, int JC, int NC>
+__global__ __launch_bounds__(256, 2) void kan_bwd_weight_reg16_act_kernel(const LayerArgs a, int nfb, int nos, int tiles_per_bg, int shared, int nbg) {
+    kan_bwd_weight_reg16_kbody<FAM, GP, JC, NC, KV_ACT_DYN>(a, nfb, nos, tiles_per_bg, shared, nbg);
+}
 
 // ordered sum of the msplit partial slabs (deterministic; no float atomics)
 __global__ __launch_bounds__(256) void kan_slab_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dw,
@@ -612,8 +631,8 @@ int launch_bwd_weight_reg_one(LayerArgs& a, const BwRegPlan& p, hipStream_t st) 
     const long long units = (long long)p.nbg * p.nfb * p.nos * p.njc;
     dim3 grid((unsigned)((units * p.slabs + 3) / 4), 1, 1);
     const size_t lds = a.ln ? (size_t)4 * p.rows_per_slab * sizeof(float2) : 0;      // four wave-private (mean, rstd) strips
-    if (lds > 64 * 1024) KV_ALLOW_LDS(160 * 1024, (kan_bwd_weight_reg_kernel<FAM, GP, NOT, BF, JC, PG>));
-    hipLaunchKernelGGL((kan_bwd_weight_reg_kernel<FAM, GP, NOT, BF, JC, PG>), grid, dim3(256), lds, st, a, p.nfb, p.nos, p.tiles_per_bg, p.shared, p.nbg);
+    if (lds > 64 * 1024) KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_bwd_weight_reg_kernel, kan_bwd_weight_reg_act_kernel, (FAM, GP, NOT, BF, JC, PG));
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_weight_reg_kernel, kan_bwd_weight_reg_act_kernel, (FAM, GP, NOT, BF, JC, PG), grid, dim3(256), lds, st, a, p.nfb, p.nos, p.tiles_per_bg, p.shared, p.nbg);
     KV_LAUNCH_CHECK("kan_bwd_weight_reg_kernel");
     return 0;
 }
@@ -641,7 +660,7 @@ int launch_bwd_weight_reg16(LayerArgs& a, const BwRegPlan& p, hipStream_t st) {
     const long long units = (long long)p.nbg * p.nfb * p.nos * p.njc;
     dim3 grid((unsigned)((units * p.slabs + 3) / 4), 1, 1);
     if (a.pg) return kv_fail(KANVIT_EINVAL, "internal: the 16-row weight-gradient kernel has no patch-gather form");
-    hipLaunchKernelGGL((kan_bwd_weight_reg16_kernel<FAM, GP, JC, NC>), grid, dim3(256), 0, st, a, p.nfb, p.nos, p.tiles_per_bg, p.shared, p.nbg);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_weight_reg16_kernel, kan_bwd_weight_reg16_act_kernel, (FAM, GP, JC, NC), grid, dim3(256), 0, st, a, p.nfb, p.nos, p.tiles_per_bg, p.shared, p.nbg);
     KV_LAUNCH_CHECK("kan_bwd_weight_reg16_kernel");
     return 0;
 }

@@ -22,7 +22,7 @@ namespace {
 // pipe idle for most of that on every second MFMA (59 % busy in the PMC pass).  GPC == 0 keeps the runtime-GP loop.
 // The body takes its block coordinates as arguments: the kernel below hands the LAST row tiles of a shared-basis (NSH = 3) launch
 // to the NSH = 1 body, one projection per work-group (kv_tail_first_tile).
-template <int FAM, int NT, int NSH, int ICH, int GPC>
+template <int FAM, int NT, int NSH, int ICH, int GPC, int ACT>
 __device__ __forceinline__ void kan_fwd_reg_body(const LayerArgs& a, float* __restrict__ smem, const int bx, const int by) {
     constexpr int BN = 32 * NT;
     constexpr int WROW = NSH * BN;
@@ -232,7 +232,7 @@ __device__ __forceinline__ void kan_fwd_reg_body(const LayerArgs& a, float* __re
             float phi[VH];
 #pragma unroll
             for (int j = 0; j < ICH; ++j) {
-                BasisGen<FAM, kv_gc(FAM, GPC)> gen;       // compile-time G: one silu per feature, no branch per value (host-checked has_base)
+                BasisGen<FAM, kv_gc(FAM, GPC), ACT> gen;       // compile-time G: one base activation per feature, no branch per value (host-checked has_base)
                 gen.init(b, xc[j], uc[j], c * IC + hf * ICH + j);
 #pragma unroll
                 for (int g = 0; g < GPC; ++g) {
@@ -261,7 +261,7 @@ __device__ __forceinline__ void kan_fwd_reg_body(const LayerArgs& a, float* __re
         } else {
 #pragma unroll
         for (int j = 0; j < ICH; ++j) {
-            BasisGen<FAM> gen;
+            BasisGen<FAM, -1, ACT> gen;
             gen.init(b, xc[j], uc[j], c * IC + hf * ICH + j);
             const float* wj = wp + (2 * j * GP) * WROW;
             for (int g = 0; g < GP; ++g) {
@@ -318,19 +318,28 @@ __device__ __forceinline__ void kan_fwd_reg_body(const LayerArgs& a, float* __re
 
 // TAIL (NSH = 3 only): grid rows [tail_y0, ...) are the sub-divided end of the launch -- row tile tail_y0 + t / 3, projection t % 3,
 // run by the one-projection body (it re-evaluates the basis; same k order per output, so the results are bitwise the shared ones).
-template <int FAM, int NT, int NSH, int ICH, int GPC = 0, bool TAIL = false>
-__global__ __launch_bounds__(256, GPC ? 2 : 1) void kan_fwd_reg_kernel(const LayerArgs a) {
+template <int FAM, int NT, int NSH, int ICH, int GPC, bool TAIL, int ACT>
+__device__ __forceinline__ void kan_fwd_reg_kbody(const LayerArgs& a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if constexpr (TAIL) {
         static_assert(NSH == 3, "the tail hands single projections of a shared-basis launch to the NSH = 1 body");
         const int ty = (int)blockIdx.y - a.tail_y0;
         if (ty >= 0) {
             const int tile = ty / 3, proj = ty - 3 * tile;
-            kan_fwd_reg_body<FAM, NT, 1, ICH, GPC>(a, smem, proj * (int)gridDim.x + (int)blockIdx.x, a.tail_y0 + tile);
+            kan_fwd_reg_body<FAM, NT, 1, ICH, GPC, ACT>(a, smem, proj * (int)gridDim.x + (int)blockIdx.x, a.tail_y0 + tile);
             return;
         }
     }
-    kan_fwd_reg_body<FAM, NT, NSH, ICH, GPC>(a, smem, (int)blockIdx.x, (int)blockIdx.y);
+    kan_fwd_reg_body<FAM, NT, NSH, ICH, GPC, ACT>(a, smem, (int)blockIdx.x, (int)blockIdx.y);
+}
+template <int FAM, int NT, int NSH, int ICH, int GPC = 0, bool TAIL = false>
+__global__ __launch_bounds__(256, GPC ? 2 : 1) void kan_fwd_reg_kernel(const LayerArgs a) {
+    kan_fwd_reg_kbody<FAM, NT, NSH, ICH, GPC, TAIL, KV_ACT_SILU>(a);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int NT, int NSH, int ICH, int GPC = 0, bool TAIL = false>
+__global__ __launch_bounds__(256, GPC ? 2 : 1) void kan_fwd_reg_act_kernel(const LayerArgs a) {
+    kan_fwd_reg_kbody<FAM, NT, NSH, ICH, GPC, TAIL, KV_ACT_DYN>(a);
 }
 
 // ---- register-operand forward (fp32 exact) --------------------------------------------------------
@@ -343,17 +352,17 @@ int launch_fwd_reg(const LayerArgs& a0, size_t lds, hipStream_t st) {
         if (t1 < tiles) {
             LayerArgs a = a0;
             a.tail_y0 = t1;
-            KV_ALLOW_LDS(160 * 1024, (kan_fwd_reg_kernel<FAM, NT, NSH, ICH, GPC, true>));
+            KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_fwd_reg_kernel, kan_fwd_reg_act_kernel, (FAM, NT, NSH, ICH, GPC, true));
             dim3 grid(gx, (unsigned)(t1 + 3 * (tiles - t1)), 1);
-            hipLaunchKernelGGL((kan_fwd_reg_kernel<FAM, NT, NSH, ICH, GPC, true>), grid, dim3(256), lds, st, a);
+            KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_reg_kernel, kan_fwd_reg_act_kernel, (FAM, NT, NSH, ICH, GPC, true), grid, dim3(256), lds, st, a);
             KV_LAUNCH_CHECK("kan_fwd_reg_kernel");
             return 0;
         }
     }
     const LayerArgs& a = a0;
-    KV_ALLOW_LDS(160 * 1024, (kan_fwd_reg_kernel<FAM, NT, NSH, ICH, GPC>));
+    KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_fwd_reg_kernel, kan_fwd_reg_act_kernel, (FAM, NT, NSH, ICH, GPC));
     dim3 grid(gx, (unsigned)tiles, 1);
-    hipLaunchKernelGGL((kan_fwd_reg_kernel<FAM, NT, NSH, ICH, GPC>), grid, dim3(256), lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_reg_kernel, kan_fwd_reg_act_kernel, (FAM, NT, NSH, ICH, GPC), grid, dim3(256), lds, st, a);
     KV_LAUNCH_CHECK("kan_fwd_reg_kernel");
     return 0;
 }

@@ -37,8 +37,8 @@ __global__ __launch_bounds__(256) void kan_pack_w_fwd_reg_kernel(const float* __
 
 // PG (kanvit_patch_embed_fwd_ws): rows gathered from the NCHW images, position embedding added and class-token rows written
 // in the epilogue -- the prologue / epilogue of kan_fwd_reg_kernel's patch form on the bf16 matrix cores.
-template <int FAM, int GP, int NT, int NSH, int ICH, bool PG = false>
-__global__ __launch_bounds__(256) void kan_fwd_reg_bf16_kernel(const LayerArgs a) {
+template <int FAM, int GP, int NT, int NSH, int ICH, bool PG, int ACT>
+__device__ __forceinline__ void kan_fwd_reg_bf16_kbody(const LayerArgs& a) {
     static_assert(!(PG && (FAM == KV_RBF || NSH != 1)), "patch gather: one plain layer, no LayerNorm'ed second input");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int BN = 32 * NT;
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void kan_fwd_reg_bf16_kernel(const LayerArgs a
             load_ph(c + 1);
         }
         const unsigned short* wp = W_s + (size_t)(c & 1) * WSZ + ((size_t)hf * WROW + l31) * 8;
-        BasisGen<FAM, kv_gc(FAM, GP)> gen;
+        BasisGen<FAM, kv_gc(FAM, GP), ACT> gen;
 #pragma unroll
         for (int ks = 0; ks < VS; ++ks) {
             float av[8];
@@ -290,6 +290,15 @@ __global__ __launch_bounds__(256) void kan_fwd_reg_bf16_kernel(const LayerArgs a
             }
         }
     }
+}
+template <int FAM, int GP, int NT, int NSH, int ICH, bool PG = false>
+__global__ __launch_bounds__(256) void kan_fwd_reg_bf16_kernel(const LayerArgs a) {
+    kan_fwd_reg_bf16_kbody<FAM, GP, NT, NSH, ICH, PG, KV_ACT_SILU>(a);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int GP, int NT, int NSH, int ICH, bool PG = false>
+__global__ __launch_bounds__(256) void kan_fwd_reg_bf16_act_kernel(const LayerArgs a) {
+    kan_fwd_reg_bf16_kbody<FAM, GP, NT, NSH, ICH, PG, KV_ACT_DYN>(a);
 }
 
 // =============================================================================================
@@ -520,15 +529,15 @@ int launch_fwd_reg_bf16(const LayerArgs& a, const FwdRegBf16Plan& p, hipStream_t
     dim3 grid((unsigned)((a.groups / NSH) * (a.O / (32 * NT))), (unsigned)((a.M + BM - 1) / BM), 1);
     if (a.pg) {         // fused patch embedding: one wide layer (NT = 4), the families whose patch embedding the model builds
         if constexpr (NT == 4 && NSH == 1 && FAM != KV_RBF && FAM != KV_LINEAR) {
-            KV_ALLOW_LDS(160 * 1024, (kan_fwd_reg_bf16_kernel<FAM, GP, NT, NSH, ICH, true>));
-            hipLaunchKernelGGL((kan_fwd_reg_bf16_kernel<FAM, GP, NT, NSH, ICH, true>), grid, dim3(256), p.lds, st, a);
+            KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_fwd_reg_bf16_kernel, kan_fwd_reg_bf16_act_kernel, (FAM, GP, NT, NSH, ICH, true));
+            KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_reg_bf16_kernel, kan_fwd_reg_bf16_act_kernel, (FAM, GP, NT, NSH, ICH, true), grid, dim3(256), p.lds, st, a);
             KV_LAUNCH_CHECK("kan_fwd_reg_bf16_kernel (patch gather)");
             return 0;
         }
         return 1;       // not covered
     }
-    KV_ALLOW_LDS(160 * 1024, (kan_fwd_reg_bf16_kernel<FAM, GP, NT, NSH, ICH>));
-    hipLaunchKernelGGL((kan_fwd_reg_bf16_kernel<FAM, GP, NT, NSH, ICH>), grid, dim3(256), p.lds, st, a);
+    KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_fwd_reg_bf16_kernel, kan_fwd_reg_bf16_act_kernel, (FAM, GP, NT, NSH, ICH));
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_reg_bf16_kernel, kan_fwd_reg_bf16_act_kernel, (FAM, GP, NT, NSH, ICH), grid, dim3(256), p.lds, st, a);
     KV_LAUNCH_CHECK("kan_fwd_reg_bf16_kernel");
     return 0;
 }

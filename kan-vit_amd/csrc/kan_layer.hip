@@ -40,6 +40,13 @@ int validate(const kanvit_layer_desc* d, const char* who) {
         if (d->bparam_stride < (int64_t)d->I * nk) return kv_fail(KANVIT_EINVAL, "%s: bparam_stride too small", who);
     }
     if (d->family == KANVIT_RBF && d->bparam_stride < d->G) return kv_fail(KANVIT_EINVAL, "%s: bparam_stride too small", who);
+    if (d->base_act < KANVIT_BASE_SILU || d->base_act > KANVIT_BASE_IDENTITY)
+        return kv_fail(KANVIT_EINVAL, "%s: unknown base activation %d (KANVIT_BASE_SILU .. KANVIT_BASE_IDENTITY)", who, d->base_act);
+    if (d->base_act != KANVIT_BASE_SILU && (d->family != KANVIT_BSPLINE && d->family != KANVIT_RBF))
+        return kv_fail(KANVIT_EINVAL, "%s: base activation %d set for family %d (only BSPLINE and RBF have a base column)", who,
+                       d->base_act, d->family);
+    if (d->base_act != KANVIT_BASE_SILU && !d->has_base)
+        return kv_fail(KANVIT_EINVAL, "%s: base activation %d set with has_base = 0", who, d->base_act);
     if ((d->flags & KANVIT_FLAG_SINE_DFREQ) && d->family != KANVIT_SINE)
         return kv_fail(KANVIT_EINVAL, "%s: KANVIT_FLAG_SINE_DFREQ is a SINE flag", who);
     if (d->flags & KANVIT_FLAG_FUSED_LN) {
@@ -75,6 +82,7 @@ LayerArgs base_args(const kanvit_layer_desc* d) {
     a.ln = (d->family == KANVIT_RBF && (d->flags & KANVIT_FLAG_FUSED_LN)) ? 1 : 0;
     a.ln_eps = d->ln_eps;
     a.tail_y0 = 0x7fffffff;             // no sub-divided tail unless a launcher sets one (kv_tail_first_tile)
+    a.base_act = d->base_act;           // validated: nonzero only for BSPLINE / RBF with the base column
     return a;
 }
 
@@ -107,7 +115,7 @@ static KvTinyArgs tiny_args(const kanvit_layer_desc* d) {
     t.M = d->M; t.ldx = d->ldx; t.ldy = d->ldy; t.bp_stride = d->bparam_stride;
     t.family = d->family; t.I = d->I; t.O = d->O; t.groups = d->groups; t.xmod = d->x_group_mod; t.G = d->G;
     t.GP = gp_of(d); t.K = d->I * t.GP; t.order = d->spline_order; t.nk = d->G + d->spline_order + 1;
-    t.has_base = d->has_base; t.flags = d->flags;
+    t.has_base = d->has_base; t.flags = d->flags; t.base_act = d->base_act;
     return t;
 }
 
@@ -230,6 +238,7 @@ int kanvit_layer_fwd(const kanvit_layer_desc* d, const float* x, const float* u,
 /* 1 when the three register kernels that can form the FastKAN LayerNorm in-kernel cover this layer (pure host function) */
 int kanvit_layer_ln_fusable(const kanvit_layer_desc* d) {
     if (!d || d->family != KANVIT_RBF || !d->has_base || !kv_rbf_reg_ok(d->flags, d->G) || d->groups < 1 || d->x_group_mod < 1) return 0;
+    if (d->base_act < KANVIT_BASE_SILU || d->base_act > KANVIT_BASE_IDENTITY) return 0;      // every valid activation has the fused kernels
     if (d->I % 32 || d->O % 32 || d->M < 256 || (d->ldx & 3) || (d->ldy & 3)) return 0;
     if (d->O > 64 && d->O % 128) return 0;                 // forward column tiling: 32, 64 or multiples of 128
     {                                                      // kanvit_layer_ln_bwd's lane-group layout

@@ -62,6 +62,7 @@ struct LayerArgs {
     // launch tail (kv_tail_tiles): row tiles >= tail_y0 are cut into smaller work-groups that sit at the END of the grid and
     // fill the wave slots the last whole work-groups leave idle (forward: one projection each; input gradient: one feature chunk each)
     int tail_y0;
+    int base_act;         // BSPLINE / RBF: KANVIT_BASE_* of the base column; nonzero launches the *_act_* kernels (KV_ACT_LAUNCH)
 };
 
 // Row tiles [T1, T) of a launch of T row tiles x P work-groups per tile (two resident work-groups per CU) that should run as
@@ -94,6 +95,7 @@ __device__ __forceinline__ BasisArgs make_basis(const LayerArgs& a, int g) {
     b.inv_h = a.rbf_inv_h;
     b.bp = a.bp ? a.bp + (long long)g * a.bp_stride : nullptr;
     b.uniform = (a.flags & KANVIT_FLAG_UNIFORM_KNOTS) && a.order == 3;
+    b.act = a.base_act;
     return b;
 }
 

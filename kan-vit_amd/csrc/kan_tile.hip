@@ -72,8 +72,8 @@ __device__ __forceinline__ void stage_rows(float* __restrict__ dst, const float*
 //   consumers: MFMA on A_s/W_s[c&1]
 //   producers: W chunk c+1 -> W_s[(c+1)&1]; basis(x_s[(c+1)&1]) -> A_s[(c+1)&1]; x chunk c+2 -> x_s[c&1]
 // =============================================================================================
-template <int FAM, int NT, int NSH, bool FAST>
-__global__ __launch_bounds__(NTHR) void kan_fwd_kernel(const LayerArgs a) {
+template <int FAM, int NT, int NSH, bool FAST, int ACT>
+__device__ __forceinline__ void kan_fwd_kbody(const LayerArgs& a) {
     // FAST (host-checked): IC is a power of two dividing I, O % BN == 0 -- every chunk and column tile is
     // interior, so the only remaining bounds question is the last row tile (wave-uniform flag full_m).
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(NTHR) void kan_fwd_kernel(const LayerArgs a) {
             const int i = c * IC + il;
             float* dst = As + (il * GP) * AS;
             if (FAST || i < a.I) {
-                basis_fwd<FAM>(b, xs[il], RBF ? us[il] : 0.0f, i, dst, AS);
+                basis_fwd<FAM, ACT>(b, xs[il], RBF ? us[il] : 0.0f, i, dst, AS);
             } else {
                 for (int j = 0; j < GP; ++j) dst[j * AS] = 0.0f;
             }
@@ -310,6 +310,15 @@ __global__ __launch_bounds__(NTHR) void kan_fwd_kernel(const LayerArgs a) {
     }
     }
 }
+template <int FAM, int NT, int NSH, bool FAST>
+__global__ __launch_bounds__(NTHR) void kan_fwd_kernel(const LayerArgs a) {
+    kan_fwd_kbody<FAM, NT, NSH, FAST, KV_ACT_SILU>(a);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int NT, int NSH, bool FAST>
+__global__ __launch_bounds__(NTHR) void kan_fwd_act_kernel(const LayerArgs a) {
+    kan_fwd_kbody<FAM, NT, NSH, FAST, KV_ACT_DYN>(a);
+}
 
 // =============================================================================================
 // bf16 matrix-core variants (KANVIT_FLAG_BF16_MFMA; the bf16 configurations of BASELINE.json).
@@ -364,8 +373,8 @@ __global__ __launch_bounds__(256) void kan_pack_w_bwd_kernel(const float* __rest
 }
 
 // Requirements (host-checked): IC is a power of two >= 8 dividing I; O % (32*NT) == 0; tile-local offsets fit 32 bits.
-template <int FAM, int NT, int NSH>
-__global__ __launch_bounds__(NTHR) void kan_fwd_bf16_kernel(const LayerArgs a) {
+template <int FAM, int NT, int NSH, int ACT>
+__device__ __forceinline__ void kan_fwd_bf16_kbody(const LayerArgs& a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int BN = 32 * NT;
     constexpr int WROW = NSH * BN;
@@ -460,7 +469,7 @@ __global__ __launch_bounds__(NTHR) void kan_fwd_bf16_kernel(const LayerArgs a) {
         const float* us = u_s + buf * XS + gr * ICP;
         float* As = A_s + buf * ASZ + gr;
         for (int il = gl0; il < IC; il += 2)
-            basis_fwd<FAM>(b, xs[il], RBF ? us[il] : 0.0f, c * IC + il, As + (il * GP) * AS, AS);
+            basis_fwd<FAM, ACT>(b, xs[il], RBF ? us[il] : 0.0f, c * IC + il, As + (il * GP) * AS, AS);
     };
 
     f32x16 acc[NSH * NT];
@@ -543,6 +552,15 @@ __global__ __launch_bounds__(NTHR) void kan_fwd_bf16_kernel(const LayerArgs a) {
         }
     }
 }
+template <int FAM, int NT, int NSH>
+__global__ __launch_bounds__(NTHR) void kan_fwd_bf16_kernel(const LayerArgs a) {
+    kan_fwd_bf16_kbody<FAM, NT, NSH, KV_ACT_SILU>(a);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int NT, int NSH>
+__global__ __launch_bounds__(NTHR) void kan_fwd_bf16_act_kernel(const LayerArgs a) {
+    kan_fwd_bf16_kbody<FAM, NT, NSH, KV_ACT_DYN>(a);
+}
 
 // =============================================================================================
 // backward w.r.t. the input.  grid (xmod, ceil(M/BM)), 512 threads.
@@ -560,8 +578,8 @@ __global__ __launch_bounds__(NTHR) void kan_fwd_bf16_kernel(const LayerArgs a) {
 // bf16 in MFMA-ready images -- dY rows [row][O+8] converted while staging (A fragment = one ds_read_b128), W^T from the
 // pre-packed [O/8][KCT][8] image (B fragment = one ds_read_b128, lane = k) -- and the contraction runs on
 // v_mfma_f32_32x32x16_bf16.  Half the barriers of the fp32 schedule, no conversions in the consumer.
-template <int FAM, int KT, bool SHARED, bool BF>
-__global__ __launch_bounds__(NTHR) void kan_bwd_input_kernel(const LayerArgs a) {
+template <int FAM, int KT, bool SHARED, bool BF, int ACT>
+__device__ __forceinline__ void kan_bwd_input_kbody(const LayerArgs& a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int KCT = 32 * KT;
     constexpr int WS = KCT + 1;
@@ -738,7 +756,7 @@ __global__ __launch_bounds__(NTHR) void kan_bwd_input_kernel(const LayerArgs a) 
             const bool valid = (il < IC) && (ci * IC + il < a.I);
             const int ilc = valid ? il : 0;
             float dxv, duv;
-            basis_bwd<FAM>(b, xs[r * ICP + ilc], RBF ? us[r * ICP + ilc] : 0.0f, ci * IC + ilc, valid,
+            basis_bwd<FAM, ACT>(b, xs[r * ICP + ilc], RBF ? us[r * ICP + ilc] : 0.0f, ci * IC + ilc, valid,
                            dA_s + (ilc * GP) * AS + r, AS, dxv, duv, SINE ? dfq_s + (p * 4 + pw) * a.G : nullptr);
             if (valid) {
                 dxs[r * ICP + il] += dxv;
@@ -870,6 +888,15 @@ __global__ __launch_bounds__(NTHR) void kan_bwd_input_kernel(const LayerArgs a) 
         }
     }
 }
+template <int FAM, int KT, bool SHARED, bool BF>
+__global__ __launch_bounds__(NTHR) void kan_bwd_input_kernel(const LayerArgs a) {
+    kan_bwd_input_kbody<FAM, KT, SHARED, BF, KV_ACT_SILU>(a);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int KT, bool SHARED, bool BF>
+__global__ __launch_bounds__(NTHR) void kan_bwd_input_act_kernel(const LayerArgs a) {
+    kan_bwd_input_kbody<FAM, KT, SHARED, BF, KV_ACT_DYN>(a);
+}
 
 // =============================================================================================
 // backward w.r.t. the packed weights.  grid (feature chunks, msplit, nsets * nchunks_n), 512 thr.
@@ -878,8 +905,8 @@ __global__ __launch_bounds__(NTHR) void kan_bwd_input_kernel(const LayerArgs a) 
 // share the basis tile (q, k, v of a head for LINEAR / CHEBY / FOURIER) are contracted against ONE
 // generated tile (dY tile is [32 x NSH*64]).
 // =============================================================================================
-template <int FAM, int NSH, bool BF>
-__global__ __launch_bounds__(NTHR) void kan_bwd_weight_kernel(const LayerArgs a) {
+template <int FAM, int NSH, bool BF, int ACT>
+__device__ __forceinline__ void kan_bwd_weight_kbody(const LayerArgs& a) {
     // BF (KANVIT_FLAG_BF16_MFMA): both operands are gathered from the fp32 LDS tiles (8 ds_read_b32 each), rounded to
     // bf16 and contracted by v_mfma_f32_32x32x16_bf16 -- 16 rows per MFMA instead of 2; LDS-read bound, ~4x the fp32 rate.
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -971,7 +998,7 @@ __global__ __launch_bounds__(NTHR) void kan_bwd_weight_kernel(const LayerArgs a)
             const int i = i0 + il;
             float* dst = As + (il * GP) * BW_AS;
             if (i < a.I) {
-                basis_fwd<FAM>(b, xs[il], RBF ? us[il] : 0.0f, i, dst, BW_AS);
+                basis_fwd<FAM, ACT>(b, xs[il], RBF ? us[il] : 0.0f, i, dst, BW_AS);
             } else {
                 for (int j = 0; j < GP; ++j) dst[j * BW_AS] = 0.0f;
             }
@@ -1063,6 +1090,15 @@ __global__ __launch_bounds__(NTHR) void kan_bwd_weight_kernel(const LayerArgs a)
         }
     }
 }
+template <int FAM, int NSH, bool BF>
+__global__ __launch_bounds__(NTHR) void kan_bwd_weight_kernel(const LayerArgs a) {
+    kan_bwd_weight_kbody<FAM, NSH, BF, KV_ACT_SILU>(a);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int NSH, bool BF>
+__global__ __launch_bounds__(NTHR) void kan_bwd_weight_act_kernel(const LayerArgs a) {
+    kan_bwd_weight_kbody<FAM, NSH, BF, KV_ACT_DYN>(a);
+}
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -1080,9 +1116,9 @@ template <int FAM, int NT, int NSH, bool FAST>
 int launch_fwd(const LayerArgs& a, hipStream_t st) {
     constexpr int BN = 32 * NT;
     const size_t lds = fwd_lds<FAM>(a.IC, a.GP, NT, NSH);
-    KV_ALLOW_LDS(160 * 1024, kan_fwd_kernel<FAM, NT, NSH, FAST>);
+    KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_fwd_kernel, kan_fwd_act_kernel, (FAM, NT, NSH, FAST));
     dim3 grid((unsigned)((a.groups / NSH) * ((a.O + BN - 1) / BN)), (unsigned)((a.M + BM - 1) / BM), 1);
-    hipLaunchKernelGGL((kan_fwd_kernel<FAM, NT, NSH, FAST>), grid, dim3(NTHR), lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_kernel, kan_fwd_act_kernel, (FAM, NT, NSH, FAST), grid, dim3(NTHR), lds, st, a);
     KV_LAUNCH_CHECK("kan_fwd_kernel");
     return 0;
 }
@@ -1094,9 +1130,9 @@ int launch_fwd_sel(const LayerArgs& a, bool fast, hipStream_t st) {
 
 template <int FAM, int NT, int NSH>
 int launch_fwd_bf16(const LayerArgs& a, const FwdBf16Plan& p, hipStream_t st) {
-    KV_ALLOW_LDS(160 * 1024, kan_fwd_bf16_kernel<FAM, NT, NSH>);
+    KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_fwd_bf16_kernel, kan_fwd_bf16_act_kernel, (FAM, NT, NSH));
     dim3 grid((unsigned)((a.groups / NSH) * (a.O / (32 * NT))), (unsigned)((a.M + BM - 1) / BM), 1);
-    hipLaunchKernelGGL((kan_fwd_bf16_kernel<FAM, NT, NSH>), grid, dim3(NTHR), p.lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_bf16_kernel, kan_fwd_bf16_act_kernel, (FAM, NT, NSH), grid, dim3(NTHR), p.lds, st, a);
     KV_LAUNCH_CHECK("kan_fwd_bf16_kernel");
     return 0;
 }
@@ -1165,9 +1201,9 @@ size_t bwd_input_lds(int ic, int gp, int G, int nshare, int bf_O = 0) {
 template <int FAM, int KT, bool SHARED, bool BF>
 int launch_bwd_input(const LayerArgs& a, hipStream_t st) {
     const size_t lds = bwd_input_lds<FAM>(a.IC, a.GP, a.G, a.groups / a.xmod, BF ? a.O : 0);
-    KV_ALLOW_LDS(160 * 1024, (kan_bwd_input_kernel<FAM, KT, SHARED, BF>));
+    KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_bwd_input_kernel, kan_bwd_input_act_kernel, (FAM, KT, SHARED, BF));
     dim3 grid((unsigned)a.xmod, (unsigned)((a.M + BM - 1) / BM), 1);
-    hipLaunchKernelGGL((kan_bwd_input_kernel<FAM, KT, SHARED, BF>), grid, dim3(NTHR), lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_kernel, kan_bwd_input_act_kernel, (FAM, KT, SHARED, BF), grid, dim3(NTHR), lds, st, a);
     KV_LAUNCH_CHECK("kan_bwd_input_kernel");
     return 0;
 }
@@ -1237,9 +1273,9 @@ int launch_bwd_weight_n(const LayerArgs& a, const BwPlan& p, hipStream_t st) {
     if (lds > 160 * 1024) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: tile does not fit the LDS");
     if (KT * BW_NT * NSH > 4 * ((NSH == 1) ? BW_TPW : 8))
         return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: internal tiling error");
-    KV_ALLOW_LDS(160 * 1024, kan_bwd_weight_kernel<FAM, NSH, BF>);
+    KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_bwd_weight_kernel, kan_bwd_weight_act_kernel, (FAM, NSH, BF));
     dim3 grid((unsigned)p.nfchunks, (unsigned)p.msplit, (unsigned)((a.groups / NSH) * p.nchunks_n));
-    hipLaunchKernelGGL((kan_bwd_weight_kernel<FAM, NSH, BF>), grid, dim3(NTHR), lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_weight_kernel, kan_bwd_weight_act_kernel, (FAM, NSH, BF), grid, dim3(NTHR), lds, st, a);
     KV_LAUNCH_CHECK("kan_bwd_weight_kernel");
     return 0;
 }

@@ -25,12 +25,13 @@ __device__ __forceinline__ BasisArgs tiny_basis(const KvTinyArgs& a, int g) {
     b.inv_h = 0.0f;
     b.bp = a.bp ? a.bp + (long long)g * a.bp_stride : nullptr;
     b.uniform = (a.flags & KANVIT_FLAG_UNIFORM_KNOTS) && a.order == 3;
+    b.act = a.base_act;
     return b;
 }
 
 // grid (ceil(M / 256), groups): thread = row
-template <int FAM, int OT>
-__global__ __launch_bounds__(256) void kan_tiny_fwd_kernel(const KvTinyArgs a) {
+template <int FAM, int OT, int ACT>
+__device__ __forceinline__ void kan_tiny_fwd_kbody(const KvTinyArgs& a) {
     const int g = blockIdx.y, gx = g % a.xmod;
     // the group's weights ([K][O] <= 4 KB) go to LDS once: every thread then reads them as broadcasts (a chain of scalar
     // loads -- one s_load + wait per (i, j) -- measured 20 us for this launch)
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256) void kan_tiny_fwd_kernel(const KvTinyArgs a) {
 #pragma unroll
     for (int o = 0; o < OT; ++o) y[o] = (a.bias && o < a.O) ? a.bias[(long long)g * a.O + o] : 0.0f;
     for (int i = 0; i < a.I; ++i) {
-        BasisGen<FAM> gen;
+        BasisGen<FAM, -1, ACT> gen;
         gen.init(b, xr[i], 0.0f, i);
 #pragma unroll 5
         for (int j = 0; j < a.GP; ++j) {           // partial unroll: several LDS reads in flight instead of read -> wait -> 8 FMAs
@@ -64,10 +65,19 @@ __global__ __launch_bounds__(256) void kan_tiny_fwd_kernel(const KvTinyArgs a) {
     for (int o = 0; o < OT; ++o)
         if (o < a.O) yr[o] = y[o];
 }
+template <int FAM, int OT>
+__global__ __launch_bounds__(256) void kan_tiny_fwd_kernel(const KvTinyArgs a) {
+    kan_tiny_fwd_kbody<FAM, OT, KV_ACT_SILU>(a);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int OT>
+__global__ __launch_bounds__(256) void kan_tiny_fwd_act_kernel(const KvTinyArgs a) {
+    kan_tiny_fwd_kbody<FAM, OT, KV_ACT_DYN>(a);
+}
 
 // grid (ceil(M / 256), xmod): thread = (row, x slice); the groups sharing the slice are summed in registers
-template <int FAM, int OT, int IT>
-__global__ __launch_bounds__(256) void kan_tiny_bwd_input_kernel(const KvTinyArgs a) {
+template <int FAM, int OT, int IT, int ACT>
+__device__ __forceinline__ void kan_tiny_bwd_input_kbody(const KvTinyArgs& a) {
     const int gx = blockIdx.y, nshare = a.groups / a.xmod;
     extern __shared__ __attribute__((aligned(16))) float w_s[];   // [nshare][K][OT]: weights of the groups sharing this x slice, zero padded
     const int kw = a.K * OT;
@@ -96,7 +106,7 @@ __global__ __launch_bounds__(256) void kan_tiny_bwd_input_kernel(const KvTinyArg
 #pragma unroll
         for (int i = 0; i < IT; ++i) {
             if (i < a.I) {
-                BasisDGen<FAM> gen;
+                BasisDGen<FAM, -1, ACT> gen;
                 gen.init(b, xv[i], 0.0f, i);
                 float acc = 0.0f;
 #pragma unroll 5
@@ -117,10 +127,19 @@ __global__ __launch_bounds__(256) void kan_tiny_bwd_input_kernel(const KvTinyArg
     for (int i = 0; i < IT; ++i)
         if (i < a.I) dxr[i] = dxv[i];
 }
+template <int FAM, int OT, int IT>
+__global__ __launch_bounds__(256) void kan_tiny_bwd_input_kernel(const KvTinyArgs a) {
+    kan_tiny_bwd_input_kbody<FAM, OT, IT, KV_ACT_SILU>(a);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int OT, int IT>
+__global__ __launch_bounds__(256) void kan_tiny_bwd_input_act_kernel(const KvTinyArgs a) {
+    kan_tiny_bwd_input_kbody<FAM, OT, IT, KV_ACT_DYN>(a);
+}
 
 // grid (slabs, groups), 256 threads; LDS: phi_s[64][K + 1] | dy_s[64][OT]
-template <int FAM, int OT>
-__global__ __launch_bounds__(256) void kan_tiny_bwd_weight_kernel(const KvTinyArgs a) {
+template <int FAM, int OT, int ACT>
+__device__ __forceinline__ void kan_tiny_bwd_weight_kbody(const KvTinyArgs& a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, g = blockIdx.y, gx = g % a.xmod, K = a.K, KS = K + 1;
     float* phi_s = smem;
@@ -138,7 +157,7 @@ __global__ __launch_bounds__(256) void kan_tiny_bwd_weight_kernel(const KvTinyAr
             const long long m = r0 + r;
             float* dst = phi_s + r * KS + i * a.GP;
             if (m < me) {
-                BasisGen<FAM> gen;
+                BasisGen<FAM, -1, ACT> gen;
                 gen.init(b, a.x[m * a.ldx + (long long)gx * a.I + i], 0.0f, i);
                 for (int j = 0; j < a.GP; ++j) dst[j] = gen.next(j);
             } else {
@@ -170,6 +189,15 @@ __global__ __launch_bounds__(256) void kan_tiny_bwd_weight_kernel(const KvTinyAr
         const int idx = tid + 256 * q;
         if (idx < nout) out[idx] = acc[q];
     }
+}
+template <int FAM, int OT>
+__global__ __launch_bounds__(256) void kan_tiny_bwd_weight_kernel(const KvTinyArgs a) {
+    kan_tiny_bwd_weight_kbody<FAM, OT, KV_ACT_SILU>(a);
+}
+// the same kernel for a BSPLINE / RBF base activation other than SiLU (code in the launch arguments)
+template <int FAM, int OT>
+__global__ __launch_bounds__(256) void kan_tiny_bwd_weight_act_kernel(const KvTinyArgs a) {
+    kan_tiny_bwd_weight_kbody<FAM, OT, KV_ACT_DYN>(a);
 }
 
 template <typename F>
@@ -210,8 +238,8 @@ int kv_tiny_fwd(const KvTinyArgs& a, hipStream_t st) {
     const dim3 grid((unsigned)((a.M + 255) / 256), (unsigned)a.groups);
     return tiny_family(a.family, [&](auto fam) {
         constexpr int F = decltype(fam)::value;
-        if (a.O <= 8) hipLaunchKernelGGL((kan_tiny_fwd_kernel<F, 8>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((kan_tiny_fwd_kernel<F, 16>), grid, dim3(256), 0, st, a);
+        if (a.O <= 8) KV_ACT_LAUNCH(F, a.base_act, kan_tiny_fwd_kernel, kan_tiny_fwd_act_kernel, (F, 8), grid, dim3(256), 0, st, a);
+        else KV_ACT_LAUNCH(F, a.base_act, kan_tiny_fwd_kernel, kan_tiny_fwd_act_kernel, (F, 16), grid, dim3(256), 0, st, a);
         KV_LAUNCH_CHECK("kan_tiny_fwd_kernel");
         return 0;
     });
@@ -223,9 +251,9 @@ int kv_tiny_bwd_input(const KvTinyArgs& a, hipStream_t st) {
         constexpr int F = decltype(fam)::value;
         const int nshare = a.groups / a.xmod;
         if (a.O <= 8 && a.I <= 8)
-            hipLaunchKernelGGL((kan_tiny_bwd_input_kernel<F, 8, 8>), grid, dim3(256), sizeof(float) * nshare * a.K * 8, st, a);
+            KV_ACT_LAUNCH(F, a.base_act, kan_tiny_bwd_input_kernel, kan_tiny_bwd_input_act_kernel, (F, 8, 8), grid, dim3(256), sizeof(float) * nshare * a.K * 8, st, a);
         else
-            hipLaunchKernelGGL((kan_tiny_bwd_input_kernel<F, 16, 16>), grid, dim3(256), sizeof(float) * nshare * a.K * 16, st, a);
+            KV_ACT_LAUNCH(F, a.base_act, kan_tiny_bwd_input_kernel, kan_tiny_bwd_input_act_kernel, (F, 16, 16), grid, dim3(256), sizeof(float) * nshare * a.K * 16, st, a);
         KV_LAUNCH_CHECK("kan_tiny_bwd_input_kernel");
         return 0;
     });
@@ -237,10 +265,10 @@ int kv_tiny_bwd_weight(const KvTinyArgs& a, hipStream_t st) {
         constexpr int F = decltype(fam)::value;
         if (a.O <= 8) {
             const size_t lds = sizeof(float) * (64 * (size_t)(a.K + 1) + 64 * 8);
-            hipLaunchKernelGGL((kan_tiny_bwd_weight_kernel<F, 8>), grid, dim3(256), lds, st, a);
+            KV_ACT_LAUNCH(F, a.base_act, kan_tiny_bwd_weight_kernel, kan_tiny_bwd_weight_act_kernel, (F, 8), grid, dim3(256), lds, st, a);
         } else {
             const size_t lds = sizeof(float) * (64 * (size_t)(a.K + 1) + 64 * 16);
-            hipLaunchKernelGGL((kan_tiny_bwd_weight_kernel<F, 16>), grid, dim3(256), lds, st, a);
+            KV_ACT_LAUNCH(F, a.base_act, kan_tiny_bwd_weight_kernel, kan_tiny_bwd_weight_act_kernel, (F, 16), grid, dim3(256), lds, st, a);
         }
         KV_LAUNCH_CHECK("kan_tiny_bwd_weight_kernel");
         return 0;

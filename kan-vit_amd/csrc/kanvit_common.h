@@ -99,6 +99,7 @@ struct KvTinyArgs {
     float* slab;
     long long M, ldx, ldy, bp_stride, rows_per_slab;
     int family, I, O, groups, xmod, G, GP, K, order, nk, has_base, flags, slabs;
+    int base_act;
 };
 bool kv_tiny_ok(const kanvit_layer_desc* d);
 int kv_tiny_slabs(const kanvit_layer_desc* d);

@@ -23,6 +23,9 @@ FLAG_SHARED_BPARAMS = 4
 FLAG_FUSED_LN = 8
 FLAG_SINE_DFREQ = 16
 FAMILY_NAMES = ["linear", "cheby", "bspline", "rbf", "sine", "fourier"]
+# base activations of the BSPLINE / RBF base column (kanvit_layer_desc.base_act, KANVIT_BASE_*)
+BASE_SILU, BASE_GELU, BASE_GELU_TANH, BASE_RELU, BASE_TANH, BASE_IDENTITY = range(6)
+BASE_NAMES = ["silu", "gelu", "gelu-tanh", "relu", "tanh", "identity"]
 
 
 class KanvitError(RuntimeError):
@@ -33,7 +36,7 @@ class LayerDesc(C.Structure):
     _fields_ = [("family", C.c_int32), ("groups", C.c_int32), ("x_group_mod", C.c_int32), ("I", C.c_int32),
                 ("O", C.c_int32), ("G", C.c_int32), ("spline_order", C.c_int32), ("has_base", C.c_int32),
                 ("rbf_inv_h", C.c_float), ("flags", C.c_int32), ("M", C.c_int64), ("ldx", C.c_int64),
-                ("ldu", C.c_int64), ("ldy", C.c_int64), ("bparam_stride", C.c_int64), ("ln_eps", C.c_float), ("reserved", C.c_int32)]
+                ("ldu", C.c_int64), ("ldy", C.c_int64), ("bparam_stride", C.c_int64), ("ln_eps", C.c_float), ("base_act", C.c_int32)]
 
 
 class AttnDesc(C.Structure):

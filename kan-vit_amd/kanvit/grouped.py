@@ -98,6 +98,13 @@ def run_qkv(q_layers: Sequence, k_layers: Sequence, v_layers: Sequence, x2d: tor
     layer acts row-wise."""
     H = len(q_layers)
     layers = list(q_layers) + list(k_layers) + list(v_layers)
+    # one grouped launch has ONE base activation (kanvit_layer_desc.base_act): layers whose activations differ (swapped after
+    # construction) run one launch each, on their own head's columns
+    acts = {ops.base_activation_code(m.base_activation) for m in layers
+            if hasattr(m, "base_activation") and getattr(m, "use_base_update", True)}
+    if len(acts) > 1:
+        dh = x2d.shape[1] // H
+        return torch.cat([run_single(m, x2d[:, (g % H) * dh:(g % H + 1) * dh]) for g, m in enumerate(layers)], dim=1)
     if isinstance(layers[0], torch.nn.Linear):
         cfg0 = linear_cfg(layers[0])
     elif hasattr(type(layers[0]), "kan_pack_grouped") and "layers" in layers[0].kan_cfg.__code__.co_varnames:

@@ -30,6 +30,7 @@ class LayerCfg:
     rbf_inv_h: float = 0.0
     flags: int = 0          # _lib.FLAG_BF16_MFMA: contract on the bf16 matrix cores (set under bf16 autocast)
     ln_eps: float = 0.0     # _lib.FLAG_FUSED_LN (FastKAN): epsilon of the LayerNorm formed inside the kernels
+    base_act: int = 0       # BSPLINE / RBF with has_base: activation of the base column (_lib.BASE_*; 0 = SiLU)
 
     @property
     def GP(self) -> int:
@@ -108,9 +109,61 @@ def _require_gpu_f32(name: str, t: Optional[torch.Tensor]):
         raise KanvitError(f"{name} has dtype {t.dtype}; the kanvit kernels compute in float32")
 
 
+SUPPORTED_BASE_ACTIVATIONS = ("nn.SiLU(), F.silu; nn.GELU(), F.gelu; nn.GELU(approximate='tanh'), "
+                              "functools.partial(F.gelu, approximate='tanh'); nn.ReLU(), F.relu, torch.relu; "
+                              "nn.Tanh(), torch.tanh, F.tanh; nn.Identity()")
+
+
+def base_activation_code(fn) -> Optional[int]:
+    """The kernels' code (_lib.BASE_*) for a base activation of KANLinear / FastKANLayer -- a module instance or a callable,
+    as the reference applies it (models/effkan.py:178, models/fastkan.py:74) -- or None when the kernels do not implement
+    it.  In-place variants are refused: the reference evaluates the B-splines of the already-activated x after them."""
+    import functools
+    import torch.nn.functional as F
+    nn = torch.nn
+    if isinstance(fn, functools.partial):
+        if fn.args or not (fn.func is F.gelu or fn.func is torch._C._nn.gelu):
+            return None
+        if set(fn.keywords) - {"approximate"}:
+            return None
+        a = fn.keywords.get("approximate", "none")
+        return {"none": _lib.BASE_GELU, "tanh": _lib.BASE_GELU_TANH}.get(a)
+    if isinstance(fn, nn.Module):
+        t = type(fn)
+        if t is nn.SiLU:
+            return None if fn.inplace else _lib.BASE_SILU
+        if t is nn.GELU:
+            return {"none": _lib.BASE_GELU, "tanh": _lib.BASE_GELU_TANH}.get(fn.approximate)
+        if t is nn.ReLU:
+            return None if fn.inplace else _lib.BASE_RELU
+        if t is nn.Tanh:
+            return _lib.BASE_TANH
+        if t is nn.Identity:
+            return _lib.BASE_IDENTITY
+        return None
+    if fn is F.silu:
+        return _lib.BASE_SILU
+    if fn is F.gelu or fn is torch._C._nn.gelu:
+        return _lib.BASE_GELU
+    if fn is F.relu or fn is torch.relu:
+        return _lib.BASE_RELU
+    if fn is torch.tanh or fn is F.tanh:
+        return _lib.BASE_TANH
+    return None
+
+
+def base_act_of(fn) -> int:
+    """base_activation_code(fn), or NotImplementedError naming the supported set."""
+    code = base_activation_code(fn)
+    if code is None:
+        raise NotImplementedError(f"base_activation {fn!r} is not implemented by the fused kernels; supported: "
+                                  f"{SUPPORTED_BASE_ACTIVATIONS}")
+    return code
+
+
 def _desc(cfg: LayerCfg, M: int, ldx: int, ldu: int, ldy: int, bp_stride: int) -> LayerDesc:
     return LayerDesc(cfg.family, cfg.groups, cfg.x_group_mod, cfg.I, cfg.O, cfg.G, cfg.spline_order, cfg.has_base,
-                     cfg.rbf_inv_h, cfg.flags, M, ldx, ldu, ldy, bp_stride, cfg.ln_eps, 0)
+                     cfg.rbf_inv_h, cfg.flags, M, ldx, ldu, ldy, bp_stride, cfg.ln_eps, cfg.base_act)
 
 
 def _workspace(nbytes: int, device):

@@ -1,7 +1,8 @@
 """KANLinear (efficient-KAN B-spline layer) -- drop-in for models/effkan.py:8-264 (family BSPLINE).
 
 Forward / backward run in the fused kernel: Cox-de Boor bases on the per-feature knot buffer
-``grid`` (half-open order-0 intervals, models/effkan.py:115), the silu base path and both
+``grid`` (half-open order-0 intervals, models/effkan.py:115), the base path (``base_activation``: SiLU by
+default, or one of ops.SUPPORTED_BASE_ACTIVATIONS, read on every forward) and both
 contractions in one pass.  Construction-time host logic (knot vector, the least-squares
 initialisation of ``spline_weight``) is plain torch, as in the reference."""
 import math
@@ -44,8 +45,6 @@ class KANLinear(torch.nn.Module):
         self.out_features = out_features
         self.grid_size = grid_size
         self.spline_order = spline_order
-        if base_activation is not torch.nn.SiLU:
-            raise NotImplementedError("the fused kernel implements the reference's default base_activation (SiLU)")
 
         # uniform knots, spline_order extra on each side (models/effkan.py:44-53)
         h = (grid_range[1] - grid_range[0]) / grid_size
@@ -63,6 +62,7 @@ class KANLinear(torch.nn.Module):
         self.scale_spline = scale_spline
         self.enable_standalone_scale_spline = enable_standalone_scale_spline
         self.base_activation = base_activation()
+        ops.base_act_of(self.base_activation)          # refuse what the kernels do not implement (NotImplementedError)
         self.grid_eps = grid_eps
         self.reset_parameters()
 
@@ -116,7 +116,8 @@ class KANLinear(torch.nn.Module):
         uniform, equal = _grid_facts(layers if layers is not None else [self])
         flags = (_lib.FLAG_UNIFORM_KNOTS if uniform and equal else 0) | (_lib.FLAG_SHARED_BPARAMS if equal and layers is not None else 0)
         return ops.LayerCfg(family=ops.BSPLINE, I=self.in_features, O=self.out_features,
-                            G=self.grid_size + self.spline_order, spline_order=self.spline_order, has_base=1, flags=flags)
+                            G=self.grid_size + self.spline_order, spline_order=self.spline_order, has_base=1, flags=flags,
+                            base_act=ops.base_act_of(self.base_activation))
 
     def kan_pack(self):
         # [O, I, nb] (scaled) and base [O, I] -> [I, nb+1, O] -> [I*(nb+1), O]; base column last

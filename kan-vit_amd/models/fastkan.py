@@ -63,7 +63,8 @@ class RadialBasisFunction(nn.Module):
 
 
 class FastKANLayer(nn.Module):
-    """y = spline_linear(rbf(layernorm(x))) + base_linear(silu(x)) (models/fastkan.py:66-76).
+    """y = spline_linear(rbf(layernorm(x))) + base_linear(base_activation(x)) (models/fastkan.py:66-76); base_activation is
+    F.silu by default or one of ops.SUPPORTED_BASE_ACTIVATIONS, read on every forward.
 
     state_dict keys as the reference: layernorm.{weight,bias}, rbf.grid, spline_linear.weight
     [O, I*num_grids] (column i*num_grids + k), base_linear.{weight,bias}."""
@@ -78,8 +79,7 @@ class FastKANLayer(nn.Module):
         self.spline_linear = SplineLinear(input_dim * num_grids, output_dim, spline_weight_init_scale)
         self.use_base_update = use_base_update
         if use_base_update:
-            if base_activation is not F.silu:
-                raise NotImplementedError("the fused kernel implements the reference's default base_activation (silu)")
+            ops.base_act_of(base_activation)        # refuse what the kernels do not implement (NotImplementedError)
             self.base_activation = base_activation
             self.base_linear = nn.Linear(input_dim, output_dim)
 
@@ -88,7 +88,8 @@ class FastKANLayer(nn.Module):
         uni = _rbf_grid_is_default(layers if layers is not None else [self])
         return ops.LayerCfg(family=ops.RBF, I=self.input_dim, O=self.output_dim, G=self.num_grids,
                             has_base=int(self.use_base_update), rbf_inv_h=1.0 / float(self.rbf.denominator),
-                            flags=_lib.FLAG_UNIFORM_KNOTS if uni else 0)
+                            flags=_lib.FLAG_UNIFORM_KNOTS if uni else 0,
+                            base_act=ops.base_act_of(self.base_activation) if self.use_base_update else 0)
 
     def kan_pack(self):
         i, g, o = self.input_dim, self.num_grids, self.output_dim

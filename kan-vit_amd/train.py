@@ -91,6 +91,29 @@ class _GraphedStep:
         return self.loss, self.logits
 
 
+def set_base_activation(model, model_type, name):
+    """--base-activation: the base activation of every KANLinear ('efficientkan') or FastKANLayer ('fast') of the model, set
+    after construction as the reference's layers allow (they read `base_activation` on every forward).  The constructors of
+    VisionTransformer / MSA take no such argument, so their signatures stay the reference's."""
+    import functools
+    import torch.nn.functional as F
+    from models.effkan import KANLinear
+    from models.fastkan import FastKANLayer
+    if name == "silu":
+        return
+    modules = {"gelu": lambda: torch.nn.GELU(), "gelu-tanh": lambda: torch.nn.GELU(approximate="tanh"),
+               "relu": lambda: torch.nn.ReLU(), "tanh": lambda: torch.nn.Tanh(), "identity": lambda: torch.nn.Identity()}
+    functions = {"gelu": F.gelu, "gelu-tanh": functools.partial(F.gelu, approximate="tanh"), "relu": F.relu,
+                 "tanh": torch.tanh, "identity": torch.nn.Identity()}
+    if model_type not in ("efficientkan", "fast"):
+        raise SystemExit(f"--base-activation {name}: only the 'efficientkan' and 'fast' model types have a base activation")
+    for m in model.modules():
+        if isinstance(m, KANLinear):
+            m.base_activation = modules[name]()
+        elif isinstance(m, FastKANLayer) and m.use_base_update:
+            m.base_activation = functions[name]
+
+
 def main(args, batches=None, init_state=None):
     rank, world, local = 0, 1, 0
     if args.dp:
@@ -121,6 +144,7 @@ def main(args, batches=None, init_state=None):
     chw = (args.in_chans, args.image_size, args.image_size)
     model = VisionTransformer(chw, n_patches=args.n_patches, n_blocks=args.n_blocks, d_hidden=args.d_hidden,
                               n_heads=args.n_heads, out_d=args.out_d, type=args.model_type)
+    set_base_activation(model, args.model_type, getattr(args, "base_activation", "silu"))
     if init_state is not None:
         model.load_state_dict(init_state)
     model = model.to(device)
@@ -247,6 +271,8 @@ def parse(argv=None):
                    help='bf16: autocast for the stock dense ops and the kanvit kernels on the bf16 matrix cores (fp32 I/O and '
                         'accumulation); off (default): the reference\'s fp32 arithmetic')
     p.add_argument('--graph', action='store_true', help='capture the whole train step in a HIP graph and replay it per batch')
+    p.add_argument('--base-activation', choices=['silu', 'gelu', 'gelu-tanh', 'relu', 'tanh', 'identity'], default='silu',
+                   help="base activation of every KANLinear / FastKANLayer ('efficientkan' and 'fast' model types)")
     p.add_argument('--no-tuned-gemms', action='store_true', help='library-default kernel selection for the stock GEMMs')
     return p.parse_args(argv)
 
