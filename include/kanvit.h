@@ -255,12 +255,16 @@ int kanvit_attn_bwd(const kanvit_attn_desc* d, const float* q, const float* k, c
  * needs k_len <= q_len: with k_len > q_len utils.py:169 shifts the diagonal so that the first k_len - q_len queries see no
  * key and the reference's answer depends on its bucket sizes -- KANVIT_EINVAL here.  d as for kanvit_attn_fwd with
  * d->N = q_len (q, o, do, dq: [B][H][q_len][D] through the q / o strides; k, v, dk, dv: [B][H][Nk][D] through the k / v
- * strides; lse [B][H][q_len]).  Exact fp32 (KANVIT_FLAG_BF16_MFMA is refused).  A query whose keys are all dead gets o = 0,
+ * strides; lse [B][H][q_len]).  Exact fp32 by default.  With KANVIT_FLAG_BF16_MFMA in d->flags and D <= KANVIT_ATTN_MAX_D (64)
+ * the products run on the bf16 matrix cores with the rounding points of kanvit_attn_fwd's bf16 mode (operands of S, dP, O, dV,
+ * dK, dQ rounded to bf16; softmax, lse, delta, accumulation and all I/O fp32); for D > 64 the flag is refused (KANVIT_EINVAL):
+ * there is no bf16 form of the wide heads, and the caller runs them exact.  kanvit_attn_x_bwd must get the flags its forward
+ * got: the lse of one mode is not valid input to the other mode's backward.  A query whose keys are all dead gets o = 0,
  * lse = -FLT_MAX, zero gradients.  Any q_len / k_len: the swept operand is walked in LDS chunks of 128 rows (running max / sum in
  * the forward, utils.py:199-221), so these entry points also serve self-attention heads too long for kanvit_attn_fwd's
  * one-head-per-work-group form (N > 224 at D = 64).  Head size: D even and <= KANVIT_ATTN_X_MAX_D, wider than
  * kanvit_attn_fwd's KANVIT_ATTN_MAX_D, so they also serve every head wider than 64 (ViT-H/14: D = 80; D = 128).  The domain
- * grew from D <= 64 to D <= 128 without a change of struct, signature or ABI version. */
+ * grew from D <= 64 to D <= 128, and then by the bf16 mode for D <= 64, without a change of struct, signature or ABI version. */
 #define KANVIT_ATTN_X_MAX_D 128
 typedef struct kanvit_attn_ext {
     int32_t Nk;              /* key / value length */

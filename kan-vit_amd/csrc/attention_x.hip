@@ -442,6 +442,410 @@ __global__ __launch_bounds__(XShape<DT>::THR) void attn_x_bwd_q_kernel(const Att
     if (qt < a.nqt) x_store_tile<DT>(dqb, a.qsn, qt * 32, a.Nq, D, T_w, lane);
 }
 
+// ---- bf16 matrix-core twins (KANVIT_FLAG_BF16_MFMA, D <= 64): the fp32 kernels' tile orientation, chunked sweep, masks and
+// running (max, sum), with every product on v_mfma_f32_32x32x16_bf16 and the rounding points of attention.hip's bf16 kernels
+// (oracle/kan_oracle.py::_RoundedAttention):
+//   forward   S^T = r(K).r(Q)^T; p = exp(scale S - max) in fp32, max = the row's maximum over ALL keys (a first sweep, see
+//             attn_x_fwd_bf16_kernel); O^T accumulates r(V)^T.r(p) and is divided by the fp32 row sum at the end
+//   backward  P = exp(scale S - lse) from the same rounded S; dP = r(dO).r(V)^T; dS = P scale (dP - delta), delta = rowsum(dO*O)
+//             in fp32 (attn_x_delta_kernel); dV = r(P)^T.r(dO), dK = r(dS)^T.r(Q), dQ = r(dS).r(K)
+// The swept operand lives in the LDS AS bf16, converted once per chunk by the work-group instead of once per wave: a row image
+// [CH][RB] (RB = 32*DT + 8: the A fragment of a lane's row is one ds_read_b128) for the products over d, and a transposed image
+// [32*DT][TB] (TB = CH + 8) with the 32 rows of each tile in accumulator slot order (kv_key_slot) for the products whose k index
+// is the accumulator's register index (the score tile packed to bf16 by kv_acc8 is the B operand; cdna guide section 3).  The
+// stationary operand (a wave's own 32 rows) is read from global straight into bf16 fragments, and the results are stored straight
+// from the accumulators (register 4q + e of O^T is column dt*32 + 8q + 4hf + e of the lane's row): no staging tile.
+// LDS per work-group (DT = 2): forward 35 KiB (K rows, V^T), dK/dV 71 KiB (Q, dO rows and transposes, lse, delta), dQ 53 KiB
+// (K, V rows, K^T).  Operand idioms as in attention.hip (kv_pk, kv_pack8, kv_acc8, kv_key_slot).
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned kv_pk(float lo, float hi) {
+    bf16x2_t v = {(__bf16)lo, (__bf16)hi};
+    return __builtin_bit_cast(unsigned, v);
+}
+__device__ __forceinline__ bf16x8_t kv_pack8(const float (&f)[8]) {
+    const u32x4 u = {kv_pk(f[0], f[1]), kv_pk(f[2], f[3]), kv_pk(f[4], f[5]), kv_pk(f[6], f[7])};
+    return __builtin_bit_cast(bf16x8_t, u);
+}
+__device__ __forceinline__ bf16x8_t kv_acc8(const f32x16& a, int s) {
+    const u32x4 u = {kv_pk(a[8 * s], a[8 * s + 1]), kv_pk(a[8 * s + 2], a[8 * s + 3]), kv_pk(a[8 * s + 4], a[8 * s + 5]),
+                     kv_pk(a[8 * s + 6], a[8 * s + 7])};
+    return __builtin_bit_cast(bf16x8_t, u);
+}
+__device__ __forceinline__ int kv_key_slot(int ko) {      // slot of row offset ko (0..31) inside its tile of a transposed image
+    const int w = ko & 15;
+    return (ko & 16) + 8 * ((w >> 2) & 1) + 4 * (w >> 3) + (w & 3);
+}
+
+template <int DT>
+struct XbShape {
+    static constexpr int RB = 32 * DT + 8;         // bf16 row image stride (elements)
+    static constexpr int TB = XCH * 32 + 8;        // bf16 transposed image stride (elements)
+    static constexpr int ROWS = XCH * 32 * RB;     // elements of a row image
+    static constexpr int TRANS = 32 * DT * TB;     // elements of a transposed image
+};
+
+// columns c..c+7 of one fp32 row rounded to bf16 (zero at columns >= D, everywhere unless ok): a wave's own rows
+__device__ __forceinline__ bf16x8_t xb_grow8(const float* __restrict__ p, int c, int D, bool ok, bool vec) {
+    float f[8];
+    if (vec) {
+        f32x4 u0 = {0.0f, 0.0f, 0.0f, 0.0f}, u1 = u0;
+        if (ok && c < D) u0 = *reinterpret_cast<const f32x4*>(p + c);
+        if (ok && c + 4 < D) u1 = *reinterpret_cast<const f32x4*>(p + c + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            f[e] = u0[e];
+            f[4 + e] = u1[e];
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = (ok && c + e < D) ? p[c + e] : 0.0f;
+    }
+    return kv_pack8(f);
+}
+
+// rows row0 .. row0 + CH - 1 of src -> the bf16 row image (ROWS) and / or transposed image (TRANS) of a chunk; zero beyond n_valid
+// rows and D columns.  A thread converts a row PAIR (2m, 2m + 1) x 4 columns: the pair is one 32-bit word of the transposed image.
+template <int DT, int NTHR, bool ROWS, bool TRANS>
+__device__ __forceinline__ void xb_fill(unsigned short* __restrict__ rimg, unsigned short* __restrict__ timg, const float* __restrict__ src,
+                                        long long stride_n, int row0, int n_valid, int D, int tid, bool vec) {
+    constexpr int W4 = 8 * DT, ITEMS = XCH * 16 * W4, RB = XbShape<DT>::RB, TB = XbShape<DT>::TB;
+    static_assert(ITEMS % NTHR == 0, "whole passes");
+#pragma unroll
+    for (int it = 0; it < ITEMS / NTHR; ++it) {
+        const int idx = it * NTHR + tid;
+        const int m = idx / W4, c = (idx - m * W4) * 4;
+        const int n0 = row0 + 2 * m;
+        f32x4 t0 = {0.0f, 0.0f, 0.0f, 0.0f}, t1 = t0;
+        if (vec) {
+            if (c < D && n0 < n_valid) t0 = *reinterpret_cast<const f32x4*>(src + (long long)n0 * stride_n + c);
+            if (c < D && n0 + 1 < n_valid) t1 = *reinterpret_cast<const f32x4*>(src + (long long)(n0 + 1) * stride_n + c);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (c + e < D && n0 < n_valid) t0[e] = src[(long long)n0 * stride_n + c + e];
+                if (c + e < D && n0 + 1 < n_valid) t1[e] = src[(long long)(n0 + 1) * stride_n + c + e];
+            }
+        }
+        if constexpr (ROWS) {
+            unsigned* r0p = reinterpret_cast<unsigned*>(rimg + (2 * m) * RB + c);
+            unsigned* r1p = reinterpret_cast<unsigned*>(rimg + (2 * m + 1) * RB + c);
+            r0p[0] = kv_pk(t0[0], t0[1]);
+            r0p[1] = kv_pk(t0[2], t0[3]);
+            r1p[0] = kv_pk(t1[0], t1[1]);
+            r1p[1] = kv_pk(t1[2], t1[3]);
+        }
+        if constexpr (TRANS) {
+            const int pos = ((2 * m) & ~31) + kv_key_slot((2 * m) & 31);      // even: rows 2m, 2m + 1 are adjacent slots
+#pragma unroll
+            for (int e = 0; e < 4; ++e) *reinterpret_cast<unsigned*>(timg + (c + e) * TB + pos) = kv_pk(t0[e], t1[e]);
+        }
+    }
+}
+
+// the lane's row of a [d][row] accumulator set (O^T, dK^T, dV^T, dQ^T: register r = column dt*32 + kv_acc_row(r, hf)) times mul
+template <int DT>
+__device__ __forceinline__ void xb_store_row(float* __restrict__ p, const f32x16 (&acc)[DT], float mul, int D, int hf, bool vec) {
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int c = dt * 32 + 8 * q + 4 * hf;
+            if (vec) {
+                if (c < D) {
+                    const f32x4 v = {acc[dt][4 * q] * mul, acc[dt][4 * q + 1] * mul, acc[dt][4 * q + 2] * mul, acc[dt][4 * q + 3] * mul};
+                    *reinterpret_cast<f32x4*>(p + c) = v;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (c + e < D) p[c + e] = acc[dt][4 * q + e] * mul;
+            }
+        }
+}
+
+constexpr int XB_THR = 512;       // 8 waves, two per SIMD, as the fp32 DT = 1, 2 kernels
+
+// S^T tiles of one key chunk (key on the register index, the lane's query on the column), dead positions -inf
+template <int DT>
+__device__ __forceinline__ void xb_fwd_scores(f32x16 (&sacc)[XCH], const unsigned short* __restrict__ Kr, const bf16x8_t (&qf)[2 * DT],
+                                              const AttnXArgs& a, const unsigned char* mb, int qrow, int kc, int l31, int hf) {
+    constexpr int RB = XbShape<DT>::RB;
+#pragma unroll
+    for (int j = 0; j < XCH; ++j) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc[j][r] = 0.0f;
+        const unsigned dbits = (kc + j < a.nkt) ? x_dead_bits<true>(a, mb, qrow, (kc + j) * 32, hf) : 0xffffu;
+        if (kc + j < a.nkt) {
+            const unsigned short* kp = Kr + (j * 32 + l31) * RB + 8 * hf;
+#pragma unroll
+            for (int ks = 0; ks < 2 * DT; ++ks)
+                sacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(kp + 16 * ks), qf[ks], sacc[j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc[j][r] = ((dbits >> r) & 1u) ? -INFINITY : sacc[j][r];
+    }
+}
+
+// forward: two sweeps over the keys.  The first forms S and keeps the row maximum only; the second rounds p = exp(scale S - max)
+// against that FINAL maximum, so r(p) is the value the one-head-per-work-group bf16 kernels (and the rounded oracle) round, whatever
+// the chunking.  A running maximum would round p against the maximum of the chunks seen so far and rescale r(p) afterwards:
+// r(p c) != r(p) c, an error of the size of the rounding itself (measured: 1e-3 of max |o|, passed on through delta to 2-3e-3 of
+// max |dq|, |dk|, against 2-5e-4 with the final maximum).  The first sweep costs the K fills and a third of the MFMAs once more.
+template <int DT>
+__global__ __launch_bounds__(XB_THR) void attn_x_fwd_bf16_kernel(const AttnXArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int TB = XbShape<DT>::TB, XW = XB_THR / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hf = lane >> 5;
+    const int bh = blockIdx.x, bi = bh / a.H, hi = bh - bi * a.H;
+    const int D = a.D, nkt = a.nkt;
+    unsigned short* Kr = reinterpret_cast<unsigned short*>(smem);        // [CH][RB]
+    unsigned short* Vt = Kr + XbShape<DT>::ROWS;                           // [32*DT][TB]
+
+    const float* qb = a.q + bi * a.qsb + hi * a.qsh;
+    const float* kb = a.k + bi * a.ksb + hi * a.ksh;
+    const float* vb = a.v + bi * a.vsb + hi * a.vsh;
+    float* ob = a.out + bi * a.osb + hi * a.osh;
+    const unsigned char* mb = a.mask ? a.mask + bi * a.msb + hi * a.msh : nullptr;
+
+    const float sc2 = a.scale * LOG2E_X;
+    const int qt = blockIdx.y * XW + wave;       // tiles past nqt run on zero rows and store nothing
+    const int qrow = qt * 32 + l31;
+    const bool q_ok = qt < a.nqt && qrow < a.Nq;
+    bf16x8_t qf[2 * DT];
+#pragma unroll
+    for (int ks = 0; ks < 2 * DT; ++ks) qf[ks] = xb_grow8(qb + (long long)(q_ok ? qrow : 0) * a.qsn, 16 * ks + 8 * hf, D, q_ok, a.vec);
+
+    f32x16 sacc[XCH];
+    float mx = -INFINITY;
+    for (int kc = 0; kc < nkt; kc += XCH) {
+        __syncthreads();
+        xb_fill<DT, XB_THR, true, false>(Kr, nullptr, kb, a.ksn, kc * 32, a.Nk, D, tid, a.vec);
+        __syncthreads();
+        xb_fwd_scores<DT>(sacc, Kr, qf, a, mb, qrow, kc, l31, hf);
+#pragma unroll
+        for (int j = 0; j < XCH; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[j][r]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float mxs = (mx == -INFINITY) ? 0.0f : mx * sc2;
+
+    f32x16 oacc[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.0f;
+    float lsum = 0.0f;
+    for (int kc = 0; kc < nkt; kc += XCH) {
+        __syncthreads();                         // every wave is done with the previous chunk
+        if (nkt > XCH) xb_fill<DT, XB_THR, true, false>(Kr, nullptr, kb, a.ksn, kc * 32, a.Nk, D, tid, a.vec);   // one chunk: still there
+        xb_fill<DT, XB_THR, false, true>(nullptr, Vt, vb, a.vsn, kc * 32, a.Nk, D, tid, a.vec);
+        __syncthreads();
+        xb_fwd_scores<DT>(sacc, Kr, qf, a, mb, qrow, kc, l31, hf);
+        float sum = 0.0f;
+#pragma unroll
+        for (int j = 0; j < XCH; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p = exp2f(sacc[j][r] * sc2 - mxs);
+                sacc[j][r] = p;
+                sum += p;
+            }
+        lsum += sum + __shfl_xor(sum, 32);
+#pragma unroll
+        for (int j = 0; j < XCH; ++j) {
+            if (kc + j < nkt) {
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    const bf16x8_t pb = kv_acc8(sacc[j], s2);
+                    const unsigned short* vp = Vt + l31 * TB + j * 32 + 16 * s2 + 8 * hf;
+#pragma unroll
+                    for (int dt = 0; dt < DT; ++dt)
+                        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(vp + dt * 32 * TB), pb, oacc[dt], 0, 0, 0);
+                }
+            }
+        }
+    }
+    if (q_ok) {
+        const float inv = lsum > 0.0f ? 1.0f / lsum : 0.0f;      // every key dead: o = 0
+        xb_store_row<DT>(ob + (long long)qrow * a.osn, oacc, inv, D, hf, a.vec && ((uintptr_t)ob % 16 == 0));
+        if (hf == 0 && a.lse) a.lse[(long long)bh * a.Nq + qrow] = lsum > 0.0f ? mx * a.scale + logf(lsum) : -FLT_MAX;
+    }
+}
+
+// dK, dV: key-stationary, as attn_x_bwd_kv_kernel.  A wave's own K, V rows are bf16 fragments in registers; the queries are swept in
+// chunks whose Q and dO images are held twice, as rows (S, dP: the reduction runs over d) and transposed (dV^T, dK^T: over queries).
+template <int DT>
+__global__ __launch_bounds__(XB_THR) void attn_x_bwd_kv_bf16_kernel(const AttnXArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int RB = XbShape<DT>::RB, TB = XbShape<DT>::TB, CH = XCH * 32, XW = XB_THR / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hf = lane >> 5;
+    const int bh = blockIdx.x, bi = bh / a.H, hi = bh - bi * a.H;
+    const int D = a.D;
+    unsigned short* Qr = reinterpret_cast<unsigned short*>(smem);         // [CH][RB]
+    unsigned short* dOr = Qr + XbShape<DT>::ROWS;                          // [CH][RB]
+    unsigned short* Qt = dOr + XbShape<DT>::ROWS;                          // [32*DT][TB]
+    unsigned short* dOt = Qt + XbShape<DT>::TRANS;                         // [32*DT][TB]
+    float* lse_s = reinterpret_cast<float*>(dOt + XbShape<DT>::TRANS);     // [CH]
+    float* dl_s = lse_s + CH;                                               // [CH]
+
+    const float* qb = a.q + bi * a.qsb + hi * a.qsh;
+    const float* kb = a.k + bi * a.ksb + hi * a.ksh;
+    const float* vb = a.v + bi * a.vsb + hi * a.vsh;
+    const float* dob = a.d_o + bi * a.osb + hi * a.osh;
+    float* dkb = a.dk + bi * a.ksb + hi * a.ksh;
+    float* dvb = a.dv + bi * a.vsb + hi * a.vsh;
+    const unsigned char* mb = a.mask ? a.mask + bi * a.msb + hi * a.msh : nullptr;
+    const float sc2 = a.scale * LOG2E_X;
+
+    const int jt = blockIdx.y * XW + wave;
+    const int key = jt * 32 + l31;
+    const bool k_ok = jt < a.nkt && key < a.Nk;
+    bf16x8_t kf[2 * DT], vf[2 * DT];
+#pragma unroll
+    for (int ks = 0; ks < 2 * DT; ++ks) {
+        kf[ks] = xb_grow8(kb + (long long)(k_ok ? key : 0) * a.ksn, 16 * ks + 8 * hf, D, k_ok, a.vec);
+        vf[ks] = xb_grow8(vb + (long long)(k_ok ? key : 0) * a.vsn, 16 * ks + 8 * hf, D, k_ok, a.vec);
+    }
+
+    f32x16 dkacc[DT], dvacc[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            dkacc[dt][r] = 0.0f;
+            dvacc[dt][r] = 0.0f;
+        }
+    for (int qc = 0; qc < a.nqt; qc += XCH) {
+        __syncthreads();
+        xb_fill<DT, XB_THR, true, true>(Qr, Qt, qb, a.qsn, qc * 32, a.Nq, D, tid, a.vec);
+        xb_fill<DT, XB_THR, true, true>(dOr, dOt, dob, a.osn, qc * 32, a.Nq, D, tid, a.vec);
+        for (int n = tid; n < CH; n += XB_THR) {
+            const int qn = qc * 32 + n;
+            lse_s[n] = (qn < a.Nq) ? a.lse_in[(long long)bh * a.Nq + qn] * LOG2E_X : INFINITY;      // exp2(-inf) = 0 on pad rows
+            dl_s[n] = (qn < a.Nq) ? a.delta_in[(long long)bh * a.Nq + qn] : 0.0f;
+        }
+        __syncthreads();
+        for (int qq = 0; qq < XCH && qc + qq < a.nqt; ++qq) {
+            f32x16 sacc, pacc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                sacc[r] = 0.0f;
+                pacc[r] = 0.0f;
+            }
+            const unsigned short* qp = Qr + (qq * 32 + l31) * RB + 8 * hf;
+            const unsigned short* dp = dOr + (qq * 32 + l31) * RB + 8 * hf;
+#pragma unroll
+            for (int ks = 0; ks < 2 * DT; ++ks) {
+                sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(qp + 16 * ks), kf[ks], sacc, 0, 0, 0);  // S[q][key]
+                pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(dp + 16 * ks), vf[ks], pacc, 0, 0, 0);  // dP[q][key]
+            }
+            const unsigned db = x_dead_bits<false>(a, mb, key, (qc + qq) * 32, hf);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int ql = qq * 32 + kv_acc_row(r, hf), qrow = qc * 32 + ql;
+                float p = exp2f(sacc[r] * sc2 - lse_s[ql]);
+                if (jt >= a.nkt || qrow >= a.Nq || ((db >> r) & 1u)) p = 0.0f;          // select, never multiply: exp2 may be inf on a dead row
+                sacc[r] = p;
+                pacc[r] = p == 0.0f ? 0.0f : p * a.scale * (pacc[r] - dl_s[ql]);
+            }
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                const bf16x8_t pb = kv_acc8(sacc, s2), sb = kv_acc8(pacc, s2);
+                const int off = l31 * TB + qq * 32 + 16 * s2 + 8 * hf;
+#pragma unroll
+                for (int dt = 0; dt < DT; ++dt) {
+                    dvacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(dOt + off + dt * 32 * TB), pb, dvacc[dt], 0, 0, 0);
+                    dkacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Qt + off + dt * 32 * TB), sb, dkacc[dt], 0, 0, 0);
+                }
+            }
+        }
+    }
+    if (k_ok) {
+        xb_store_row<DT>(dkb + (long long)key * a.ksn, dkacc, 1.0f, D, hf, a.vec && ((uintptr_t)dkb % 16 == 0));
+        xb_store_row<DT>(dvb + (long long)key * a.vsn, dvacc, 1.0f, D, hf, a.vec && ((uintptr_t)dvb % 16 == 0));
+    }
+}
+
+// dQ: query-stationary, as attn_x_bwd_q_kernel.  Own Q, dO rows as bf16 fragments; K, V chunks as rows, K also transposed (dQ^T).
+template <int DT>
+__global__ __launch_bounds__(XB_THR) void attn_x_bwd_q_bf16_kernel(const AttnXArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int RB = XbShape<DT>::RB, TB = XbShape<DT>::TB, XW = XB_THR / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hf = lane >> 5;
+    const int bh = blockIdx.x, bi = bh / a.H, hi = bh - bi * a.H;
+    const int D = a.D, nkt = a.nkt;
+    unsigned short* Kr = reinterpret_cast<unsigned short*>(smem);         // [CH][RB]
+    unsigned short* Vr = Kr + XbShape<DT>::ROWS;                           // [CH][RB]
+    unsigned short* Kt = Vr + XbShape<DT>::ROWS;                           // [32*DT][TB]
+
+    const float* qb = a.q + bi * a.qsb + hi * a.qsh;
+    const float* kb = a.k + bi * a.ksb + hi * a.ksh;
+    const float* vb = a.v + bi * a.vsb + hi * a.vsh;
+    const float* dob = a.d_o + bi * a.osb + hi * a.osh;
+    float* dqb = a.dq + bi * a.qsb + hi * a.qsh;
+    const unsigned char* mb = a.mask ? a.mask + bi * a.msb + hi * a.msh : nullptr;
+    const float sc2 = a.scale * LOG2E_X;
+
+    const int qt = blockIdx.y * XW + wave;
+    const int qrow = qt * 32 + l31;
+    const bool q_ok = (qt < a.nqt) && (qrow < a.Nq);
+    bf16x8_t qf[2 * DT], dof[2 * DT];
+#pragma unroll
+    for (int ks = 0; ks < 2 * DT; ++ks) {
+        qf[ks] = xb_grow8(qb + (long long)(q_ok ? qrow : 0) * a.qsn, 16 * ks + 8 * hf, D, q_ok, a.vec);
+        dof[ks] = xb_grow8(dob + (long long)(q_ok ? qrow : 0) * a.osn, 16 * ks + 8 * hf, D, q_ok, a.vec);
+    }
+    const float lse2 = q_ok ? a.lse_in[(long long)bh * a.Nq + qrow] * LOG2E_X : INFINITY;
+    const float dl = q_ok ? a.delta_in[(long long)bh * a.Nq + qrow] : 0.0f;
+
+    f32x16 dqacc[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dqacc[dt][r] = 0.0f;
+    for (int kc = 0; kc < nkt; kc += XCH) {
+        __syncthreads();
+        xb_fill<DT, XB_THR, true, true>(Kr, Kt, kb, a.ksn, kc * 32, a.Nk, D, tid, a.vec);
+        xb_fill<DT, XB_THR, true, false>(Vr, nullptr, vb, a.vsn, kc * 32, a.Nk, D, tid, a.vec);
+        __syncthreads();
+        for (int j = 0; j < XCH && kc + j < nkt; ++j) {
+            f32x16 sacc, pacc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                sacc[r] = 0.0f;
+                pacc[r] = 0.0f;
+            }
+            const unsigned short* kp = Kr + (j * 32 + l31) * RB + 8 * hf;
+            const unsigned short* vp = Vr + (j * 32 + l31) * RB + 8 * hf;
+#pragma unroll
+            for (int ks = 0; ks < 2 * DT; ++ks) {
+                sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(kp + 16 * ks), qf[ks], sacc, 0, 0, 0);   // S^T[key][q]
+                pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(vp + 16 * ks), dof[ks], pacc, 0, 0, 0);  // dP^T[key][q]
+            }
+            const unsigned db = x_dead_bits<true>(a, mb, qrow, (kc + j) * 32, hf);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p = exp2f(sacc[r] * sc2 - lse2);
+                const bool dead = !q_ok || ((db >> r) & 1u);
+                pacc[r] = dead ? 0.0f : p * a.scale * (pacc[r] - dl);                             // dS^T
+            }
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                const bf16x8_t sb = kv_acc8(pacc, s2);
+                const unsigned short* kt = Kt + l31 * TB + j * 32 + 16 * s2 + 8 * hf;
+#pragma unroll
+                for (int dt = 0; dt < DT; ++dt)
+                    dqacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(kt + dt * 32 * TB), sb, dqacc[dt], 0, 0, 0);
+            }
+        }
+    }
+    if (q_ok) xb_store_row<DT>(dqb + (long long)qrow * a.qsn, dqacc, 1.0f, D, hf, a.vec && ((uintptr_t)dqb % 16 == 0));
+}
+
 int x_check(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const char* who) {
     if (!d || !e) return kv_fail(KANVIT_EINVAL, "%s: null descriptor", who);
     if (d->B < 0 || d->H < 1 || d->N < 1 || e->Nk < 1 || d->D < 1) return kv_fail(KANVIT_EINVAL, "%s: bad sizes", who);
@@ -450,7 +854,9 @@ int x_check(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const char* who
     if (!(d->scale > 0.0f)) return kv_fail(KANVIT_EINVAL, "%s: scale=%g must be positive (the running maximum is taken over the raw scores)", who, (double)d->scale);
     if (d->causal && e->Nk > d->N)
         return kv_fail(KANVIT_EINVAL, "%s: causal with k_len=%d > q_len=%d is ill-defined in the reference (utils.py:169,183: the first k_len - q_len queries see no key)", who, e->Nk, d->N);
-    if (d->flags & KANVIT_FLAG_BF16_MFMA) return kv_fail(KANVIT_EINVAL, "%s: the general attention kernels are exact fp32 (no KANVIT_FLAG_BF16_MFMA)", who);
+    if ((d->flags & KANVIT_FLAG_BF16_MFMA) && d->D > KANVIT_ATTN_MAX_D)
+        return kv_fail(KANVIT_EINVAL, "%s: KANVIT_FLAG_BF16_MFMA covers D <= %d in the general attention kernels; D=%d runs exact fp32 only (pass no flag)",
+                       who, KANVIT_ATTN_MAX_D, d->D);
     if ((long long)(d->N + 127) / 128 > 65535 || (long long)(e->Nk + 127) / 128 > 65535) return kv_fail(KANVIT_EINVAL, "%s: sequence too long for one launch", who);
     return 0;
 }
@@ -504,6 +910,32 @@ int x_launch_bwd(const AttnXArgs& a, hipStream_t st) {
     return 0;
 }
 
+// bf16 twins: LDS of the three kernels (bf16 images; the dK/dV kernel also keeps the chunk's lse and delta)
+template <int DT>
+int xb_launch_fwd(const AttnXArgs& a, hipStream_t st) {
+    constexpr int XW = XB_THR / 64;
+    constexpr size_t lds = 2 * ((size_t)XbShape<DT>::ROWS + XbShape<DT>::TRANS);
+    KV_ALLOW_LDS(lds, (attn_x_fwd_bf16_kernel<DT>));
+    hipLaunchKernelGGL((attn_x_fwd_bf16_kernel<DT>), dim3((unsigned)(a.B * a.H), (unsigned)((a.nqt + XW - 1) / XW)), dim3(XB_THR), lds, st, a);
+    KV_LAUNCH_CHECK("attn_x_fwd_bf16_kernel");
+    return 0;
+}
+
+template <int DT>
+int xb_launch_bwd(const AttnXArgs& a, hipStream_t st) {
+    constexpr int XW = XB_THR / 64;
+    constexpr size_t lds_kv = 2 * (2 * (size_t)XbShape<DT>::ROWS + 2 * (size_t)XbShape<DT>::TRANS) + sizeof(float) * 2 * XCH * 32;
+    constexpr size_t lds_q = 2 * (2 * (size_t)XbShape<DT>::ROWS + XbShape<DT>::TRANS);
+    static_assert(lds_kv <= 160 * 1024 && (2 * (2 * (size_t)XbShape<DT>::ROWS + 2 * (size_t)XbShape<DT>::TRANS)) % 16 == 0, "dK/dV LDS");
+    KV_ALLOW_LDS(lds_kv, (attn_x_bwd_kv_bf16_kernel<DT>));
+    KV_ALLOW_LDS(lds_q, (attn_x_bwd_q_bf16_kernel<DT>));
+    hipLaunchKernelGGL((attn_x_bwd_kv_bf16_kernel<DT>), dim3((unsigned)(a.B * a.H), (unsigned)((a.nkt + XW - 1) / XW)), dim3(XB_THR), lds_kv, st, a);
+    KV_LAUNCH_CHECK("attn_x_bwd_kv_bf16_kernel");
+    hipLaunchKernelGGL((attn_x_bwd_q_bf16_kernel<DT>), dim3((unsigned)(a.B * a.H), (unsigned)((a.nqt + XW - 1) / XW)), dim3(XB_THR), lds_q, st, a);
+    KV_LAUNCH_CHECK("attn_x_bwd_q_bf16_kernel");
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -517,6 +949,7 @@ int kanvit_attn_x_fwd(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const
     a.q = q; a.k = k; a.v = v; a.out = o; a.lse = lse;
     a.vec = a.vec && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0);
     hipStream_t st = (hipStream_t)stream;
+    if (d->flags & KANVIT_FLAG_BF16_MFMA) return d->D <= 32 ? xb_launch_fwd<1>(a, st) : xb_launch_fwd<2>(a, st);     // x_check: D <= 64
     return d->D <= 32 ? x_launch_fwd<1>(a, st) : d->D <= 64 ? x_launch_fwd<2>(a, st) : d->D <= 96 ? x_launch_fwd<3>(a, st) : x_launch_fwd<4>(a, st);
 }
 
@@ -541,6 +974,7 @@ int kanvit_attn_x_bwd(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const
     const long long rows = (long long)d->B * d->H * d->N;
     hipLaunchKernelGGL(attn_x_delta_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, a);
     KV_LAUNCH_CHECK("attn_x_delta_kernel");
+    if (d->flags & KANVIT_FLAG_BF16_MFMA) return d->D <= 32 ? xb_launch_bwd<1>(a, st) : xb_launch_bwd<2>(a, st);
     return d->D <= 32 ? x_launch_bwd<1>(a, st) : d->D <= 64 ? x_launch_bwd<2>(a, st) : d->D <= 96 ? x_launch_bwd<3>(a, st) : x_launch_bwd<4>(a, st);
 }
 

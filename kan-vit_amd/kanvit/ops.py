@@ -511,9 +511,16 @@ def _attn_fits_one_workgroup(N: int, D: int) -> bool:
     return N <= 256 and 4 * (2 * npad * ks + 2 * npad + 4 * 32 * ks) <= 160 * 1024
 
 
+def _attn_x_flags(flags: int, D: int) -> int:
+    """The flags a head routed to the general kernels takes: their bf16 twins cover D <= 64 (KANVIT_ATTN_MAX_D); wider heads run
+    exact fp32 with or without autocast.  The forward and the backward of one head derive the same flags, as they must (lse
+    of one mode is not valid input to the other's backward)."""
+    return flags & _lib.FLAG_BF16_MFMA if D <= 64 else 0
+
+
 def _attn_fwd(q, k, v, o, causal, scale, flags=0):
     if q.dim() == 4 and tuple(k.shape) == tuple(q.shape) and not _attn_fits_one_workgroup(q.shape[2], q.shape[3]):
-        return _attn_x_fwd(q, k, v, o, None, causal, scale)
+        return _attn_x_fwd(q, k, v, o, None, causal, scale, flags=_attn_x_flags(flags, q.shape[3]))
     B, H, N, _ = q.shape
     lse = torch.empty(B, H, N, device=q.device, dtype=torch.float32)
     d = _attn_desc(q, k, v, o, causal, scale, flags)
@@ -526,7 +533,7 @@ def _attn_fwd(q, k, v, o, causal, scale, flags=0):
 
 def _attn_bwd(q, k, v, o, lse, do, dq, dk, dv, causal, scale, flags=0):
     if q.dim() == 4 and tuple(k.shape) == tuple(q.shape) and not _attn_fits_one_workgroup(q.shape[2], q.shape[3]):
-        return _attn_x_bwd(q, k, v, o, lse, do, dq, dk, dv, None, causal, scale)
+        return _attn_x_bwd(q, k, v, o, lse, do, dq, dk, dv, None, causal, scale, flags=_attn_x_flags(flags, q.shape[3]))
     d = _attn_desc(q, k, v, o, causal, scale, flags)
     if (do.stride() != o.stride()) or dq.stride() != q.stride() or dk.stride() != k.stride() or dv.stride() != v.stride():
         raise KanvitError("attention backward: gradient layouts must match their forward tensors")
@@ -541,7 +548,7 @@ def _attn_bwd(q, k, v, o, lse, do, dq, dk, dv, causal, scale, flags=0):
                                 _ptr(dv), _ptr(ws), C.c_size_t(nbytes), _stream()), "kanvit_attn_bwd")
 
 
-def _attn_x_desc(q, k, v, o, mask, causal: bool, scale: float):
+def _attn_x_desc(q, k, v, o, mask, causal: bool, scale: float, flags: int = 0):
     """Descriptor pair of the general attention kernels (kanvit_attn_x_*): q, o [B, H, Nq, D]; k, v [B, H, Nk, D]; mask None or a
     torch.bool tensor already expanded (views, no copy) to [B, H, Nq, Nk]."""
     for n, t in (("q", q), ("k", k), ("v", v), ("o", o)):
@@ -553,7 +560,7 @@ def _attn_x_desc(q, k, v, o, mask, causal: bool, scale: float):
     for n, t in (("q", q), ("k", k), ("v", v), ("o", o)):
         if t.stride(3) != 1:
             raise KanvitError(f"{n}: innermost dimension must be contiguous")
-    d = AttnDesc(B, H, Nq, D, int(bool(causal)), float(scale), 0, 0,
+    d = AttnDesc(B, H, Nq, D, int(bool(causal)), float(scale), int(flags), 0,
                  q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
                  v.stride(0), v.stride(1), v.stride(2), o.stride(0), o.stride(1), o.stride(2))
     if mask is None:
@@ -565,18 +572,20 @@ def _attn_x_desc(q, k, v, o, mask, causal: bool, scale: float):
     return d, e
 
 
-def _attn_x_fwd(q, k, v, o, mask, causal, scale):
+def _attn_x_fwd(q, k, v, o, mask, causal, scale, flags=0):
+    """flags = _lib.FLAG_BF16_MFMA runs the bf16 matrix-core twins (D <= 64); the backward must then take the same flags."""
     B, H, Nq, D = q.shape
     lse = torch.empty(B, H, Nq, device=q.device, dtype=torch.float32)
-    d, e = _attn_x_desc(q, k, v, o, mask, causal, scale)
+    d, e = _attn_x_desc(q, k, v, o, mask, causal, scale, flags)
     Nk = k.shape[2]
-    with torch.cuda.device(q.device), _timed("attn_x_fwd", 4 * B * H * Nq * Nk * D, 4 * 2 * B * H * (Nq + Nk) * D):
+    tag = "attn_x_fwd" + ("_bf16" if flags & _lib.FLAG_BF16_MFMA else "")
+    with torch.cuda.device(q.device), _timed(tag, 4 * B * H * Nq * Nk * D, 4 * 2 * B * H * (Nq + Nk) * D):
         check(_lib.lib().kanvit_attn_x_fwd(C.byref(d), C.byref(e), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _stream()), "kanvit_attn_x_fwd")
     return lse
 
 
-def _attn_x_bwd(q, k, v, o, lse, do, dq, dk, dv, mask, causal, scale):
-    d, e = _attn_x_desc(q, k, v, o, mask, causal, scale)
+def _attn_x_bwd(q, k, v, o, lse, do, dq, dk, dv, mask, causal, scale, flags=0):
+    d, e = _attn_x_desc(q, k, v, o, mask, causal, scale, flags)
     if (do.stride() != o.stride()) or dq.stride() != q.stride() or dk.stride() != k.stride() or dv.stride() != v.stride():
         raise KanvitError("attention backward: gradient layouts must match their forward tensors")
     L = _lib.lib()
@@ -584,7 +593,8 @@ def _attn_x_bwd(q, k, v, o, lse, do, dq, dk, dv, mask, causal, scale):
     ws = torch.empty(max(nbytes // 4, 1), device=q.device, dtype=torch.float32)
     B, H, Nq, D = q.shape
     Nk = k.shape[2]
-    with torch.cuda.device(q.device), _timed("attn_x_bwd", 14 * B * H * Nq * Nk * D, 4 * 4 * B * H * (Nq + Nk) * D):
+    tag = "attn_x_bwd" + ("_bf16" if flags & _lib.FLAG_BF16_MFMA else "")
+    with torch.cuda.device(q.device), _timed(tag, 14 * B * H * Nq * Nk * D, 4 * 4 * B * H * (Nq + Nk) * D):
         check(L.kanvit_attn_x_bwd(C.byref(d), C.byref(e), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _ptr(do), _ptr(dq), _ptr(dk),
                                   _ptr(dv), _ptr(ws), C.c_size_t(nbytes), _stream()), "kanvit_attn_x_bwd")
 
@@ -652,8 +662,9 @@ def _autocast_flags() -> int:
 
 def attention_packed(qkv: torch.Tensor, causal: bool = False, scale: Optional[float] = None) -> torch.Tensor:
     """Self-attention on qkv[B, N, 3, H, D] -> o[B, N, H*D].  D even and <= 128.  Heads of D <= 64 that fit one work-group run the
-    ViT kernels (on the bf16 matrix cores under bf16 autocast); longer sequences and heads wider than 64 run the exact-fp32 general
-    kernels, with or without autocast (they take no KANVIT_FLAG_BF16_MFMA)."""
+    ViT kernels, longer sequences the chunked general kernels; under bf16 autocast both run on the bf16 matrix cores
+    (KANVIT_FLAG_BF16_MFMA).  Heads wider than 64 run the exact-fp32 general kernels, with or without autocast (the general
+    kernels' bf16 twins cover D <= 64)."""
     return _AttnPackedFn.apply(qkv, causal, qkv.shape[-1] ** -0.5 if scale is None else scale, _autocast_flags())
 
 
