@@ -516,12 +516,6 @@ __global__ __launch_bounds__(BF ? 256 : 512, 2) void attn_fwd2_kernel(const Attn
 // AGPR <-> VGPR copies of the accumulators (all three measured) -- that is the open item.
 // =============================================================================================
 constexpr int kv_pad4(int d) { return d + 4; }
-// persistent kernels: as many work-groups as are resident at once (LDS-limited), never more than heads
-inline int kv_persistent_grid(int nbh, size_t lds_bytes) {
-    const int per_cu = lds_bytes * 2 <= 160 * 1024 ? 2 : 1;
-    const int g = kv_config().attn_grid > 0 ? kv_config().attn_grid : KV_N_CU * per_cu;      // KANVIT_ATTN_GRID: tuning knob
-    return nbh < g ? nbh : g;
-}
 
 #ifdef KANVIT_CLOCK_PROBE
 #ifndef KV_CLK_TID
@@ -2161,6 +2155,15 @@ int check_desc(const kanvit_attn_desc* d, const char* who) {
     return 0;
 }
 
+// float4 rows: D and every stride a multiple of four floats (the 16-byte alignment of the pointers is the caller's to add)
+bool desc_vec(const kanvit_attn_desc* d) {
+    bool vec = d->D % 4 == 0;
+    for (long long sd : {d->q_stride_b, d->q_stride_h, d->q_stride_n, d->k_stride_b, d->k_stride_h, d->k_stride_n,
+                         d->v_stride_b, d->v_stride_h, d->v_stride_n, d->o_stride_b, d->o_stride_h, d->o_stride_n})
+        vec = vec && (sd % 4 == 0);
+    return vec;
+}
+
 AttnArgs make_args(const kanvit_attn_desc* d) {
     AttnArgs a{};
     a.B = d->B; a.H = d->H; a.N = d->N; a.D = d->D; a.causal = d->causal; a.scale = d->scale;
@@ -2169,208 +2172,86 @@ AttnArgs make_args(const kanvit_attn_desc* d) {
     a.ksb = d->k_stride_b; a.ksh = d->k_stride_h; a.ksn = d->k_stride_n;
     a.vsb = d->v_stride_b; a.vsh = d->v_stride_h; a.vsn = d->v_stride_n;
     a.osb = d->o_stride_b; a.osh = d->o_stride_h; a.osn = d->o_stride_n;
-    const long long strides[] = {a.qsb, a.qsh, a.qsn, a.ksb, a.ksh, a.ksn, a.vsb, a.vsh, a.vsn, a.osb, a.osh, a.osn};
-    a.vec = (d->D % 4 == 0);
-    for (long long sd : strides) a.vec = a.vec && (sd % 4 == 0);
+    a.vec = desc_vec(d);
     return a;
 }
 
-template <int DT, int NKT, bool BF>
-int launch_fwd(const AttnArgs& a, hipStream_t st) {
-    constexpr int KS = 32 * DT + 1;
-    const size_t lds = sizeof(float) * ((size_t)2 * a.nkt * 32 * KS + (size_t)4 * 32 * KS);
-    KV_ALLOW_LDS(160 * 1024, attn_fwd_kernel<DT, NKT, BF>);
-    hipLaunchKernelGGL((attn_fwd_kernel<DT, NKT, BF>), dim3((unsigned)(a.B * a.H)), dim3(ATHR), lds, st, a);
-    KV_LAUNCH_CHECK("attn_fwd_kernel");
+// f(std::integral_constant<int, K>) for the K of the list that equals v: a bucket of the plan becomes a template argument
+template <int... K, typename F>
+int kv_pick(int v, F&& f) {
+    int rc = 0;
+    const bool hit = ((v == K && ((rc = f(std::integral_constant<int, K>{})), true)) || ...);
+    return hit ? rc : kv_fail(KANVIT_EINVAL, "attention: no kernel instance for %d", v);
+}
+
+// one launch: the LDS opt-in of this kernel, the launch, its error check
+template <auto KERNEL>
+int kv_launch(const char* name, unsigned grid, int threads, size_t lds, const AttnArgs& a, hipStream_t st) {
+    KV_ALLOW_LDS(160 * 1024, KERNEL);
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3((unsigned)threads), lds, st, a);
+    KV_LAUNCH_CHECK(name);
     return 0;
 }
 
-template <int DT, int NKT, bool BF>
-int launch_fwd2(const AttnArgs& a, hipStream_t st) {
-    constexpr int D = 32 * DT;
-    const int NP = a.nkt * 32;
-    const size_t lds = BF ? sizeof(unsigned short) * ((size_t)NP * (D + 8) + (size_t)D * (NP + 8))
-                          : sizeof(float) * (size_t)2 * NP * (D + 1);
-    KV_ALLOW_LDS(160 * 1024, attn_fwd2_kernel<DT, NKT, BF>);
-    hipLaunchKernelGGL((attn_fwd2_kernel<DT, NKT, BF>), dim3((unsigned)(a.B * a.H)), dim3(BF ? 256 : 512), lds, st, a);
-    KV_LAUNCH_CHECK("attn_fwd2_kernel");
-    return 0;
+// the fourth to first forms of the forward; the plan's bucket and precision pick the instance
+int launch_fwd(const AttnArgs& a, const AttnFwdPlan& p, hipStream_t st) {
+    return kv_pick<1, 2>(a.D <= 32 ? 1 : 2, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        switch (p.form) {
+            case ATTN_FWD_FOURTH:
+                return kv_pick<4, 7>(p.nkt, [&](auto n) { return kv_launch<attn_fwd4_kernel<2, decltype(n)::value>>("attn_fwd4_kernel", p.grid, KV_A3_THREADS, p.lds, a, st); });
+            case ATTN_FWD_THIRD:
+                return kv_pick<1, 2, 4, 7>(p.nkt, [&](auto n) { return kv_launch<attn_fwd3_kernel<DT, decltype(n)::value>>("attn_fwd3_kernel", p.grid, KV_A3_THREADS, p.lds, a, st); });
+            case ATTN_FWD_SECOND:
+                return kv_pick<1, 2, 4, 7>(p.nkt, [&](auto n) {
+                    constexpr int NKT = decltype(n)::value;
+                    return p.bf16 ? kv_launch<attn_fwd2_kernel<DT, NKT, true>>("attn_fwd2_kernel", p.grid, 256, p.lds, a, st)
+                                  : kv_launch<attn_fwd2_kernel<DT, NKT, false>>("attn_fwd2_kernel", p.grid, 512, p.lds, a, st);
+                });
+            default:
+                return kv_pick<1, 2, 4, 7, 8>(p.nkt, [&](auto n) {
+                    constexpr int NKT = decltype(n)::value;
+                    return p.bf16 ? kv_launch<attn_fwd_kernel<DT, NKT, true>>("attn_fwd_kernel", p.grid, ATHR, p.lds, a, st)
+                                  : kv_launch<attn_fwd_kernel<DT, NKT, false>>("attn_fwd_kernel", p.grid, ATHR, p.lds, a, st);
+                });
+        }
+    });
 }
 
-template <int DT, int NKT>
-int launch_fwd3(const AttnArgs& a, hipStream_t st) {
-    const size_t lds = sizeof(float) * (size_t)2 * a.nkt * 32 * kv_pad4(32 * DT);
-    KV_ALLOW_LDS(160 * 1024, attn_fwd3_kernel<DT, NKT>);
-    hipLaunchKernelGGL((attn_fwd3_kernel<DT, NKT>), dim3((unsigned)kv_persistent_grid(a.B * a.H, lds)), dim3(KV_A3_THREADS), lds, st, a);
-    KV_LAUNCH_CHECK("attn_fwd3_kernel");
-    return 0;
+// every two-kernel backward: the key-stationary kernel, then the query-stationary / dQ kernel
+template <auto KV, auto DQ>
+int launch_pair(const char* kv_name, const char* dq_name, int threads, const AttnArgs& a, const AttnBwdPlan& p, hipStream_t st) {
+    if (int rc = kv_launch<KV>(kv_name, p.grid, threads, p.lds, a, st)) return rc;
+    return kv_launch<DQ>(dq_name, p.grid_q, threads, p.lds_q, a, st);
 }
 
-template <int NKT>
-int launch_fwd4(const AttnArgs& a, hipStream_t st) {
-    const size_t lds = kv_a4_lds(a.N, 64);
-    KV_ALLOW_LDS(160 * 1024, (attn_fwd4_kernel<2, NKT>));
-    const int nbh = a.B * a.H;
-    const int g = kv_config().attn_grid > 0 ? kv_config().attn_grid : KV_N_CU;       // one work-group per CU (three images fill its LDS)
-    hipLaunchKernelGGL((attn_fwd4_kernel<2, NKT>), dim3((unsigned)(nbh < g ? nbh : g)), dim3(KV_A3_THREADS), lds, st, a);
-    KV_LAUNCH_CHECK("attn_fwd4_kernel");
-    return 0;
-}
-
-template <int DT, bool BF>
-int dispatch_fwd(const AttnArgs& a, hipStream_t st) {
-    if constexpr (!BF && DT == 2) {
-        // 16-row tiles (round 4, csrc/attention16.hip): D = 64, 64 < N <= 204
-        if (!kv_config().attn_v1 && !kv_config().attn_v2 && !kv_config().attn_v3) {
-            const int rc = kv_attn16_fwd(a, st);
-            if (rc <= 0) return rc;
+int launch_bwd(const AttnArgs& a, const AttnBwdPlan& p, hipStream_t st) {
+    return kv_pick<1, 2>(a.D <= 32 ? 1 : 2, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        switch (p.form) {
+            case ATTN_BWD_KV4_DQ3:
+                return kv_pick<4, 8>(p.nkt, [&](auto n) {
+                    return launch_pair<attn_bwd_kv4_kernel<2>, attn_bwd_dq3_kernel<2, decltype(n)::value>>("attn_bwd_kv4_kernel", "attn_bwd_dq3_kernel", 512, a, p, st);
+                });
+            case ATTN_BWD_KV3_DQ3:
+                return kv_pick<2, 4, 8>(p.nkt, [&](auto n) {
+                    constexpr int NKT = decltype(n)::value;
+                    return launch_pair<attn_bwd_kv3_kernel<DT, NKT>, attn_bwd_dq3_kernel<DT, NKT>>("attn_bwd_kv3_kernel", "attn_bwd_dq3_kernel", 512, a, p, st);
+                });
+            case ATTN_BWD_KV2DS_DQ:
+                return launch_pair<attn_bwd_kv2_kernel<DT, false, true>, attn_bwd_dq_kernel<DT>>("attn_bwd_kv2_kernel", "attn_bwd_dq_kernel", 512, a, p, st);
+            case ATTN_BWD_KV2DS_DQ_BF16:
+                return kv_pick<4, 8>(p.nkt, [&](auto n) {
+                    return launch_pair<attn_bwd_kv2_kernel<DT, true, true>, attn_bwd_dq_bf16_kernel<DT, decltype(n)::value>>("attn_bwd_kv2_kernel", "attn_bwd_dq_bf16_kernel", 512, a, p, st);
+                });
+            case ATTN_BWD_KV2_Q2:
+                return p.bf16 ? launch_pair<attn_bwd_kv2_kernel<DT, true, false>, attn_bwd_q2_kernel<DT, true>>("attn_bwd_kv2_kernel", "attn_bwd_q2_kernel", 512, a, p, st)
+                              : launch_pair<attn_bwd_kv2_kernel<DT, false, false>, attn_bwd_q2_kernel<DT, false>>("attn_bwd_kv2_kernel", "attn_bwd_q2_kernel", 512, a, p, st);
+            default:
+                return p.bf16 ? launch_pair<attn_bwd_kv_kernel<DT, true>, attn_bwd_q_kernel<DT, true>>("attn_bwd_kv_kernel", "attn_bwd_q_kernel", ATHR, a, p, st)
+                              : launch_pair<attn_bwd_kv_kernel<DT, false>, attn_bwd_q_kernel<DT, false>>("attn_bwd_kv_kernel", "attn_bwd_q_kernel", ATHR, a, p, st);
         }
-        // fourth form: D = 64, 64 < N (below, a head is a few tiles and the third form's single fill is cheap), three swizzled
-        // images within the 160 KiB, 16-byte aligned rows for the LDS-DMA fills
-        if (a.vec && a.D == 64 && a.nkt >= 3 && a.nkt <= 7 && kv_a4_lds(a.N, 64) <= 160 * 1024 && !kv_config().attn_v1 && !kv_config().attn_v2 &&
-            !kv_config().attn_v3 && (((uintptr_t)a.out | (uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 16 == 0)) {
-            if (a.nkt <= 4) return launch_fwd4<4>(a, st);
-            return launch_fwd4<7>(a, st);
-        }
-    }
-    if constexpr (BF && DT == 2) {      // bf16 matrix cores on the 16-row-tile structure (round 4): N = 193 .. 204
-        if (!kv_config().attn_v1 && !kv_config().attn_v2 && !kv_config().attn_v3) {
-            const int rc = kv_attn16_fwd_bf16(a, st);
-            if (rc <= 0) return rc;
-        }
-    }
-    if constexpr (!BF) {
-        if (a.vec && a.D == 32 * DT && ((uintptr_t)a.out % 16 == 0) && !kv_config().attn_v1 && !kv_config().attn_v2) {
-            if (a.nkt <= 1) return launch_fwd3<DT, 1>(a, st);
-            if (a.nkt <= 2) return launch_fwd3<DT, 2>(a, st);
-            if (a.nkt <= 4) return launch_fwd3<DT, 4>(a, st);
-            if (a.nkt <= 7) return launch_fwd3<DT, 7>(a, st);
-        }
-    }
-    if (a.vec && a.D == 32 * DT && ((uintptr_t)a.out % 16 == 0) && !kv_config().attn_v1) {
-        if (a.nkt <= 1) return launch_fwd2<DT, 1, BF>(a, st);
-        if (a.nkt <= 2) return launch_fwd2<DT, 2, BF>(a, st);
-        if (a.nkt <= 4) return launch_fwd2<DT, 4, BF>(a, st);
-        if (a.nkt <= 7) return launch_fwd2<DT, 7, BF>(a, st);
-    }
-    if (a.nkt <= 1) return launch_fwd<DT, 1, BF>(a, st);
-    if (a.nkt <= 2) return launch_fwd<DT, 2, BF>(a, st);
-    if (a.nkt <= 4) return launch_fwd<DT, 4, BF>(a, st);
-    if (a.nkt <= 7) return launch_fwd<DT, 7, BF>(a, st);
-    return launch_fwd<DT, 8, BF>(a, st);
-}
-
-template <int DT, bool BF>
-int launch_bwd2(const AttnArgs& a, hipStream_t st) {
-    constexpr int D = 32 * DT;
-    const int NP = a.nkt * 32;
-    const size_t row = sizeof(unsigned short) * (size_t)NP * (D + 8), tr = sizeof(unsigned short) * (size_t)D * (NP + 8);
-    const size_t f32img = sizeof(float) * (size_t)NP * (D + 1);
-    const size_t lds_kv = (BF ? 2 * row + 2 * tr : 2 * f32img) + sizeof(float) * 2 * (size_t)NP;
-    const size_t lds_q = BF ? 2 * row + tr : 2 * f32img;
-    KV_ALLOW_LDS(160 * 1024, (attn_bwd_kv2_kernel<DT, BF, false>));
-    KV_ALLOW_LDS(160 * 1024, (attn_bwd_q2_kernel<DT, BF>));
-    if constexpr (!BF) {
-        if constexpr (DT == 2) {
-            // fourth form of the key-stationary kernel (LDS-DMA ring, loader wave): D = 64, 64 < N, a wave without a key tile
-            if (a.ds && a.third && a.nkt >= 3 && a.nkt <= 7 && kv_b4_lds(a.N, D) <= 160 * 1024 && !kv_config().attn_v3 &&
-                (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.o | (uintptr_t)a.d_o) % 16 == 0)) {
-                const size_t lds4 = kv_b4_lds(a.N, D), ldsq = sizeof(float) * (size_t)NP * kv_pad4(D);
-                const int nbh = a.B * a.H;
-                const int g4 = kv_config().attn_grid > 0 ? kv_config().attn_grid : KV_N_CU;
-                if (a.nkt <= 4) {
-                    KV_ALLOW_LDS(160 * 1024, (attn_bwd_kv4_kernel<2>));
-                    KV_ALLOW_LDS(160 * 1024, (attn_bwd_dq3_kernel<DT, 4>));
-                    hipLaunchKernelGGL((attn_bwd_kv4_kernel<2>), dim3((unsigned)(nbh < g4 ? nbh : g4)), dim3(512), lds4, st, a);
-                    KV_LAUNCH_CHECK("attn_bwd_kv4_kernel");
-                    hipLaunchKernelGGL((attn_bwd_dq3_kernel<DT, 4>), dim3((unsigned)kv_persistent_grid(nbh, ldsq)), dim3(512), ldsq, st, a);
-                } else {
-                    KV_ALLOW_LDS(160 * 1024, (attn_bwd_kv4_kernel<2>));
-                    KV_ALLOW_LDS(160 * 1024, (attn_bwd_dq3_kernel<DT, 8>));
-                    hipLaunchKernelGGL((attn_bwd_kv4_kernel<2>), dim3((unsigned)(nbh < g4 ? nbh : g4)), dim3(512), lds4, st, a);
-                    KV_LAUNCH_CHECK("attn_bwd_kv4_kernel");
-                    hipLaunchKernelGGL((attn_bwd_dq3_kernel<DT, 8>), dim3((unsigned)kv_persistent_grid(nbh, ldsq)), dim3(512), ldsq, st, a);
-                }
-                KV_LAUNCH_CHECK("attn_bwd_dq3_kernel");
-                return 0;
-            }
-        }
-        if (a.ds && a.third) {      // third form: same dS hand-off, pipelined LDS reads, rowsum(dO*O) in the prologue
-            const size_t lds3 = sizeof(float) * ((size_t)2 * NP * kv_pad4(D) + 2 * (size_t)NP);
-            const size_t ldsq = sizeof(float) * (size_t)NP * kv_pad4(D);
-            const int nbh = a.B * a.H;
-            if (a.nkt <= 2) {
-                KV_ALLOW_LDS(160 * 1024, (attn_bwd_kv3_kernel<DT, 2>));
-                KV_ALLOW_LDS(160 * 1024, (attn_bwd_dq3_kernel<DT, 2>));
-                hipLaunchKernelGGL((attn_bwd_kv3_kernel<DT, 2>), dim3((unsigned)kv_persistent_grid(nbh, lds3)), dim3(512), lds3, st, a);
-                KV_LAUNCH_CHECK("attn_bwd_kv3_kernel");
-                hipLaunchKernelGGL((attn_bwd_dq3_kernel<DT, 2>), dim3((unsigned)kv_persistent_grid(nbh, ldsq)), dim3(512), ldsq, st, a);
-                KV_LAUNCH_CHECK("attn_bwd_dq3_kernel");
-            } else if (a.nkt <= 4) {
-                KV_ALLOW_LDS(160 * 1024, (attn_bwd_kv3_kernel<DT, 4>));
-                KV_ALLOW_LDS(160 * 1024, (attn_bwd_dq3_kernel<DT, 4>));
-                hipLaunchKernelGGL((attn_bwd_kv3_kernel<DT, 4>), dim3((unsigned)kv_persistent_grid(nbh, lds3)), dim3(512), lds3, st, a);
-                KV_LAUNCH_CHECK("attn_bwd_kv3_kernel");
-                hipLaunchKernelGGL((attn_bwd_dq3_kernel<DT, 4>), dim3((unsigned)kv_persistent_grid(nbh, ldsq)), dim3(512), ldsq, st, a);
-                KV_LAUNCH_CHECK("attn_bwd_dq3_kernel");
-            } else {
-                KV_ALLOW_LDS(160 * 1024, (attn_bwd_kv3_kernel<DT, 8>));
-                KV_ALLOW_LDS(160 * 1024, (attn_bwd_dq3_kernel<DT, 8>));
-                hipLaunchKernelGGL((attn_bwd_kv3_kernel<DT, 8>), dim3((unsigned)kv_persistent_grid(nbh, lds3)), dim3(512), lds3, st, a);
-                KV_LAUNCH_CHECK("attn_bwd_kv3_kernel");
-                hipLaunchKernelGGL((attn_bwd_dq3_kernel<DT, 8>), dim3((unsigned)kv_persistent_grid(nbh, ldsq)), dim3(512), ldsq, st, a);
-                KV_LAUNCH_CHECK("attn_bwd_dq3_kernel");
-            }
-            return 0;
-        }
-        if (a.ds) {      // dS spill: the key-stationary kernel stores dS, dQ is one plain product (5 MFMA products instead of 7)
-            KV_ALLOW_LDS(160 * 1024, (attn_bwd_kv2_kernel<DT, false, true>));
-            KV_ALLOW_LDS(160 * 1024, (attn_bwd_dq_kernel<DT>));
-            hipLaunchKernelGGL((attn_bwd_kv2_kernel<DT, false, true>), dim3((unsigned)(a.B * a.H)), dim3(512), lds_kv, st, a);
-            KV_LAUNCH_CHECK("attn_bwd_kv2_kernel");
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<DT>), dim3((unsigned)(a.B * a.H)), dim3(512), f32img, st, a);
-            KV_LAUNCH_CHECK("attn_bwd_dq_kernel");
-            return 0;
-        }
-    }
-    if constexpr (BF) {
-        if (a.ds && a.nkt <= 8) {      // bf16 dS hand-off: the key-stationary kernel stores dS as bf16, dQ is one product (no recomputation)
-            KV_ALLOW_LDS(160 * 1024, (attn_bwd_kv2_kernel<DT, true, true>));
-            hipLaunchKernelGGL((attn_bwd_kv2_kernel<DT, true, true>), dim3((unsigned)(a.B * a.H)), dim3(512), lds_kv, st, a);
-            KV_LAUNCH_CHECK("attn_bwd_kv2_kernel");
-            if (a.nkt <= 4) hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<DT, 4>), dim3((unsigned)(a.B * a.H)), dim3(512), tr, st, a);
-            else hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<DT, 8>), dim3((unsigned)(a.B * a.H)), dim3(512), tr, st, a);
-            KV_LAUNCH_CHECK("attn_bwd_dq_bf16_kernel");
-            return 0;
-        }
-    }
-    hipLaunchKernelGGL((attn_bwd_kv2_kernel<DT, BF, false>), dim3((unsigned)(a.B * a.H)), dim3(512), lds_kv, st, a);
-    KV_LAUNCH_CHECK("attn_bwd_kv2_kernel");
-    hipLaunchKernelGGL((attn_bwd_q2_kernel<DT, BF>), dim3((unsigned)(a.B * a.H)), dim3(512), lds_q, st, a);
-    KV_LAUNCH_CHECK("attn_bwd_q2_kernel");
-    return 0;
-}
-
-template <int DT, bool BF>
-int launch_bwd(const AttnArgs& a, hipStream_t st) {
-    if (a.vec && a.D == 32 * DT && !kv_config().attn_v1 &&
-        (((uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv) % 16 == 0)) {
-        const int NPc = a.nkt * 32;
-        const size_t need = BF ? sizeof(unsigned short) * ((size_t)2 * NPc * (32 * DT + 8) + (size_t)2 * 32 * DT * (NPc + 8)) + 8 * (size_t)NPc
-                               : sizeof(float) * ((size_t)2 * NPc * (32 * DT + 1) + 2 * (size_t)NPc);
-        if (need <= 160 * 1024) return launch_bwd2<DT, BF>(a, st);
-    }
-    constexpr int KS = 32 * DT + 1;
-    const int NP = a.nkt * 32;
-    const size_t lds_kv = sizeof(float) * ((size_t)2 * NP * KS + 2 * (size_t)NP + (size_t)4 * 32 * KS);
-    const size_t lds_q = sizeof(float) * ((size_t)2 * NP * KS + (size_t)4 * 32 * KS);
-    KV_ALLOW_LDS(160 * 1024, (attn_bwd_kv_kernel<DT, BF>));
-    KV_ALLOW_LDS(160 * 1024, (attn_bwd_q_kernel<DT, BF>));
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<DT, BF>), dim3((unsigned)(a.B * a.H)), dim3(ATHR), lds_kv, st, a);
-    KV_LAUNCH_CHECK("attn_bwd_kv_kernel");
-    hipLaunchKernelGGL((attn_bwd_q_kernel<DT, BF>), dim3((unsigned)(a.B * a.H)), dim3(ATHR), lds_q, st, a);
-    KV_LAUNCH_CHECK("attn_bwd_q_kernel");
-    return 0;
+    });
 }
 
 // =============================================================================================
@@ -2525,9 +2406,140 @@ __global__ __launch_bounds__(256) void attn_small_bwd_kernel(const AttnArgs a) {
     }
 }
 
-bool attn_small_ok(const kanvit_attn_desc* d) { return d->N <= 32 && d->D <= 32 && !kv_config().attn_v1 && !kv_config().attn_v2; }
+// The KANVIT_ATTN_* switches (kanvit_common.h) as the plans read them; nothing else on the attention path looks at kv_config()
+struct AttnSwitches {
+    bool v1, v2, v3, v4, no_ds, no_bf16;
+    int grid;      // KANVIT_ATTN_GRID: work-groups of the persistent kernels (tuning; 0 = one round of resident ones)
+};
+AttnSwitches attn_switches() {
+    const KvConfig& c = kv_config();
+    return {c.attn_v1 != 0, c.attn_v2 != 0, c.attn_v3 != 0, c.attn_v4 != 0, c.attn_no_ds != 0, c.no_bf16 != 0, c.attn_grid};
+}
+
+// persistent kernels: as many work-groups as are resident at once, never more than heads
+unsigned grid_per_cu(int nbh, int per_cu, int grid_override) {
+    const int g = grid_override > 0 ? grid_override : KV_N_CU * per_cu;
+    return (unsigned)(nbh < g ? nbh : g);
+}
+unsigned grid_resident(int nbh, size_t lds, int grid_override) { return grid_per_cu(nbh, lds * 2 <= 160 * 1024 ? 2 : 1, grid_override); }
+
+int nkt_bucket(int nkt) { return nkt <= 2 ? nkt : nkt <= 4 ? 4 : nkt <= 7 ? 7 : 8; }
 
 }  // namespace
+
+AttnFwdPlan plan_attn_fwd(const kanvit_attn_desc* d, uintptr_t align) {
+    const AttnSwitches sw = attn_switches();
+    const int nbh = d->B * d->H, nkt = (d->N + 31) / 32, D = d->D <= 32 ? 32 : 64;      // D: the padded head size of the kernel templates (32 * DT)
+    const size_t NP = (size_t)nkt * 32;
+    AttnFwdPlan p{};
+    if (d->N <= 32 && d->D <= 32 && !sw.v1 && !sw.v2) {      // one wave per head, exact fp32 (the bf16 flag allows, never requires, bf16 products)
+        p.form = ATTN_FWD_SMALL;                             // (KANVIT_ATTN_V3 / V4 do not switch it off: kept as it was)
+        p.grid = (unsigned)((nbh + 3) / 4);
+        return p;
+    }
+    p.bf16 = (d->flags & KANVIT_FLAG_BF16_MFMA) && d->D % 16 == 0 && !sw.no_bf16;
+    const bool rows16 = desc_vec(d) && align % 16 == 0;      // float4 / LDS-DMA rows: every form but the first
+    const bool newest = rows16 && !sw.v1 && !sw.v2 && !sw.v3;
+    const int t16 = kv_attn16_tiles(d);
+    if (newest && !sw.v4 && !d->causal && t16 && (!p.bf16 || t16 == KV_ATTN16_TILES)) {      // 16-row tiles: D = 64, 64 < N <= 204
+        p.form = p.bf16 ? ATTN_FWD_16_BF16 : ATTN_FWD_16;
+        p.nkt = t16;
+        p.lds = kv_attn16_fwd_lds(d->N);
+        p.grid = grid_per_cu(nbh, 1, sw.grid);      // one work-group per CU (the three images fill its LDS)
+    } else if (newest && !p.bf16 && d->D == 64 && nkt >= 3 && nkt <= 7 && kv_a4_lds(d->N, 64) <= 160 * 1024) {
+        // fourth form: below 64 < N a head is a few tiles and the third form's single fill is cheap
+        p.form = ATTN_FWD_FOURTH;
+        p.nkt = nkt <= 4 ? 4 : 7;
+        p.lds = kv_a4_lds(d->N, 64);
+        p.grid = grid_per_cu(nbh, 1, sw.grid);
+    } else if (rows16 && !p.bf16 && d->D == D && !sw.v1 && !sw.v2 && nkt <= 7) {
+        p.form = ATTN_FWD_THIRD;
+        p.nkt = nkt_bucket(nkt);
+        p.lds = sizeof(float) * 2 * NP * kv_pad4(D);
+        p.grid = grid_resident(nbh, p.lds, sw.grid);
+    } else if (rows16 && d->D == D && !sw.v1 && nkt <= 7) {
+        p.form = ATTN_FWD_SECOND;
+        p.nkt = nkt_bucket(nkt);
+        p.lds = p.bf16 ? sizeof(unsigned short) * (NP * (D + 8) + D * (NP + 8)) : sizeof(float) * 2 * NP * (D + 1);
+        p.grid = (unsigned)nbh;
+    } else {
+        p.form = ATTN_FWD_FIRST;
+        p.nkt = nkt_bucket(nkt);
+        p.lds = sizeof(float) * (2 * NP * (D + 1) + (size_t)4 * 32 * (D + 1));
+        p.grid = (unsigned)nbh;
+    }
+    return p;
+}
+
+AttnBwdPlan plan_attn_bwd(const kanvit_attn_desc* d, const AttnAlign& al) {
+    const AttnSwitches sw = attn_switches();
+    const int nbh = d->B * d->H, nkt = (d->N + 31) / 32, D = d->D <= 32 ? 32 : 64;
+    const size_t NP = (size_t)nkt * 32;
+    AttnBwdPlan p{};
+    p.bf16 = (d->flags & KANVIT_FLAG_BF16_MFMA) && d->D % 16 == 0 && !sw.no_bf16;
+    // the one-kernel 16-row backward, as far as the descriptor and the switches say (it forms dQ itself: nothing crosses HBM).
+    // KANVIT_ATTN_NO_DS switches it off although it hands no dS over, and the forward's 16-row forms do not look at that switch: kept.
+    const bool want16 = !sw.v1 && !sw.v2 && !sw.v3 && !sw.v4 && !sw.no_ds && d->D == 64 && !d->causal && (d->N + 15) / 16 == KV_ATTN16_TILES;
+    // dS buffer behind rowsum(dO*O): reserved from the descriptor and the switches alone, so the bytes hold for every alignment.
+    // N = 205 .. 208 is `want16` but outside kv_attn16_tiles: the exact path then runs kv2+q2, which needs no dS (kept, not a fix).
+    // In bf16 mode the buffer is reserved even where the 16-row kernel runs and leaves it unused (kept as well).
+    // The bf16 dQ kernel needs one query tile per wave of its 512 threads: N <= 256.
+    const bool ds = (d->D == 32 || d->D == 64) && !d->causal && !sw.no_ds && !sw.v1 && !(want16 && !p.bf16) && (!p.bf16 || d->N <= 256);
+    p.ws_bytes = (sizeof(float) * (size_t)d->B * d->H * d->N + 15) / 16 * 16 + (ds ? (p.bf16 ? sizeof(unsigned short) : sizeof(float)) * (size_t)d->B * d->H * NP * NP : 0);
+    p.grid = p.grid_q = (unsigned)nbh;
+    if (d->N <= 32 && d->D <= 32 && !sw.v1 && !sw.v2) {
+        p.form = ATTN_BWD_SMALL;
+        p.bf16 = false;
+        p.grid = (unsigned)((nbh + 3) / 4);
+        return p;
+    }
+    const bool rows16 = desc_vec(d) && al.rows % 16 == 0;
+    if (want16 && rows16 && kv_attn16_tiles(d) && al.o % 16 == 0 && al.lse % 4 == 0) {
+        p.form = p.bf16 ? ATTN_BWD_16_BF16 : ATTN_BWD_16;
+        p.nkt = KV_ATTN16_TILES;
+        p.lds = kv_attn16_bwd_lds();
+        p.grid = grid_per_cu(nbh, 1, sw.grid);
+        return p;
+    }
+    // third and fourth forms (exact fp32): pipelined LDS reads, rowsum(dO*O) in the prologue; every other form reads it from the workspace
+    const size_t lds3 = sizeof(float) * (2 * NP * kv_pad4(D) + 2 * NP), lds_dq3 = sizeof(float) * NP * kv_pad4(D);
+    const bool third = ds && !p.bf16 && !sw.v2 && rows16 && al.o % 16 == 0 && lds3 <= 160 * 1024;
+    p.delta = !third;
+    // second-form images: bf16 row and transposed images, or padded fp32 images
+    const size_t row = sizeof(unsigned short) * NP * (D + 8), tr = sizeof(unsigned short) * D * (NP + 8), f32img = sizeof(float) * NP * (D + 1);
+    const size_t lds_kv2 = (p.bf16 ? 2 * row + 2 * tr : 2 * f32img) + sizeof(float) * 2 * NP;
+    if (!(rows16 && d->D == D && !sw.v1 && lds_kv2 <= 160 * 1024)) {
+        p.form = ATTN_BWD_KV_Q;
+        p.lds_q = sizeof(float) * (2 * NP * (D + 1) + (size_t)4 * 32 * (D + 1));
+        p.lds = p.lds_q + sizeof(float) * 2 * NP;
+    } else if (third && D == 64 && nkt >= 3 && nkt <= 7 && kv_b4_lds(d->N, 64) <= 160 * 1024 && !sw.v3) {
+        // fourth form of the key-stationary kernel (LDS-DMA ring, loader wave): 64 < N, a wave without a key tile
+        p.form = ATTN_BWD_KV4_DQ3;
+        p.nkt = nkt <= 4 ? 4 : 8;
+        p.lds = kv_b4_lds(d->N, 64);
+        p.grid = grid_per_cu(nbh, 1, sw.grid);
+        p.lds_q = lds_dq3;
+        p.grid_q = grid_resident(nbh, lds_dq3, sw.grid);
+    } else if (third) {
+        p.form = ATTN_BWD_KV3_DQ3;
+        p.nkt = nkt <= 2 ? 2 : nkt <= 4 ? 4 : 8;
+        p.lds = lds3;
+        p.grid = grid_resident(nbh, lds3, sw.grid);
+        p.lds_q = lds_dq3;
+        p.grid_q = grid_resident(nbh, lds_dq3, sw.grid);
+    } else if (ds) {      // the key-stationary kernel stores dS, dQ is one plain product (5 MFMA products instead of 7)
+        p.form = p.bf16 ? ATTN_BWD_KV2DS_DQ_BF16 : ATTN_BWD_KV2DS_DQ;
+        p.nkt = nkt <= 4 ? 4 : 8;
+        p.lds = lds_kv2;
+        p.lds_q = p.bf16 ? tr : f32img;
+    } else {
+        p.form = ATTN_BWD_KV2_Q2;
+        p.lds = lds_kv2;
+        p.lds_q = p.bf16 ? 2 * row + tr : 2 * f32img;
+    }
+    p.ds = p.form == ATTN_BWD_KV2DS_DQ_BF16 ? ATTN_DS_BF16 : p.form == ATTN_BWD_KV4_DQ3 || p.form == ATTN_BWD_KV3_DQ3 || p.form == ATTN_BWD_KV2DS_DQ ? ATTN_DS_F32 : ATTN_DS_NONE;
+    return p;
+}
 
 extern "C" {
 
@@ -2546,34 +2558,24 @@ int kanvit_attn_fwd(const kanvit_attn_desc* d, const float* q, const float* k, c
     a.q = q; a.k = k; a.v = v; a.out = o; a.lse = lse;
     a.vec = a.vec && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0);
     hipStream_t st = (hipStream_t)stream;
-    if (attn_small_ok(d)) {           // one wave per head (exact fp32; the bf16 flag allows, never requires, bf16 products)
-        hipLaunchKernelGGL(attn_small_fwd_kernel, dim3((unsigned)((d->B * d->H + 3) / 4)), dim3(256), 0, st, a);
-        KV_LAUNCH_CHECK("attn_small_fwd_kernel");
-        return 0;
+    const AttnFwdPlan p = plan_attn_fwd(d, (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o);
+    switch (p.form) {
+        case ATTN_FWD_SMALL:
+            hipLaunchKernelGGL(attn_small_fwd_kernel, dim3(p.grid), dim3(256), 0, st, a);
+            KV_LAUNCH_CHECK("attn_small_fwd_kernel");
+            return 0;
+        case ATTN_FWD_16:
+        case ATTN_FWD_16_BF16:
+            return kv_attn16_launch_fwd(a, p, st);
+        default:
+            return launch_fwd(a, p, st);
     }
-    if ((d->flags & KANVIT_FLAG_BF16_MFMA) && d->D % 16 == 0 && !kv_config().no_bf16)
-        return d->D <= 32 ? dispatch_fwd<1, true>(a, st) : dispatch_fwd<2, true>(a, st);
-    return d->D <= 32 ? dispatch_fwd<1, false>(a, st) : dispatch_fwd<2, false>(a, st);
 }
 
-// rowsum(dO*O) [B*H*N] (rounded up to 16 bytes), then -- exact fp32 path with D in {32, 64} only -- dS [B*H][NP][NP]
-static size_t attn_delta_bytes(const kanvit_attn_desc* d) { return (sizeof(float) * (size_t)d->B * d->H * d->N + 15) / 16 * 16; }
-static bool attn_bf16_mode(const kanvit_attn_desc* d) { return (d->flags & KANVIT_FLAG_BF16_MFMA) && d->D % 16 == 0 && !kv_config().no_bf16; }
-// dS hand-off from the key-stationary kernel to the dQ kernel: fp32 values on the exact path, bf16 values in bf16 mode (there the
-// dQ product consumes them as a bf16 operand anyway; needs one query tile per wave of the 512-thread kernels: N <= 256)
-static bool attn_ds_spill(const kanvit_attn_desc* d) {
-    if (!(d->D == 32 || d->D == 64) || d->causal || kv_config().attn_no_ds || kv_config().attn_v1) return false;
-    if (kv_attn16_bwd_ok(d)) return false;       // the 16-row-tile backward forms dQ in the same kernel: nothing crosses HBM
-    return attn_bf16_mode(d) ? d->N <= 256 : true;
-}
+// every alignment has the same bytes (the dS buffer is reserved for the aligned case, the largest): null pointers stand for it
 size_t kanvit_attn_bwd_workspace(const kanvit_attn_desc* d) {
     if (!d || d->B < 0 || d->H < 1 || d->N < 1) return 0;
-    size_t n = attn_delta_bytes(d);
-    if (attn_ds_spill(d)) {
-        const size_t np = (size_t)(d->N + 31) / 32 * 32;
-        n += (attn_bf16_mode(d) ? sizeof(unsigned short) : sizeof(float)) * (size_t)d->B * d->H * np * np;
-    }
-    return n;
+    return plan_attn_bwd(d, AttnAlign{}).ws_bytes;
 }
 
 /* dq/dk/dv are fully written (no accumulation into the outputs). */
@@ -2584,41 +2586,32 @@ int kanvit_attn_bwd(const kanvit_attn_desc* d, const float* q, const float* k, c
     if (!q || !k || !v || !o || !lse || !d_o || !dq || !dk || !dv)
         return kv_fail(KANVIT_EINVAL, "kanvit_attn_bwd: null argument");
     if (d->B == 0) return 0;
-    if (!workspace || workspace_bytes < kanvit_attn_bwd_workspace(d))
-        return kv_fail(KANVIT_ENOMEM, "kanvit_attn_bwd: workspace %zu bytes < required %zu", workspace_bytes,
-                       kanvit_attn_bwd_workspace(d));
-    float* delta_ws = (float*)workspace;
+    const uintptr_t in = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)d_o;
+    const AttnBwdPlan p = plan_attn_bwd(d, AttnAlign{in | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv, (uintptr_t)o, (uintptr_t)lse});
+    if (!workspace || workspace_bytes < p.ws_bytes)
+        return kv_fail(KANVIT_ENOMEM, "kanvit_attn_bwd: workspace %zu bytes < required %zu", workspace_bytes, p.ws_bytes);
     AttnArgs a = make_args(d);
     a.q = q; a.k = k; a.v = v; a.o = o; a.lse_in = lse; a.d_o = d_o;
-    a.dq = dq; a.dk = dk; a.dv = dv; a.delta = delta_ws; a.delta_in = delta_ws;
-    a.ds = attn_ds_spill(d) ? (float*)((char*)workspace + attn_delta_bytes(d)) : nullptr;
-    a.vec = a.vec && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)d_o) % 16 == 0);
+    a.dq = dq; a.dk = dk; a.dv = dv; a.delta = (float*)workspace; a.delta_in = a.delta;
+    a.ds = p.ds != ATTN_DS_NONE ? (float*)((char*)workspace + (sizeof(float) * (size_t)d->B * d->H * d->N + 15) / 16 * 16) : nullptr;
+    a.vec = a.vec && in % 16 == 0;
+    a.third = !p.delta;
     hipStream_t st = (hipStream_t)stream;
-    if (attn_small_ok(d)) {
-        hipLaunchKernelGGL(attn_small_bwd_kernel, dim3((unsigned)((d->B * d->H + 3) / 4)), dim3(256), 0, st, a);
-        KV_LAUNCH_CHECK("attn_small_bwd_kernel");
-        return 0;
+    switch (p.form) {
+        case ATTN_BWD_SMALL:
+            hipLaunchKernelGGL(attn_small_bwd_kernel, dim3(p.grid), dim3(256), 0, st, a);
+            KV_LAUNCH_CHECK("attn_small_bwd_kernel");
+            return 0;
+        case ATTN_BWD_16:
+        case ATTN_BWD_16_BF16:
+            return kv_attn16_launch_bwd(a, p, st);
+        default:
+            if (p.delta) {
+                hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)(((long long)d->B * d->H * d->N + 15) / 16)), dim3(256), 0, st, a);
+                KV_LAUNCH_CHECK("attn_delta_kernel");
+            }
+            return launch_bwd(a, p, st);
     }
-    if (kv_attn16_bwd_ok(d) && a.vec) {      // one kernel, five products (csrc/attention16.hip); a refusal (alignment) falls through to the older forms
-        const int rc = kv_attn16_bwd(a, st);
-        if (rc <= 0) return rc;
-    }
-    if (attn_bf16_mode(d) && a.vec && !kv_config().attn_v1 && !kv_config().attn_v2 && !kv_config().attn_v3 && !kv_config().attn_no_ds) {      // the same kernel on the bf16 matrix cores
-        const int rc = kv_attn16_bwd_bf16(a, st);
-        if (rc <= 0) return rc;
-    }
-    const long long rows = (long long)d->B * d->H * d->N;
-    // the third-form fp32 kernels form rowsum(dO*O) themselves; every other path reads it from the workspace
-    const size_t lds3 = sizeof(float) * ((size_t)2 * a.nkt * 32 * kv_pad4(d->D) + 2 * (size_t)a.nkt * 32);
-    const bool third = a.ds && !attn_bf16_mode(d) && !kv_config().attn_v2 && !kv_config().attn_v1 && a.vec && (d->D == 32 || d->D == 64) &&
-                       (((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)o) % 16 == 0) && lds3 <= 160 * 1024;
-    a.third = third ? 1 : 0;
-    if (!third) {
-        hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, a);
-        KV_LAUNCH_CHECK("attn_delta_kernel");
-    }
-    if (attn_bf16_mode(d)) return d->D <= 32 ? launch_bwd<1, true>(a, st) : launch_bwd<2, true>(a, st);
-    return d->D <= 32 ? launch_bwd<1, false>(a, st) : launch_bwd<2, false>(a, st);
 }
 
 }  // extern "C"

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(A16_THREADS) void attn16_fwd_kernel(const AttnArgs 
         int l = lane;                        // (opaque: the per-lane offset is re-formed per head instead of being hoisted and spilled)
         asm volatile("" : "+v"(l));
         const int qr = 16 * wave + (l & 15);
-        const float* qp = a.q + bi * a.qsb + hi * a.qsh + (qr < N ? qr : 0) * (int)a.qsn + 16 * (l >> 4);      // 32-bit row offsets: a16_shape_ok
+        const float* qp = a.q + bi * a.qsb + hi * a.qsh + (qr < N ? qr : 0) * (int)a.qsn + 16 * (l >> 4);      // 32-bit row offsets: kv_attn16_tiles
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const f32x4 u = *reinterpret_cast<const f32x4*>(qp + 4 * i);
@@ -529,28 +529,13 @@ __global__ __launch_bounds__(A16_THREADS) void attn16_fwd_kernel(const AttnArgs 
     store_o();
 }
 
-template <int NKT, bool CAUSAL, bool BF>
-int launch_fwd16c(const AttnArgs& a, hipStream_t st) {
-    const size_t lds = a16_lds_bytes(a.N);
-    KV_ALLOW_LDS(160 * 1024, (attn16_fwd_kernel<NKT, CAUSAL, BF>));
-    const int nbh = a.B * a.H;
-    const int gmax = kv_config().attn_grid > 0 ? kv_config().attn_grid : KV_N_CU;      // one work-group per CU (the three images fill its LDS)
-    hipLaunchKernelGGL((attn16_fwd_kernel<NKT, CAUSAL, BF>), dim3((unsigned)(nbh < gmax ? nbh : gmax)), dim3(A16_THREADS), lds, st, a);
+template <int NKT, bool BF>
+int launch_fwd16(const AttnArgs& a, const AttnFwdPlan& p, hipStream_t st) {      // (the causal instantiation of 13 tiles spills: causal launches keep the fourth form)
+    KV_ALLOW_LDS(160 * 1024, (attn16_fwd_kernel<NKT, false, BF>));
+    hipLaunchKernelGGL((attn16_fwd_kernel<NKT, false, BF>), dim3(p.grid), dim3(A16_THREADS), p.lds, st, a);
     KV_LAUNCH_CHECK("attn16_fwd_kernel");
     return 0;
 }
-
-template <int NKT>
-int launch_fwd16(const AttnArgs& a, hipStream_t st) { return launch_fwd16c<NKT, false, false>(a, st); }      // (the causal instantiation of 13 tiles spills: causal launches keep the fourth form)
-
-bool a16_shape_ok(const AttnArgs& a) {
-    if (a.D != A16_D || a.N <= 64 || a16_lds_bytes(a.N) > 160 * 1024 || (a.N + 15) / 16 > A16_MAXT || !a.vec) return false;
-    // 32-bit row offsets inside a head's operand (row * stride elements)
-    for (long long sn : {a.qsn, a.ksn, a.vsn, a.osn})
-        if (sn * (long long)(a.N + 1) >= (1LL << 31)) return false;
-    return true;
-}
-
 
 // =============================================================================================
 // backward: ONE kernel, all five products, no dS hand-off through HBM
@@ -617,7 +602,6 @@ constexpr int B16_NPT = 2;
 constexpr int B16_NCNT = 32;
 enum { BC_READY = 0, BC_DELTA = 6, BC_DONE = 12, BC_DSW = 18, BC_DSR = 22, BC_PW = 26, BC_PR = 28 };
 constexpr int b16_lds_floats() { return B16_NDS * B16_DSS + B16_NPT * B16_PART + B16_NSL * B16_SL + B16_NCNT; }
-inline size_t b16_lds_bytes(int) { return sizeof(float) * (size_t)b16_lds_floats(); }
 
 __device__ __forceinline__ void b16_wait(const unsigned* c, unsigned target) {
     if constexpr (!(B16_ABLATE & 32)) a16_wait(c, target);
@@ -1080,26 +1064,33 @@ __global__ __launch_bounds__(B16_THREADS) void attn16_bwd_kernel(const AttnArgs 
     else attn16_bwd_body<1, BF>(a, smem, lane, wave);
 }
 
-bool b16_shape_ok(const AttnArgs& a) {
-    return a16_shape_ok(a) && (a.N + 15) / 16 == B16_NT && b16_lds_bytes(a.N) <= 160 * 1024 && !a.causal;
-}
+static_assert(B16_NT == KV_ATTN16_TILES && A16_MAXT == KV_ATTN16_TILES && sizeof(float) * b16_lds_floats() <= 160 * 1024, "the backward's tiles and LDS");
 
 }  // namespace
 
-int kv_attn16_fwd(const AttnArgs& a, hipStream_t st) {
-    if (!a16_shape_ok(a) || a.causal || kv_config().attn_v4) return 1;
-    if (((uintptr_t)a.out | (uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 16) return 1;
-    switch ((a.N + 15) / 16) {
-        case 5: return launch_fwd16<5>(a, st);
-        case 6: return launch_fwd16<6>(a, st);
-        case 7: return launch_fwd16<7>(a, st);
-        case 8: return launch_fwd16<8>(a, st);
-        case 9: return launch_fwd16<9>(a, st);
-        case 10: return launch_fwd16<10>(a, st);
-        case 11: return launch_fwd16<11>(a, st);
-        case 12: return launch_fwd16<12>(a, st);
-        case 13: return launch_fwd16<13>(a, st);
-        default: return 1;
+int kv_attn16_tiles(const kanvit_attn_desc* d) {
+    if (d->D != A16_D || d->N <= 64 || a16_lds_bytes(d->N) > 160 * 1024 || (d->N + 15) / 16 > A16_MAXT) return 0;
+    // 32-bit row offsets inside a head's operand (row * stride elements)
+    for (long long sn : {d->q_stride_n, d->k_stride_n, d->v_stride_n, d->o_stride_n})
+        if (sn * (long long)(d->N + 1) >= (1LL << 31)) return 0;
+    return (d->N + 15) / 16;
+}
+size_t kv_attn16_fwd_lds(int N) { return a16_lds_bytes(N); }
+size_t kv_attn16_bwd_lds() { return sizeof(float) * (size_t)b16_lds_floats(); }
+
+// the bf16 forward (its two products on the bf16 matrix cores, KANVIT_FLAG_BF16_MFMA) exists for 13 tiles only (N = 193 .. 204)
+int kv_attn16_launch_fwd(const AttnArgs& a, const AttnFwdPlan& p, hipStream_t st) {
+    if (p.bf16) return launch_fwd16<A16_MAXT, true>(a, p, st);
+    switch (p.nkt) {
+        case 5: return launch_fwd16<5, false>(a, p, st);
+        case 6: return launch_fwd16<6, false>(a, p, st);
+        case 7: return launch_fwd16<7, false>(a, p, st);
+        case 8: return launch_fwd16<8, false>(a, p, st);
+        case 9: return launch_fwd16<9, false>(a, p, st);
+        case 10: return launch_fwd16<10, false>(a, p, st);
+        case 11: return launch_fwd16<11, false>(a, p, st);
+        case 12: return launch_fwd16<12, false>(a, p, st);
+        default: return launch_fwd16<13, false>(a, p, st);
     }
 }
 
@@ -1109,31 +1100,11 @@ extern "C" __attribute__((visibility("default"))) int kanvit_debug_clock16(unsig
 }
 #endif
 
-// the same forward with its two products on the bf16 matrix cores (KANVIT_FLAG_BF16_MFMA), 13 tiles only (N = 193 .. 204)
-int kv_attn16_fwd_bf16(const AttnArgs& a, hipStream_t st) {
-    if (!a16_shape_ok(a) || a.causal || kv_config().attn_v4 || (a.N + 15) / 16 != A16_MAXT) return 1;
-    if (((uintptr_t)a.out | (uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 16) return 1;
-    return launch_fwd16c<A16_MAXT, false, true>(a, st);
-}
-
-bool kv_attn16_bwd_ok(const kanvit_attn_desc* d) {
-    if (!d || kv_config().attn_v4 || kv_config().attn_v1 || kv_config().attn_v2 || kv_config().attn_v3 || kv_config().attn_no_ds) return false;
-    if ((d->flags & KANVIT_FLAG_BF16_MFMA) && !kv_config().no_bf16) return false;
-    return d->D == A16_D && !d->causal && (d->N + 15) / 16 == B16_NT && b16_lds_bytes(d->N) <= 160 * 1024;
-}
-
 template <bool BF>
-static int launch_bwd16(const AttnArgs& a, hipStream_t st) {
-    if (!b16_shape_ok(a) || kv_config().attn_v4) return 1;
-    if (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.o | (uintptr_t)a.d_o | (uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv) % 16) return 1;
-    if ((uintptr_t)a.lse_in % 4) return 1;
-    const size_t lds = b16_lds_bytes(a.N);
+static int launch_bwd16(const AttnArgs& a, const AttnBwdPlan& p, hipStream_t st) {
     KV_ALLOW_LDS(160 * 1024, attn16_bwd_kernel<BF>);
-    const int nbh = a.B * a.H;
-    const int gmax = kv_config().attn_grid > 0 ? kv_config().attn_grid : KV_N_CU;
-    hipLaunchKernelGGL(attn16_bwd_kernel<BF>, dim3((unsigned)(nbh < gmax ? nbh : gmax)), dim3(B16_THREADS), lds, st, a);
+    hipLaunchKernelGGL(attn16_bwd_kernel<BF>, dim3(p.grid), dim3(B16_THREADS), p.lds, st, a);
     KV_LAUNCH_CHECK("attn16_bwd_kernel");
     return 0;
 }
-int kv_attn16_bwd(const AttnArgs& a, hipStream_t st) { return launch_bwd16<false>(a, st); }
-int kv_attn16_bwd_bf16(const AttnArgs& a, hipStream_t st) { return launch_bwd16<true>(a, st); }
+int kv_attn16_launch_bwd(const AttnArgs& a, const AttnBwdPlan& p, hipStream_t st) { return p.bf16 ? launch_bwd16<true>(a, p, st) : launch_bwd16<false>(a, p, st); }

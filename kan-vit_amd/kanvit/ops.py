@@ -485,19 +485,27 @@ def kan_layer(x: torch.Tensor, w: torch.Tensor, cfg: LayerCfg, u: Optional[torch
 _attn_flags = 0      # set by attention()/attention_packed() from the ambient autocast state (the Functions run with autocast off)
 
 
-def _attn_desc(q, k, v, o, causal: bool, scale: float, flags: int = 0) -> AttnDesc:
-    B, H, N, D = q.shape
-    for n, t in (("q", q), ("k", k), ("v", v), ("o", o)):
-        if t.dim() != 4 or tuple(t.shape) != (B, H, N, D):
+def _attn_build_desc(q, k, v, o, causal: bool, scale: float, flags: int, self_attention: bool) -> AttnDesc:
+    """kanvit_attn_desc of q, o [B, H, Nq, D] and k, v [B, H, Nk, D] (self-attention: Nk = Nq), after the shape and stride checks."""
+    B, H, Nq, D = q.shape
+    Nk = Nq if self_attention else k.shape[2]
+    for n, t, L in (("q", q, Nq), ("k", k, Nk), ("v", v, Nk), ("o", o, Nq)):
+        if t.dim() != 4 or tuple(t.shape) != (B, H, L, D):
+            if not self_attention:
+                raise KanvitError(f"attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, o {tuple(o.shape)} do not agree")
             # kanvit_attn_desc carries ONE sequence length: a shorter k/v would be read out of bounds, a longer one silently
             # truncated.  The reference's FlashAttentionFunction accepts q_len != k_len (utils.py:150-160); this path does not.
-            raise KanvitError(f"attention: {n} has shape {tuple(t.shape)}, expected {(B, H, N, D)} "
+            raise KanvitError(f"attention: {n} has shape {tuple(t.shape)}, expected {(B, H, L, D)} "
                               "(self-attention only: q, k, v and o must agree in batch, heads, length and head size)")
         if t.stride(3) != 1:
             raise KanvitError(f"{n}: innermost dimension must be contiguous")
-    return AttnDesc(B, H, N, D, int(bool(causal)), float(scale), int(flags), 0,
+    return AttnDesc(B, H, Nq, D, int(bool(causal)), float(scale), int(flags), 0,
                     q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
                     v.stride(0), v.stride(1), v.stride(2), o.stride(0), o.stride(1), o.stride(2))
+
+
+def _attn_desc(q, k, v, o, causal: bool, scale: float, flags: int = 0) -> AttnDesc:
+    return _attn_build_desc(q, k, v, o, causal, scale, flags, True)
 
 
 def _attn_fits_one_workgroup(N: int, D: int) -> bool:
@@ -518,8 +526,13 @@ def _attn_x_flags(flags: int, D: int) -> int:
     return flags & _lib.FLAG_BF16_MFMA if D <= 64 else 0
 
 
+def _attn_takes_general_kernels(q, k) -> bool:
+    """The one routing decision of a self-attention head, for its forward and its backward alike."""
+    return q.dim() == 4 and tuple(k.shape) == tuple(q.shape) and not _attn_fits_one_workgroup(q.shape[2], q.shape[3])
+
+
 def _attn_fwd(q, k, v, o, causal, scale, flags=0):
-    if q.dim() == 4 and tuple(k.shape) == tuple(q.shape) and not _attn_fits_one_workgroup(q.shape[2], q.shape[3]):
+    if _attn_takes_general_kernels(q, k):
         return _attn_x_fwd(q, k, v, o, None, causal, scale, flags=_attn_x_flags(flags, q.shape[3]))
     B, H, N, _ = q.shape
     lse = torch.empty(B, H, N, device=q.device, dtype=torch.float32)
@@ -532,7 +545,7 @@ def _attn_fwd(q, k, v, o, causal, scale, flags=0):
 
 
 def _attn_bwd(q, k, v, o, lse, do, dq, dk, dv, causal, scale, flags=0):
-    if q.dim() == 4 and tuple(k.shape) == tuple(q.shape) and not _attn_fits_one_workgroup(q.shape[2], q.shape[3]):
+    if _attn_takes_general_kernels(q, k):
         return _attn_x_bwd(q, k, v, o, lse, do, dq, dk, dv, None, causal, scale, flags=_attn_x_flags(flags, q.shape[3]))
     d = _attn_desc(q, k, v, o, causal, scale, flags)
     if (do.stride() != o.stride()) or dq.stride() != q.stride() or dk.stride() != k.stride() or dv.stride() != v.stride():
@@ -553,16 +566,8 @@ def _attn_x_desc(q, k, v, o, mask, causal: bool, scale: float, flags: int = 0):
     torch.bool tensor already expanded (views, no copy) to [B, H, Nq, Nk]."""
     for n, t in (("q", q), ("k", k), ("v", v), ("o", o)):
         _require_gpu_f32(n, t)
-    B, H, Nq, D = q.shape
-    Nk = k.shape[2]
-    if tuple(k.shape) != (B, H, Nk, D) or tuple(v.shape) != (B, H, Nk, D) or tuple(o.shape) != (B, H, Nq, D):
-        raise KanvitError(f"attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, o {tuple(o.shape)} do not agree")
-    for n, t in (("q", q), ("k", k), ("v", v), ("o", o)):
-        if t.stride(3) != 1:
-            raise KanvitError(f"{n}: innermost dimension must be contiguous")
-    d = AttnDesc(B, H, Nq, D, int(bool(causal)), float(scale), int(flags), 0,
-                 q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
-                 v.stride(0), v.stride(1), v.stride(2), o.stride(0), o.stride(1), o.stride(2))
+    d = _attn_build_desc(q, k, v, o, causal, scale, flags, False)
+    B, H, Nq, Nk = d.B, d.H, d.N, k.shape[2]
     if mask is None:
         e = _lib.AttnExt(Nk, 0, None, 0, 0, 0, 0)
     else:

@@ -64,6 +64,17 @@ def test_routing_predicate_sends_wide_heads_to_the_general_kernels(n, d, fits):
     assert ops._attn_fits_one_workgroup(n, d) is fits
 
 
+def test_routing_predicate_agrees_with_the_library(lib):
+    """ops._attn_fits_one_workgroup is a copy of check_desc's bounds (csrc/attention.hip): it holds exactly where kanvit_attn_fwd
+    with null tensors gets as far as its null check instead of refusing the size or the LDS need."""
+    from kanvit import _lib, ops
+    for D in range(2, 65, 2):
+        for N in range(1, 301):
+            a = _lib.AttnDesc(B=2, H=3, N=N, D=D, scale=0.125)
+            assert lib.kanvit_attn_fwd(ctypes.byref(a), None, None, None, None, None, None) == -22
+            assert ops._attn_fits_one_workgroup(N, D) is (b"null q/k/v/o" in lib.kanvit_last_error()), (N, D, lib.kanvit_last_error())
+
+
 def test_wide_general_kernels_use_no_scratch_and_spill_no_vgprs(lib):
     spec = importlib.util.spec_from_file_location("kernel_meta", os.path.join(ROOT, "tools", "kernel_meta.py"))
     km = importlib.util.module_from_spec(spec)
