@@ -175,6 +175,37 @@ size_t kanvit_layer_bwd_weight_workspace(const kanvit_layer_desc* d);
 int kanvit_layer_bwd_weight(const kanvit_layer_desc* d, const float* x, const float* u, const float* bparams,
                             const float* dy, float* dw, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-edge mean absolute activation: the KAN paper's regulariser without the (rows, in, out) tensor -------------
+ * The reference cannot compute it (models/effkan.py:244-264 says so and regularises the spline WEIGHTS instead); a kernel
+ * that generates the basis on the fly can, at the memory cost of its [O, I] result.  d, w, bparams as for kanvit_layer_fwd
+ * (groups, x_group_mod, ldx, family, G, spline_order, has_base, base_act, KANVIT_FLAG_UNIFORM_KNOTS mean the same; ldy and
+ * the bias are unused):
+ *     phi[m, g, i, o] = sum_j Phi_j(x[m, (g % x_group_mod)*I + i]) * w[g][i*GP + j][o]
+ *     A[g][i][o]      = (1/M) sum_m |phi[m, g, i, o]|                                   fwd: A [groups][I][O], written
+ * bwd, given gA[groups][I][O] = d loss / d A, with s = sign(phi) * gA / M and sign(0) = 0 (as torch.abs differentiates):
+ *     dw[g][i*GP + j][o] = sum_m Phi_j(x) * s[m, i, o]
+ *     dx[m, c*I + i]     = sum over the groups g with g % x_group_mod == c of
+ *                          sum_j Phi_j'(x) * sum_o s[m, i, o] * w[g][i*GP + j][o]       (written; dx may be NULL; row stride ldx)
+ * Families: BSPLINE (closed-form uniform cubic under KANVIT_FLAG_UNIFORM_KNOTS, Cox-de Boor for every other order / knot
+ * layout, has_base 0 or 1 with any KANVIT_BASE_*), CHEBY, RBF; at most 24 generated columns per feature.  RBF takes the
+ * LayerNorm'ed spline input as x; with has_base = 1 the base column reads the layer's raw input from the SAME rows, ldu
+ * columns further right (x[m*ldx + ldu + c*I + i]; ldu = 0: the same values, else ldu >= x_group_mod*I), and dx carries both
+ * gradients in that layout.
+ * LINEAR, SINE, FOURIER, KANVIT_FLAG_FUSED_LN and KANVIT_FLAG_BF16_MFMA (the statistic has no bf16 mode: callers clear the
+ * flag and it runs exact fp32 under autocast) are KANVIT_EINVAL, named in kanvit_last_error.
+ * The rows are cut into kanvit_edge_l1_row_bands(d) bands (a function of M alone); every band writes a partial result to the
+ * workspace (bands x the result's size) and a second kernel adds the partials in band order: no atomics, bitwise
+ * reproducible, and a group's result does not depend on the other groups of the launch.  M = 0 writes zeros.
+ * kanvit_edge_l1_supported and kanvit_edge_l1_row_bands are pure host functions.  (ABI 7: no struct or version change) */
+int kanvit_edge_l1_supported(const kanvit_layer_desc* d);
+int64_t kanvit_edge_l1_row_bands(const kanvit_layer_desc* d);
+size_t kanvit_edge_l1_fwd_workspace(const kanvit_layer_desc* d);
+int kanvit_edge_l1_fwd(const kanvit_layer_desc* d, const float* x, const float* w, const float* bparams, float* A, void* workspace,
+                       size_t workspace_bytes, void* stream);
+size_t kanvit_edge_l1_bwd_workspace(const kanvit_layer_desc* d);
+int kanvit_edge_l1_bwd(const kanvit_layer_desc* d, const float* x, const float* w, const float* bparams, const float* gA, float* dw,
+                       float* dx, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- fused patch embedding --------------------------------------
  * The patch-embedding layer of VisionTransformer.forward (model.py:144-152) with its prologue and epilogue inside the
  * kernel: the rows of x are gathered straight from the NCHW image batch -- row m = (image m / P, patch m % P),

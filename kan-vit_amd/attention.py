@@ -80,6 +80,44 @@ class MSA(torch.nn.Module):
         self.d_head = dh
         self.softmax = nn.Softmax(dim=-1)
 
+    REGULARIZED_TYPES = ("efficientkan", "cheby", "fast")
+
+    def edge_activation_l1(self, x, include_base=False):
+        """[3, H, d_head(out), d_head(in)]: the mean absolute activation of every edge of the 3*H per-head q, k and v layers on
+        the rows of x [..., d] (the quantity the KAN paper regularises), from ONE grouped launch of kanvit.ops.edge_l1 with the
+        packing of grouped.run_qkv.  `include_base` adds the base term of the efficient-KAN / FastKAN edge functions."""
+        from dataclasses import replace
+        layers = list(self.q_mappings) + list(self.k_mappings) + list(self.v_mappings)
+        l0 = layers[0]
+        if not isinstance(l0, (KANLinear, ChebyKANLayer, FastKANLayer)):
+            raise NotImplementedError(f"edge_activation_l1: per-head layers of type {type(l0).__name__} have no edge-activation "
+                                      f"statistic; supported MSA types: {', '.join(self.REGULARIZED_TYPES)}")
+        H, dh = self.n_heads, self.d_head
+        x2d = x.reshape(-1, self.d)
+        cfg = l0.kan_cfg() if isinstance(l0, ChebyKANLayer) else l0.kan_cfg(layers)
+        w, bp, _ = type(l0).kan_pack_grouped(layers)
+        base = bool(include_base) and cfg.has_base
+        if base and len({ops.base_activation_code(m.base_activation) for m in layers}) > 1:
+            raise NotImplementedError("edge_activation_l1(include_base=True): one grouped launch has one base activation")
+        if cfg.has_base and not base:        # spline path only: drop the base column of the packed weights
+            w = w.reshape(3 * H, dh, cfg.GP, dh)[:, :, :cfg.G].reshape(3 * H, dh * cfg.G, dh)
+            cfg = replace(cfg, has_base=0, base_act=0)
+        if isinstance(l0, FastKANLayer):     # every layer has its own LayerNorm: u[M, 3*H*dh], one column block per group
+            xin = FastKANLayer.kan_u_grouped(layers, x2d, H)
+            if base:
+                xin = torch.cat([xin, x2d.to(xin.dtype).repeat(1, 3)], dim=1)
+            cfg = replace(cfg, groups=3 * H, x_group_mod=3 * H)
+        else:
+            xin = x2d
+            cfg = replace(cfg, groups=3 * H, x_group_mod=H)
+        A = ops.edge_l1(xin, w, cfg, bp)                       # [3*H, in, out]
+        return A.view(3, H, dh, dh).transpose(-1, -2)
+
+    def regularization_loss(self, x, regularize_activation=1.0, regularize_entropy=1.0, include_base=False):
+        """Sum over the 3*H per-head layers of the L1 and entropy terms (models/effkan.py:258-264) of their sample-based edge
+        magnitudes on the rows of x -- one grouped launch (edge_activation_l1)."""
+        return ops.l1_entropy_loss(self.edge_activation_l1(x, include_base), regularize_activation, regularize_entropy)
+
     def forward(self, sequences):
         b, n, d = sequences.shape
         qkv = grouped.run_qkv(self.q_mappings, self.k_mappings, self.v_mappings, sequences.reshape(b * n, d))

@@ -88,6 +88,12 @@ SYMBOLS = {
     "kanvit_layer_sine_dfreq_ok": (C.c_int, [C.POINTER(LayerDesc)]),
     "kanvit_layer_bwd_weight_workspace": (C.c_size_t, [C.POINTER(LayerDesc)]),
     "kanvit_layer_bwd_weight": (C.c_int, _LAYER_BWD_W),
+    "kanvit_edge_l1_supported": (C.c_int, [C.POINTER(LayerDesc)]),
+    "kanvit_edge_l1_row_bands": (C.c_int64, [C.POINTER(LayerDesc)]),
+    "kanvit_edge_l1_fwd_workspace": (C.c_size_t, [C.POINTER(LayerDesc)]),
+    "kanvit_edge_l1_fwd": (C.c_int, [C.POINTER(LayerDesc), _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "kanvit_edge_l1_bwd_workspace": (C.c_size_t, [C.POINTER(LayerDesc)]),
+    "kanvit_edge_l1_bwd": (C.c_int, [C.POINTER(LayerDesc), _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_patch_embed_fwd": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(PatchDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     "kanvit_patch_embed_fwd_ws": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(PatchDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_patch_embed_bwd_weight_ok": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(PatchDesc)]),

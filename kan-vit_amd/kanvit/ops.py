@@ -480,6 +480,98 @@ def kan_layer(x: torch.Tensor, w: torch.Tensor, cfg: LayerCfg, u: Optional[torch
 
 
 # ------------------------------------------------------------------------------------------------
+# per-edge mean absolute activation (the KAN paper's regulariser; csrc/kan_edge_l1.hip)
+# ------------------------------------------------------------------------------------------------
+EDGE_L1_FAMILIES = (BSPLINE, CHEBY, RBF)
+
+
+def _edge_l1_desc(cfg: LayerCfg, x: torch.Tensor, bparams) -> LayerDesc:
+    M, cols = x.shape
+    two = cfg.family == RBF and cfg.has_base                 # [u | x]: the base column reads the raw input, ldu columns to the right
+    want = cfg.x_group_mod * cfg.I * (2 if two else 1)
+    if cols != want:
+        raise KanvitError(f"edge_l1: x has {cols} columns, expected {want}" + (" ([u | x] for RBF with the base column)" if two else ""))
+    ldx = max(x.stride(0), cols) if M > 1 else cols
+    return _desc(cfg, M, ldx, cfg.x_group_mod * cfg.I if two else 0, cfg.groups * cfg.O, 0 if bparams is None else bparams.shape[1])
+
+
+class _EdgeL1Fn(torch.autograd.Function):
+    """A[groups, I, O] = mean over the rows of |phi_{g,i,o}(x)|; gradients to x and to the packed weights."""
+
+    @staticmethod
+    @_fwd_f32
+    def forward(ctx, x, w, bparams, cfg: LayerCfg):
+        for n, t in (("x", x), ("w", w), ("bparams", bparams)):
+            _require_gpu_f32(n, t)
+        if x.dim() != 2:
+            raise KanvitError(f"edge_l1: x must be 2-D, got {tuple(x.shape)}")
+        if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):      # a column slice of a wider matrix is read in place
+            x = x.contiguous()                                                       # (ldx), any other layout is copied
+        w = w.contiguous()
+        bparams = None if bparams is None else bparams.contiguous()
+        if tuple(w.shape) != (cfg.groups, cfg.K, cfg.O):
+            raise KanvitError(f"packed weight shape {tuple(w.shape)} != {(cfg.groups, cfg.K, cfg.O)}")
+        d = _edge_l1_desc(cfg, x, bparams)
+        L = _lib.lib()
+        A = torch.empty(cfg.groups, cfg.I, cfg.O, device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            nbytes = int(L.kanvit_edge_l1_fwd_workspace(C.byref(d)))
+            ws = _workspace(nbytes, x.device)
+            with _timed("edge_l1_fwd", 2 * x.shape[0] * cfg.K * cfg.O * cfg.groups, 4 * (x.numel() + w.numel() + A.numel())):
+                check(L.kanvit_edge_l1_fwd(C.byref(d), _ptr(x), _ptr(w), _ptr(bparams), _ptr(A), _ptr(ws), C.c_size_t(nbytes), _stream()),
+                      "kanvit_edge_l1_fwd")
+        ctx.cfg = cfg
+        ctx.save_for_backward(x, w, bparams)
+        return A
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gA):
+        x, w, bparams = ctx.saved_tensors
+        cfg = ctx.cfg
+        gA = gA.float().contiguous()
+        d = _edge_l1_desc(cfg, x, bparams)
+        L = _lib.lib()
+        dw = torch.empty_like(w)
+        # dx in x's own row stride (the descriptor has one ldx); NULL when nobody asks for it: the kernel then skips the derivatives
+        dx = torch.empty_strided(x.shape, (d.ldx, 1), device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        with torch.cuda.device(x.device):
+            nbytes = int(L.kanvit_edge_l1_bwd_workspace(C.byref(d)))
+            ws = _workspace(nbytes, x.device)
+            with _timed("edge_l1_bwd", (6 if dx is not None else 4) * x.shape[0] * cfg.K * cfg.O * cfg.groups,
+                        4 * ((1 if dx is None else 2) * x.numel() + 2 * w.numel() + gA.numel())):
+                check(L.kanvit_edge_l1_bwd(C.byref(d), _ptr(x), _ptr(w), _ptr(bparams), _ptr(gA), _ptr(dw), _ptr(dx), _ptr(ws),
+                                           C.c_size_t(nbytes), _stream()), "kanvit_edge_l1_bwd")
+        return dx, dw, None, None
+
+
+def edge_l1(x2d: torch.Tensor, w_packed: torch.Tensor, cfg: LayerCfg, bparams: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A[groups, I, O] = mean_m |phi_{g,i,o}(x2d[m, (g % x_group_mod)*I + i])|, the mean absolute activation of every edge of
+    `cfg.groups` KAN layers sharing the rows of x2d (kanvit_edge_l1_*; include/kanvit.h): the quantity the KAN paper's L1 and
+    entropy regulariser is built from, computed without the (rows, in, out) activation tensor.  w_packed [groups, K, O] and
+    bparams as for kan_layer(); families BSPLINE, CHEBY and RBF.  RBF takes the LayerNorm'ed input; with cfg.has_base its
+    x2d is [u | x] (the base column reads the raw input).  Differentiable w.r.t. x2d and w_packed; always exact fp32, also
+    under autocast (the statistic has no bf16 mode); deterministic; no host synchronisation (HIP-graph capturable)."""
+    if cfg.family not in EDGE_L1_FAMILIES:
+        raise NotImplementedError(f"edge_l1: family {_lib.FAMILY_NAMES[cfg.family]} is not supported (supported: bspline, cheby, rbf)")
+    keep = _lib.FLAG_UNIFORM_KNOTS | _lib.FLAG_SHARED_BPARAMS
+    if cfg.flags & ~keep:
+        from dataclasses import replace
+        cfg = replace(cfg, flags=cfg.flags & keep)
+    return _EdgeL1Fn.apply(x2d, w_packed, bparams, cfg)
+
+
+def l1_entropy_loss(l1: torch.Tensor, regularize_activation: float = 1.0, regularize_entropy: float = 1.0) -> torch.Tensor:
+    """The two regularisation terms of models/effkan.py:258-264 on per-edge magnitudes l1[..., out, in]: for every layer (the
+    leading dimensions) activation * sum(l1) - entropy * sum(p log p) with p = l1 / sum(l1); summed over the layers.  An edge
+    whose magnitude is exactly 0 (every sample outside the knot range) contributes the limit 0 to the entropy term."""
+    total = l1.sum((-2, -1), keepdim=True)
+    p = l1 / total
+    per_layer = regularize_activation * total.squeeze(-1).squeeze(-1) - regularize_entropy * torch.special.xlogy(p, p).sum((-2, -1))
+    return per_layer.sum()
+
+
+# ------------------------------------------------------------------------------------------------
 # attention
 # ------------------------------------------------------------------------------------------------
 _attn_flags = 0      # set by attention()/attention_packed() from the ambient autocast state (the Functions run with autocast off)

@@ -33,13 +33,20 @@ class TransformerBlock(nn.Module):
         x, f = self.run(x, None)
         return x + f
 
-    def run(self, x, pending):
+    def run(self, x, pending, reg=None):
         """The block with its residual adds fused into the LayerNorms (kanvit.ops.add_layernorm: one pass instead of an
         add kernel + a LayerNorm kernel forward, one pass instead of three + an add backward).  `pending` is the previous
         block's feed-forward output that has not been added to the stream yet (None for the first block); returns
         (stream after the attention add, this block's feed-forward output) -- same arithmetic as model.py:31-37:
-            x = x + MSA(LN1(x));  x = x + FF(LN2(x))."""
+            x = x + MSA(LN1(x));  x = x + FF(LN2(x)).
+        reg (a dict of MSA.regularization_loss keywords, or None): also return, as a third value, the sample-based KAN
+        regulariser of the per-head q|k|v layers on the rows they read, LN1(x) -- the tensor this forward already holds."""
         x, h1 = add_layernorm(x, pending, self.norm1)
+        if reg is not None:
+            return self._rest(x, h1) + (self.attn.regularization_loss(h1, **reg),)
+        return self._rest(x, h1)
+
+    def _rest(self, x, h1):
         if x.dim() == 3 and ff_small_supported(self.ff[0].in_features, self.ff[0].out_features):
             # small geometries: residual add + LN2 + feed-forward in one launch (SURVEY 8(f)1); ln_feed_forward itself falls
             # back to add_layernorm + feed_forward for inputs the fused kernel refuses (dtype, autocast, row count)
@@ -102,6 +109,13 @@ def split_types(kind: str):
     if len(kinds) > 1 and any(k in ("flash-attn",) for k in kinds):
         raise ValueError("'flash-attn' stacks bare FlashAttention modules (model.py:113-117) and cannot be mixed per block")
     return kinds
+
+
+def patch_embedding_type(model) -> str:
+    """The layer type of a model's patch embedding (the first entry of its type list)."""
+    lm = model.linear_mapper
+    return {KANLinear: "efficientkan", ChebyKANLayer: "cheby", FastKANLayer: "fast", SineKANLayer: "sine",
+            NaiveFourierKANLayer: "fourier"}.get(type(lm), "vanilla")
 
 
 class VisionTransformer(nn.Module):
@@ -183,10 +197,35 @@ class VisionTransformer(nn.Module):
         self._fused_embed[mode] = True
         return out
 
-    def forward(self, images):
+    REGULARIZED_TYPES = MSA.REGULARIZED_TYPES
+
+    def layer_types(self):
+        """The KAN layer types of the model: its blocks' and its patch embedding's."""
+        return set(self.block_types) | {patch_embedding_type(self)}
+
+    def forward(self, images, return_regularization=False, regularize_activation=1.0, regularize_entropy=1.0):
+        """logits; with return_regularization=True, (logits, reg): reg is the KAN paper's sample-based L1 + entropy regulariser
+        (KANLinear.regularization_loss(x=...), MSA.regularization_loss) summed over the patch embedding, on the patch rows, and
+        every block's per-head q|k|v layers, on norm1(x) -- computed on the tensors this forward holds anyway, by the fused
+        edge-activation kernel (no second forward, no (rows, in, out) tensor).  Model types efficientkan, cheby and fast."""
+        reg, reg_kw, patches = None, None, None
+        if return_regularization:
+            kinds = self.layer_types()
+            if not kinds <= set(self.REGULARIZED_TYPES):
+                raise NotImplementedError(f"return_regularization: model type(s) {sorted(kinds - set(self.REGULARIZED_TYPES))} have no "
+                                          f"edge-activation regulariser; supported: {', '.join(self.REGULARIZED_TYPES)}")
+            reg_kw = dict(regularize_activation=regularize_activation, regularize_entropy=regularize_entropy)
+            # the fused patch embedding gathers from NCHW and never holds the patch matrix: build it once for the regulariser
+            patches = self.patchify(images, self.n_patches)
+            rows = patches.reshape(-1, self.input_d)
+            if isinstance(self.linear_mapper, KANLinear):
+                reg = self.linear_mapper.regularization_loss(x=rows, **reg_kw)
+            else:
+                reg = self.linear_mapper.regularization_loss(rows, **reg_kw)
         out = self._embed_fused(images)
         if out is None:
-            patches = self.patchify(images, self.n_patches)
+            if patches is None:
+                patches = self.patchify(images, self.n_patches)
             b, p, _ = patches.shape
             if isinstance(self.linear_mapper, nn.Linear):
                 tokens = self.linear_mapper(patches)
@@ -197,7 +236,10 @@ class VisionTransformer(nn.Module):
             out = torch.cat((cls, tokens), dim=1) + self.pos_embeddings[: p + 1]
         pending = None
         for blk in self.blocks:
-            if isinstance(blk, TransformerBlock):
+            if isinstance(blk, TransformerBlock) and reg_kw is not None:
+                out, pending, r = blk.run(out, pending, reg_kw)
+                reg = reg + r
+            elif isinstance(blk, TransformerBlock):
                 out, pending = blk.run(out, pending)
             else:                                     # 'flash-attn' models stack bare FlashAttention modules (model.py:113-117)
                 out = blk(out)
@@ -205,4 +247,6 @@ class VisionTransformer(nn.Module):
             out = _ClsToken.apply(out, pending)   # only the class token feeds the head (model.py:166-169)
         else:
             out = out[:, 0]
+        if return_regularization:
+            return self.mlp_head(out), reg
         return self.mlp_head(out)

@@ -39,5 +39,16 @@ class ChebyKANLayer(nn.Module):
         g, i, d1, o = c.shape
         return c.view(g, i * d1, o), None, None
 
+    def edge_activation_l1(self, x):
+        """[out, in]: mean over the samples of |sum_d T_d(tanh x_i) cheby_coeffs[i, o, d]|, the per-edge activation magnitude
+        of the KAN paper's regulariser, reduced over the samples inside the fused kernel (kanvit.ops.edge_l1)."""
+        w, _, _ = self.kan_pack()
+        x2d = x if x.dim() == 2 else x.reshape(-1, self.inputdim)
+        return ops.edge_l1(x2d, w.unsqueeze(0), self.kan_cfg())[0].t()
+
+    def regularization_loss(self, x, regularize_activation=1.0, regularize_entropy=1.0):
+        """The L1 and entropy terms of models/effkan.py:258-264 on edge_activation_l1(x)."""
+        return ops.l1_entropy_loss(self.edge_activation_l1(x), regularize_activation, regularize_entropy)
+
     def forward(self, x):
         return grouped.run_single(self, x.reshape(-1, self.inputdim))

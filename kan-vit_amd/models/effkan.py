@@ -145,8 +145,27 @@ class KANLinear(torch.nn.Module):
         raise NotImplementedError("update_grid (models/effkan.py:189-242) has no caller in the reference "
                                   "repository and is outside the accelerated path (SURVEY.md section 2)")
 
-    def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0):
-        """L1 / entropy surrogate on the spline weights (models/effkan.py:244-264); parameter-only math."""
+    def edge_activation_l1(self, x: torch.Tensor, include_base=False):
+        """[out, in]: the mean over the samples of |phi_{o,i}(x[.., i])|, the per-edge activation magnitude the KAN paper
+        regularises and prunes by -- which the reference says it cannot form behind F.linear (models/effkan.py:244-264).  The
+        fused kernel reduces over the samples as it generates the basis; the (batch, in, out) tensor never exists.  Without
+        the base it is the spline path (scaled_spline_weight), with it the full edge function.  x: any leading dimensions."""
+        from dataclasses import replace
+        assert x.size(-1) == self.in_features
+        x2d = x if x.dim() == 2 else x.reshape(-1, self.in_features)
+        cfg = self.kan_cfg()
+        if include_base:
+            w, bp, _ = self.kan_pack()
+        else:
+            cfg = replace(cfg, has_base=0, base_act=0)
+            w, bp = self.scaled_spline_weight.permute(1, 2, 0).reshape(-1, self.out_features), self.grid.reshape(-1)
+        return ops.edge_l1(x2d, w.unsqueeze(0), cfg, bp.unsqueeze(0))[0].t()
+
+    def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0, x=None, include_base=False):
+        """Without x: the L1 / entropy surrogate on the spline weights (models/effkan.py:244-264); parameter-only math.
+        With x: the same two terms on the sample-based edge_activation_l1(x, include_base), the paper's regulariser."""
+        if x is not None:
+            return ops.l1_entropy_loss(self.edge_activation_l1(x, include_base), regularize_activation, regularize_entropy)
         l1 = self.spline_weight.abs().mean(-1)
         total = l1.sum()
         p = l1 / total

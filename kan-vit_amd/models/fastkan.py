@@ -131,6 +131,28 @@ class FastKANLayer(nn.Module):
         beta = grouped.stack_params([l.layernorm.bias for l in layers]).view(1, 3, n_heads, dh)
         return torch.addcmul(beta, xhat.unsqueeze(1), gamma).reshape(M, 3 * n_heads * dh)
 
+    def edge_activation_l1(self, x, include_base=False):
+        """[out, in]: mean over the samples of |phi_{o,i}|, phi = sum_k exp(-((LN(x)_i - c_k)/h)^2) w[o, i*G + k] (+ the base
+        term base_weight[o, i] * base_activation(x_i) iff use_base_update and include_base): the per-edge activation magnitude
+        of the KAN paper's regulariser, reduced over the samples inside the fused kernel (kanvit.ops.edge_l1).  The LayerNorm is
+        torch's; the kernel reads its output (and, for the base column, the raw input next to it)."""
+        from dataclasses import replace
+        i, g, o = self.input_dim, self.num_grids, self.output_dim
+        x2d = x if x.dim() == 2 else x.reshape(-1, i)
+        u = self.layernorm(x2d)
+        cfg = self.kan_cfg()
+        if self.use_base_update and include_base:
+            w, bp, _ = self.kan_pack()
+            xin = torch.cat([u, x2d.to(u.dtype)], dim=1)
+        else:
+            cfg = replace(cfg, has_base=0, base_act=0)
+            w, bp, xin = self.spline_linear.weight.view(o, i, g).permute(1, 2, 0).reshape(-1, o), self.rbf.grid.detach(), u
+        return ops.edge_l1(xin, w.unsqueeze(0), cfg, bp.unsqueeze(0))[0].t()
+
+    def regularization_loss(self, x, regularize_activation=1.0, regularize_entropy=1.0, include_base=False):
+        """The L1 and entropy terms of models/effkan.py:258-264 on edge_activation_l1(x, include_base)."""
+        return ops.l1_entropy_loss(self.edge_activation_l1(x, include_base), regularize_activation, regularize_entropy)
+
     def forward(self, x, time_benchmark=False):
         self._use_ln = not time_benchmark        # time_benchmark skips the LayerNorm (models/fastkan.py:67-70)
         try:

@@ -9,7 +9,8 @@ train.py:31-40), running on the MI355X kernels, with optional pure data parallel
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py --dp --synthetic ...
 
 Additions over the reference (none change a default): --synthetic / --image-size / --in-chans /
---n-patches / --out-d (geometry), --seed, --dp, --steps-per-epoch, --amp, --graph, --no-tuned-gemms,
+--n-patches / --out-d (geometry), --seed, --dp, --steps-per-epoch, --amp, --graph, --no-tuned-gemms, --reg-lambda /
+--reg-activation / --reg-entropy (the sample-based KAN regulariser added to the step's loss),
 --no-step-metrics (the per-step metrics stay on the device either way: one host sync per epoch instead of the
 reference's three per step, train.py:37,42-44).
 
@@ -160,8 +161,13 @@ def main(args, batches=None, init_state=None):
     logging.info(f"Using device: {device} ({torch.cuda.get_device_name(device)}), world {world}, amp {args.amp}, "
                  f"graph {bool(args.graph)}")
     amp = args.amp == "bf16"
+    reg_lambda = float(getattr(args, "reg_lambda", 0.0))
+    if reg_lambda > 0 and not model.layer_types() <= set(VisionTransformer.REGULARIZED_TYPES):
+        raise SystemExit(f"--reg-lambda: the edge-activation regulariser covers the model types {', '.join(VisionTransformer.REGULARIZED_TYPES)}")
 
     def eager_step(x, y):
+        if reg_lambda > 0:
+            return regularized_step(x, y)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
             y_hat = model(x)
             loss = criterion(y_hat.float(), y)
@@ -172,6 +178,24 @@ def main(args, batches=None, init_state=None):
         else:
             optimizer.zero_grad()
             loss.backward()
+        optimizer.step()
+        return loss.detach(), y_hat.detach()
+
+    def regularized_step(x, y):
+        """The step with the KAN paper's sample-based regulariser: loss = CE + lambda * reg, reg from the same forward (exact fp32
+        also under --amp bf16).  The returned (logged) loss stays the CE term, so trajectories with and without it compare."""
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+            y_hat, reg = model(x, return_regularization=True, regularize_activation=float(getattr(args, "reg_activation", 1.0)),
+                               regularize_entropy=float(getattr(args, "reg_entropy", 1.0)))
+            loss = criterion(y_hat.float(), y)
+        total = loss + reg_lambda * reg.float()
+        if reducer is not None:
+            reducer.zero_grad()
+            reducer.scale_loss(total).backward()
+            reducer.finish()
+        else:
+            optimizer.zero_grad()
+            total.backward()
         optimizer.step()
         return loss.detach(), y_hat.detach()
 
@@ -273,6 +297,11 @@ def parse(argv=None):
     p.add_argument('--graph', action='store_true', help='capture the whole train step in a HIP graph and replay it per batch')
     p.add_argument('--base-activation', choices=['silu', 'gelu', 'gelu-tanh', 'relu', 'tanh', 'identity'], default='silu',
                    help="base activation of every KANLinear / FastKANLayer ('efficientkan' and 'fast' model types)")
+    p.add_argument('--reg-lambda', type=float, default=0.0,
+                   help="weight of the KAN paper's sample-based L1 + entropy regulariser in the step's loss (CE + lambda * reg); "
+                        "'efficientkan', 'cheby' and 'fast' model types; 0 (default): the plain step")
+    p.add_argument('--reg-activation', type=float, default=1.0, help='weight of the L1 term inside the regulariser')
+    p.add_argument('--reg-entropy', type=float, default=1.0, help='weight of the entropy term inside the regulariser')
     p.add_argument('--no-tuned-gemms', action='store_true', help='library-default kernel selection for the stock GEMMs')
     return p.parse_args(argv)
 
