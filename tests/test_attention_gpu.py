@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from oracle import kan_oracle as ko
-from tests._util import T, close, load_npz, max_err, rel_err
+from tests._util import T, close, load_npz, max_err, record_kernels, rel_err
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -317,13 +317,25 @@ def test_flash_attention_module_with_context_and_mask():
     assert rel_err(x.grad.cpu(), xd.grad) < 1e-4 and rel_err(ctxt.grad.cpu(), cd.grad) < 1e-4
 
 
+# key-tile buckets of the forward / of attn_bwd_dq3_kernel at the sequence lengths of the two form tests below (D = 64)
+FWD_BUCKET = {65: 4, 96: 4, 127: 4, 128: 4, 129: 7, 160: 7, 197: 7, 200: 7, 201: 7, 208: 7}
+DQ3_BUCKET = {65: 4, 80: 4, 96: 4, 127: 4, 128: 4, 129: 8, 160: 8, 176: 8, 192: 8, 197: 8, 200: 8, 201: 8, 208: 8}
+KV2_Q2_EXACT = {"attn_delta_kernel", "attn_bwd_kv2_kernel<2, false, false>", "attn_bwd_q2_kernel<2, false>"}
+
+
+def _attn_kernels(names):
+    return {x for x in names if x.startswith("attn")}
+
+
 @pytest.mark.parametrize("n", [65, 96, 127, 128, 129, 160, 197, 200, 201, 208])
 @pytest.mark.parametrize("causal", [False, True])
 def test_fourth_form_ring_kernels(n, causal, monkeypatch):
-    """The LDS-DMA ring kernels (attn_fwd4 / attn_bwd_kv4: D = 64, 64 < N <= 208) at every tile-count / ragged-tile case, with
+    """The LDS-DMA ring kernels (attn_fwd4 / attn_bwd_kv4: D = 64, 64 < N <= 200) at every tile-count / ragged-tile case, with
     MORE heads than work-groups (KANVIT_ATTN_GRID = 5: each persistent work-group walks 6 heads, i.e. the three-buffer ring, the
     loader wave's progressive dO fill and the tile counters wrap around twice) -- against the fp64 oracle, and against the
-    third-form kernels (KANVIT_ATTN_V3) on the same inputs."""
+    third-form kernels (KANVIT_ATTN_V3) on the same inputs.  The kernels of the first run of each arm are recorded and asserted:
+    at N = 201 and 208 three images of a head no longer fit the LDS, so both arms run the third forms there (kept as the cases
+    just past the ring kernels' upper edge, N = 200)."""
     from kanvit import _lib, ops
     torch.manual_seed(1000 + n)
     b, h, d = 5, 6, 64
@@ -343,16 +355,24 @@ def test_fourth_form_ring_kernels(n, causal, monkeypatch):
     monkeypatch.setenv("KANVIT_ATTN_V4", "1")          # (since round 4 the default for these shapes is the 16-row-tile form: next test)
     assert "attn_grid=5" in _lib.reload_config()
     try:
-        ring = run()
+        with record_kernels() as ring_names:
+            ring = run()
         again = run()
         monkeypatch.setenv("KANVIT_ATTN_V3", "1")
         assert "attn_v3=1" in _lib.reload_config()
-        third = run()
+        with record_kernels() as third_names:
+            third = run()
     finally:
         monkeypatch.delenv("KANVIT_ATTN_GRID")
         monkeypatch.delenv("KANVIT_ATTN_V4")
         monkeypatch.delenv("KANVIT_ATTN_V3", raising=False)
         _lib.reload_config()
+    third_form = {"attn_fwd3_kernel<2, %d>" % FWD_BUCKET[n]} | (
+        KV2_Q2_EXACT if causal else {"attn_bwd_kv3_kernel<2, %d>" % DQ3_BUCKET[n], "attn_bwd_dq3_kernel<2, %d>" % DQ3_BUCKET[n]})
+    ring_form = {"attn_fwd4_kernel<2, %d>" % FWD_BUCKET[n]} | (
+        KV2_Q2_EXACT if causal else {"attn_bwd_kv4_kernel<2>", "attn_bwd_dq3_kernel<2, %d>" % DQ3_BUCKET[n]})
+    assert _attn_kernels(ring_names) == (ring_form if n <= 200 else third_form), sorted(ring_names)
+    assert _attn_kernels(third_names) == third_form, sorted(third_names)
     assert all(torch.equal(a, c) for a, c in zip(ring, again))            # no atomics, fixed order: bitwise run to run
     assert max_err(ring[0], o_ref) < 1e-5
     for g, ref in zip(ring[1:], (qd.grad, kd.grad, vd.grad)):
@@ -388,7 +408,8 @@ def test_sixteen_row_tile_kernels(n, bh, monkeypatch):
     monkeypatch.setenv("KANVIT_ATTN_GRID", "5")
     assert "attn_grid=5" in _lib.reload_config() and "attn_v4=0" in _lib.active_config()
     try:
-        new = run()
+        with record_kernels() as names:
+            new = run()
         again = run()
         monkeypatch.setenv("KANVIT_ATTN_V4", "1")
         assert "attn_v4=1" in _lib.reload_config()
@@ -397,6 +418,10 @@ def test_sixteen_row_tile_kernels(n, bh, monkeypatch):
         monkeypatch.delenv("KANVIT_ATTN_GRID")
         monkeypatch.delenv("KANVIT_ATTN_V4", raising=False)
         _lib.reload_config()
+    # the first run: the 16-row forward; the one-kernel backward where a head is 13 tiles, below that the ring kernel + dQ from its dS
+    backward = {"attn16_bwd_kernel<false>"} if n >= 193 else {"attn_bwd_kv4_kernel<2>", "attn_bwd_dq3_kernel<2, %d>" % DQ3_BUCKET[n]}
+    forward = _attn_kernels(names) - backward
+    assert backward <= names and len(forward) == 1 and next(iter(forward)).startswith("attn16_fwd_kernel<"), sorted(names)
     assert all(torch.equal(a, c) for a, c in zip(new, again))             # counters order the hand-offs, sums have a fixed order: bitwise
     assert max_err(new[0], o_ref) < 1e-5
     for g_, ref in zip(new[1:], (qd.grad, kd.grad, vd.grad)):
