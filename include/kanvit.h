@@ -206,6 +206,36 @@ size_t kanvit_edge_l1_bwd_workspace(const kanvit_layer_desc* d);
 int kanvit_edge_l1_bwd(const kanvit_layer_desc* d, const float* x, const float* w, const float* bparams, const float* gA, float* dw,
                        float* dx, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- B-spline refit to a new knot table: the numerical half of KANLinear.update_grid (models/effkan.py:189-242) -------
+ * The reference evaluates the per-edge spline output on the OLD knots into a (rows, in, out) tensor and fits new coefficients
+ * to it with lstsq.  The target is a spline in the old basis, so per feature two nb x nb matrices carry the whole problem
+ * (nb = d->G = grid_size + spline_order, c = g % x_group_mod):
+ *     N[c][i][j][k] = sum_m Bnew_j(x[m, c*I + i]) Bnew_k(x[m, c*I + i])          [x_group_mod][I][nb][nb], float64, written
+ *     C[g][i][j][k] = sum_m Bnew_j(x[m, c*I + i]) Bold_k(x[m, c*I + i])          [groups][I][nb][nb],      float64, written
+ *     w_new[g][i*nb + :][o] = N[c][i]^-1 C[g][i] w_old[g][i*nb + :][o]           packed as kanvit_layer_fwd's w with has_base = 0
+ * d as for kanvit_layer_fwd: family BSPLINE only (every other family is KANVIT_EINVAL, named in kanvit_last_error), has_base = 0
+ * and base_act = 0 (the spline weights alone), any spline_order < G and any knots within 40 per feature, G <= 24 (more is
+ * KANVIT_EINVAL), KANVIT_FLAG_UNIFORM_KNOTS vouches for the OLD knots only (closed-form cubic for Bold); KANVIT_FLAG_BF16_MFMA
+ * is refused (callers clear it: exact fp32 / float64 also under autocast).  old_knots: [groups][bparam_stride] with knots[I][nk]
+ * in front, as kanvit_layer_fwd's bparams; new_knots: [x_group_mod][I][nk] contiguous, one table per x slice; ldy and the bias
+ * are unused.
+ * kanvit_bspline_refit_gram: fp32 sums inside a row band, the bands of kanvit_edge_l1_row_bands (a function of M alone); band
+ * partials go to the workspace (bands x 4 x (x_group_mod + groups) x I x nb x nb bytes) and are added in band order in
+ * float64: no atomics, bitwise reproducible, and a group's result does not depend on the other groups of the launch.
+ * kanvit_bspline_refit_solve: float64 Cholesky of N[c][i], right-hand side and both triangular solves on the device (no host
+ * synchronisation, no solver library).  ok[x_group_mod][I] (bytes) is 1 where the fit exists; a feature whose N[c][i] has a
+ * Cholesky pivot <= KANVIT_BSPLINE_REFIT_TAU * max_j N[c][i][j][j] or whose matrices hold a non-finite entry (a constant x
+ * column, fewer distinct samples than nb, knot intervals of zero width) gets ok = 0 and NOTHING is written to its rows of
+ * w_new: the caller keeps that feature's old knots and weights, i.e. its old function.  M = 0: ok = 0 everywhere, no launch.
+ * kanvit_bspline_refit_supported and kanvit_bspline_refit_workspace are pure host functions.  (ABI 7: no struct or version change) */
+#define KANVIT_BSPLINE_REFIT_TAU 1e-5
+int kanvit_bspline_refit_supported(const kanvit_layer_desc* d);
+size_t kanvit_bspline_refit_workspace(const kanvit_layer_desc* d);
+int kanvit_bspline_refit_gram(const kanvit_layer_desc* d, const float* x, const float* old_knots, const float* new_knots, double* N,
+                              double* C, void* workspace, size_t workspace_bytes, void* stream);
+int kanvit_bspline_refit_solve(const kanvit_layer_desc* d, const double* N, const double* C, const float* w_old, float* w_new,
+                               unsigned char* ok, void* stream);
+
 /* ---- fused patch embedding --------------------------------------
  * The patch-embedding layer of VisionTransformer.forward (model.py:144-152) with its prologue and epilogue inside the
  * kernel: the rows of x are gathered straight from the NCHW image batch -- row m = (image m / P, patch m % P),

@@ -59,6 +59,7 @@ class MSA(torch.nn.Module):
         super().__init__()
         self.d = d
         self.n_heads = n_heads
+        self.type = type
         assert d % n_heads == 0
         dh = d // n_heads
         makers = {
@@ -117,6 +118,35 @@ class MSA(torch.nn.Module):
         """Sum over the 3*H per-head layers of the L1 and entropy terms (models/effkan.py:258-264) of their sample-based edge
         magnitudes on the rows of x -- one grouped launch (edge_activation_l1)."""
         return ops.l1_entropy_loss(self.edge_activation_l1(x, include_base), regularize_activation, regularize_entropy)
+
+    @torch.no_grad()
+    def update_grid(self, x, margin=0.01):
+        """KANLinear.update_grid for all 3*H per-head q, k and v layers on the rows of x [..., d], from ONE grouped refit launch
+        (groups = 3*H, x_group_mod = H, packing as edge_activation_l1).  The q, k and v layers of a head read the same columns
+        with the same constructor arguments, so they share their new knots: one table per head slice.  Every layer ends bit
+        for bit as its own update_grid on its head's slice would leave it.  Returns the number of (head, feature) pairs kept
+        unchanged (0-d device tensor).  type='efficientkan' only."""
+        from dataclasses import replace
+        layers = list(self.q_mappings) + list(self.k_mappings) + list(self.v_mappings)
+        l0 = layers[0]
+        if not isinstance(l0, KANLinear):
+            raise NotImplementedError(f"update_grid: MSA type '{self.type}' has no B-spline grid to update (only 'efficientkan' has)")
+        for m in layers[1:]:
+            assert (m.grid_size, m.spline_order, m.grid_eps, m.enable_standalone_scale_spline) == \
+                (l0.grid_size, l0.spline_order, l0.grid_eps, l0.enable_standalone_scale_spline), \
+                "update_grid: the per-head layers of one MSA must agree in grid_size, spline_order and grid_eps"
+        H, dh = self.n_heads, self.d_head
+        nb = l0.grid_size + l0.spline_order
+        x2d = x.reshape(-1, self.d).float()
+        new_grid = KANLinear.adapted_grid(x2d, l0.grid_size, l0.spline_order, l0.grid_eps, margin).view(H, dh, -1)
+        cfg = replace(l0.kan_cfg(layers), has_base=0, base_act=0, groups=3 * H, x_group_mod=H)
+        sw = torch.stack([m.scaled_spline_weight for m in layers])                       # [g, O, I, nb]
+        w_old = sw.permute(0, 2, 3, 1).reshape(3 * H, dh * nb, dh)
+        old = torch.stack([m.grid.reshape(-1) for m in layers])
+        w_new, ok = ops.bspline_refit(x2d, w_old, cfg, old, new_grid)
+        for g, m in enumerate(layers):
+            m.apply_refit(new_grid[g % H], w_new[g], ok[g % H])
+        return (~ok).sum()
 
     def forward(self, sequences):
         b, n, d = sequences.shape

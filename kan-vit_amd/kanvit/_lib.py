@@ -94,6 +94,10 @@ SYMBOLS = {
     "kanvit_edge_l1_fwd": (C.c_int, [C.POINTER(LayerDesc), _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_edge_l1_bwd_workspace": (C.c_size_t, [C.POINTER(LayerDesc)]),
     "kanvit_edge_l1_bwd": (C.c_int, [C.POINTER(LayerDesc), _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "kanvit_bspline_refit_supported": (C.c_int, [C.POINTER(LayerDesc)]),
+    "kanvit_bspline_refit_workspace": (C.c_size_t, [C.POINTER(LayerDesc)]),
+    "kanvit_bspline_refit_gram": (C.c_int, [C.POINTER(LayerDesc), _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "kanvit_bspline_refit_solve": (C.c_int, [C.POINTER(LayerDesc), _P, _P, _P, _P, _P, _P]),
     "kanvit_patch_embed_fwd": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(PatchDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     "kanvit_patch_embed_fwd_ws": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(PatchDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_patch_embed_bwd_weight_ok": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(PatchDesc)]),

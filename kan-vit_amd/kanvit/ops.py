@@ -572,9 +572,65 @@ def l1_entropy_loss(l1: torch.Tensor, regularize_activation: float = 1.0, regula
 
 
 # ------------------------------------------------------------------------------------------------
+# B-spline refit to a new knot table (KANLinear.update_grid; csrc/kan_bspline_refit.hip)
+# ------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def bspline_refit(x2d: torch.Tensor, w_old_packed: torch.Tensor, cfg: LayerCfg, old_knots: torch.Tensor,
+                  new_knots: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(w_new_packed [groups, I*nb, O], ok [x_group_mod, I] bool): the spline weights of `cfg.groups` B-spline layers refitted
+    from old_knots [groups, I*nk] to new_knots [x_group_mod, I, nk] (one table per x slice) on the rows of x2d, so that every
+    edge computes the function it computed before wherever the rows sample it -- what models/effkan.py:189-242 obtains from a
+    (rows, in, out) tensor and lstsq, here from two nb x nb Gram matrices per feature (kanvit_bspline_refit_*; include/kanvit.h).
+    cfg: family BSPLINE, G = nb = grid_size + spline_order, has_base = 0; w_old_packed as edge_l1's weights without the base
+    column.  ok is False for a feature whose fit does not exist (constant column, fewer distinct samples than nb, ...): its rows
+    of w_new_packed are w_old_packed's.  Exact fp32 / float64 also under autocast, deterministic, no autograd, no host
+    synchronisation (HIP-graph capturable); workspace and matrices come from the torch allocator."""
+    if cfg.family != BSPLINE:
+        raise NotImplementedError(f"bspline_refit: family {_lib.FAMILY_NAMES[cfg.family]} has no knot table to refit (bspline only)")
+    from dataclasses import replace
+    cfg = replace(cfg, flags=cfg.flags & (_lib.FLAG_UNIFORM_KNOTS | _lib.FLAG_SHARED_BPARAMS))
+    for n, t in (("x", x2d), ("w_old", w_old_packed), ("old_knots", old_knots), ("new_knots", new_knots)):
+        _require_gpu_f32(n, t)
+    x = x2d
+    if x.dim() != 2:
+        raise KanvitError(f"bspline_refit: x must be 2-D, got {tuple(x.shape)}")
+    if x.shape[1] != cfg.x_group_mod * cfg.I:
+        raise KanvitError(f"bspline_refit: x has {x.shape[1]} columns, expected {cfg.x_group_mod * cfg.I}")
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):      # a column slice of a wider matrix is read in place
+        x = x.contiguous()
+    M = x.shape[0]
+    ldx = max(x.stride(0), x.shape[1]) if M > 1 else x.shape[1]
+    nb, nk = cfg.G, cfg.G + cfg.spline_order + 1
+    w_old = w_old_packed.contiguous()
+    if tuple(w_old.shape) != (cfg.groups, cfg.I * nb, cfg.O):
+        raise KanvitError(f"bspline_refit: packed weight shape {tuple(w_old.shape)} != {(cfg.groups, cfg.I * nb, cfg.O)}")
+    old_knots = old_knots.reshape(cfg.groups, -1).contiguous()
+    new_knots = new_knots.contiguous()
+    if old_knots.shape[1] < cfg.I * nk or tuple(new_knots.shape) != (cfg.x_group_mod, cfg.I, nk):
+        raise KanvitError(f"bspline_refit: knot tables {tuple(old_knots.shape)} / {tuple(new_knots.shape)} do not hold "
+                          f"[{cfg.groups}][{cfg.I}*{nk}] / [{cfg.x_group_mod}][{cfg.I}][{nk}]")
+    d = _desc(cfg, M, ldx, 0, cfg.groups * cfg.O, old_knots.shape[1])
+    L = _lib.lib()
+    dev = x.device
+    gram_n = torch.empty(cfg.x_group_mod, cfg.I, nb, nb, device=dev, dtype=torch.float64)
+    gram_c = torch.empty(cfg.groups, cfg.I, nb, nb, device=dev, dtype=torch.float64)
+    w_new = w_old.clone()                                    # the rows of a flagged feature are not written: they stay the old ones
+    ok = torch.empty(cfg.x_group_mod, cfg.I, device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        nbytes = int(L.kanvit_bspline_refit_workspace(C.byref(d)))
+        ws = _workspace(nbytes, dev)
+        with _timed("bspline_refit", 2 * M * (cfg.groups + cfg.x_group_mod) * cfg.I * nb * nb, 4 * (x.numel() + 2 * w_old.numel())):
+            check(L.kanvit_bspline_refit_gram(C.byref(d), _ptr(x), _ptr(old_knots), _ptr(new_knots), _ptr(gram_n), _ptr(gram_c), _ptr(ws),
+                                              C.c_size_t(nbytes), _stream()), "kanvit_bspline_refit_gram")
+            check(L.kanvit_bspline_refit_solve(C.byref(d), _ptr(gram_n), _ptr(gram_c), _ptr(w_old), _ptr(w_new), _ptr(ok), _stream()),
+                  "kanvit_bspline_refit_solve")
+    return w_new, ok.bool()
+
+
+# ------------------------------------------------------------------------------------------------
 # attention
 # ------------------------------------------------------------------------------------------------
-_attn_flags = 0      # set by attention()/attention_packed() from the ambient autocast state (the Functions run with autocast off)
+_attn_flags = 0     # set by attention()/attention_packed() from the ambient autocast state (the Functions run with autocast off)
 
 
 def _attn_build_desc(q, k, v, o, causal: bool, scale: float, flags: int, self_attention: bool) -> AttnDesc:

@@ -197,6 +197,48 @@ class VisionTransformer(nn.Module):
         self._fused_embed[mode] = True
         return out
 
+    def _embed(self, images, patches=None):
+        """The token sequence the first block reads: patch embedding, class token, position embedding (model.py:144-152)."""
+        out = self._embed_fused(images)
+        if out is None:
+            if patches is None:
+                patches = self.patchify(images, self.n_patches)
+            b, p, _ = patches.shape
+            if isinstance(self.linear_mapper, nn.Linear):
+                tokens = self.linear_mapper(patches)
+            else:
+                # ChebyKANLayer returns (B*P, d) like the reference's; restore (B, P, d) (SURVEY.md D3)
+                tokens = self.linear_mapper(patches).reshape(b, p, self.d_hidden)
+            cls = self.v_class.unsqueeze(0).expand(b, -1, -1)
+            out = torch.cat((cls, tokens), dim=1) + self.pos_embeddings[: p + 1]
+        return out
+
+    @torch.no_grad()
+    def update_grid(self, images, margin=0.01):
+        """KANLinear.update_grid (models/effkan.py:189-242) for every efficient-KAN layer of the model on one image batch: the
+        patch embedding on the patch rows, then block by block the per-head q|k|v layers on norm1 of the block's input
+        (MSA.update_grid, one grouped launch per block).  A block runs after its own update, so later blocks adapt to the
+        activations of the already-updated earlier ones.  Blocks of other types in a mixed model just run.  Afterwards the
+        updated layers evaluate the general Cox-de Boor kernels instead of the uniform closed form.  Returns the number of
+        features kept unchanged (0-d device tensor)."""
+        kan_blocks = [isinstance(blk, TransformerBlock) and isinstance(blk.attn.q_mappings[0], KANLinear) for blk in self.blocks]
+        if not isinstance(self.linear_mapper, KANLinear) and not any(kan_blocks):
+            raise NotImplementedError(f"update_grid: model type(s) {sorted(self.layer_types())} have no KANLinear, the only layer "
+                                      "with a B-spline grid to update ('efficientkan')")
+        kept = torch.zeros((), dtype=torch.int64, device=images.device)
+        if isinstance(self.linear_mapper, KANLinear):
+            kept = kept + self.linear_mapper.update_grid(self.patchify(images, self.n_patches).reshape(-1, self.input_d), margin)
+        # whether the fused patch embedding covers this model was decided for the old grid's flags
+        self._fused_embed = None
+        out = self._embed(images)
+        for blk, is_kan in zip(self.blocks, kan_blocks):
+            if is_kan:
+                kept = kept + blk.attn.update_grid(blk.norm1(out), margin)
+            if blk is not self.blocks[-1]:
+                out = blk(out)
+        self._fused_embed = None
+        return kept
+
     REGULARIZED_TYPES = MSA.REGULARIZED_TYPES
 
     def layer_types(self):
@@ -222,18 +264,7 @@ class VisionTransformer(nn.Module):
                 reg = self.linear_mapper.regularization_loss(x=rows, **reg_kw)
             else:
                 reg = self.linear_mapper.regularization_loss(rows, **reg_kw)
-        out = self._embed_fused(images)
-        if out is None:
-            if patches is None:
-                patches = self.patchify(images, self.n_patches)
-            b, p, _ = patches.shape
-            if isinstance(self.linear_mapper, nn.Linear):
-                tokens = self.linear_mapper(patches)
-            else:
-                # ChebyKANLayer returns (B*P, d) like the reference's; restore (B, P, d)
-                tokens = self.linear_mapper(patches).reshape(b, p, self.d_hidden)
-            cls = self.v_class.unsqueeze(0).expand(b, -1, -1)
-            out = torch.cat((cls, tokens), dim=1) + self.pos_embeddings[: p + 1]
+        out = self._embed(images, patches)
         pending = None
         for blk in self.blocks:
             if isinstance(blk, TransformerBlock) and reg_kw is not None:

@@ -4,7 +4,9 @@ Forward / backward run in the fused kernel: Cox-de Boor bases on the per-feature
 ``grid`` (half-open order-0 intervals, models/effkan.py:115), the base path (``base_activation``: SiLU by
 default, or one of ops.SUPPORTED_BASE_ACTIVATIONS, read on every forward) and both
 contractions in one pass.  Construction-time host logic (knot vector, the least-squares
-initialisation of ``spline_weight``) is plain torch, as in the reference."""
+initialisation of ``spline_weight``) is plain torch, as in the reference.  ``update_grid`` computes the new
+knots with the reference's torch expressions and refits the weights in the fused Gram-matrix kernels
+(kanvit.ops.bspline_refit)."""
 import math
 
 import torch
@@ -13,7 +15,7 @@ import torch.nn.functional as F
 from kanvit import _lib, grouped, ops
 
 
-_GRID_FACTS = {}      # (ids, versions, data_ptrs of the knot buffers) -> (uniform, all_equal)
+_GRID_FACTS = {}      # (ids, versions, data_ptrs of the knot buffers) -> (uniform, all_equal, the knot buffers)
 
 
 def _grid_facts(layers):
@@ -22,6 +24,10 @@ def _grid_facts(layers):
     counters, so an in-place change of any grid is noticed."""
     key = tuple((id(m), m.grid._version, m.grid.data_ptr()) for m in layers)
     hit = _GRID_FACTS.get(key)
+    # An entry keeps its knot tensors: a buffer replaced by `.to()` / `.cpu().cuda()` starts again at version 0 and may get a
+    # freed buffer's address, and since update_grid a replaced buffer need not hold what the old one held.
+    if hit is not None and any(t is not m.grid for t, m in zip(hit[2], layers)):
+        hit = None
     if hit is None:
         g0 = layers[0].grid
         row = g0[0].double()
@@ -32,8 +38,8 @@ def _grid_facts(layers):
         equal = all(m.grid.shape == g0.shape and bool((m.grid == g0).all()) for m in layers[1:])
         if len(_GRID_FACTS) > 256:
             _GRID_FACTS.clear()
-        hit = _GRID_FACTS[key] = (uniform and layers[0].spline_order == 3, equal)
-    return hit
+        hit = _GRID_FACTS[key] = (uniform and layers[0].spline_order == 3, equal, tuple(m.grid for m in layers))
+    return hit[:2]
 
 
 class KANLinear(torch.nn.Module):
@@ -140,10 +146,47 @@ class KANLinear(torch.nn.Module):
         y = grouped.run_single(self, x.reshape(-1, self.in_features))
         return y.reshape(*x.shape[:-1], self.out_features)
 
+    @staticmethod
+    def adapted_grid(x: torch.Tensor, grid_size, spline_order, grid_eps, margin=0.01):
+        """[in, grid_size + 2*spline_order + 1]: the knots update_grid moves to -- per channel the blend of the sample quantiles
+        and a uniform grid over the sample range, extended by spline_order uniform steps on each side.  The arithmetic of
+        models/effkan.py:204-238 operation for operation (same dtypes, same order of the float operations, the same truncating
+        int64 linspace for the sample indices), in torch on x's device, so the knots are the reference's up to contraction."""
+        xs = x.sort(dim=0).values                                       # every channel on its own
+        lo, hi = xs[0], xs[-1]
+        picks = torch.linspace(0, x.size(0) - 1, grid_size + 1, dtype=torch.int64, device=x.device)
+        step = (hi - lo + 2 * margin) / grid_size
+        ramp = torch.arange(grid_size + 1, dtype=torch.float32, device=x.device).unsqueeze(1)
+        inner = grid_eps * (ramp * step + lo - margin) + (1 - grid_eps) * xs[picks]
+        away = torch.arange(1, spline_order + 1, device=x.device).unsqueeze(1)
+        knots = torch.cat([inner[:1] - step * away.flip(0), inner, inner[-1:] + step * away], dim=0)
+        return knots.t().contiguous()
+
     @torch.no_grad()
     def update_grid(self, x: torch.Tensor, margin=0.01):
-        raise NotImplementedError("update_grid (models/effkan.py:189-242) has no caller in the reference "
-                                  "repository and is outside the accelerated path (SURVEY.md section 2)")
+        """Move the knots to where the rows of x (batch, in) lie and refit spline_weight so that the layer computes the same
+        function on them (models/effkan.py:189-242), with the reference's quirk kept: the fit target is scaled_spline_weight, the
+        result goes into spline_weight, spline_scaler stays.  The refit runs in the fused Gram-matrix kernels
+        (ops.bspline_refit): no (batch, in, out) tensor, no lstsq.  A feature whose fit does not exist (a constant column,
+        fewer distinct samples than basis functions) keeps its knots and weights, i.e. its function; the reference's answer
+        there depends on the LAPACK driver.  Returns the number of features kept unchanged, a 0-d device tensor (the reference
+        returns None)."""
+        from dataclasses import replace
+        assert x.dim() == 2 and x.size(1) == self.in_features
+        x = x.float()
+        new_grid = self.adapted_grid(x, self.grid_size, self.spline_order, self.grid_eps, margin)
+        cfg = replace(self.kan_cfg(), has_base=0, base_act=0)
+        w_old = self.scaled_spline_weight.permute(1, 2, 0).reshape(1, -1, self.out_features)
+        w_new, ok = ops.bspline_refit(x, w_old, cfg, self.grid.reshape(1, -1), new_grid.unsqueeze(0))
+        self.apply_refit(new_grid, w_new[0], ok[0])
+        return (~ok).sum()
+
+    def apply_refit(self, new_grid, w_new, ok):
+        """Take the refitted knots [in, nk] and packed weights [in*nb, out] for the features with ok[in] set."""
+        nb = self.grid_size + self.spline_order
+        sw = w_new.view(self.in_features, nb, self.out_features).permute(2, 0, 1)
+        self.grid.copy_(torch.where(ok[:, None], new_grid, self.grid))
+        self.spline_weight.data.copy_(torch.where(ok[None, :, None], sw, self.spline_weight))
 
     def edge_activation_l1(self, x: torch.Tensor, include_base=False):
         """[out, in]: the mean over the samples of |phi_{o,i}(x[.., i])|, the per-edge activation magnitude the KAN paper

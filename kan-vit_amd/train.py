@@ -10,7 +10,8 @@ train.py:31-40), running on the MI355X kernels, with optional pure data parallel
 
 Additions over the reference (none change a default): --synthetic / --image-size / --in-chans /
 --n-patches / --out-d (geometry), --seed, --dp, --steps-per-epoch, --amp, --graph, --no-tuned-gemms, --reg-lambda /
---reg-activation / --reg-entropy (the sample-based KAN regulariser added to the step's loss),
+--reg-activation / --reg-entropy (the sample-based KAN regulariser added to the step's loss), --grid-update-every
+(KANLinear.update_grid on the step's batch every N-th step),
 --no-step-metrics (the per-step metrics stay on the device either way: one host sync per epoch instead of the
 reference's three per step, train.py:37,42-44).
 
@@ -117,6 +118,18 @@ def set_base_activation(model, model_type, name):
 
 def main(args, batches=None, init_state=None):
     rank, world, local = 0, 1, 0
+    grid_every = int(getattr(args, "grid_update_every", 0))
+    if grid_every > 0:
+        from model import split_types
+        if args.graph:
+            raise SystemExit("--grid-update-every is not combined with --graph: the captured step bakes in the kernel forms the "
+                             "grids' flags selected, and a grid update changes them")
+        if args.dp:
+            raise SystemExit("--grid-update-every is not combined with --dp: every rank would fit its own shard and the replicas "
+                             "would diverge (a gathered update is not implemented)")
+        if "efficientkan" not in split_types(args.model_type):
+            raise SystemExit(f"--grid-update-every: model type '{args.model_type}' has no KANLinear, the only layer with a B-spline "
+                             "grid to update ('efficientkan')")
     if args.dp:
         import torch.distributed as dist
         rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
@@ -205,6 +218,7 @@ def main(args, batches=None, init_state=None):
     if batches is None and not args.synthetic:
         train_loader, test_loader, sampler = cifar_loaders(per_rank, rank, world)
     history = {"losses": [], "epoch_loss": []}
+    n_steps = 0
     model.train()
     for epoch in range(args.epochs):
         if batches is not None:
@@ -221,6 +235,9 @@ def main(args, batches=None, init_state=None):
             x, y = x.to(device, non_blocking=True), y.to(device, non_blocking=True)
             if args.graph and step is eager_step:
                 step = _GraphedStep(eager_step, model, optimizer, x, y)
+            n_steps += 1
+            if grid_every > 0 and n_steps % grid_every == 0:
+                model.update_grid(x)            # before the step, on the step's own batch; Adam's moments stay as they are
             loss, y_hat = step(x, y)
             step_losses.append(loss.clone() if args.graph else loss)
             if not args.no_step_metrics:
@@ -302,6 +319,10 @@ def parse(argv=None):
                         "'efficientkan', 'cheby' and 'fast' model types; 0 (default): the plain step")
     p.add_argument('--reg-activation', type=float, default=1.0, help='weight of the L1 term inside the regulariser')
     p.add_argument('--reg-entropy', type=float, default=1.0, help='weight of the entropy term inside the regulariser')
+    p.add_argument('--grid-update-every', type=int, default=0,
+                   help="every N-th step, before the step, move the B-spline knots of every KANLinear to that step's batch and refit "
+                        "the spline weights (VisionTransformer.update_grid; 'efficientkan' model types; not with --graph or --dp). "
+                        "Adam's moments of spline_weight are left as they are, as upstream practice has it; 0 (default): never")
     p.add_argument('--no-tuned-gemms', action='store_true', help='library-default kernel selection for the stock GEMMs')
     return p.parse_args(argv)
 
