@@ -13,13 +13,11 @@ namespace {
 // The contraction index n is split per 32-column chunk as n = n0 + hf*16 + s so a lane consumes 16 CONSECUTIVE dY values.
 // 256 threads = 4 waves x 32 rows; LDS = two W^T chunk buffers [32 n][KCT+1]; one barrier per 32 dY columns.
 // SHARED: q, k, v of a head are summed in the accumulators (one chain rule per head); otherwise one chain rule per group.
-// Requirements (host-checked): GP compile time, I % (2*FPH) == 0, O % 32 == 0, 16-byte aligned rows.
+// Requirements (plan_layer_bwd_input): GP compile time, I % (2*FPH) == 0, O % 32 == 0, 16-byte aligned rows.
 // SINE (GP = 5): d loss / d freq is summed per lane over the features of a step, wave-reduced into per-wave LDS slots and
 // written as this row tile's partials to dparam (same protocol as the LDS-tile kernel).
 // =============================================================================================
-constexpr int kv_bwi_g0(int fam) { return fam == KV_CHEBY ? 1 : 0; }
-constexpr int kv_bwi_kt(int fam, int gp, int kt) { return ((16 * kt) / gp * (gp - kv_bwi_g0(fam)) + 15) / 16; }
-
+// (kv_bwi_g0 / kv_bwi_kt: kan_layer_common.h -- the plan sizes the LDS with them)
 // CHEBY: dT0/dx = 0, so the T0 slots are left out of the permutation -- slot q <-> (feature q / (GP-1), basis index q % (GP-1) + 1) --
 // and KT = 5 accumulators become kv_bwi_kt = 4 (the template keeps KT = 5: FPH = 16 features per half either way).  Every dPhi value
 // is the same contraction as before, only in another accumulator slot: dx is bitwise unchanged.
@@ -300,62 +298,41 @@ __global__ __launch_bounds__(256, (FAM == KV_SINE || FAM == KV_FOURIER) ? 1 : 2)
     kan_bwd_input_reg_kbody<FAM, GP, KT, SHARED, KV_ACT_DYN>(a);
 }
 
-// ---- register-form input gradient (fp32 exact) ---------------------------------------------------
+// ---- register-form input gradient (fp32 exact): launches what plan_layer_bwd_input chose (a.tail_y0 = p.tail_y0) ----
 template <int FAM, int GP, int KT>
-int launch_bwd_input_reg(const LayerArgs& a0, hipStream_t st) {
-    constexpr int FPH = (16 * KT) / GP, IC = 2 * FPH;
-    const int nshare = a0.groups / a0.xmod;
-    LayerArgs a = a0;
-    if (a.I % IC || a.O % 32) return 1;
-    if ((a.ldx & 3) || (a.ldy & 3) || (a.O & 3) || (FPH & 3 ? false : ((a.I & 3) != 0)) || ((uintptr_t)a.x & 15) ||
-        ((uintptr_t)a.dx & 15) || ((uintptr_t)a.dy & 15) || ((uintptr_t)a.w & 15))
-        return 1;
-    if ((long long)IC * GP * a.O >= (1LL << 30)) return 1;
-    constexpr int KCT_ = 32 * kv_bwi_kt(FAM, GP, KT), HOFF_ = (KCT_ % 64 == 32) ? KCT_ : KCT_ + 32, WS2_ = ((HOFF_ + KCT_ + 13) / 16) * 16 + 2;
-    const size_t lds = sizeof(float) * (2 * 16 * WS2_ + (FAM == KV_SINE ? (size_t)nshare * 4 * GP : 0));
-    if (FAM == KV_SINE && !a.dparam) return 1;
-    const bool shared = kv_shared_basis<FAM>() && kv_share_ok(FAM, a.flags) && nshare > 1;
-    const long long tiles = (a0.M + BM - 1) / BM;
-    const int nci = a.I / IC;
-    if (FAM != KV_SINE && nci > 1) a.tail_y0 = kv_tail_first_tile(tiles, a.xmod);
-    const long long t1 = a.tail_y0 < tiles ? a.tail_y0 : tiles;
-    dim3 grid((unsigned)a.xmod, (unsigned)(t1 + nci * (tiles - t1)), 1);
-    if (shared) {
+int launch_bwd_input_reg(const LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st) {
+    const dim3 grid(p.gx, p.gy, 1);
+    if (p.shared) {
         if constexpr (kv_shared_basis<FAM>()) {
-            KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_kernel, kan_bwd_input_reg_act_kernel, (FAM, GP, KT, true), grid, dim3(256), lds, st, a);
+            KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_kernel, kan_bwd_input_reg_act_kernel, (FAM, GP, KT, true), grid, dim3(256), p.lds, st, a);
             KV_LAUNCH_CHECK("kan_bwd_input_reg_kernel");
             return 0;
         }
     }
-    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_kernel, kan_bwd_input_reg_act_kernel, (FAM, GP, KT, false), grid, dim3(256), lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_kernel, kan_bwd_input_reg_act_kernel, (FAM, GP, KT, false), grid, dim3(256), p.lds, st, a);
     KV_LAUNCH_CHECK("kan_bwd_input_reg_kernel");
     return 0;
 }
 
-// returns 1 when not covered (fall back to the LDS-tile kernel)
+// the <GP, KT> instantiations: KV_REG_BASES' rows with bwi_kt (the plan holds one of them)
 template <int FAM>
-int try_bwd_input_reg(const LayerArgs& a, hipStream_t st) {
-    if (kv_config().no_reg) return 1;
-    if constexpr (FAM == KV_LINEAR) { if (a.GP == 1) return launch_bwd_input_reg<FAM, 1, 2>(a, st); }
-    if constexpr (FAM == KV_CHEBY) { if (a.GP == 5) return launch_bwd_input_reg<FAM, 5, 5>(a, st); }
-    if constexpr (FAM == KV_BSPLINE) {
-        if (a.GP == 9 && a.has_base && (a.flags & KANVIT_FLAG_UNIFORM_KNOTS) && a.order == 3) return launch_bwd_input_reg<FAM, 9, 5>(a, st);
+int dispatch_bwd_input_reg(const LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st) {
+    if constexpr (FAM == KV_LINEAR) return launch_bwd_input_reg<FAM, 1, 2>(a, p, st);
+    if constexpr (FAM == KV_CHEBY) return launch_bwd_input_reg<FAM, 5, 5>(a, p, st);
+    if constexpr (FAM == KV_BSPLINE || FAM == KV_RBF) return launch_bwd_input_reg<FAM, 9, 5>(a, p, st);
+    if constexpr (FAM == KV_FOURIER) return launch_bwd_input_reg<FAM, 56, 7>(a, p, st);
+    if constexpr (FAM == KV_SINE) {
+        if (p.gp == 4) return launch_bwd_input_reg<FAM, 4, 4>(a, p, st);
+        if (p.gp == 5) return launch_bwd_input_reg<FAM, 5, 5>(a, p, st);
+        return launch_bwd_input_reg<FAM, 28, 7>(a, p, st);
     }
-    if constexpr (FAM == KV_RBF) { if (a.GP == 9 && a.has_base && kv_rbf_reg_ok(a.flags, a.G)) return launch_bwd_input_reg<FAM, 9, 5>(a, st); }
-    if constexpr (FAM == KV_FOURIER) { if (a.GP == 56) return launch_bwd_input_reg<FAM, 56, 7>(a, st); }
-    if constexpr (FAM == KV_SINE) {   // attention.py:140 builds the per-head sine mappings with grid_size = 4; 5 is the layer's default
-        if (a.GP == 4) return launch_bwd_input_reg<FAM, 4, 4>(a, st);
-        if (a.GP == 5) return launch_bwd_input_reg<FAM, 5, 5>(a, st);
-        if (a.GP == 28) return launch_bwd_input_reg<FAM, 28, 7>(a, st);      // the G = 28 patch embedding (model.py:72)
-    }
-    return 1;
+    return kv_fail(KANVIT_EINVAL, "internal: register input-gradient dispatch");
 }
-
 
 }  // namespace
 
-int kv_try_bwd_input_reg(int family, const LayerArgs& a, hipStream_t st) {
-#define KV_CALL(F) try_bwd_input_reg<F>(a, st)
+int kv_bwd_input_reg(int family, const LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st) {
+#define KV_CALL(F) dispatch_bwd_input_reg<F>(a, p, st)
     KV_FAMILY_SWITCH(family, KV_CALL)
 #undef KV_CALL
 }

@@ -564,11 +564,12 @@ __global__ __launch_bounds__(256, 1) void kan_bwd_input_res_bf16_act_kernel(cons
 }
 
 template <int FAM, int GP, int KT>
-int launch_bwd_input_reg_bf16(LayerArgs& a, const BwdRegBf16Plan& p, hipStream_t st) {
+int launch_bwd_input_reg_bf16(LayerArgs& a, const LayerBwdInputPlan& pl, hipStream_t st) {
+    const BwdRegBf16Plan& p = pl.rb;
     const long long total = (long long)a.groups * p.nci * (a.O / 16) * 2 * 32 * KT;
-    if (p.vcols) {
-        // one wide layer (the patch embedding: O = 384 / 768): its 64-column chunks are contracted one per step into the SAME
-        // accumulators -- exactly the SHARED schedule with the chunks in the role of the groups that share x and the basis
+    const dim3 grid(pl.gx, pl.gy, 1);
+    if (pl.form == LAYER_BWI_REG_BF16_WIDE) {
+        // one wide layer: its 64-column chunks run as the "groups" of a SHARED launch (plan_layer_bwd_input)
         hipLaunchKernelGGL(kan_pack_w_bwd_reg_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.w,
                            const_cast<unsigned short*>(a.wb2), a.K, 64, GP, p.fph, 32 * KT, p.nci, total, (long long)a.O, 64LL);
         KV_LAUNCH_CHECK("kan_pack_w_bwd_reg_kernel");
@@ -577,68 +578,56 @@ int launch_bwd_input_reg_bf16(LayerArgs& a, const BwdRegBf16Plan& p, hipStream_t
         v.xmod = 1;
         v.O = 64;
         v.vcols = 1;
-        dim3 vgrid(1, (unsigned)((a.M + BM - 1) / BM), 1);
-        KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_bf16_kernel, kan_bwd_input_reg_bf16_act_kernel, (FAM, GP, KT, true), vgrid, dim3(256), p.lds, st, v);
+        KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_bf16_kernel, kan_bwd_input_reg_bf16_act_kernel, (FAM, GP, KT, true), grid, dim3(256), pl.lds, st, v);
         KV_LAUNCH_CHECK("kan_bwd_input_reg_bf16_kernel");
         return 0;
     }
     hipLaunchKernelGGL(kan_pack_w_bwd_reg_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.w,
                        const_cast<unsigned short*>(a.wb2), a.K, a.O, GP, p.fph, 32 * KT, p.nci, total, (long long)a.O, (long long)a.K * a.O);
     KV_LAUNCH_CHECK("kan_pack_w_bwd_reg_kernel");
-    const int nshare = a.groups / a.xmod;
-    const bool shared = kv_shared_basis<FAM>() && kv_share_ok(FAM, a.flags) && nshare > 1;
-    dim3 grid((unsigned)a.xmod, (unsigned)((a.M + BM - 1) / BM), 1);
     if constexpr (FAM != KV_SINE) {
-        if (a.O == 64 && (nshare == 1 || nshare == 3) && !kv_config().bi_no_res) {      // the per-head layers: dY resident (see the kernel)
-            const long long tiles = (a.M + BM - 1) / BM;
-            if (p.nci > 1) a.tail_y0 = kv_tail_first_tile(tiles, a.xmod);
-            const long long t1 = a.tail_y0 < tiles ? a.tail_y0 : tiles;
-            grid.y = (unsigned)(t1 + (long long)p.nci * (tiles - t1));
-            constexpr int IC_ = 2 * ((16 * KT) / GP);
-            const size_t lds3 = (size_t)3 * 4 * 2 * 32 * KT * 16 + sizeof(float) * 4 * 32 * (IC_ + 4);      // a ring of three W step images + four store strips
-            if (nshare == 1) {
+        if (pl.form == LAYER_BWI_RES_BF16) {      // the per-head layers: dY resident (see the kernel)
+            if (pl.nsh == 1) {
                 KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 1, false));
-                KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 1, false), grid, dim3(256), lds3, st, a);
+                KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 1, false), grid, dim3(256), pl.lds, st, a);
                 KV_LAUNCH_CHECK("kan_bwd_input_res_bf16_kernel");
                 return 0;
             }
-            if (shared) {
+            if (pl.shared) {
                 if constexpr (kv_shared_basis<FAM>()) {
                     KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 3, true));
-                    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 3, true), grid, dim3(256), lds3, st, a);
+                    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 3, true), grid, dim3(256), pl.lds, st, a);
                     KV_LAUNCH_CHECK("kan_bwd_input_res_bf16_kernel");
                     return 0;
                 }
             } else {
                 KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 3, false));
-                KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 3, false), grid, dim3(256), lds3, st, a);
+                KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_res_bf16_kernel, kan_bwd_input_res_bf16_act_kernel, (FAM, GP, KT, 3, false), grid, dim3(256), pl.lds, st, a);
                 KV_LAUNCH_CHECK("kan_bwd_input_res_bf16_kernel");
                 return 0;
             }
         }
     }
-    if (shared) {
+    if (pl.shared) {
         if constexpr (kv_shared_basis<FAM>()) {
-            KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_bf16_kernel, kan_bwd_input_reg_bf16_act_kernel, (FAM, GP, KT, true), grid, dim3(256), p.lds, st, a);
+            KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_bf16_kernel, kan_bwd_input_reg_bf16_act_kernel, (FAM, GP, KT, true), grid, dim3(256), pl.lds, st, a);
             KV_LAUNCH_CHECK("kan_bwd_input_reg_bf16_kernel");
             return 0;
         }
     }
-    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_bf16_kernel, kan_bwd_input_reg_bf16_act_kernel, (FAM, GP, KT, false), grid, dim3(256), p.lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_reg_bf16_kernel, kan_bwd_input_reg_bf16_act_kernel, (FAM, GP, KT, false), grid, dim3(256), pl.lds, st, a);
     KV_LAUNCH_CHECK("kan_bwd_input_reg_bf16_kernel");
     return 0;
 }
 
+// the <GP, KT> instantiations: KV_REG_BASES' rows with bwi_bf16_kt (the plan holds one of them)
 template <int FAM>
-int dispatch_bwd_input_reg_bf16(LayerArgs& a, const BwdRegBf16Plan& p, hipStream_t st) {
+int dispatch_bwd_input_reg_bf16(LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st) {
     if constexpr (FAM == KV_LINEAR) return launch_bwd_input_reg_bf16<FAM, 1, 2>(a, p, st);
     if constexpr (FAM == KV_CHEBY) return launch_bwd_input_reg_bf16<FAM, 5, 5>(a, p, st);
     if constexpr (FAM == KV_BSPLINE) return launch_bwd_input_reg_bf16<FAM, 9, 5>(a, p, st);
     if constexpr (FAM == KV_RBF) return launch_bwd_input_reg_bf16<FAM, 9, 5>(a, p, st);
-    if constexpr (FAM == KV_SINE) {
-        if (!a.dparam) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_input: SINE needs dparam");
-        return p.gp == 28 ? launch_bwd_input_reg_bf16<FAM, 28, 7>(a, p, st) : launch_bwd_input_reg_bf16<FAM, 4, 4>(a, p, st);
-    }
+    if constexpr (FAM == KV_SINE) return p.gp == 28 ? launch_bwd_input_reg_bf16<FAM, 28, 7>(a, p, st) : launch_bwd_input_reg_bf16<FAM, 4, 4>(a, p, st);
     return kv_fail(KANVIT_EINVAL, "internal: bf16 register input-gradient dispatch");
 }
 
@@ -650,13 +639,9 @@ BwdRegBf16Plan plan_bwd_input_reg_bf16(const kanvit_layer_desc* d) {
     if (kv_config().no_reg || kv_config().no_bf16 || !(d->flags & KANVIT_FLAG_BF16_MFMA)) return p;
     p.gp = gp_of(d);
     const int fam = d->family;
-    if (fam == KANVIT_LINEAR && p.gp == 1) p.kt = 2;
-    else if (fam == KANVIT_CHEBY && p.gp == 5) p.kt = 5;
-    else if (fam == KANVIT_BSPLINE && p.gp == 9 && d->has_base && (d->flags & KANVIT_FLAG_UNIFORM_KNOTS) && d->spline_order == 3) p.kt = 5;
-    else if (fam == KANVIT_RBF && p.gp == 9 && d->has_base && kv_rbf_reg_ok(d->flags, d->G)) p.kt = 5;
-    else if (fam == KANVIT_SINE && p.gp == 4) p.kt = 4;        // the per-head mappings (attention.py:140)
-    else if (fam == KANVIT_SINE && p.gp == 28) p.kt = 7;       // the G = 28 patch embedding (model.py:72)
-    else return p;
+    const RegBasis* rb = kv_reg_basis(d);
+    if (!rb || !rb->bwi_bf16_kt) return p;
+    p.kt = rb->bwi_bf16_kt;
     p.fph = 16 * p.kt / p.gp;
     const int ic = 2 * p.fph;
     const bool wide = d->groups == 1 && d->x_group_mod == 1 && d->O > 64 && d->O % 64 == 0 && d->O <= 64 * 64;
@@ -672,15 +657,7 @@ BwdRegBf16Plan plan_bwd_input_reg_bf16(const kanvit_layer_desc* d) {
     return p;
 }
 
-bool bwd_input_bf16_ok(const kanvit_layer_desc* d) {
-    const bool wide = d->groups == 1 && d->x_group_mod == 1 && d->O > 64 && d->O % 64 == 0 && d->O <= 64 * 64;      // register kernel only
-    // SINE has no bf16 register kernel (its d loss / d freq partials), and the bf16 LDS-tile kernel measures SLOWER than the exact
-    // fp32 register kernel (0.81 vs 0.38 ms on the ViT-B q|k|v launch): the flag allows bf16, it does not require it
-    if (d->family == KANVIT_SINE && !kv_config().no_reg && !plan_bwd_input_reg_bf16(d).ok) return false;
-    return (d->flags & KANVIT_FLAG_BF16_MFMA) && (d->O == 16 || d->O == 32 || d->O == 64 || wide) && (d->ldy % 4 == 0) && !kv_config().no_bf16;
-}
-
-int kv_bwd_input_reg_bf16(int family, LayerArgs& a, const BwdRegBf16Plan& p, hipStream_t st) {
+int kv_bwd_input_reg_bf16(int family, LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st) {
 #define KV_CALL(F) dispatch_bwd_input_reg_bf16<F>(a, p, st)
     KV_FAMILY_SWITCH(family, KV_CALL)
 #undef KV_CALL

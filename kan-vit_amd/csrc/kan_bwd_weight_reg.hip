@@ -698,23 +698,21 @@ BwRegPlan plan_bwd_weight_reg(const kanvit_layer_desc* d) {
     p.njc = 1;
     p.gp = gp_of(d);
     const int fam = d->family;
-    if (fam == KANVIT_LINEAR && p.gp == 1) p.nt = 6;
-    else if (fam == KANVIT_CHEBY && p.gp == 5) p.nt = 3;
+    // column tiles per wave unit and basis windows of the <family, GP> instantiations: KV_REG_BASES (kan_layer_common.h).  Why these:
     // BSPLINE (GP = 9: 8 cubic bases + silu): two windows of FIVE basis slots (0..4 | 5..7, silu, one idle slot), each window
     // its own wave unit that contracts its values against three column tiles -- the Chebyshev schedule (240 accumulators, 15
     // MFMAs per basis evaluation), a window evaluating only its own values (compile-time window start).  The idle slot
     // costs 10 % of the MFMAs; 3 x 6 tiles (no idle slot, 288 accumulators) and round 2's 9 x 2 both spill accumulators
     // inside the token loop (the allocator cannot place more than 256 of them) and lose to the LDS-tile kernel.
-    // (bf16 mode runs the same two-window schedule on v_mfma_f32_32x32x16_bf16, see below)
-    else if (fam == KANVIT_BSPLINE && p.gp == 9 && (d->flags & KANVIT_FLAG_UNIFORM_KNOTS) && d->spline_order == 3 && d->has_base &&
-             !((d->flags & KANVIT_FLAG_BF16_MFMA) && !kv_config().no_bf16 && kv_config().bs_bw_bf16 == 1)) { p.nt = 3; p.njc = 2; }
-    else if (fam == KANVIT_RBF && p.gp == 9 && d->has_base && kv_rbf_reg_ok(d->flags, d->G)) p.nt = 2;      // (windows of 3 measured slower for both: the basis is re-evaluated per window)
-    else if (fam == KANVIT_SINE && (p.gp == 4 || p.gp == 5)) p.nt = 2;
+    // (bf16 mode runs the same two-window schedule on v_mfma_f32_32x32x16_bf16, see below; windows of 3 measured slower for
+    // BSPLINE and RBF: the basis is re-evaluated per window)
     // SINE G = 28: windows of 4 basis functions x 4 column tiles.  (Windows of 2 x 6 tiles -- 12 MFMAs per pair of sines instead
     // of 16 per four, 7.4 -> 4.4 VALU instructions per MFMA -- measured SLOWER, 8.6 -> 13.1 ms: twice the wave units re-read dY.)
-    else if (fam == KANVIT_SINE && p.gp == 28) { p.nt = 4; p.njc = 7; }
-    else if (fam == KANVIT_FOURIER && p.gp == 56) { p.nt = 4; p.njc = 14; }
-    else return p;
+    const RegBasis* rb = kv_reg_basis(d);
+    if (!rb) return p;
+    if (fam == KANVIT_BSPLINE && (d->flags & KANVIT_FLAG_BF16_MFMA) && !kv_config().no_bf16 && kv_config().bs_bw_bf16 == 1) return p;      // A/B: the LDS-tile bf16 kernel
+    p.nt = rb->bww_nt;
+    p.njc = rb->bww_njc;
     if (d->I % 32 || d->O % 32 || d->M < 256) return p;
     const int nshare = d->groups / d->x_group_mod;
     // B-spline (exact fp32): the 16-row-tile kernel -- three windows of three values x 12 (or 4) column tiles of 16, no idle

@@ -12,8 +12,9 @@ namespace {
 //   from a BasisGen in registers, and the W chunk is staged with the same permutation (row (s, hf) <- k = feature*GP + g).
 // 256 threads = 4 waves x 32 rows; LDS holds only two W chunk buffers (float4 global loads prefetched into registers one
 // chunk ahead); x is read by each lane directly (ICH consecutive floats of its row per chunk); one barrier per chunk.
-// Epilogue: each wave transposes its 32x32 tiles through a private LDS patch and writes float4 row segments.
-// Requirements (host-checked): O % (32*NT) == 0, I % IC == 0, IC in {8, 4, 2}, 16-byte aligned rows when IC == 8.
+// Epilogue: the product is computed flipped (accumulator registers run along the output row), so every lane stores float4 row
+// segments straight from its registers -- no transposition through the LDS.
+// Requirements (plan_fwd_reg in kan_layer.hip): O % (32*NT) == 0, I % IC == 0, IC in {8, 4, 2}, 16-byte aligned rows when IC == 8.
 // =============================================================================================
 // GPC > 0: the number of basis functions per feature is a compile-time constant (the shapes the reference instantiates).  The
 // chunk body is then fully unrolled and the W fragments are read from LDS ONE K-STEP AHEAD into a second register set, with
@@ -29,7 +30,6 @@ __device__ __forceinline__ void kan_fwd_reg_body(const LayerArgs& a, float* __re
     constexpr int V4 = BN / 4;
     constexpr int IC = 2 * ICH;
     constexpr bool RBF = (FAM == KV_RBF);
-    constexpr int TS = 36;                        // staging patch row stride (floats): 16-byte aligned, conflict free
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hf = lane >> 5;
     const int ntn = a.O / BN;
     const int gs = bx / ntn;
@@ -342,109 +342,63 @@ __global__ __launch_bounds__(256, GPC ? 2 : 1) void kan_fwd_reg_act_kernel(const
     kan_fwd_reg_kbody<FAM, NT, NSH, ICH, GPC, TAIL, KV_ACT_DYN>(a);
 }
 
-// ---- register-operand forward (fp32 exact) --------------------------------------------------------
+// ---- register-operand forward (fp32 exact): launches what plan_fwd_reg (kan_layer.hip) chose --------------------------
 template <int FAM, int NT, int NSH, int ICH, int GPC = 0>
-int launch_fwd_reg(const LayerArgs& a0, size_t lds, hipStream_t st) {
-    const unsigned gx = (unsigned)((a0.groups / NSH) * (a0.O / (32 * NT)));
-    const long long tiles = (a0.M + BM - 1) / BM;
+int launch_fwd_reg(const LayerArgs& a, const LayerFwdPlan& p, hipStream_t st) {
+    const dim3 grid(p.gx, p.gy, 1);
     if constexpr (NSH == 3 && GPC > 0) {
-        const int t1 = kv_tail_first_tile(tiles, (int)gx);
-        if (t1 < tiles) {
-            LayerArgs a = a0;
-            a.tail_y0 = t1;
+        if (p.tail_y0 != 0x7fffffff) {            // a.tail_y0 = p.tail_y0: the sub-divided end of the launch
             KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_fwd_reg_kernel, kan_fwd_reg_act_kernel, (FAM, NT, NSH, ICH, GPC, true));
-            dim3 grid(gx, (unsigned)(t1 + 3 * (tiles - t1)), 1);
-            KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_reg_kernel, kan_fwd_reg_act_kernel, (FAM, NT, NSH, ICH, GPC, true), grid, dim3(256), lds, st, a);
+            KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_reg_kernel, kan_fwd_reg_act_kernel, (FAM, NT, NSH, ICH, GPC, true), grid, dim3(256), p.lds, st, a);
             KV_LAUNCH_CHECK("kan_fwd_reg_kernel");
             return 0;
         }
     }
-    const LayerArgs& a = a0;
     KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_fwd_reg_kernel, kan_fwd_reg_act_kernel, (FAM, NT, NSH, ICH, GPC));
-    dim3 grid(gx, (unsigned)tiles, 1);
-    KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_reg_kernel, kan_fwd_reg_act_kernel, (FAM, NT, NSH, ICH, GPC), grid, dim3(256), lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_reg_kernel, kan_fwd_reg_act_kernel, (FAM, NT, NSH, ICH, GPC), grid, dim3(256), p.lds, st, a);
     KV_LAUNCH_CHECK("kan_fwd_reg_kernel");
     return 0;
 }
 
+// the instantiations: p.gpc > 0 names the pipelined compile-time-GP twin of (family, ICH) in KV_REG_BASES, 0 the run-time-GP loop
 template <int FAM, int NT, int NSH>
-int launch_fwd_reg_ich(const LayerArgs& a, int ich, size_t lds, hipStream_t st) {
-    // compile-time GP instantiations (pipelined chunk body): the basis sizes the reference's call sites build
-    if (!kv_config().no_pipe) {
-        if (ich == 4) {
-            if constexpr (FAM == KV_LINEAR) { if (a.GP == 1) return launch_fwd_reg<FAM, NT, NSH, 4, 1>(a, lds, st); }
-            if constexpr (FAM == KV_CHEBY) { if (a.GP == 5) return launch_fwd_reg<FAM, NT, NSH, 4, 5>(a, lds, st); }
-            if constexpr (FAM == KV_BSPLINE || FAM == KV_RBF) { if (a.GP == 9 && a.has_base) return launch_fwd_reg<FAM, NT, NSH, 4, 9>(a, lds, st); }
-            if constexpr (FAM == KV_SINE) { if (a.GP == 4) return launch_fwd_reg<FAM, NT, NSH, 4, 4>(a, lds, st); }
-        }
-        if (ich == 2) {     // GP = 9 (B-spline, FastKAN): eight features x 9 rows x three projections overflow the W staging registers
-            if constexpr (FAM == KV_BSPLINE || FAM == KV_RBF) { if (a.GP == 9 && a.has_base) return launch_fwd_reg<FAM, NT, NSH, 2, 9>(a, lds, st); }
-        }
-        if (ich == 1) {
-            if constexpr (FAM == KV_SINE) { if (a.GP == 28) return launch_fwd_reg<FAM, NT, NSH, 1, 28>(a, lds, st); }
-            if constexpr (FAM == KV_FOURIER) { if (a.GP == 56) return launch_fwd_reg<FAM, NT, NSH, 1, 56>(a, lds, st); }
-        }
+int launch_fwd_reg_ich(const LayerArgs& a, const LayerFwdPlan& p, hipStream_t st) {
+    if (p.gpc && p.ich == 4) {
+        if constexpr (FAM == KV_LINEAR) return launch_fwd_reg<FAM, NT, NSH, 4, 1>(a, p, st);
+        if constexpr (FAM == KV_CHEBY) return launch_fwd_reg<FAM, NT, NSH, 4, 5>(a, p, st);
+        if constexpr (FAM == KV_BSPLINE || FAM == KV_RBF) return launch_fwd_reg<FAM, NT, NSH, 4, 9>(a, p, st);
+        if constexpr (FAM == KV_SINE) return launch_fwd_reg<FAM, NT, NSH, 4, 4>(a, p, st);
     }
-    if (ich == 4) return launch_fwd_reg<FAM, NT, NSH, 4>(a, lds, st);
-    if (ich == 2) return launch_fwd_reg<FAM, NT, NSH, 2>(a, lds, st);
-    return launch_fwd_reg<FAM, NT, NSH, 1>(a, lds, st);
+    if (p.gpc && p.ich == 2) {
+        if constexpr (FAM == KV_BSPLINE || FAM == KV_RBF) return launch_fwd_reg<FAM, NT, NSH, 2, 9>(a, p, st);
+    }
+    if (p.gpc && p.ich == 1) {
+        if constexpr (FAM == KV_SINE) return launch_fwd_reg<FAM, NT, NSH, 1, 28>(a, p, st);
+        if constexpr (FAM == KV_FOURIER) return launch_fwd_reg<FAM, NT, NSH, 1, 56>(a, p, st);
+    }
+    if (p.gpc) return kv_fail(KANVIT_EINVAL, "internal: no register forward <family %d, ICH %d, GP %d>", FAM, p.ich, p.gpc);
+    if (p.ich == 4) return launch_fwd_reg<FAM, NT, NSH, 4>(a, p, st);
+    if (p.ich == 2) return launch_fwd_reg<FAM, NT, NSH, 2>(a, p, st);
+    return launch_fwd_reg<FAM, NT, NSH, 1>(a, p, st);
 }
 
-// returns 1 when the shape is not covered (caller falls back to the LDS-tile kernel), 0 on success, < 0 on error
 template <int FAM>
-int try_fwd_reg(const LayerArgs& a, hipStream_t st) {
-    if (kv_config().no_reg) return 1;
-    if (FAM == KV_BSPLINE && !((a.flags & KANVIT_FLAG_UNIFORM_KNOTS) && a.order == 3)) return 1;
-    if (FAM == KV_RBF && !kv_rbf_reg_ok(a.flags, a.G)) return 1;
-    // (Measured and rejected, round 3: EIGHT column tiles per generated value for SineKAN's G = 28 patch embedding -- it halves the
-    // sine evaluations per MFMA, 5.5 -> 2.9 VALU instructions, but its 114 KB of W per work-group leave one wave per SIMD:
-    // 10.06 -> 10.49 ms.)
-    int nt = a.O <= 32 ? 1 : (a.O <= 64 ? 2 : 4);
-    if (a.O % (32 * nt)) return 1;
-    const int nshare = a.groups / a.xmod;
-    // Launches that cannot fill the chip (the small geometries' patch embedding: 2048 rows x 64 columns = 16 work-groups of two column
-    // tiles): a wave's MFMA chain IS the kernel time there, so one column tile per work-group -- twice (four times) the work-groups, half
-    // (a quarter of) the chain each; the basis is re-evaluated per column tile, the k order of every output is unchanged (bitwise equal).
-    if (nt > 1 && ((a.M + BM - 1) / BM) * (long long)a.groups * (a.O / (32 * nt)) < N_CU) nt = 1;
-    // q|k|v sharing one basis evaluation (NSH = 3) triples the MFMA chain of every wave; when the launch has fewer
-    // work-groups than CUs (the small geometries: 50 row tiles x 2 heads) the chain length IS the kernel time, so each
-    // projection gets its own work-groups there and re-evaluates the basis
-    const bool share3 = kv_shared_basis<FAM>() && kv_share_ok(FAM, a.flags) && nshare == 3 && nt <= 2 &&
-                        ((a.M + BM - 1) / BM) * a.xmod >= N_CU;
-    const int nsh = share3 ? 3 : 1;
-    if ((a.O & 3) || (a.ldy & 3) || ((uintptr_t)a.y & 15) || ((uintptr_t)a.w & 15) || (a.bias && ((uintptr_t)a.bias & 15))) return 1;
-    if (FAM == KV_SINE && (((uintptr_t)a.bp & 15) || (a.bp_stride & 3))) return 1;      // the phase rows are prefetched as 16-byte vectors
-    const int wrow = 32 * nt * nsh, wrs = 256 / (8 * nt);
-    for (int ich = 4; ich >= 1; ich >>= 1) {
-        const int ic = 2 * ich, kc = ic * a.GP;
-        if (a.I % ic) continue;
-        if (a.pg && (((a.pg_W / a.pg_n) % ic) || (ich == 4 && (a.pg_W & 3)))) continue;     // a chunk is ic consecutive pixels of one line
-        if (ich == 4 && ((a.ldx & 3) || (a.I & 3) || ((uintptr_t)a.x & 15) ||
-                         (FAM == KV_RBF && a.u && ((a.ldu & 3) || ((uintptr_t)a.u & 15)))))
-            continue;
-        if ((kc + wrs - 1) / wrs > (share3 ? 4 : 8)) continue;                   // W passes held in registers
-        if ((long long)kc * a.O >= (1LL << 30)) continue;
-        size_t lds = sizeof(float) * 2 * (size_t)kc * wrow;
-        if (lds < sizeof(float) * 4 * 32 * 36) lds = sizeof(float) * 4 * 32 * 36;   // epilogue patches alias the W buffers
-        if (lds > 160 * 1024) continue;
-        if (share3) {
-            if constexpr (kv_shared_basis<FAM>()) {
-                if (nt == 1) return launch_fwd_reg_ich<FAM, 1, 3>(a, ich, lds, st);
-                return launch_fwd_reg_ich<FAM, 2, 3>(a, ich, lds, st);
-            }
+int launch_fwd_reg_shape(const LayerArgs& a, const LayerFwdPlan& p, hipStream_t st) {
+    if (p.nsh == 3) {
+        if constexpr (kv_shared_basis<FAM>()) {
+            if (p.nt == 1) return launch_fwd_reg_ich<FAM, 1, 3>(a, p, st);
+            return launch_fwd_reg_ich<FAM, 2, 3>(a, p, st);
         }
-        if (nt == 1) return launch_fwd_reg_ich<FAM, 1, 1>(a, ich, lds, st);
-        if (nt == 2) return launch_fwd_reg_ich<FAM, 2, 1>(a, ich, lds, st);
-        return launch_fwd_reg_ich<FAM, 4, 1>(a, ich, lds, st);
     }
-    return 1;
+    if (p.nt == 1) return launch_fwd_reg_ich<FAM, 1, 1>(a, p, st);
+    if (p.nt == 2) return launch_fwd_reg_ich<FAM, 2, 1>(a, p, st);
+    return launch_fwd_reg_ich<FAM, 4, 1>(a, p, st);
 }
-
 
 }  // namespace
 
-int kv_try_fwd_reg(int family, const LayerArgs& a, hipStream_t st) {
-#define KV_CALL(F) try_fwd_reg<F>(a, st)
+int kv_fwd_reg(int family, const LayerArgs& a, const LayerFwdPlan& p, hipStream_t st) {
+#define KV_CALL(F) launch_fwd_reg_shape<F>(a, p, st)
     KV_FAMILY_SWITCH(family, KV_CALL)
 #undef KV_CALL
 }

@@ -215,8 +215,6 @@ __device__ __forceinline__ void kan_fwd_reg_bf16_kbody(const LayerArgs& a) {
             float av[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                constexpr int dummy = 0;
-                (void)dummy;
                 const int vi = ks * 8 + e;                        // compile-time after unrolling
                 const int j = vi / GP, g = vi - j * GP;
                 if (vi < VH) {
@@ -312,7 +310,6 @@ __global__ __launch_bounds__(256) void kan_fwd_reg_bf16_act_kernel(const LayerAr
 //     no staging tile;
 //   * x of the next (tile, chunk) is prefetched while the current chunk is contracted; 8 waves (2 per SIMD) of 32 rows.
 // =============================================================================================
-constexpr int KV_WS_THREADS = 512;   // 8 waves (12 measured slower: 66 row tiles over 21 work-groups per head quantise to 79 %)
 //   * (round 4) the stores: an accumulator quad is 16 bytes of the lane's own row, so a store instruction used to touch 32 rows with
 //     32 bytes each -- four instructions, 128 write transactions per 128-byte line set; without its stores the ViT-B q|k|v launch
 //     ran in 59 instead of 100 us.  With ST a tile passes through a wave-private LDS strip ([32 rows][36 floats]: b128 writes and
@@ -428,7 +425,6 @@ __global__ __launch_bounds__(KV_WS_THREADS, KV_WS_THREADS / 256) void kan_fwd_ws
         const unsigned short* wp = W_s + ((size_t)hf * WROW + l31) * 8;
 #pragma unroll 1
         for (int t0 = 0; t0 < NTT; t0 += 2) {     // a real loop: unrolled, the scheduler hoists every ds_read of every pair and spills
-            constexpr bool PAIR = true;
             const bool two = t0 + 1 < NTT;
             f32x16 acc0, acc1;
 #pragma unroll
@@ -446,7 +442,7 @@ __global__ __launch_bounds__(KV_WS_THREADS, KV_WS_THREADS / 256) void kan_fwd_ws
                     w1[(s2 + 1) & 1] = *reinterpret_cast<const bf16x8_t*>(wp + ((size_t)(2 * (s2 + 1)) * WROW + (two ? t0 + 1 : t0) * 32) * 8);
                 }
                 acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0[s2 & 1], phi[s2], acc0, 0, 0, 0);     // Y^T tile: rows = columns of y
-                if (PAIR && two) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1[s2 & 1], phi[s2], acc1, 0, 0, 0);
+                if (two) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1[s2 & 1], phi[s2], acc1, 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);            // keep the one-step-ahead fragment prefetch, no further hoisting
             }
             // accumulator registers 4q..4q+3 of a tile are y[row][.. + 8q + 4hf + 0..3] of this lane's row
@@ -503,39 +499,30 @@ __global__ __launch_bounds__(KV_WS_THREADS, KV_WS_THREADS / 256) void kan_fwd_ws
 }
 
 template <int FAM, int GP, int NT, int NSH, int ICH>
-int launch_fwd_reg_bf16(const LayerArgs& a, const FwdRegBf16Plan& p, hipStream_t st) {
-    // W-stationary persistent form when the whole weight image of a column set fits the LDS and there are enough row tiles
-    // (instantiated for I = 64 per group: 4 chunks of 16 features -- the per-head q|k|v launches of ViT-B/S)
-    if constexpr (ICH == 8 && (FAM == KV_LINEAR || FAM == KV_CHEBY)) {     // the families whose basis fragments fit the register file
-        const size_t wlds = (size_t)p.nch * p.vs * 2 * 32 * NT * NSH * 16 + sizeof(float) * 32 * NT * NSH;
-        const int gx = (a.groups / NSH) * (a.O / (32 * NT));
-        if (wlds <= 150 * 1024 && p.nch == 4 && a.M >= 4096 && gx <= N_CU && !((uintptr_t)a.y & 15) && !kv_config().no_ws && !a.pg) {
-            const long long ntiles = (a.M + KV_WS_THREADS / 2 - 1) / (KV_WS_THREADS / 2);
-            long long py = N_CU / gx;             // one work-group per CU (the image fills the LDS)
-            if (py > ntiles) py = ntiles;
-            if (py < 1) py = 1;
-            const size_t slds = wlds + sizeof(float) * (KV_WS_THREADS / 64) * 32 * 36;       // + the store strips (see the kernel), when they fit
-            if (slds <= 160 * 1024 && !kv_config().ws_no_strip) {
+int launch_fwd_reg_bf16(const LayerArgs& a, const LayerFwdPlan& p, hipStream_t st) {
+    const dim3 grid(p.gx, p.gy, 1);
+    if (p.form == LAYER_FWD_WS_BF16) {            // W-stationary persistent form (plan_fwd_reg_bf16_form in kan_layer.hip)
+        if constexpr (ICH == 8 && (FAM == KV_LINEAR || FAM == KV_CHEBY)) {
+            if (p.strip) {
                 KV_ALLOW_LDS(160 * 1024, (kan_fwd_ws_bf16_kernel<FAM, GP, NT, NSH, ICH, 4, true>));
-                hipLaunchKernelGGL((kan_fwd_ws_bf16_kernel<FAM, GP, NT, NSH, ICH, 4, true>), dim3((unsigned)gx, (unsigned)py, 1), dim3(KV_WS_THREADS), slds, st, a);
+                hipLaunchKernelGGL((kan_fwd_ws_bf16_kernel<FAM, GP, NT, NSH, ICH, 4, true>), grid, dim3(KV_WS_THREADS), p.lds, st, a);
             } else {
                 KV_ALLOW_LDS(160 * 1024, (kan_fwd_ws_bf16_kernel<FAM, GP, NT, NSH, ICH, 4>));
-                hipLaunchKernelGGL((kan_fwd_ws_bf16_kernel<FAM, GP, NT, NSH, ICH, 4>), dim3((unsigned)gx, (unsigned)py, 1), dim3(KV_WS_THREADS), wlds, st, a);
+                hipLaunchKernelGGL((kan_fwd_ws_bf16_kernel<FAM, GP, NT, NSH, ICH, 4>), grid, dim3(KV_WS_THREADS), p.lds, st, a);
             }
             KV_LAUNCH_CHECK("kan_fwd_ws_bf16_kernel");
             return 0;
         }
     }
-    dim3 grid((unsigned)((a.groups / NSH) * (a.O / (32 * NT))), (unsigned)((a.M + BM - 1) / BM), 1);
-    if (a.pg) {         // fused patch embedding: one wide layer (NT = 4), the families whose patch embedding the model builds
+    if (p.form == LAYER_FWD_REG_BF16_PATCH) {     // fused patch embedding: one wide layer (NT = 4), the families whose patch embedding the model builds
         if constexpr (NT == 4 && NSH == 1 && FAM != KV_RBF && FAM != KV_LINEAR) {
             KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_fwd_reg_bf16_kernel, kan_fwd_reg_bf16_act_kernel, (FAM, GP, NT, NSH, ICH, true));
             KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_reg_bf16_kernel, kan_fwd_reg_bf16_act_kernel, (FAM, GP, NT, NSH, ICH, true), grid, dim3(256), p.lds, st, a);
             KV_LAUNCH_CHECK("kan_fwd_reg_bf16_kernel (patch gather)");
             return 0;
         }
-        return 1;       // not covered
     }
+    if (p.form != LAYER_FWD_REG_BF16) return kv_fail(KANVIT_EINVAL, "internal: bf16 register forward form %d has no <family %d, NT %d, NSH %d>", (int)p.form, FAM, NT, NSH);
     KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_fwd_reg_bf16_kernel, kan_fwd_reg_bf16_act_kernel, (FAM, GP, NT, NSH, ICH));
     KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_reg_bf16_kernel, kan_fwd_reg_bf16_act_kernel, (FAM, GP, NT, NSH, ICH), grid, dim3(256), p.lds, st, a);
     KV_LAUNCH_CHECK("kan_fwd_reg_bf16_kernel");
@@ -543,7 +530,7 @@ int launch_fwd_reg_bf16(const LayerArgs& a, const FwdRegBf16Plan& p, hipStream_t
 }
 
 template <int FAM, int GP, int ICH>
-int launch_fwd_reg_bf16_shape(const LayerArgs& a, const FwdRegBf16Plan& p, hipStream_t st) {
+int launch_fwd_reg_bf16_shape(const LayerArgs& a, const LayerFwdPlan& p, hipStream_t st) {
     if (p.nsh == 3) {
         if constexpr (kv_shared_basis<FAM>()) {
             if (p.nt == 1) return launch_fwd_reg_bf16<FAM, GP, 1, 3, ICH>(a, p, st);
@@ -555,23 +542,25 @@ int launch_fwd_reg_bf16_shape(const LayerArgs& a, const FwdRegBf16Plan& p, hipSt
     return launch_fwd_reg_bf16<FAM, GP, 4, 1, ICH>(a, p, st);
 }
 
+// the <GP, ICH> instantiations: KV_REG_BASES' rows with fwd_bf16_ich (the plan holds one of them)
 template <int FAM>
-int dispatch_fwd_reg_bf16(LayerArgs& a, const FwdRegBf16Plan& p, void* ws, hipStream_t st) {
+int dispatch_fwd_reg_bf16(LayerArgs& a, const LayerFwdPlan& pl, void* ws, hipStream_t st) {
+    const FwdRegBf16Plan& p = pl.rb;
     unsigned short* wb = (unsigned short*)ws;
     const long long total = (long long)a.groups * p.nch * p.vs * 2 * a.O;
     hipLaunchKernelGGL(kan_pack_w_fwd_reg_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.w, wb, a.K, a.O, p.gp,
                        p.ich, p.vs, p.nch, total);
     KV_LAUNCH_CHECK("kan_pack_w_fwd_reg_kernel");
     a.wb = wb;
-    if constexpr (FAM == KV_LINEAR) return launch_fwd_reg_bf16_shape<FAM, 1, 8>(a, p, st);
-    if constexpr (FAM == KV_CHEBY) return launch_fwd_reg_bf16_shape<FAM, 5, 8>(a, p, st);
-    if constexpr (FAM == KV_BSPLINE) return launch_fwd_reg_bf16_shape<FAM, 9, 8>(a, p, st);
-    if constexpr (FAM == KV_RBF) return launch_fwd_reg_bf16_shape<FAM, 9, 8>(a, p, st);
+    if constexpr (FAM == KV_LINEAR) return launch_fwd_reg_bf16_shape<FAM, 1, 8>(a, pl, st);
+    if constexpr (FAM == KV_CHEBY) return launch_fwd_reg_bf16_shape<FAM, 5, 8>(a, pl, st);
+    if constexpr (FAM == KV_BSPLINE) return launch_fwd_reg_bf16_shape<FAM, 9, 8>(a, pl, st);
+    if constexpr (FAM == KV_RBF) return launch_fwd_reg_bf16_shape<FAM, 9, 8>(a, pl, st);
     if constexpr (FAM == KV_SINE) {
-        if (p.gp == 4) return launch_fwd_reg_bf16_shape<FAM, 4, 8>(a, p, st);
-        return launch_fwd_reg_bf16_shape<FAM, 28, 1>(a, p, st);
+        if (p.gp == 4) return launch_fwd_reg_bf16_shape<FAM, 4, 8>(a, pl, st);
+        return launch_fwd_reg_bf16_shape<FAM, 28, 1>(a, pl, st);
     }
-    if constexpr (FAM == KV_FOURIER) return launch_fwd_reg_bf16_shape<FAM, 56, 1>(a, p, st);
+    if constexpr (FAM == KV_FOURIER) return launch_fwd_reg_bf16_shape<FAM, 56, 1>(a, pl, st);
     return kv_fail(KANVIT_EINVAL, "internal: bf16 register forward dispatch");
 }
 
@@ -583,16 +572,13 @@ FwdRegBf16Plan plan_fwd_reg_bf16(const kanvit_layer_desc* d) {
     if (kv_config().no_reg) return p;
     p.gp = gp_of(d);
     const int fam = d->family;
-    const bool gp_ok = (fam == KANVIT_LINEAR && p.gp == 1) || (fam == KANVIT_CHEBY && p.gp == 5) ||
-                       (fam == KANVIT_BSPLINE && p.gp == 9 && d->has_base && (d->flags & KANVIT_FLAG_UNIFORM_KNOTS) && d->spline_order == 3) ||
-                       (fam == KANVIT_RBF && p.gp == 9 && d->has_base && kv_rbf_reg_ok(d->flags, d->G)) || (fam == KANVIT_SINE && (p.gp == 4 || p.gp == 28)) ||
-                       (fam == KANVIT_FOURIER && p.gp == 56);
-    if (!gp_ok) return p;
+    const RegBasis* rb = kv_reg_basis(d);
+    if (!rb || !rb->fwd_bf16_ich) return p;
     p.nt = d->O <= 32 ? 1 : (d->O <= 64 ? 2 : 4);
     if (d->O % (32 * p.nt) || (d->O & 3) || (d->ldy & 3)) return p;
     const int nshare = d->groups / d->x_group_mod;
     p.nsh = (kv_share_ok(fam, d->flags) && nshare == 3 && p.nt <= 2) ? 3 : 1;
-    p.ich = p.gp >= 28 ? 1 : 8;                   // features per lane half and chunk (instantiated: 8, or 1 for the wide bases)
+    p.ich = rb->fwd_bf16_ich;                     // features per lane half and chunk (instantiated: 8, or 1 for the wide bases)
     if (d->I % (2 * p.ich)) return p;
     if (p.ich == 8 && ((d->ldx & 3) || (d->I & 3) || (fam == KANVIT_RBF && (d->ldu & 3)))) return p;
     p.vs = (p.ich * p.gp + 7) / 8;
@@ -607,7 +593,7 @@ FwdRegBf16Plan plan_fwd_reg_bf16(const kanvit_layer_desc* d) {
     return p;
 }
 
-int kv_fwd_reg_bf16(int family, LayerArgs& a, const FwdRegBf16Plan& p, void* ws, hipStream_t st) {
+int kv_fwd_reg_bf16(int family, LayerArgs& a, const LayerFwdPlan& p, void* ws, hipStream_t st) {
 #define KV_CALL(F) dispatch_fwd_reg_bf16<F>(a, p, ws, st)
     KV_FAMILY_SWITCH(family, KV_CALL)
 #undef KV_CALL

@@ -6,8 +6,11 @@
 //     fwd         Y    = Phi(X) . W
 //     bwd_input   dPhi = dY . W^T, then dX = sum_j dPhi_j * phi_j'(X)
 //     bwd_weight  dW   = Phi(X)^T . dY          (split over row ranges -> slabs -> ordered reduce)
-// Selection order per call: tiny per-head layers (kan_tiny.hip) -> register-form kernels (the shapes the reference
-// instantiates on its 224x224 path) -> the general LDS-tile kernels (every other shape).
+// Which kernel runs is decided ONCE per call, on the host, by plan_layer_fwd / plan_layer_bwd_input (below; the weight gradient:
+// plan_bwd_weight_reg / plan_bwd_weight): tiny per-head layers (kan_tiny.hip) -> the bf16 forms under KANVIT_FLAG_BF16_MFMA ->
+// the exact register-form kernels (the shapes the reference instantiates on its 224x224 path, KV_REG_BASES) -> the general
+// LDS-tile kernels (every other shape).  Every entry point is: validate, build the arguments, plan, check the workspace against
+// the plan, launch the plan's form.  The workspace queries and kanvit_layer_ln_fusable read the same plans.
 #include "kan_layer_common.h"
 
 extern "C" int kanvit_layer_ln_fusable(const kanvit_layer_desc* d);
@@ -88,27 +91,289 @@ LayerArgs base_args(const kanvit_layer_desc* d) {
 
 int needs_bparams(int family) { return family == KANVIT_BSPLINE || family == KANVIT_RBF || family == KANVIT_SINE; }
 
-// forward / input gradient: register-form kernel when the shape allows it, else the LDS-tile kernel
-int dispatch_fwd(int family, LayerArgs& a, hipStream_t st) {
-    const int rc = kv_try_fwd_reg(family, a, st);
-    if (rc <= 0) return rc;
-    if (a.ln) return kv_fail(KANVIT_EINVAL, "kanvit_layer_fwd: KANVIT_FLAG_FUSED_LN needs the register kernel (alignment / shape)");
-    return kv_tile_fwd(family, a, st);
+// the argument checks every host query shares (a query answers 0 for a descriptor it cannot read)
+bool desc_ok(const kanvit_layer_desc* d) {
+    return d && gp_of(d) >= 1 && d->groups >= 1 && d->x_group_mod >= 1 && d->I >= 1 && d->O >= 1;
 }
 
-int dispatch_bwd_input(int family, LayerArgs& a, hipStream_t st) {
-    if ((long long)BM * a.ldx >= (1LL << 30) || (long long)BM * a.ldy >= (1LL << 30) || (long long)BM * a.ldu >= (1LL << 30) ||
-        (long long)a.K * a.O >= (1LL << 30))
-        return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_input: row strides / weight slab too large for 32-bit tile offsets");
-    if (!a.wb2) {                                       // wb2 is set by the entry point when the bf16 path applies
-        const int rc = kv_try_bwd_input_reg(family, a, st);
-        if (rc <= 0) return rc;
-        if (a.ln) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_input: KANVIT_FLAG_FUSED_LN needs the register kernel (alignment / shape)");
+LayerAlign layer_align(const void* x, const void* u, const void* w, const void* bp, const void* bias, const void* y, const void* dy,
+                       const void* dx, const void* du) {
+    return LayerAlign{(uintptr_t)x, (uintptr_t)u, (uintptr_t)w, (uintptr_t)bp, (uintptr_t)bias, (uintptr_t)y, (uintptr_t)dy, (uintptr_t)dx,
+                      (uintptr_t)du, u ? 1 : 0};
+}
+
+bool is_ln(const kanvit_layer_desc* d) { return d->family == KANVIT_RBF && (d->flags & KANVIT_FLAG_FUSED_LN); }
+
+// form = NONE: the call fails with KANVIT_EINVAL and the text `why` (a printf format taking the two integers)
+template <typename P>
+P plan_none(P p, const char* why, int a = 0, int b = 0) {
+    p.form = {};          // *_NONE
+    p.why = why;
+    p.why_a = a;
+    p.why_b = b;
+    return p;
+}
+
+// exact fp32 register forward (kan_fwd_reg.hip): sets form = REG when the shape and the operands are covered
+void plan_fwd_reg(const kanvit_layer_desc* d, const kanvit_patch_desc* pd, const LayerAlign& al, LayerFwdPlan& p) {
+    const int fam = d->family, gp = gp_of(d);
+    if (kv_config().no_reg || !kv_reg_family_ok(fam, d->flags, d->spline_order, d->G)) return;
+    // (Measured and rejected, round 3: EIGHT column tiles per generated value for SineKAN's G = 28 patch embedding -- it halves the
+    // sine evaluations per MFMA, 5.5 -> 2.9 VALU instructions, but its 114 KB of W per work-group leave one wave per SIMD:
+    // 10.06 -> 10.49 ms.)
+    int nt = d->O <= 32 ? 1 : (d->O <= 64 ? 2 : 4);
+    if (d->O % (32 * nt)) return;
+    const long long tiles = (d->M + BM - 1) / BM;
+    const int nshare = d->groups / d->x_group_mod;
+    // Launches that cannot fill the chip (the small geometries' patch embedding: 2048 rows x 64 columns = 16 work-groups of two column
+    // tiles): a wave's MFMA chain IS the kernel time there, so one column tile per work-group -- twice (four times) the work-groups, half
+    // (a quarter of) the chain each; the basis is re-evaluated per column tile, the k order of every output is unchanged (bitwise equal).
+    if (nt > 1 && tiles * (long long)d->groups * (d->O / (32 * nt)) < N_CU) nt = 1;
+    // q|k|v sharing one basis evaluation (NSH = 3) triples the MFMA chain of every wave; when the launch has fewer
+    // work-groups than CUs (the small geometries: 50 row tiles x 2 heads) the chain length IS the kernel time, so each
+    // projection gets its own work-groups there and re-evaluates the basis
+    const bool share3 = kv_share_ok(fam, d->flags) && nshare == 3 && nt <= 2 && tiles * d->x_group_mod >= N_CU;
+    const int nsh = share3 ? 3 : 1;
+    if ((d->O & 3) || (d->ldy & 3) || ((al.y | al.w | al.bias) & 15)) return;
+    if (fam == KANVIT_SINE && ((al.bp & 15) || (d->bparam_stride & 3))) return;      // the phase rows are prefetched as 16-byte vectors
+    const long long ldx = pd ? d->I : d->ldx;                                         // the gather has no row stride
+    const bool has_u = fam == KANVIT_RBF && al.has_u && !is_ln(d);                    // FUSED_LN: the u slot carries the statistics
+    const int wrow = 32 * nt * nsh, wrs = 256 / (8 * nt);
+    const RegBasis* rb = kv_config().no_pipe ? nullptr : kv_reg_basis(d);             // the pipelined compile-time-GP twins
+    for (int ich = 4; ich >= 1; ich >>= 1) {
+        const int ic = 2 * ich, kc = ic * gp;
+        if (d->I % ic) continue;
+        if (pd && (((pd->W / pd->n_patches) % ic) || (ich == 4 && (pd->W & 3)))) continue;     // a chunk is ic consecutive pixels of one line
+        if (ich == 4 && ((ldx & 3) || (d->I & 3) || (al.x & 15) || (has_u && ((d->ldu & 3) || (al.u & 15))))) continue;
+        if ((kc + wrs - 1) / wrs > (share3 ? 4 : 8)) continue;                   // W passes held in registers
+        if ((long long)kc * d->O >= (1LL << 30)) continue;
+        size_t lds = sizeof(float) * 2 * (size_t)kc * wrow;
+        // floor (the size of the four transposition patches the epilogue had before the flipped product; it stores straight from
+        // registers now): kept as a number, what still reads this area after the last chunk are the T0 column sums of the CHEBY
+        // compile-time-GP kernels, 5 x (32 * NT * NSH) floats, which a one-feature-pair chunk of a narrow layer would not cover
+        if (lds < sizeof(float) * 4 * 32 * 36) lds = sizeof(float) * 4 * 32 * 36;
+        if (lds > 160 * 1024) continue;
+        p.form = LAYER_FWD_REG;
+        p.nt = nt;
+        p.nsh = nsh;
+        p.ich = ich;
+        p.gpc = rb ? rb->fwd_gpc[ich == 4 ? 0 : (ich == 2 ? 1 : 2)] : 0;
+        p.lds = lds;
+        p.gx = (unsigned)((d->groups / nsh) * (d->O / (32 * nt)));
+        p.gy = (unsigned)tiles;
+        if (nsh == 3 && p.gpc > 0) {              // the launch tail (kv_tail_first_tile): the last row tiles run one projection per work-group
+            const int t1 = kv_tail_first_tile(tiles, (int)p.gx);
+            if (t1 < tiles) {
+                p.tail_y0 = t1;
+                p.gy = (unsigned)(t1 + 3 * (tiles - t1));
+            }
+        }
+        return;
     }
-    return kv_tile_bwd_input(family, a, st);
+}
+
+// bf16 register forward (kan_fwd_reg_bf16.hip): the W-stationary persistent form when the whole weight image of a column set fits the
+// LDS and there are enough row tiles (instantiated for I = 64 per group: 4 chunks of 16 features -- the per-head q|k|v launches of
+// ViT-B/S; LINEAR and CHEBY: the families whose basis fragments fit the register file), else one work-group per row tile
+void plan_fwd_reg_bf16_form(const kanvit_layer_desc* d, const kanvit_patch_desc* pd, LayerFwdPlan& p) {
+    const FwdRegBf16Plan& r = p.rb;
+    p.nt = r.nt;
+    p.nsh = r.nsh;
+    p.ich = r.ich;
+    p.ws_bytes = r.ws_bytes;
+    p.gx = (unsigned)((d->groups / r.nsh) * (d->O / (32 * r.nt)));
+    p.gy = (unsigned)((d->M + BM - 1) / BM);
+    p.lds = r.lds;
+    p.form = pd ? LAYER_FWD_REG_BF16_PATCH : LAYER_FWD_REG_BF16;
+    if (pd || r.ich != 8 || !(d->family == KANVIT_LINEAR || d->family == KANVIT_CHEBY)) return;
+    const size_t wlds = (size_t)r.nch * r.vs * 2 * 32 * r.nt * r.nsh * 16 + sizeof(float) * 32 * r.nt * r.nsh;
+    if (wlds > 150 * 1024 || r.nch != 4 || d->M < 4096 || p.gx > N_CU || kv_config().no_ws) return;
+    const long long ntiles = (d->M + KV_WS_THREADS / 2 - 1) / (KV_WS_THREADS / 2);
+    long long py = N_CU / p.gx;                   // one work-group per CU (the image fills the LDS)
+    if (py > ntiles) py = ntiles;
+    if (py < 1) py = 1;
+    const size_t slds = wlds + sizeof(float) * (KV_WS_THREADS / 64) * 32 * 36;       // + the store strips (see the kernel), when they fit
+    p.form = LAYER_FWD_WS_BF16;
+    p.strip = (slds <= 160 * 1024 && !kv_config().ws_no_strip) ? 1 : 0;
+    p.gy = (unsigned)py;
+    p.lds = p.strip ? slds : wlds;
+}
+
+// general LDS-tile forward (kan_tile.hip): every shape whose chunk fits the LDS
+LayerFwdPlan plan_fwd_tile(const kanvit_layer_desc* d, LayerFwdPlan p) {
+    const int fam = d->family, gp = gp_of(d);
+    p.nt = d->O <= 32 ? 1 : (d->O <= 64 ? 2 : 4);
+    p.nsh = (kv_share_ok(fam, d->flags) && d->groups / d->x_group_mod == 3 && p.nt <= 2) ? 3 : 1;
+    // largest feature chunk whose two operand buffers fit the 160 KiB LDS (cap 80 columns)
+    int ic = 80 / gp;
+    if (ic < 1) ic = 1;
+    if (ic > d->I) ic = d->I;
+    while (ic > 1 && kv_tile_fwd_lds(fam, ic, gp, p.nt, p.nsh) > 160 * 1024) --ic;
+    if (kv_tile_fwd_lds(fam, ic, gp, p.nt, p.nsh) > 160 * 1024)
+        return plan_none(p, "kanvit_layer_fwd: %d generated columns per feature with O=%d does not fit the LDS", gp, d->O);
+    // fast path: power-of-two chunk dividing I, whole column tiles, 32-bit tile-local offsets
+    int icf = 1;
+    while (icf * 2 <= ic) icf *= 2;
+    p.fast = (icf >= 8) && (d->I % icf == 0) && (d->O % (32 * p.nt) == 0) && ((long long)BM * d->ldx < (1LL << 30)) &&
+             ((long long)BM * d->ldy < (1LL << 30)) && ((long long)BM * d->ldu < (1LL << 30)) &&
+             ((long long)d->I * gp * d->O < (1LL << 30)) && !kv_config().no_fast;
+    p.ic = p.fast ? icf : ic;
+    p.form = LAYER_FWD_TILE;
+    p.gx = (unsigned)((d->groups / p.nsh) * ((d->O + 32 * p.nt - 1) / (32 * p.nt)));
+    p.gy = (unsigned)((d->M + BM - 1) / BM);
+    p.lds = kv_tile_fwd_lds(fam, p.ic, gp, p.nt, p.nsh);
+    return p;
 }
 
 }  // namespace
+
+// pd != nullptr: the fused patch embedding (register forms only; x is the image batch, validated 16-byte aligned by the entry point)
+LayerFwdPlan plan_layer_fwd(const kanvit_layer_desc* d, const kanvit_patch_desc* pd, const LayerAlign& al) {
+    LayerFwdPlan p{};
+    p.tail_y0 = 0x7fffffff;
+    const char* uncovered = "kanvit_patch_embed_fwd: shape not covered by the fused kernel (O %% 32, patch width %% chunk, basis size); "
+                            "use patchify + kanvit_layer_fwd";
+    if (d->flags & KANVIT_FLAG_BF16_MFMA) {
+        p.rb = plan_fwd_reg_bf16(d);
+        if (!pd) p.tb = plan_fwd_bf16(d);
+        const size_t a1 = p.rb.ok ? p.rb.ws_bytes : 0, a2 = p.tb.ok ? p.tb.ws_bytes : 0;
+        p.ws_max = a1 > a2 ? a1 : a2;
+    }
+    if (!pd && kv_tiny_ok(d)) {       // tiny per-head layers (I, O <= 16): vector-pipe kernels, csrc/kan_tiny.hip
+        p.form = LAYER_FWD_TINY;
+        return p;
+    }
+    if ((d->flags & KANVIT_FLAG_BF16_MFMA) && !kv_config().no_bf16) {
+        const FwdRegBf16Plan& r = p.rb;
+        if (pd) {
+            // the register-form forward in its patch form (one wide layer: four column tiles per work-group; a lane's feature chunk
+            // must be consecutive pixels of one image line); nothing else gathers
+            const int pw = pd->W / pd->n_patches;
+            if (!(r.ok && r.nt == 4 && r.nsh == 1 && d->family != KANVIT_RBF && d->family != KANVIT_LINEAR && pw % (2 * r.ich) == 0 &&
+                  (r.ich < 4 || (pd->W & 3) == 0) && !((al.y | al.bias | al.bp) & 15)))
+                return plan_none(p, uncovered);
+            plan_fwd_reg_bf16_form(d, pd, p);
+            return p;
+        }
+        if (r.ok && !((al.x | al.y | al.u | al.bias | al.bp) & 15)) {
+            plan_fwd_reg_bf16_form(d, pd, p);
+            return p;
+        }
+        if (p.tb.ok && !is_ln(d)) {
+            p.form = LAYER_FWD_TILE_BF16;
+            p.nt = p.tb.nt;
+            p.nsh = p.tb.nsh;
+            p.ic = p.tb.ic;
+            p.ws_bytes = p.tb.ws_bytes;
+            p.gx = (unsigned)((d->groups / p.nsh) * (d->O / (32 * p.nt)));
+            p.gy = (unsigned)((d->M + BM - 1) / BM);
+            p.lds = p.tb.lds;
+            return p;
+        }
+    }
+    plan_fwd_reg(d, pd, al, p);
+    if (p.form == LAYER_FWD_REG) return p;
+    if (pd) return plan_none(p, uncovered);
+    if (is_ln(d)) return plan_none(p, "kanvit_layer_fwd: KANVIT_FLAG_FUSED_LN needs the register kernel (alignment / shape)");
+    return plan_fwd_tile(d, p);
+}
+
+LayerBwdInputPlan plan_layer_bwd_input(const kanvit_layer_desc* d, const LayerAlign& al) {
+    LayerBwdInputPlan p{};
+    p.tail_y0 = 0x7fffffff;
+    const int fam = d->family, gp = gp_of(d), nshare = d->groups / d->x_group_mod;
+    const long long tiles = (d->M + BM - 1) / BM;
+    p.gp = gp;
+    p.shared = (kv_share_ok(fam, d->flags) && nshare > 1) ? 1 : 0;
+    p.gx = (unsigned)d->x_group_mod;
+    p.gy = (unsigned)tiles;
+    // KANVIT_FLAG_BF16_MFMA allows bf16, it does not require it: the layer widths the bf16 kernels are built for ...
+    p.rb = plan_bwd_input_reg_bf16(d);
+    const bool wide = d->groups == 1 && d->x_group_mod == 1 && d->O > 64 && d->O % 64 == 0 && d->O <= 64 * 64;      // register kernel only
+    bool bf = (d->flags & KANVIT_FLAG_BF16_MFMA) && !kv_config().no_bf16 && (d->O == 16 || d->O == 32 || d->O == 64 || wide) && (d->ldy % 4 == 0);
+    // ... and for SINE only the register one: the bf16 LDS-tile kernel measures SLOWER than the exact fp32 register kernel (0.81 vs
+    // 0.38 ms on the ViT-B q|k|v launch)
+    if (fam == KANVIT_SINE && !kv_config().no_reg && !p.rb.ok) bf = false;
+    const int ic_bf = bf ? kv_tile_bwd_input_ic(fam, d->I, gp, d->G, nshare, d->O) : 0;
+    if (bf) {
+        const size_t reg_ws = p.rb.ok ? p.rb.ws_bytes : 0;
+        const size_t lds_ws = ic_bf ? (size_t)d->groups * ((d->I + ic_bf - 1) / ic_bf) * (d->O / 8) * (32 * ((ic_bf * gp + 31) / 32)) * 16 : 0;
+        p.ws_max = reg_ws > lds_ws ? reg_ws : lds_ws;
+    }
+    if (kv_tiny_ok(d)) {
+        p.form = LAYER_BWI_TINY;
+        return p;
+    }
+    bool wb = bf && !(al.dy & 15) && p.ws_max > 0;        // a bf16 form may run: the repacked weights go to the workspace
+    p.ws_bytes = wb ? p.ws_max : 0;
+    if (wb) {
+        const BwdRegBf16Plan& r = p.rb;
+        if (r.ok && !((al.x | al.dx | al.dy | al.u | al.du) & 15)) {
+            p.kt = r.kt;
+            p.ic = 2 * r.fph;
+            p.nci = r.nci;
+            p.lds = r.lds;
+            if (r.vcols) {
+                // one wide layer (the patch embedding: O = 384 / 768): its 64-column chunks are contracted one per step into the SAME
+                // accumulators -- exactly the SHARED schedule with the chunks in the role of the groups that share x and the basis
+                p.form = LAYER_BWI_REG_BF16_WIDE;
+                p.shared = 1;
+                p.gx = 1;
+            } else if (fam != KANVIT_SINE && d->O == 64 && (nshare == 1 || nshare == 3) && !kv_config().bi_no_res) {
+                p.form = LAYER_BWI_RES_BF16;      // the per-head layers: dY resident (see the kernel)
+                p.nsh = nshare;
+                if (r.nci > 1) p.tail_y0 = kv_tail_first_tile(tiles, d->x_group_mod);
+                const long long t1 = p.tail_y0 < tiles ? p.tail_y0 : tiles;
+                p.gy = (unsigned)(t1 + (long long)r.nci * (tiles - t1));
+                p.lds = (size_t)3 * 4 * 2 * 32 * r.kt * 16 + sizeof(float) * 4 * 32 * (p.ic + 4);      // a ring of three W step images + four store strips
+            } else {
+                p.form = LAYER_BWI_REG_BF16;
+            }
+            return p;
+        }
+        // no LayerNorm fusion, no wide layers and no SINE in the LDS-tile bf16 kernel: the exact kernels run instead
+        if (is_ln(d) || d->O > 64 || fam == KANVIT_SINE) wb = false;
+    }
+    // every form below addresses its tiles with 32-bit offsets
+    if ((long long)BM * d->ldx >= (1LL << 30) || (long long)BM * d->ldy >= (1LL << 30) || (long long)BM * d->ldu >= (1LL << 30) ||
+        (long long)d->I * gp * d->O >= (1LL << 30))
+        return plan_none(p, "kanvit_layer_bwd_input: row strides / weight slab too large for 32-bit tile offsets");
+    if (wb) {
+        // the bf16 tile does not fit the LDS (no basis size of today's kernels: GP <= 80, O <= 64 always fits): the exact LDS-tile
+        // kernel, NOT the register one -- what this route has always done once the workspace was claimed
+        p.form = ic_bf ? LAYER_BWI_TILE_BF16 : LAYER_BWI_TILE;
+        p.ic = ic_bf ? ic_bf : kv_tile_bwd_input_ic(fam, d->I, gp, d->G, nshare, 0);
+        if (!p.ic) return plan_none(p, "kanvit_layer_bwd_input: tile does not fit the LDS");
+    } else {
+        // exact fp32 register kernel (kan_bwd_input_reg.hip): the table's basis sizes, whole chunks and column tiles, 16-byte rows
+        const RegBasis* rb = kv_config().no_reg ? nullptr : kv_reg_basis(d);
+        if (rb && rb->bwi_kt) {
+            const int kt = rb->bwi_kt, fph = (16 * kt) / gp, ic = 2 * fph;
+            if (!(d->I % ic || d->O % 32 || (d->ldx & 3) || (d->ldy & 3) || ((fph & 3) == 0 && (d->I & 3)) || ((al.x | al.dx | al.dy | al.w) & 15) ||
+                  (long long)ic * gp * d->O >= (1LL << 30))) {
+                const int kct = 32 * kv_bwi_kt(fam, gp, kt), hoff = (kct % 64 == 32) ? kct : kct + 32, ws2 = ((hoff + kct + 13) / 16) * 16 + 2;
+                p.form = LAYER_BWI_REG;
+                p.kt = kt;
+                p.ic = ic;
+                p.nci = d->I / ic;
+                p.lds = sizeof(float) * (2 * 16 * ws2 + (fam == KANVIT_SINE ? (size_t)nshare * 4 * gp : 0));
+                if (fam != KANVIT_SINE && p.nci > 1) p.tail_y0 = kv_tail_first_tile(tiles, d->x_group_mod);
+                const long long t1 = p.tail_y0 < tiles ? p.tail_y0 : tiles;
+                p.gy = (unsigned)(t1 + p.nci * (tiles - t1));
+                return p;
+            }
+        }
+        if (is_ln(d)) return plan_none(p, "kanvit_layer_bwd_input: KANVIT_FLAG_FUSED_LN needs the register kernel (alignment / shape)");
+        p.form = LAYER_BWI_TILE;
+        p.ic = kv_tile_bwd_input_ic(fam, d->I, gp, d->G, nshare, 0);
+        if (!p.ic) return plan_none(p, "kanvit_layer_bwd_input: tile does not fit the LDS");
+    }
+    // general LDS-tile kernel (kan_tile.hip), exact or with the bf16 contraction
+    p.kt = (p.ic * gp + 31) / 32;
+    p.nci = (d->I + p.ic - 1) / p.ic;
+    p.lds = kv_tile_bwd_input_lds(fam, p.ic, gp, d->G, nshare, p.form == LAYER_BWI_TILE_BF16 ? d->O : 0);
+    return p;
+}
 
 static KvTinyArgs tiny_args(const kanvit_layer_desc* d) {
     KvTinyArgs t{};
@@ -180,12 +445,25 @@ int kanvit_device_count(void) {
 }
 
 size_t kanvit_layer_fwd_workspace(const kanvit_layer_desc* d) {
-    if (!d || !(d->flags & KANVIT_FLAG_BF16_MFMA) || gp_of(d) < 1 || d->groups < 1 || d->x_group_mod < 1 || d->I < 1 || d->O < 1)
-        return 0;
-    const FwdRegBf16Plan pr = plan_fwd_reg_bf16(d);
-    const FwdBf16Plan p = plan_fwd_bf16(d);          // fallback when the register kernel's alignment checks fail at launch
-    const size_t a1 = pr.ok ? pr.ws_bytes : 0, a2 = p.ok ? p.ws_bytes : 0;
-    return a1 > a2 ? a1 : a2;
+    if (!desc_ok(d) || !(d->flags & KANVIT_FLAG_BF16_MFMA)) return 0;
+    return plan_layer_fwd(d, nullptr, LayerAlign{}).ws_max;
+}
+
+// the forms both forward entry points launch; `who` names the entry point in the workspace message
+static int launch_layer_fwd(const kanvit_layer_desc* d, LayerArgs& a, const LayerFwdPlan& p, const char* who, void* workspace,
+                            size_t workspace_bytes, hipStream_t st) {
+    if (p.form == LAYER_FWD_NONE) return kv_fail(KANVIT_EINVAL, p.why, p.why_a, p.why_b);
+    if (p.ws_bytes && (!workspace || workspace_bytes < p.ws_bytes || ((uintptr_t)workspace & 15)))
+        return kv_fail(KANVIT_ENOMEM, "%s: workspace %zu bytes < required %zu (or not 16-byte aligned)", who, workspace_bytes, p.ws_bytes);
+    a.tail_y0 = p.tail_y0;
+    switch (p.form) {
+        case LAYER_FWD_WS_BF16:
+        case LAYER_FWD_REG_BF16:
+        case LAYER_FWD_REG_BF16_PATCH: return kv_fwd_reg_bf16(d->family, a, p, workspace, st);
+        case LAYER_FWD_TILE_BF16: return kv_tile_fwd_bf16(d->family, a, p, workspace, st);
+        case LAYER_FWD_REG: return kv_fwd_reg(d->family, a, p, st);
+        default: return kv_tile_fwd(d->family, a, p, st);
+    }
 }
 
 int kanvit_layer_fwd(const kanvit_layer_desc* d, const float* x, const float* u, const float* w, const float* bparams,
@@ -197,8 +475,8 @@ int kanvit_layer_fwd(const kanvit_layer_desc* d, const float* x, const float* u,
     if (needs_bparams(d->family) && !bparams) return kv_fail(KANVIT_EINVAL, "kanvit_layer_fwd: family %d needs bparams", d->family);
     if (d->family == KANVIT_RBF && u && d->ldu < (int64_t)d->groups * d->I)
         return kv_fail(KANVIT_EINVAL, "kanvit_layer_fwd: ldu < groups*I");
-    if (d->M == 0) return 0;
-    if (kv_tiny_ok(d)) {              // tiny per-head layers (I, O <= 16): vector-pipe kernels, csrc/kan_tiny.hip
+    const LayerFwdPlan p = plan_layer_fwd(d, nullptr, layer_align(x, u, w, bparams, bias, y, nullptr, nullptr, nullptr));
+    if (p.form == LAYER_FWD_TINY) {
         KvTinyArgs t = tiny_args(d);
         t.x = x; t.w = w; t.bp = bparams; t.bias = bias; t.y = y;
         return kv_tiny_fwd(t, (hipStream_t)stream);
@@ -215,42 +493,31 @@ int kanvit_layer_fwd(const kanvit_layer_desc* d, const float* x, const float* u,
         a.stats = const_cast<float*>(u);
         a.u = nullptr;
     }
-    hipStream_t st = (hipStream_t)stream;
-    if ((d->flags & KANVIT_FLAG_BF16_MFMA) && !kv_config().no_bf16) {
-        const FwdRegBf16Plan pr = plan_fwd_reg_bf16(d);
-        if (pr.ok && !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)(u ? u : x) | (uintptr_t)(bias ? bias : x) | (uintptr_t)(bparams ? bparams : x)) & 15)) {
-            if (!workspace || workspace_bytes < pr.ws_bytes || ((uintptr_t)workspace & 15))
-                return kv_fail(KANVIT_ENOMEM, "kanvit_layer_fwd: workspace %zu bytes < required %zu (or not 16-byte aligned)",
-                               workspace_bytes, pr.ws_bytes);
-            return kv_fwd_reg_bf16(d->family, a, pr, workspace, st);
-        }
-        const FwdBf16Plan p = plan_fwd_bf16(d);
-        if (p.ok && !a.ln) {
-            if (!workspace || workspace_bytes < p.ws_bytes || ((uintptr_t)workspace & 15))
-                return kv_fail(KANVIT_ENOMEM, "kanvit_layer_fwd: workspace %zu bytes < required %zu (or not 16-byte aligned)",
-                               workspace_bytes, p.ws_bytes);
-            return kv_tile_fwd_bf16(d->family, a, p, workspace, st);
-        }
-    }
-    return dispatch_fwd(d->family, a, st);
+    return launch_layer_fwd(d, a, p, "kanvit_layer_fwd", workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-/* 1 when the three register kernels that can form the FastKAN LayerNorm in-kernel cover this layer (pure host function) */
+/* 1 when the three register kernels that can form the FastKAN LayerNorm in-kernel cover this layer (pure host function): asks the
+   three plans, for aligned operands, whether each would run a register form with the flag set */
 int kanvit_layer_ln_fusable(const kanvit_layer_desc* d) {
-    if (!d || d->family != KANVIT_RBF || !d->has_base || !kv_rbf_reg_ok(d->flags, d->G) || d->groups < 1 || d->x_group_mod < 1) return 0;
+    if (!desc_ok(d) || d->family != KANVIT_RBF || d->groups % d->x_group_mod) return 0;
     if (d->base_act < KANVIT_BASE_SILU || d->base_act > KANVIT_BASE_IDENTITY) return 0;      // every valid activation has the fused kernels
-    if (d->I % 32 || d->O % 32 || d->M < 256 || (d->ldx & 3) || (d->ldy & 3)) return 0;
-    if (d->O > 64 && d->O % 128) return 0;                 // forward column tiling: 32, 64 or multiples of 128
-    {                                                      // kanvit_layer_ln_bwd's lane-group layout
+    if (d->M < 256) return 0;                              // fewer rows: the weight gradient's register kernel does not start, and the route is all three kernels or none
+    {                                                      // kanvit_layer_ln_bwd's lane-group layout: one layer or q|k|v per x slice, a row of I features per lane group
         const int ns = d->groups / d->x_group_mod;
-        if (d->groups % d->x_group_mod || (ns != 1 && ns != 3) || d->I > (ns == 3 ? 512 : 1024)) return 0;
+        if ((ns != 1 && ns != 3) || d->I > (ns == 3 ? 512 : 1024)) return 0;
     }
-    if (kv_config().no_reg || kv_config().no_reg_bw || kv_config().no_fused_ln) return 0;
+    if (kv_config().no_reg || kv_config().no_reg_bw || kv_config().no_fused_ln) return 0;      // the A/B switches that take a register kernel (or the route) away
+    // Everything else is the plans' own and is no longer restated here: whole 32-feature / 32-column blocks and 16-byte rows (the
+    // three register kernels), the forward's column tiling (32, 64, multiples of 128), the base column and FastKAN's 8-centre grid
+    // (KV_REG_BASES), and the kernels' 32-bit offset bounds -- plan_bwd_weight_reg's rows-per-slab bound as before, and now also
+    // plan_layer_bwd_input's tile-offset bound (row strides below 2^23 floats), which kanvit_layer_bwd_input has always refused.
     kanvit_layer_desc e = *d;
     e.flags |= KANVIT_FLAG_FUSED_LN;
-    if (!plan_bwd_weight_reg(&e).ok) return 0;
-    if ((d->flags & KANVIT_FLAG_BF16_MFMA) && !kv_config().no_bf16 && !plan_fwd_reg_bf16(&e).ok) return 0;
-    return 1;
+    const bool bf = (d->flags & KANVIT_FLAG_BF16_MFMA) && !kv_config().no_bf16;
+    if (plan_layer_fwd(&e, nullptr, LayerAlign{}).form != (bf ? LAYER_FWD_REG_BF16 : LAYER_FWD_REG)) return 0;
+    const LayerBwdInputForm bi = plan_layer_bwd_input(&e, LayerAlign{}).form;
+    if (bi != LAYER_BWI_REG && bi != LAYER_BWI_REG_BF16 && bi != LAYER_BWI_REG_BF16_WIDE && bi != LAYER_BWI_RES_BF16) return 0;
+    return plan_bwd_weight_reg(&e).ok ? 1 : 0;
 }
 
 // ---- fused patch embedding (model.py:111-126 patchify, :144-152 class token + position embedding) ----
@@ -278,7 +545,7 @@ static void patch_args(LayerArgs& a, const kanvit_patch_desc* p, const float* cl
     a.pg_pre = p->prepend_rows;
     a.cls = cls;
     a.pos = pos;
-    a.ldx = a.I;                         // unused by the gather; keeps the alignment checks of the dispatcher meaningful
+    a.ldx = a.I;                         // unused by the gather; the value plan_fwd_reg tests in its place
 }
 
 int kanvit_patch_embed_fwd_ws(const kanvit_layer_desc* d, const kanvit_patch_desc* p, const float* images, const float* w,
@@ -299,27 +566,9 @@ int kanvit_patch_embed_fwd_ws(const kanvit_layer_desc* d, const kanvit_patch_des
     a.bias = bias;
     a.y = y;
     patch_args(a, p, cls, pos);
-    hipStream_t st = (hipStream_t)stream;
-    int rc = 1;
-    if ((d->flags & KANVIT_FLAG_BF16_MFMA) && !kv_config().no_bf16) {
-        // bf16 matrix cores: the register-form forward in its patch form (one wide layer: four column tiles per work-group; a
-        // lane's feature chunk must be consecutive pixels of one image line)
-        const FwdRegBf16Plan pr = plan_fwd_reg_bf16(d);
-        const int pw = p->W / p->n_patches;
-        if (pr.ok && pr.nt == 4 && pr.nsh == 1 && d->family != KANVIT_RBF && d->family != KANVIT_LINEAR && pw % (2 * pr.ich) == 0 &&
-            (pr.ich < 4 || (p->W & 3) == 0) && !(((uintptr_t)y | (uintptr_t)(bias ? bias : w) | (uintptr_t)(bparams ? bparams : w)) & 15)) {
-            if (!workspace || workspace_bytes < pr.ws_bytes || ((uintptr_t)workspace & 15))
-                return kv_fail(KANVIT_ENOMEM, "kanvit_patch_embed_fwd: workspace %zu bytes < required %zu (or not 16-byte aligned)",
-                               workspace_bytes, pr.ws_bytes);
-            rc = kv_fwd_reg_bf16(d->family, a, pr, workspace, st);
-        }
-    } else {
-        rc = (kv_config().no_reg || d->family == KANVIT_RBF) ? 1 : kv_try_fwd_reg(d->family, a, st);
-    }
-    if (rc == 1)
-        return kv_fail(KANVIT_EINVAL, "kanvit_patch_embed_fwd: shape not covered by the fused kernel (O %% 32, patch width %% chunk, "
-                                      "basis size); use patchify + kanvit_layer_fwd");
-    return rc;
+    // (an absent bias / bparams is tested as w: what this entry point has always done, so a misaligned w is refused only then)
+    const LayerFwdPlan pl = plan_layer_fwd(d, p, layer_align(images, nullptr, w, bparams ? bparams : w, bias ? bias : w, y, nullptr, nullptr, nullptr));
+    return launch_layer_fwd(d, a, pl, "kanvit_patch_embed_fwd", workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int kanvit_patch_embed_fwd(const kanvit_layer_desc* d, const kanvit_patch_desc* p, const float* images, const float* w,
@@ -332,7 +581,7 @@ int kanvit_patch_embed_fwd(const kanvit_layer_desc* d, const kanvit_patch_desc* 
 // Weight gradient of the patch-embedding layer with the same gather: x rows from the NCHW images, dY rows from the token-sequence
 // gradient [B][P + prepend_rows][ldy] (the class-token rows are stepped over) -- no transient patch matrix, no dY copy.
 int kanvit_patch_embed_bwd_weight_ok(const kanvit_layer_desc* d, const kanvit_patch_desc* p) {
-    if (!d || !p || gp_of(d) < 1 || d->groups != 1 || d->x_group_mod != 1 || d->I < 1 || d->O < 1 || d->M < 1) return 0;
+    if (!desc_ok(d) || !p || d->groups != 1 || d->x_group_mod != 1 || d->M < 1) return 0;
     if (p->C < 1 || p->H < 1 || p->W < 1 || p->n_patches < 1 || p->H % p->n_patches || p->W % p->n_patches) return 0;
     if (p->prepend_rows != 0 && p->prepend_rows != 1) return 0;
     const long long P = (long long)p->n_patches * p->n_patches;
@@ -384,7 +633,7 @@ int kanvit_patch_embed_bwd_weight(const kanvit_layer_desc* d, const kanvit_patch
 }
 
 int kanvit_layer_sine_dfreq_ok(const kanvit_layer_desc* d) {
-    if (!d || d->family != KANVIT_SINE || gp_of(d) < 1 || d->groups < 1 || d->x_group_mod < 1 || d->I < 1 || d->O < 1 || d->M < 1) return 0;
+    if (!desc_ok(d) || d->family != KANVIT_SINE || d->M < 1) return 0;
     if (kv_tiny_ok(d)) return 0;
     return plan_bwd_weight_reg(d).ok ? 1 : 0;
 }
@@ -395,14 +644,8 @@ int64_t kanvit_layer_dparam_tiles(const kanvit_layer_desc* d) {
 }
 
 size_t kanvit_layer_bwd_input_workspace(const kanvit_layer_desc* d) {
-    if (!d || gp_of(d) < 1 || d->groups < 1 || d->x_group_mod < 1 || d->I < 1 || d->O < 1 || !bwd_input_bf16_ok(d)) return 0;
-    size_t reg_ws = 0;
-    {
-        const BwdRegBf16Plan pr = plan_bwd_input_reg_bf16(d);
-        if (pr.ok) reg_ws = pr.ws_bytes;
-    }
-    const size_t lds_ws = kv_tile_bwd_input_ws(d);
-    return reg_ws > lds_ws ? reg_ws : lds_ws;
+    if (!desc_ok(d)) return 0;
+    return plan_layer_bwd_input(d, LayerAlign{}).ws_max;
 }
 
 int kanvit_layer_bwd_input(const kanvit_layer_desc* d, const float* x, const float* u, const float* w,
@@ -418,11 +661,12 @@ int kanvit_layer_bwd_input(const kanvit_layer_desc* d, const float* x, const flo
         return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_input: ldu < groups*I");
     if (d->family == KANVIT_SINE && (d->groups / d->x_group_mod) * 4 * d->G > 4096)
         return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_input: SINE G too large");
-    if (d->M == 0) return 0;
-    if (kv_tiny_ok(d)) {
+    const LayerBwdInputPlan p = plan_layer_bwd_input(d, layer_align(x, u, w, bparams, nullptr, nullptr, dy, dx, du));
+    hipStream_t st = (hipStream_t)stream;
+    if (p.form == LAYER_BWI_TINY) {
         KvTinyArgs t = tiny_args(d);
         t.x = x; t.w = w; t.bp = bparams; t.dy = dy; t.dx = dx;
-        return kv_tiny_bwd_input(t, (hipStream_t)stream);
+        return kv_tiny_bwd_input(t, st);
     }
     LayerArgs a = base_args(d);
     a.x = x;
@@ -433,34 +677,32 @@ int kanvit_layer_bwd_input(const kanvit_layer_desc* d, const float* x, const flo
     a.dx = dx;
     a.du = du;
     a.dparam = dparam;
-    a.wb2 = nullptr;
     if (a.ln) {
         if (!u) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_input: KANVIT_FLAG_FUSED_LN needs the statistics buffer in the u argument");
         a.stats = const_cast<float*>(u);
         a.u = nullptr;
     }
-    if (bwd_input_bf16_ok(d) && (((uintptr_t)dy & 15) == 0)) {
-        const size_t need = kanvit_layer_bwd_input_workspace(d);
-        if (need) {
-            if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))
-                return kv_fail(KANVIT_ENOMEM, "kanvit_layer_bwd_input: workspace %zu bytes < required %zu (or not 16-byte aligned)",
-                               workspace_bytes, need);
+    if (p.ws_bytes && (!workspace || workspace_bytes < p.ws_bytes || ((uintptr_t)workspace & 15)))
+        return kv_fail(KANVIT_ENOMEM, "kanvit_layer_bwd_input: workspace %zu bytes < required %zu (or not 16-byte aligned)",
+                       workspace_bytes, p.ws_bytes);
+    a.tail_y0 = p.tail_y0;
+    switch (p.form) {
+        case LAYER_BWI_NONE: return kv_fail(KANVIT_EINVAL, p.why, p.why_a, p.why_b);
+        case LAYER_BWI_RES_BF16:
+        case LAYER_BWI_REG_BF16:
+        case LAYER_BWI_REG_BF16_WIDE:
+            a.wb2 = (const unsigned short*)workspace;      // the repacked weights
+            return kv_bwd_input_reg_bf16(d->family, a, p, st);
+        case LAYER_BWI_TILE_BF16:
             a.wb2 = (const unsigned short*)workspace;
-        }
+            return kv_tile_bwd_input(d->family, a, p, st);
+        case LAYER_BWI_REG: return kv_bwd_input_reg(d->family, a, p, st);
+        default: return kv_tile_bwd_input(d->family, a, p, st);
     }
-    hipStream_t st = (hipStream_t)stream;
-    if (a.wb2) {
-        const BwdRegBf16Plan pr = plan_bwd_input_reg_bf16(d);
-        if (pr.ok && !(((uintptr_t)x | (uintptr_t)dx | (uintptr_t)dy | (uintptr_t)(u ? u : x) | (uintptr_t)(du ? du : dx)) & 15)) {
-            return kv_bwd_input_reg_bf16(d->family, a, pr, st);
-        }
-        if (a.ln || d->O > 64 || d->family == KANVIT_SINE) a.wb2 = nullptr;     // no LayerNorm fusion / no wide layers in the LDS-tile bf16 kernel: the exact register kernel runs instead
-    }
-    return dispatch_bwd_input(d->family, a, st);
 }
 
 size_t kanvit_layer_bwd_weight_workspace(const kanvit_layer_desc* d) {
-    if (!d || gp_of(d) < 1 || d->groups < 1 || d->I < 1 || d->O < 1) return 0;
+    if (!desc_ok(d)) return 0;
     if (kv_tiny_ok(d)) {
         const int s = kv_tiny_slabs(d);
         return s > 1 ? sizeof(float) * (size_t)s * d->groups * ((size_t)d->I * gp_of(d)) * d->O : 0;

@@ -1,7 +1,7 @@
 // Internal header of the fused KAN layer kernels (csrc/kan_*.hip): launch arguments, tile constants, the plan structs the
 // host entry points (kan_layer.hip) share with the kernel translation units, and the functions that cross between them.
 // One translation unit per kernel generation keeps a rebuild at the size of the kernel that changed:
-//     kan_layer.hip               C ABI entry points, validation, run-time switches
+//     kan_layer.hip               C ABI entry points, validation, run-time switches, plan_layer_fwd / plan_layer_bwd_input
 //     kan_tile.hip                general LDS-tile producer/consumer kernels (every shape; fp32 and bf16 contraction)
 //     kan_fwd_reg.hip             register-form forward (fp32 exact; also the fused patch embedding)
 //     kan_fwd_reg_bf16.hip        register-form and W-stationary forward on the bf16 matrix cores
@@ -181,18 +181,6 @@ __device__ __forceinline__ unsigned kv_pack_bf16(float lo, float hi) {
 // ---------------------------------------------------------------------------------------------
 // host side: what the translation units share
 // ---------------------------------------------------------------------------------------------
-inline int gp_of(const kanvit_layer_desc* d) {
-    switch (d->family) {
-        case KANVIT_LINEAR: return 1;
-        case KANVIT_CHEBY: return d->G;
-        case KANVIT_BSPLINE: return d->G + (d->has_base ? 1 : 0);
-        case KANVIT_RBF: return d->G + (d->has_base ? 1 : 0);
-        case KANVIT_SINE: return d->G;
-        case KANVIT_FOURIER: return 2 * d->G;
-        default: return -1;
-    }
-}
-
 // RBF in the register kernels: only FastKAN's own uniform 8-centre grid (kv_rbf8: two exp anchors + recurrence); the caller
 // vouches with KANVIT_FLAG_UNIFORM_KNOTS, anything else takes the LDS-tile kernels (direct exp per centre)
 inline bool kv_rbf_reg_ok(int flags, int G) { return (flags & KANVIT_FLAG_UNIFORM_KNOTS) && G == 8; }
@@ -218,6 +206,55 @@ inline bool kv_share_ok(int family, int flags) {
         case KANVIT_FOURIER: return CALL(KV_FOURIER);                 \
         default: return kv_fail(KANVIT_EINVAL, "unknown family %d", fam); \
     }
+
+// ---- the compile-time basis sizes of the register kernels: ONE table --------------------------------------------------
+// Which (family, generated columns per feature GP) have register kernels built for exactly that basis size (the shapes the
+// reference's call sites build), and with which template arguments.  The five kernel generations differ on purpose:
+//   * the fp32 forward takes ANY basis size through its run-time-GP loop (GPC = 0); fwd_gpc only names the pipelined twins;
+//   * the bf16 forward and both input gradients exist for the listed sizes only, and the bf16 input gradient has neither
+//     SINE GP = 5 (the layer's default grid; attention.py:140 builds 4) nor FOURIER;
+//   * the weight gradient reads nt / njc (plan_bwd_weight_reg).
+// kan_tiny.hip keeps its own list: a different kernel family (run-time basis size on the vector pipe).
+struct RegBasis {
+    int family, gp;
+    int fwd_gpc[3];             // fp32 forward <.., ICH, GPC>: GPC of the ICH = 4 / 2 / 1 instantiation, 0 = run-time GP
+    int fwd_bf16_ich;           // bf16 forward <GP, .., ICH>: features per lane half and chunk, 0 = no kernel
+    int bwi_kt, bwi_bf16_kt;    // input gradient <GP, KT>: exact fp32 / bf16 matrix cores, 0 = no kernel
+    int bww_nt, bww_njc;        // weight gradient: column tiles per wave unit, basis windows
+};
+constexpr RegBasis KV_REG_BASES[] = {
+    {KANVIT_LINEAR, 1, {1, 0, 0}, 8, 2, 2, 6, 1},
+    {KANVIT_CHEBY, 5, {5, 0, 0}, 8, 5, 5, 3, 1},
+    {KANVIT_BSPLINE, 9, {9, 9, 0}, 8, 5, 5, 3, 2},      // 8 uniform cubic bases + the base column; ICH = 2: eight features x 9 rows x three projections overflow the W staging registers
+    {KANVIT_RBF, 9, {9, 9, 0}, 8, 5, 5, 2, 1},          // FastKAN's 8 centres + the base column
+    {KANVIT_SINE, 4, {4, 0, 0}, 8, 4, 4, 2, 1},         // the per-head mappings (attention.py:140)
+    {KANVIT_SINE, 5, {0, 0, 0}, 0, 5, 0, 2, 1},         // the layer's default grid
+    {KANVIT_SINE, 28, {0, 0, 28}, 1, 7, 7, 4, 7},       // the G = 28 patch embedding (model.py:72)
+    {KANVIT_FOURIER, 56, {0, 0, 56}, 1, 7, 0, 4, 14},
+};
+
+// the families the register kernels evaluate at all: B-splines on uniform cubic knots, FastKAN's own grid (kv_rbf_reg_ok), every parameter-free one
+inline bool kv_reg_family_ok(int family, int flags, int order, int G) {
+    if (family == KANVIT_BSPLINE) return (flags & KANVIT_FLAG_UNIFORM_KNOTS) && order == 3;
+    if (family == KANVIT_RBF) return kv_rbf_reg_ok(flags, G);
+    return true;
+}
+
+// the table's row for a layer, nullptr when its basis size has no compile-time register kernel
+inline const RegBasis* kv_reg_basis(int family, int gp, int has_base, int flags, int order, int G) {
+    if (!kv_reg_family_ok(family, flags, order, G)) return nullptr;
+    if ((family == KANVIT_BSPLINE || family == KANVIT_RBF) && !has_base) return nullptr;
+    for (const RegBasis& r : KV_REG_BASES)
+        if (r.family == family && r.gp == gp) return &r;
+    return nullptr;
+}
+inline const RegBasis* kv_reg_basis(const kanvit_layer_desc* d) {
+    return kv_reg_basis(d->family, gp_of(d), d->has_base, d->flags, d->spline_order, d->G);
+}
+
+// accumulators the fp32 register input gradient contracts: CHEBY leaves the T0 slots out (dT0/dx = 0), see kan_bwd_input_reg.hip
+constexpr int kv_bwi_g0(int fam) { return fam == KV_CHEBY ? 1 : 0; }
+constexpr int kv_bwi_kt(int fam, int gp, int kt) { return ((16 * kt) / gp * (gp - kv_bwi_g0(fam)) + 15) / 16; }
 
 // ---- plans: pure host functions of the descriptor (the workspace queries and the launches must agree) ----
 struct FwdRegBf16Plan {
@@ -254,23 +291,98 @@ struct BwRegPlan {
     size_t ws_bytes;
 };
 
+// ---- the plan of a forward / input-gradient call (kan_layer.hip: plan_layer_fwd, plan_layer_bwd_input) ----------------
+// Pure functions of the descriptor, kv_config() and the alignment of the operands: the workspace queries, kanvit_layer_ln_fusable
+// and the launchers read the same plan, and the launchers below cannot refuse (DESIGN.md section 4.5a, table of forms).
+enum LayerFwdForm { LAYER_FWD_NONE, LAYER_FWD_TINY, LAYER_FWD_WS_BF16, LAYER_FWD_REG_BF16, LAYER_FWD_REG_BF16_PATCH, LAYER_FWD_TILE_BF16,
+                    LAYER_FWD_REG, LAYER_FWD_TILE };
+enum LayerBwdInputForm { LAYER_BWI_NONE, LAYER_BWI_TINY, LAYER_BWI_RES_BF16, LAYER_BWI_REG_BF16, LAYER_BWI_REG_BF16_WIDE, LAYER_BWI_TILE_BF16,
+                         LAYER_BWI_REG, LAYER_BWI_TILE };
 
-// ---- kan_tile.hip: the general LDS-tile kernels -------------------------------------------------------------------
-int kv_tile_fwd(int family, LayerArgs& a, hipStream_t st);
+// The operand pointers whose alignment the plans look at (null pointers as 0; all 0 = aligned, the workspace queries' case)
+struct LayerAlign {
+    uintptr_t x, u, w, bp, bias, y, dy, dx, du;
+    int has_u;            // RBF: the call passes the spline-path input u (its row stride ldu counts only then)
+};
+
+struct LayerFwdPlan {
+    LayerFwdForm form;
+    const char* why;      // form == NONE: the call fails with KANVIT_EINVAL and this text (a printf format taking why_a, why_b)
+    int why_a, why_b;
+    int nt, nsh;          // 32-column tiles per work-group, groups sharing one basis evaluation (1 or 3)
+    int ich, gpc;         // REG: features per lane half and chunk, compile-time basis size (0 = the run-time-GP kernel)
+    int ic, fast;         // TILE: feature chunk, predicate-free variant
+    int strip;            // WS_BF16: the store strips fit the LDS beside the weight image
+    int tail_y0;          // REG with nsh = 3: first row tile of the sub-divided tail (kv_tail_first_tile), 0x7fffffff = none
+    unsigned gx, gy;      // grid of the layer kernel (the repack kernels size themselves)
+    size_t lds;           // its dynamic LDS bytes
+    size_t ws_bytes;      // workspace this form needs
+    size_t ws_max;        // kanvit_layer_fwd_workspace: the most any alignment outcome needs (KANVIT_NO_BF16 does not lower it)
+    FwdRegBf16Plan rb;    // WS_BF16, REG_BF16, REG_BF16_PATCH
+    FwdBf16Plan tb;       // TILE_BF16
+};
+
+struct LayerBwdInputPlan {
+    LayerBwdInputForm form;
+    const char* why;
+    int why_a, why_b;
+    int gp, kt;           // register forms: the <GP, KT> instantiation (the table's row); TILE forms: kt = 32-row k tiles of a chunk
+    int shared;           // the groups that read one x slice are summed in the accumulators (one chain rule per slice)
+    int nsh;              // RES_BF16: projections per head (1 or 3)
+    int ic, nci;          // features per chunk, chunks
+    int tail_y0;          // REG, RES_BF16: first row tile of the sub-divided tail, 0x7fffffff = none
+    unsigned gx, gy;
+    size_t lds;
+    size_t ws_bytes;      // workspace the call must bring: ws_max whenever dy allows a bf16 form (one size for all of them: the query cannot see the pointers)
+    size_t ws_max;        // kanvit_layer_bwd_input_workspace
+    BwdRegBf16Plan rb;    // RES_BF16, REG_BF16, REG_BF16_WIDE
+};
+
+LayerFwdPlan plan_layer_fwd(const kanvit_layer_desc* d, const kanvit_patch_desc* pd, const LayerAlign& al);
+LayerBwdInputPlan plan_layer_bwd_input(const kanvit_layer_desc* d, const LayerAlign& al);
+
+// LDS bytes of the LDS-tile kernels (kan_tile.hip) for a feature chunk of ic
+inline size_t kv_tile_fwd_lds(int family, int ic, int gp, int nt, int nsh) {
+    const int kcp = (ic * gp + 1) & ~1;
+    const size_t xarea = 2 * (size_t)BM * (ic | 1) * (family == KANVIT_RBF ? 2 : 1);
+    const size_t opnd = 2 * ((size_t)kcp * AS + (size_t)kcp * 32 * nt * nsh);
+    const size_t otile = (size_t)BM * (32 * nt * nsh + 4);          // staged output tile (FAST epilogue) aliases the operands
+    return sizeof(float) * (xarea + (opnd > otile ? opnd : otile));
+}
+constexpr int KV_WS_THREADS = 512;   // W-stationary bf16 forward: 8 waves (12 measured slower: 66 row tiles over 21 work-groups per head quantise to 79 %)
+
+inline size_t kv_tile_bwd_input_lds(int family, int ic, int gp, int G, int nshare, int bf_O) {
+    const int kct = 32 * ((ic * gp + 31) / 32);
+    const size_t ops = bf_O ? ((size_t)BM * (bf_O + 8) / 2 + (size_t)(bf_O / 8) * kct * 4)
+                            : ((size_t)BIN_NC * AS + (size_t)BIN_NC * (kct + 1));
+    return sizeof(float) * ((size_t)BM * (ic | 1) * (family == KANVIT_RBF ? 8 : 4) + (family == KANVIT_SINE ? (size_t)nshare * 4 * G : 0) +
+                            (size_t)kct * AS + 2 * ops);
+}
+
+// chunking of the LDS-tile input-gradient kernel: the largest feature chunk (cap 96 columns) that fits the LDS, 0 = none does
+inline int kv_tile_bwd_input_ic(int family, int I, int gp, int G, int nshare, int bf_O) {
+    int ic = 96 / gp;
+    if (ic < 1) ic = 1;
+    if (ic > I) ic = I;
+    while (ic > 1 && kv_tile_bwd_input_lds(family, ic, gp, G, nshare, bf_O) > 160 * 1024) --ic;
+    return kv_tile_bwd_input_lds(family, ic, gp, G, nshare, bf_O) > 160 * 1024 ? 0 : ic;
+}
+
+// ---- launchers: each runs the form its plan names, with the plan's numbers; none of them decides or refuses ----------
+int kv_fwd_reg(int family, const LayerArgs& a, const LayerFwdPlan& p, hipStream_t st);                     // kan_fwd_reg.hip
+int kv_fwd_reg_bf16(int family, LayerArgs& a, const LayerFwdPlan& p, void* ws, hipStream_t st);            // kan_fwd_reg_bf16.hip
+int kv_tile_fwd(int family, LayerArgs& a, const LayerFwdPlan& p, hipStream_t st);                          // kan_tile.hip
+int kv_tile_fwd_bf16(int family, LayerArgs& a, const LayerFwdPlan& p, void* ws, hipStream_t st);
+int kv_bwd_input_reg(int family, const LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st);         // kan_bwd_input_reg.hip
+int kv_bwd_input_reg_bf16(int family, LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st);          // kan_bwd_input_reg_bf16.hip
+int kv_tile_bwd_input(int family, LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st);              // kan_tile.hip; TILE_BF16: a.wb2 = the workspace
+// the shape side of the bf16 plans (no alignment): members of the layer plans
+FwdRegBf16Plan plan_fwd_reg_bf16(const kanvit_layer_desc* d);
 FwdBf16Plan plan_fwd_bf16(const kanvit_layer_desc* d);
-int kv_tile_fwd_bf16(int family, LayerArgs& a, const FwdBf16Plan& p, void* ws, hipStream_t st);
-int kv_tile_bwd_input(int family, LayerArgs& a, hipStream_t st);        // a.wb2 != nullptr: bf16 contraction (workspace = repacked W)
-size_t kv_tile_bwd_input_ws(const kanvit_layer_desc* d);
+BwdRegBf16Plan plan_bwd_input_reg_bf16(const kanvit_layer_desc* d);
+// ---- weight gradient ----
 BwPlan plan_bwd_weight(const kanvit_layer_desc* d);
 int kv_tile_bwd_weight(int family, const LayerArgs& a, const BwPlan& p, bool bf, hipStream_t st);
-// ---- register-form kernels: "try" functions return 1 when the shape is not covered (the caller falls back), 0 on success, < 0 on error
-int kv_try_fwd_reg(int family, const LayerArgs& a, hipStream_t st);
-FwdRegBf16Plan plan_fwd_reg_bf16(const kanvit_layer_desc* d);
-int kv_fwd_reg_bf16(int family, LayerArgs& a, const FwdRegBf16Plan& p, void* ws, hipStream_t st);
-int kv_try_bwd_input_reg(int family, const LayerArgs& a, hipStream_t st);
-BwdRegBf16Plan plan_bwd_input_reg_bf16(const kanvit_layer_desc* d);
-bool bwd_input_bf16_ok(const kanvit_layer_desc* d);
-int kv_bwd_input_reg_bf16(int family, LayerArgs& a, const BwdRegBf16Plan& p, hipStream_t st);
 BwRegPlan plan_bwd_weight_reg(const kanvit_layer_desc* d);
 int kv_bwd_weight_reg(int family, LayerArgs& a, const BwRegPlan& p, bool bf, hipStream_t st);
 int kv_slab_reduce(const float* slab, float* dw, long long total, int slabs, hipStream_t st);

@@ -1103,42 +1103,30 @@ __global__ __launch_bounds__(NTHR) void kan_bwd_weight_act_kernel(const LayerArg
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-template <int FAM>
-size_t fwd_lds(int ic, int gp, int nt, int nsh) {
-    const int kcp = (ic * gp + 1) & ~1;
-    const size_t xarea = 2 * (size_t)BM * (ic | 1) * (FAM == KV_RBF ? 2 : 1);
-    const size_t opnd = 2 * ((size_t)kcp * AS + (size_t)kcp * 32 * nt * nsh);
-    const size_t otile = (size_t)BM * (32 * nt * nsh + 4);          // staged output tile (FAST epilogue) aliases the operands
-    return sizeof(float) * (xarea + (opnd > otile ? opnd : otile));
-}
-
 template <int FAM, int NT, int NSH, bool FAST>
-int launch_fwd(const LayerArgs& a, hipStream_t st) {
-    constexpr int BN = 32 * NT;
-    const size_t lds = fwd_lds<FAM>(a.IC, a.GP, NT, NSH);
+int launch_fwd(const LayerArgs& a, const LayerFwdPlan& p, hipStream_t st) {
     KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_fwd_kernel, kan_fwd_act_kernel, (FAM, NT, NSH, FAST));
-    dim3 grid((unsigned)((a.groups / NSH) * ((a.O + BN - 1) / BN)), (unsigned)((a.M + BM - 1) / BM), 1);
-    KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_kernel, kan_fwd_act_kernel, (FAM, NT, NSH, FAST), grid, dim3(NTHR), lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_kernel, kan_fwd_act_kernel, (FAM, NT, NSH, FAST), dim3(p.gx, p.gy, 1), dim3(NTHR), p.lds, st, a);
     KV_LAUNCH_CHECK("kan_fwd_kernel");
     return 0;
 }
 
 template <int FAM, int NT, int NSH>
-int launch_fwd_sel(const LayerArgs& a, bool fast, hipStream_t st) {
-    return fast ? launch_fwd<FAM, NT, NSH, true>(a, st) : launch_fwd<FAM, NT, NSH, false>(a, st);
+int launch_fwd_sel(const LayerArgs& a, const LayerFwdPlan& p, hipStream_t st) {
+    return p.fast ? launch_fwd<FAM, NT, NSH, true>(a, p, st) : launch_fwd<FAM, NT, NSH, false>(a, p, st);
 }
 
 template <int FAM, int NT, int NSH>
-int launch_fwd_bf16(const LayerArgs& a, const FwdBf16Plan& p, hipStream_t st) {
+int launch_fwd_bf16(const LayerArgs& a, const LayerFwdPlan& p, hipStream_t st) {
     KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_fwd_bf16_kernel, kan_fwd_bf16_act_kernel, (FAM, NT, NSH));
-    dim3 grid((unsigned)((a.groups / NSH) * (a.O / (32 * NT))), (unsigned)((a.M + BM - 1) / BM), 1);
-    KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_bf16_kernel, kan_fwd_bf16_act_kernel, (FAM, NT, NSH), grid, dim3(NTHR), p.lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_fwd_bf16_kernel, kan_fwd_bf16_act_kernel, (FAM, NT, NSH), dim3(p.gx, p.gy, 1), dim3(NTHR), p.lds, st, a);
     KV_LAUNCH_CHECK("kan_fwd_bf16_kernel");
     return 0;
 }
 
 template <int FAM>
-int dispatch_fwd_bf16(LayerArgs& a, const FwdBf16Plan& p, void* ws, hipStream_t st) {
+int dispatch_fwd_bf16(LayerArgs& a, const LayerFwdPlan& pl, void* ws, hipStream_t st) {
+    const FwdBf16Plan& p = pl.tb;
     unsigned short* wb = (unsigned short*)ws;
     const long long total = (long long)a.groups * p.nch * (p.kcp / 8) * a.O;
     hipLaunchKernelGGL(kan_pack_w_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.w, wb, a.K, a.O, p.kc,
@@ -1148,120 +1136,64 @@ int dispatch_fwd_bf16(LayerArgs& a, const FwdBf16Plan& p, void* ws, hipStream_t 
     a.IC = p.ic;
     if (p.nsh == 3) {
         if constexpr (kv_shared_basis<FAM>()) {
-            if (p.nt == 1) return launch_fwd_bf16<FAM, 1, 3>(a, p, st);
-            return launch_fwd_bf16<FAM, 2, 3>(a, p, st);
+            if (p.nt == 1) return launch_fwd_bf16<FAM, 1, 3>(a, pl, st);
+            return launch_fwd_bf16<FAM, 2, 3>(a, pl, st);
         }
     }
-    if (p.nt == 1) return launch_fwd_bf16<FAM, 1, 1>(a, p, st);
-    if (p.nt == 2) return launch_fwd_bf16<FAM, 2, 1>(a, p, st);
-    return launch_fwd_bf16<FAM, 4, 1>(a, p, st);
+    if (p.nt == 1) return launch_fwd_bf16<FAM, 1, 1>(a, pl, st);
+    if (p.nt == 2) return launch_fwd_bf16<FAM, 2, 1>(a, pl, st);
+    return launch_fwd_bf16<FAM, 4, 1>(a, pl, st);
 }
 
 template <int FAM>
-int tile_fwd(LayerArgs& a, hipStream_t st) {
-    const int nt = a.O <= 32 ? 1 : (a.O <= 64 ? 2 : 4);
-    const int nshare = a.groups / a.xmod;
-    const bool share3 = kv_shared_basis<FAM>() && kv_share_ok(FAM, a.flags) && nshare == 3 && nt <= 2;
-    const int nsh = share3 ? 3 : 1;
-    // largest feature chunk whose two operand buffers fit the 160 KiB LDS (cap 80 columns)
-    int ic = 80 / a.GP;
-    if (ic < 1) ic = 1;
-    if (ic > a.I) ic = a.I;
-    while (ic > 1 && fwd_lds<FAM>(ic, a.GP, nt, nsh) > 160 * 1024) --ic;
-    if (fwd_lds<FAM>(ic, a.GP, nt, nsh) > 160 * 1024)
-        return kv_fail(KANVIT_EINVAL, "kanvit_layer_fwd: %d generated columns per feature with O=%d does not fit the LDS", a.GP, a.O);
-    // fast path: power-of-two chunk dividing I, whole column tiles, 32-bit tile-local offsets
-    int icf = 1;
-    while (icf * 2 <= ic) icf *= 2;
-    const bool fast = (icf >= 8) && (a.I % icf == 0) && (a.O % (32 * nt) == 0) &&
-                      ((long long)BM * a.ldx < (1LL << 30)) && ((long long)BM * a.ldy < (1LL << 30)) &&
-                      ((long long)BM * a.ldu < (1LL << 30)) && ((long long)a.K * a.O < (1LL << 30)) && !kv_config().no_fast;
-    a.IC = fast ? icf : ic;
-    if (share3) {
+int tile_fwd(LayerArgs& a, const LayerFwdPlan& p, hipStream_t st) {
+    a.IC = p.ic;
+    if (p.nsh == 3) {
         if constexpr (kv_shared_basis<FAM>()) {
-            if (nt == 1) return launch_fwd_sel<FAM, 1, 3>(a, fast, st);
-            return launch_fwd_sel<FAM, 2, 3>(a, fast, st);
+            if (p.nt == 1) return launch_fwd_sel<FAM, 1, 3>(a, p, st);
+            return launch_fwd_sel<FAM, 2, 3>(a, p, st);
         }
     }
-    if (nt == 1) return launch_fwd_sel<FAM, 1, 1>(a, fast, st);
-    if (nt == 2) return launch_fwd_sel<FAM, 2, 1>(a, fast, st);
-    return launch_fwd_sel<FAM, 4, 1>(a, fast, st);
+    if (p.nt == 1) return launch_fwd_sel<FAM, 1, 1>(a, p, st);
+    if (p.nt == 2) return launch_fwd_sel<FAM, 2, 1>(a, p, st);
+    return launch_fwd_sel<FAM, 4, 1>(a, p, st);
 }
 
 // ---- backward input ------------------------------------------------------------------------------
-template <int FAM>
-size_t bwd_input_lds(int ic, int gp, int G, int nshare, int bf_O = 0) {
-    const int kct = 32 * ((ic * gp + 31) / 32);
-    const size_t ops = bf_O ? ((size_t)BM * (bf_O + 8) / 2 + (size_t)(bf_O / 8) * kct * 4)
-                            : ((size_t)BIN_NC * AS + (size_t)BIN_NC * (kct + 1));
-    return sizeof(float) * ((size_t)BM * (ic | 1) * (FAM == KV_RBF ? 8 : 4) + (FAM == KV_SINE ? (size_t)nshare * 4 * G : 0) +
-                            (size_t)kct * AS + 2 * ops);
-}
-
 template <int FAM, int KT, bool SHARED, bool BF>
-int launch_bwd_input(const LayerArgs& a, hipStream_t st) {
-    const size_t lds = bwd_input_lds<FAM>(a.IC, a.GP, a.G, a.groups / a.xmod, BF ? a.O : 0);
+int launch_bwd_input(const LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st) {
     KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_bwd_input_kernel, kan_bwd_input_act_kernel, (FAM, KT, SHARED, BF));
-    dim3 grid((unsigned)a.xmod, (unsigned)((a.M + BM - 1) / BM), 1);
-    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_kernel, kan_bwd_input_act_kernel, (FAM, KT, SHARED, BF), grid, dim3(NTHR), lds, st, a);
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_input_kernel, kan_bwd_input_act_kernel, (FAM, KT, SHARED, BF), dim3(p.gx, p.gy, 1), dim3(NTHR), p.lds, st, a);
     KV_LAUNCH_CHECK("kan_bwd_input_kernel");
     return 0;
 }
 
 template <int FAM, bool SHARED>
-int launch_bwd_input_kt(const LayerArgs& a, int kt, bool bf, hipStream_t st) {
-    if (bf) {
-        if (kt == 1) return launch_bwd_input<FAM, 1, SHARED, true>(a, st);
-        if (kt == 2) return launch_bwd_input<FAM, 2, SHARED, true>(a, st);
-        return launch_bwd_input<FAM, 3, SHARED, true>(a, st);
+int launch_bwd_input_kt(const LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st) {
+    if (p.form == LAYER_BWI_TILE_BF16) {
+        if (p.kt == 1) return launch_bwd_input<FAM, 1, SHARED, true>(a, p, st);
+        if (p.kt == 2) return launch_bwd_input<FAM, 2, SHARED, true>(a, p, st);
+        return launch_bwd_input<FAM, 3, SHARED, true>(a, p, st);
     }
-    if (kt == 1) return launch_bwd_input<FAM, 1, SHARED, false>(a, st);
-    if (kt == 2) return launch_bwd_input<FAM, 2, SHARED, false>(a, st);
-    return launch_bwd_input<FAM, 3, SHARED, false>(a, st);
-}
-
-// chunking of the input-gradient kernel (shared by the workspace query and the launch)
-template <int FAM>
-int bwd_input_ic(int I, int gp, int G, int nshare, int bf_O) {
-    int ic = 96 / gp;
-    if (ic < 1) ic = 1;
-    if (ic > I) ic = I;
-    while (ic > 1 && bwd_input_lds<FAM>(ic, gp, G, nshare, bf_O) > 160 * 1024) --ic;
-    return bwd_input_lds<FAM>(ic, gp, G, nshare, bf_O) > 160 * 1024 ? 0 : ic;
+    if (p.kt == 1) return launch_bwd_input<FAM, 1, SHARED, false>(a, p, st);
+    if (p.kt == 2) return launch_bwd_input<FAM, 2, SHARED, false>(a, p, st);
+    return launch_bwd_input<FAM, 3, SHARED, false>(a, p, st);
 }
 
 template <int FAM>
-size_t bwd_input_ws(const kanvit_layer_desc* d) {
-    const int gp = gp_of(d), nshare = d->groups / d->x_group_mod;
-    const int ic = bwd_input_ic<FAM>(d->I, gp, d->G, nshare, d->O);
-    if (!ic) return 0;
-    const int kct = 32 * ((ic * gp + 31) / 32), nci = (d->I + ic - 1) / ic;
-    return (size_t)d->groups * nci * (d->O / 8) * kct * 16;
-}
-
-template <int FAM>
-int tile_bwd_input(LayerArgs& a, hipStream_t st) {
-    const int nshare = a.groups / a.xmod;
-    bool bf = a.wb2 != nullptr;                         // set by the entry point when the bf16 path applies
-    int ic = bwd_input_ic<FAM>(a.I, a.GP, a.G, nshare, bf ? a.O : 0);
-    if (!ic && bf) {
-        bf = false;
-        ic = bwd_input_ic<FAM>(a.I, a.GP, a.G, nshare, 0);
-    }
-    if (!ic) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_input: tile does not fit the LDS");
-    a.IC = ic;
-    const int kt = (ic * a.GP + 31) / 32;
-    if (bf) {
-        const int kct = 32 * kt, nci = (a.I + ic - 1) / ic;
-        const long long total = (long long)a.groups * nci * (a.O / 8) * kct;
+int tile_bwd_input(LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st) {
+    a.IC = p.ic;
+    if (p.form == LAYER_BWI_TILE_BF16) {          // a.wb2 = the workspace: the bf16 repack of W goes there first
+        const int kct = 32 * p.kt;
+        const long long total = (long long)a.groups * p.nci * (a.O / 8) * kct;
         hipLaunchKernelGGL(kan_pack_w_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.w,
-                           const_cast<unsigned short*>(a.wb2), a.K, a.O, ic * a.GP, kct, nci, total);
+                           const_cast<unsigned short*>(a.wb2), a.K, a.O, p.ic * a.GP, kct, p.nci, total);
         KV_LAUNCH_CHECK("kan_pack_w_bwd_kernel");
     }
-    if constexpr (kv_shared_basis<FAM>()) {
-        if (kv_share_ok(FAM, a.flags) && nshare > 1) return launch_bwd_input_kt<FAM, true>(a, kt, bf, st);
+    if (p.shared) {
+        if constexpr (kv_shared_basis<FAM>()) return launch_bwd_input_kt<FAM, true>(a, p, st);
     }
-    return launch_bwd_input_kt<FAM, false>(a, kt, bf, st);
+    return launch_bwd_input_kt<FAM, false>(a, p, st);
 }
 
 template <int FAM, int NSH, bool BF>
@@ -1351,18 +1283,18 @@ BwPlan plan_bwd_weight(const kanvit_layer_desc* d) {
     return p;
 }
 
-int kv_tile_fwd(int family, LayerArgs& a, hipStream_t st) {
-#define KV_CALL(F) tile_fwd<F>(a, st)
+int kv_tile_fwd(int family, LayerArgs& a, const LayerFwdPlan& p, hipStream_t st) {
+#define KV_CALL(F) tile_fwd<F>(a, p, st)
     KV_FAMILY_SWITCH(family, KV_CALL)
 #undef KV_CALL
 }
-int kv_tile_fwd_bf16(int family, LayerArgs& a, const FwdBf16Plan& p, void* ws, hipStream_t st) {
+int kv_tile_fwd_bf16(int family, LayerArgs& a, const LayerFwdPlan& p, void* ws, hipStream_t st) {
 #define KV_CALL(F) dispatch_fwd_bf16<F>(a, p, ws, st)
     KV_FAMILY_SWITCH(family, KV_CALL)
 #undef KV_CALL
 }
-int kv_tile_bwd_input(int family, LayerArgs& a, hipStream_t st) {
-#define KV_CALL(F) tile_bwd_input<F>(a, st)
+int kv_tile_bwd_input(int family, LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st) {
+#define KV_CALL(F) tile_bwd_input<F>(a, p, st)
     KV_FAMILY_SWITCH(family, KV_CALL)
 #undef KV_CALL
 }
@@ -1370,15 +1302,4 @@ int kv_tile_bwd_weight(int family, const LayerArgs& a, const BwPlan& p, bool bf,
 #define KV_CALL(F) launch_bwd_weight<F>(a, p, bf, st)
     KV_FAMILY_SWITCH(family, KV_CALL)
 #undef KV_CALL
-}
-size_t kv_tile_bwd_input_ws(const kanvit_layer_desc* d) {
-    switch (d->family) {
-        case KANVIT_LINEAR: return bwd_input_ws<KV_LINEAR>(d);
-        case KANVIT_CHEBY: return bwd_input_ws<KV_CHEBY>(d);
-        case KANVIT_BSPLINE: return bwd_input_ws<KV_BSPLINE>(d);
-        case KANVIT_RBF: return bwd_input_ws<KV_RBF>(d);
-        case KANVIT_SINE: return bwd_input_ws<KV_SINE>(d);
-        case KANVIT_FOURIER: return bwd_input_ws<KV_FOURIER>(d);
-        default: return 0;
-    }
 }

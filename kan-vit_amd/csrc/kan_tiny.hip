@@ -216,12 +216,11 @@ int tiny_family(int family, F&& f) {
 bool kv_tiny_ok(const kanvit_layer_desc* d) {
     if (kv_config().no_tiny || d->I > 16 || d->O > 16 || d->I < 1 || d->O < 1) return false;
     const int fam = d->family;
-    int gp;
-    if (fam == KANVIT_LINEAR) gp = 1;
-    else if (fam == KANVIT_CHEBY) gp = d->G;
-    else if (fam == KANVIT_FOURIER) gp = 2 * d->G;
-    else if (fam == KANVIT_BSPLINE && (d->flags & KANVIT_FLAG_UNIFORM_KNOTS) && d->spline_order == 3) gp = d->G + d->has_base;
-    else return false;
+    // this kernel family's own list: the parameter-free families and B-splines on uniform cubic knots, any basis size
+    if (!(fam == KANVIT_LINEAR || fam == KANVIT_CHEBY || fam == KANVIT_FOURIER ||
+          (fam == KANVIT_BSPLINE && (d->flags & KANVIT_FLAG_UNIFORM_KNOTS) && d->spline_order == 3)))
+        return false;
+    const int gp = gp_of(d);
     if (gp < 1 || d->I * gp > 200 || d->I * gp * d->O > 1024) return false;      // K <= 200: the weight gradient's phi tile [64][K + 1] stays under 64 KB of LDS
     if (d->x_group_mod < 1 || d->groups % d->x_group_mod || (d->groups / d->x_group_mod) * d->I * gp * 16 > 15 * 1024) return false;
     return d->M >= 64;                               // fewer rows: the general kernels' single tile is as good

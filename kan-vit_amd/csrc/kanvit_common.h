@@ -87,6 +87,19 @@ static inline hipError_t kv_allow_lds(K kernel, size_t bytes) {
         }                                                                                         \
     } while (0)
 
+// generated columns per input feature (the basis size GP), -1 for an unknown family
+inline int gp_of(const kanvit_layer_desc* d) {
+    switch (d->family) {
+        case KANVIT_LINEAR: return 1;
+        case KANVIT_CHEBY: return d->G;
+        case KANVIT_BSPLINE: return d->G + (d->has_base ? 1 : 0);
+        case KANVIT_RBF: return d->G + (d->has_base ? 1 : 0);
+        case KANVIT_SINE: return d->G;
+        case KANVIT_FOURIER: return 2 * d->G;
+        default: return -1;
+    }
+}
+
 // tiny per-head layers on the vector pipe (csrc/kan_tiny.hip), called by kan_layer.hip's entry points
 struct KvTinyArgs {
     const float* x;

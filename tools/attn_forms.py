@@ -3,8 +3,8 @@ fixed table of shapes, precisions, KANVIT_ATTN_* switches and pointer alignments
 printing the row's label and kanvit_attn_bwd_workspace.  Two builds of the library choose the same forms when their outputs and the
 ordered attn* kernel names, grids and LDS sizes of their kernel traces agree:
     python tools/attn_forms.py --workspace-only                 (host only: no GPU needed)
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d <dir> -- python tools/attn_forms.py
-    KANVIT_LIB=<other build> timeout -k 10 300 rocprofv3 --kernel-trace --stats -d <dir2> -- python tools/attn_forms.py
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/attn_forms.py
+    KANVIT_LIB=<other build> timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d <dir2> -- python tools/attn_forms.py
     python tools/attn_forms.py --diff <dir> <dir2>             (compares the two traces)"""
 import csv
 import ctypes as C
@@ -30,25 +30,30 @@ def rows():
                         yield sw, n, d, causal, flags, off
 
 
-def trace_launches(directory):
-    """(kernel name, grid, LDS bytes) of the attn* launches of a rocprofv3 --kernel-trace run, in launch order."""
+def trace_launches(directory, pattern=r"\battn(16)?_\w+_kernel"):
+    """(kernel name, grid, LDS bytes) of the launches of a rocprofv3 --kernel-trace run whose kernel name matches `pattern`, in launch order."""
     out = []
     for path in sorted(glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True)):
-        recs = [r for r in csv.DictReader(open(path)) if re.search(r"\battn(16)?_\w+_kernel", r["Kernel_Name"])]
+        recs = [r for r in csv.DictReader(open(path)) if re.search(pattern, r["Kernel_Name"])]
         recs.sort(key=lambda r: int(r["Start_Timestamp"]))
-        grid = "Grid_Size_X" if recs and "Grid_Size_X" in recs[0] else "Grid_Size"
-        out += [(r["Kernel_Name"], r[grid], r["LDS_Block_Size"]) for r in recs]
+        grid = [c for c in ("Grid_Size_X", "Grid_Size_Y", "Grid_Size_Z") if recs and c in recs[0]] or ["Grid_Size"]
+        out += [(r["Kernel_Name"], " x ".join(r[c] for c in grid), r["LDS_Block_Size"]) for r in recs]
     return out
+
+
+def diff_traces(directories, what="attn*", **kw):
+    """Compare the ordered launches of two traces; the exit status (0 = equal and not empty)."""
+    a, b = (trace_launches(p, **kw) for p in directories[:2])
+    bad = [(i, x, y) for i, (x, y) in enumerate(zip(a, b)) if x != y]
+    for i, x, y in bad[:20]:
+        print(f"launch {i}: {x} != {y}")
+    print(f"{len(a)} and {len(b)} {what} launches, {len(bad)} differ")
+    return 1 if bad or len(a) != len(b) or not a else 0
 
 
 def main():
     if "--diff" in sys.argv:
-        a, b = (trace_launches(p) for p in sys.argv[sys.argv.index("--diff") + 1:][:2])
-        bad = [(i, x, y) for i, (x, y) in enumerate(zip(a, b)) if x != y]
-        for i, x, y in bad[:20]:
-            print(f"launch {i}: {x} != {y}")
-        print(f"{len(a)} and {len(b)} attn* launches, {len(bad)} differ")
-        sys.exit(1 if bad or len(a) != len(b) or not a else 0)
+        sys.exit(diff_traces(sys.argv[sys.argv.index("--diff") + 1:]))
     host_only = "--workspace-only" in sys.argv
     from kanvit import _lib
     L = _lib.lib()
