@@ -338,8 +338,9 @@ __global__ __launch_bounds__(256) void kan_bwd_weight_dma_kernel(const LayerArgs
 }
 
 template <int FAM, int GP, int NOT, bool BF>
-int launch_dma(LayerArgs& a, const BwRegPlan& p, hipStream_t st) {
-    const long long gsz = (long long)p.nfb * p.nos, sets = (long long)p.nbg * p.slabs;
+int launch_dma(LayerArgs& a, const LayerBwdWeightPlan& pl, hipStream_t st) {
+    const BwRegPlan& p = pl.r;
+    const long long gsz = (long long)p.nfb * p.nos, sets = (long long)p.nbg * pl.slabs;
     const long long per_xcd = (sets * gsz + 7) / 8;
     const int placed = gsz <= 32 ? 1 : 0;
     const long long cap = placed ? (per_xcd + gsz - 1) / gsz * gsz : per_xcd;       // slots of an XCD: whole sharing sets (see the kernel)
@@ -347,19 +348,14 @@ int launch_dma(LayerArgs& a, const BwRegPlan& p, hipStream_t st) {
     constexpr size_t lds = sizeof(float) * 4 * KVD_NSLOT * (KVD_BLK * 32 * (1 + NOT));
     KV_ALLOW_LDS(160 * 1024, (kan_bwd_weight_dma_kernel<FAM, GP, NOT, BF>));
     hipLaunchKernelGGL((kan_bwd_weight_dma_kernel<FAM, GP, NOT, BF>), grid, dim3(256), lds, st, a, p.nfb, p.nos, p.tiles_per_bg, p.shared, p.nbg,
-                       (int)(p.rows_per_slab / 4), (int)cap, placed);
+                       (int)(pl.rows_per_slab / 4), (int)cap, placed);
     KV_LAUNCH_CHECK("kan_bwd_weight_dma_kernel");
     return 0;
 }
 
 }  // namespace
 
-// 16-byte DMA pieces: the rows of x and dY this launch reads must start on 16-byte boundaries
-bool kv_bwd_weight_dma_aligned(const LayerArgs& a) {
-    return !(((uintptr_t)a.x | (uintptr_t)a.dy) & 15) && a.ldx % 4 == 0 && a.ldy % 4 == 0 && a.I % 4 == 0 && a.O % 4 == 0;
-}
-
-int kv_bwd_weight_dma(int family, LayerArgs& a, const BwRegPlan& p, bool bf, hipStream_t st) {
-    if (family != KANVIT_CHEBY || p.gp != 5 || p.nt != 3 || a.pg) return kv_fail(KANVIT_EINVAL, "internal: LDS-DMA weight-gradient dispatch");
-    return bf ? launch_dma<KV_CHEBY, 5, 3, true>(a, p, st) : launch_dma<KV_CHEBY, 5, 3, false>(a, p, st);
+// LAYER_BWW_DMA: ChebyKAN degree 4, three column tiles per wave, rows of x and dY on 16-byte boundaries (plan_layer_bwd_weight)
+int kv_bwd_weight_dma(LayerArgs& a, const LayerBwdWeightPlan& p, hipStream_t st) {
+    return p.bf ? launch_dma<KV_CHEBY, 5, 3, true>(a, p, st) : launch_dma<KV_CHEBY, 5, 3, false>(a, p, st);
 }

@@ -627,70 +627,70 @@ __global__ __launch_bounds__(256) void kan_slab_reduce_kernel(const float* __res
 }
 
 template <int FAM, int GP, int NOT, bool BF, int JC, bool PG>
-int launch_bwd_weight_reg_one(LayerArgs& a, const BwRegPlan& p, hipStream_t st) {
+int launch_bwd_weight_reg_one(LayerArgs& a, const LayerBwdWeightPlan& pl, hipStream_t st) {
+    const BwRegPlan& p = pl.r;
     const long long units = (long long)p.nbg * p.nfb * p.nos * p.njc;
-    dim3 grid((unsigned)((units * p.slabs + 3) / 4), 1, 1);
-    const size_t lds = a.ln ? (size_t)4 * p.rows_per_slab * sizeof(float2) : 0;      // four wave-private (mean, rstd) strips
+    dim3 grid((unsigned)((units * pl.slabs + 3) / 4), 1, 1);
+    const size_t lds = a.ln ? (size_t)4 * pl.rows_per_slab * sizeof(float2) : 0;      // four wave-private (mean, rstd) strips
     if (lds > 64 * 1024) KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_bwd_weight_reg_kernel, kan_bwd_weight_reg_act_kernel, (FAM, GP, NOT, BF, JC, PG));
     KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_weight_reg_kernel, kan_bwd_weight_reg_act_kernel, (FAM, GP, NOT, BF, JC, PG), grid, dim3(256), lds, st, a, p.nfb, p.nos, p.tiles_per_bg, p.shared, p.nbg);
     KV_LAUNCH_CHECK("kan_bwd_weight_reg_kernel");
     return 0;
 }
 
-// HAS_PG: the instantiation also exists in its patch-gather form (the patch-embedding layers the model builds: kv_bwd_weight_reg_pg_ok)
-template <int FAM, int GP, int NOT, int JC = GP, bool HAS_BF = true, bool HAS_PG = false>
-int launch_bwd_weight_reg(LayerArgs& a, const BwRegPlan& p, bool bf, hipStream_t st) {
-    if (bf && !HAS_BF) return kv_fail(KANVIT_EINVAL, "internal: this register weight-gradient instantiation has no bf16 form");
-    if (a.pg && !HAS_PG) return kv_fail(KANVIT_EINVAL, "internal: this register weight-gradient instantiation has no patch-gather form");
-    if constexpr (HAS_PG) {
-        if (a.pg) {      // exact fp32 only: on the bf16 matrix cores the MFMA phases are too short to hide the scalar row walker (SineKAN G = 28:
-                         // 2.76 -> 3.15 ms per pass, ChebyKAN 0.37 -> 0.50 ms -- more than the patch-matrix copies cost), kv_bwd_weight_reg_pg_ok
-            if (bf) return kv_fail(KANVIT_EINVAL, "internal: the patch-gather weight gradient is an exact-fp32 form");
-            return launch_bwd_weight_reg_one<FAM, GP, NOT, false, JC, true>(a, p, st);
-        }
+// LAYER_BWW_REG_PATCH, the patch-gather form, is instantiated for the rows of KV_REG_BASES with bww_pg = 1 and nowhere else (the
+// patch-embedding layers VisionTransformer builds, model.py:67-80: ChebyKAN degree 4, SineKAN / FourierKAN at grid 28).  Exact fp32 only:
+// on the bf16 matrix cores the MFMA phases are too short to hide the scalar row walker (SineKAN G = 28: 2.76 -> 3.15 ms per pass,
+// ChebyKAN 0.37 -> 0.50 ms -- more than the patch-matrix copies cost).  B-splines are NOT among them: their kernels are at the register
+// limit, and the walker's scalar state spilled (19 scalar registers in the 16-row kernel, 16 vector registers in the 32-row one): 2.97
+// against 2.80 ms for the ViT-B patch embedding, 1.82 against 1.13 ms in bf16 mode.  efficient-KAN's patch embedding and every bf16-mode
+// one keep the transient patch matrix.
+template <int FAM, int GP, int NOT, int JC = GP>
+int launch_bwd_weight_reg(LayerArgs& a, const LayerBwdWeightPlan& p, hipStream_t st) {
+    if constexpr (kv_bww_pg(FAM, GP)) {
+        if (p.form == LAYER_BWW_REG_PATCH) return launch_bwd_weight_reg_one<FAM, GP, NOT, false, JC, true>(a, p, st);
     }
-    if constexpr (HAS_BF) {
-        if (bf) return launch_bwd_weight_reg_one<FAM, GP, NOT, true, JC, false>(a, p, st);
-    }
+    if (p.bf) return launch_bwd_weight_reg_one<FAM, GP, NOT, true, JC, false>(a, p, st);
     return launch_bwd_weight_reg_one<FAM, GP, NOT, false, JC, false>(a, p, st);
 }
 
 template <int FAM, int GP, int JC, int NC>
-int launch_bwd_weight_reg16(LayerArgs& a, const BwRegPlan& p, hipStream_t st) {
+int launch_bwd_weight_reg16(LayerArgs& a, const LayerBwdWeightPlan& pl, hipStream_t st) {
+    const BwRegPlan& p = pl.r;
     const long long units = (long long)p.nbg * p.nfb * p.nos * p.njc;
-    dim3 grid((unsigned)((units * p.slabs + 3) / 4), 1, 1);
-    if (a.pg) return kv_fail(KANVIT_EINVAL, "internal: the 16-row weight-gradient kernel has no patch-gather form");
+    dim3 grid((unsigned)((units * pl.slabs + 3) / 4), 1, 1);
     KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_weight_reg16_kernel, kan_bwd_weight_reg16_act_kernel, (FAM, GP, JC, NC), grid, dim3(256), 0, st, a, p.nfb, p.nos, p.tiles_per_bg, p.shared, p.nbg);
     KV_LAUNCH_CHECK("kan_bwd_weight_reg16_kernel");
     return 0;
 }
 
-int dispatch_bwd_weight_reg(int family, LayerArgs& a, const BwRegPlan& p, bool bf, hipStream_t st) {
-    if (p.t16) {
-        if (bf || (family != KANVIT_BSPLINE && family != KANVIT_RBF)) return kv_fail(KANVIT_EINVAL, "internal: 16-row weight-gradient dispatch");
+}  // namespace
+
+// (Measured and removed, round 3: an XCD-aware order of the work-groups -- every XCD one contiguous range of the (slab, unit) order, so
+// that waves sharing a dY tile or an x feature block meet in one L2 -- changed no weight-gradient launch by more than the run-to-run
+// noise (ChebyKAN / B-spline / FastKAN / SineKAN G = 28, fp32 and bf16): these kernels wait on their prefetch depth, not on L2 misses.)
+int kv_bwd_weight_reg(int family, LayerArgs& a, const LayerBwdWeightPlan& p, hipStream_t st) {
+    if (p.form == LAYER_BWW_REG16) {      // B-splines and FastKAN, exact fp32
         if (family == KANVIT_RBF) return launch_bwd_weight_reg16<KV_RBF, 9, 9, 4>(a, p, st);
-        return p.nt == 12 ? launch_bwd_weight_reg16<KV_BSPLINE, 9, 3, 12>(a, p, st) : launch_bwd_weight_reg16<KV_BSPLINE, 9, 3, 4>(a, p, st);
+        return p.r.nt == 12 ? launch_bwd_weight_reg16<KV_BSPLINE, 9, 3, 12>(a, p, st) : launch_bwd_weight_reg16<KV_BSPLINE, 9, 3, 4>(a, p, st);
     }
     switch (family) {
-        case KANVIT_LINEAR: return launch_bwd_weight_reg<KV_LINEAR, 1, 6>(a, p, bf, st);
-        case KANVIT_CHEBY: return p.nt == 1 ? launch_bwd_weight_reg<KV_CHEBY, 5, 1, 5, true, true>(a, p, bf, st) : launch_bwd_weight_reg<KV_CHEBY, 5, 3, 5, true, true>(a, p, bf, st);
+        case KANVIT_LINEAR: return launch_bwd_weight_reg<KV_LINEAR, 1, 6>(a, p, st);
+        case KANVIT_CHEBY: return p.r.nt == 1 ? launch_bwd_weight_reg<KV_CHEBY, 5, 1>(a, p, st) : launch_bwd_weight_reg<KV_CHEBY, 5, 3>(a, p, st);
         case KANVIT_BSPLINE:      // two windows of five basis slots (exact fp32 when the 16-row kernel does not apply; bf16 mode)
-            return p.nt == 3 ? launch_bwd_weight_reg<KV_BSPLINE, 9, 3, 5, true>(a, p, bf, st) : launch_bwd_weight_reg<KV_BSPLINE, 9, 2, 5, true>(a, p, bf, st);
-        case KANVIT_RBF: return launch_bwd_weight_reg<KV_RBF, 9, 2>(a, p, bf, st);
+            return p.r.nt == 3 ? launch_bwd_weight_reg<KV_BSPLINE, 9, 3, 5>(a, p, st) : launch_bwd_weight_reg<KV_BSPLINE, 9, 2, 5>(a, p, st);
+        case KANVIT_RBF: return launch_bwd_weight_reg<KV_RBF, 9, 2>(a, p, st);
         case KANVIT_SINE:
             if (a.flags & KANVIT_FLAG_SINE_DFREQ) {      // the x * cos operand (d loss / d freq through a weight-gradient pass; kanvit.h)
-                if (a.GP == 28) return launch_bwd_weight_reg<KV_SINE_DF, 28, 4, 4, true, true>(a, p, bf, st);
-                return a.GP == 4 ? launch_bwd_weight_reg<KV_SINE_DF, 4, 2>(a, p, bf, st) : launch_bwd_weight_reg<KV_SINE_DF, 5, 2>(a, p, bf, st);
+                if (a.GP == 28) return launch_bwd_weight_reg<KV_SINE_DF, 28, 4, 4>(a, p, st);
+                return a.GP == 4 ? launch_bwd_weight_reg<KV_SINE_DF, 4, 2>(a, p, st) : launch_bwd_weight_reg<KV_SINE_DF, 5, 2>(a, p, st);
             }
-            if (a.GP == 28) return launch_bwd_weight_reg<KV_SINE, 28, 4, 4, true, true>(a, p, bf, st);
-            return a.GP == 4 ? launch_bwd_weight_reg<KV_SINE, 4, 2>(a, p, bf, st) : launch_bwd_weight_reg<KV_SINE, 5, 2>(a, p, bf, st);
-        case KANVIT_FOURIER: return launch_bwd_weight_reg<KV_FOURIER, 56, 4, 4, true, true>(a, p, bf, st);
-        default: return kv_fail(KANVIT_EINVAL, "internal: register weight-gradient dispatch");
+            if (a.GP == 28) return launch_bwd_weight_reg<KV_SINE, 28, 4, 4>(a, p, st);
+            return a.GP == 4 ? launch_bwd_weight_reg<KV_SINE, 4, 2>(a, p, st) : launch_bwd_weight_reg<KV_SINE, 5, 2>(a, p, st);
+        case KANVIT_FOURIER: return launch_bwd_weight_reg<KV_FOURIER, 56, 4, 4>(a, p, st);
+        default: return kv_fail(KANVIT_EINVAL, "unknown family %d", family);
     }
 }
-
-
-}  // namespace
 
 BwRegPlan plan_bwd_weight_reg(const kanvit_layer_desc* d) {
     BwRegPlan p{};
@@ -698,16 +698,7 @@ BwRegPlan plan_bwd_weight_reg(const kanvit_layer_desc* d) {
     p.njc = 1;
     p.gp = gp_of(d);
     const int fam = d->family;
-    // column tiles per wave unit and basis windows of the <family, GP> instantiations: KV_REG_BASES (kan_layer_common.h).  Why these:
-    // BSPLINE (GP = 9: 8 cubic bases + silu): two windows of FIVE basis slots (0..4 | 5..7, silu, one idle slot), each window
-    // its own wave unit that contracts its values against three column tiles -- the Chebyshev schedule (240 accumulators, 15
-    // MFMAs per basis evaluation), a window evaluating only its own values (compile-time window start).  The idle slot
-    // costs 10 % of the MFMAs; 3 x 6 tiles (no idle slot, 288 accumulators) and round 2's 9 x 2 both spill accumulators
-    // inside the token loop (the allocator cannot place more than 256 of them) and lose to the LDS-tile kernel.
-    // (bf16 mode runs the same two-window schedule on v_mfma_f32_32x32x16_bf16, see below; windows of 3 measured slower for
-    // BSPLINE and RBF: the basis is re-evaluated per window)
-    // SINE G = 28: windows of 4 basis functions x 4 column tiles.  (Windows of 2 x 6 tiles -- 12 MFMAs per pair of sines instead
-    // of 16 per four, 7.4 -> 4.4 VALU instructions per MFMA -- measured SLOWER, 8.6 -> 13.1 ms: twice the wave units re-read dY.)
+    // column tiles per wave unit and basis windows of the <family, GP> instantiations: KV_REG_BASES (why these: DESIGN.md 4.5a)
     const RegBasis* rb = kv_reg_basis(d);
     if (!rb) return p;
     if (fam == KANVIT_BSPLINE && (d->flags & KANVIT_FLAG_BF16_MFMA) && !kv_config().no_bf16 && kv_config().bs_bw_bf16 == 1) return p;      // A/B: the LDS-tile bf16 kernel
@@ -756,7 +747,6 @@ BwRegPlan plan_bwd_weight_reg(const kanvit_layer_desc* d) {
             long long ld = d->ldx > d->ldy ? d->ldx : d->ldy;
             if (d->ldu > ld) ld = d->ldu;
             if (rps * ld + ld >= (1LL << 29) || units > (1LL << 30)) return BwRegPlan{};
-            p.ws_bytes = p.slabs > 1 ? sizeof(float) * (size_t)p.slabs * d->groups * ((size_t)d->I * p.gp) * d->O : 0;
             p.ok = true;
             return p;
         }
@@ -794,7 +784,6 @@ BwRegPlan plan_bwd_weight_reg(const kanvit_layer_desc* d) {
                 p.dma = 1;
                 p.rows_per_slab = rps;
                 p.slabs = (int)((d->M + rps - 1) / rps);
-                p.ws_bytes = p.slabs > 1 ? sizeof(float) * (size_t)p.slabs * d->groups * ((size_t)d->I * p.gp) * d->O : 0;
                 p.ok = true;
                 return p;
             }
@@ -824,34 +813,8 @@ BwRegPlan plan_bwd_weight_reg(const kanvit_layer_desc* d) {
         if (d->ldu > ld) ld = d->ldu;
         if (rps * ld + ld >= (1LL << 29)) return p;
     }
-    p.ws_bytes = p.slabs > 1 ? sizeof(float) * (size_t)p.slabs * d->groups * ((size_t)d->I * p.gp) * d->O : 0;
     p.ok = true;
     return p;
-}
-
-// (Measured and removed, round 3: an XCD-aware order of the work-groups -- every XCD one contiguous range of the (slab, unit) order, so
-// that waves sharing a dY tile or an x feature block meet in one L2 -- changed no weight-gradient launch by more than the run-to-run
-// noise (ChebyKAN / B-spline / FastKAN / SineKAN G = 28, fp32 and bf16): these kernels wait on their prefetch depth, not on L2 misses.)
-int kv_bwd_weight_reg(int family, LayerArgs& a, const BwRegPlan& p, bool bf, hipStream_t st) {
-    // (rows of x / dY off the 16-byte grid -- a view into the middle of a tensor: the register form runs the same plan, correct and slower)
-    if (p.dma && kv_bwd_weight_dma_aligned(a)) return kv_bwd_weight_dma(family, a, p, bf, st);
-    return dispatch_bwd_weight_reg(family, a, p, bf, st);
-}
-
-// the plans whose kernels exist in the patch-gather form (dispatch_bwd_weight_reg's HAS_PG instantiations): the patch-embedding
-// layers VisionTransformer builds (model.py:67-80: ChebyKAN degree 4, SineKAN / FourierKAN at grid 28)
-bool kv_bwd_weight_reg_pg_ok(const kanvit_layer_desc* d, const BwRegPlan& p) {
-    if (!p.ok || d->groups != 1 || p.bf) return false;      // (bf16 mode keeps the patch matrix: see launch_bwd_weight_reg)
-    // B-splines are NOT among them: their kernels are at the register limit, and the walker's scalar state spilled (19 scalar registers
-    // in the 16-row kernel, 16 vector registers in the 32-row one): 2.97 against 2.80 ms for the ViT-B patch embedding, 1.82 against
-    // 1.13 ms in bf16 mode -- more than the patch-matrix copy costs.  efficient-KAN's patch embedding keeps the transient patch matrix.
-    if (p.t16) return false;
-    switch (d->family) {
-        case KANVIT_CHEBY: return p.gp == 5 && (p.nt == 3 || p.nt == 1);
-        case KANVIT_SINE: return p.gp == 28;
-        case KANVIT_FOURIER: return p.gp == 56;
-        default: return false;
-    }
 }
 
 // dw[e] = sum over the `slabs` partial slabs (each `total` floats), in slab order

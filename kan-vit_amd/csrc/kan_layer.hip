@@ -6,11 +6,11 @@
 //     fwd         Y    = Phi(X) . W
 //     bwd_input   dPhi = dY . W^T, then dX = sum_j dPhi_j * phi_j'(X)
 //     bwd_weight  dW   = Phi(X)^T . dY          (split over row ranges -> slabs -> ordered reduce)
-// Which kernel runs is decided ONCE per call, on the host, by plan_layer_fwd / plan_layer_bwd_input (below; the weight gradient:
-// plan_bwd_weight_reg / plan_bwd_weight): tiny per-head layers (kan_tiny.hip) -> the bf16 forms under KANVIT_FLAG_BF16_MFMA ->
-// the exact register-form kernels (the shapes the reference instantiates on its 224x224 path, KV_REG_BASES) -> the general
-// LDS-tile kernels (every other shape).  Every entry point is: validate, build the arguments, plan, check the workspace against
-// the plan, launch the plan's form.  The workspace queries and kanvit_layer_ln_fusable read the same plans.
+// Which kernel runs is decided ONCE per call, on the host, by plan_layer_fwd / plan_layer_bwd_input / plan_layer_bwd_weight (below):
+// tiny per-head layers (kan_tiny.hip) -> the bf16 forms under KANVIT_FLAG_BF16_MFMA -> the exact register-form kernels (the shapes
+// the reference instantiates on its 224x224 path, KV_REG_BASES) -> the general LDS-tile kernels (every other shape).  Every entry point is: validate, build the arguments, plan, check the workspace against
+// the plan, launch the plan's form.  The workspace queries, kanvit_layer_ln_fusable, kanvit_layer_sine_dfreq_ok and
+// kanvit_patch_embed_bwd_weight_ok read the same plans.
 #include "kan_layer_common.h"
 
 extern "C" int kanvit_layer_ln_fusable(const kanvit_layer_desc* d);
@@ -375,6 +375,63 @@ LayerBwdInputPlan plan_layer_bwd_input(const kanvit_layer_desc* d, const LayerAl
     return p;
 }
 
+static const char* const KV_PATCH_BWW_UNCOVERED =
+    "kanvit_patch_embed_bwd_weight: layer / geometry not covered by the gathering weight-gradient kernels "
+    "(kanvit_patch_embed_bwd_weight_ok); use patchify + kanvit_layer_bwd_weight";
+
+// pd != nullptr: the patch embedding's gather (REG_PATCH or nothing).  Of the operands only the alignment of x and dy counts.
+LayerBwdWeightPlan plan_layer_bwd_weight(const kanvit_layer_desc* d, const kanvit_patch_desc* pd, const LayerAlign& al) {
+    LayerBwdWeightPlan p{};
+    p.total = (long long)d->groups * d->I * gp_of(d) * d->O;
+    auto slabs = [&p](int ws_slabs, int n, long long rows) {      // the partial slabs are the only workspace of every form
+        p.slabs = n;
+        p.rows_per_slab = rows;
+        p.ws_bytes = ws_slabs > 1 ? sizeof(float) * (size_t)ws_slabs * (size_t)p.total : 0;
+    };
+    if (kv_tiny_ok(d)) {              // tiny per-head layers (I, O <= 16): csrc/kan_tiny.hip
+        if (pd) return plan_none(p, KV_PATCH_BWW_UNCOVERED);
+        // 128 rows (two staged chunks) per slab, at most 64 slabs: the chunks of a work-group run back to back behind a global-load latency
+        // each, so few chunks per group beats few partials.  The rows are rounded to the kernel's 64-row chunks, which can lower the slab
+        // count (M = 129: two slabs become one); the workspace stays what the query has always answered, the count BEFORE the rounding
+        const int s = (int)((d->M + 127) / 128 < 64 ? (d->M + 127) / 128 : 64);      // >= 1: kv_tiny_ok has M >= 64
+        const long long rows = ((d->M + s - 1) / s + 63) / 64 * 64;
+        slabs(s, (int)((d->M + rows - 1) / rows), rows);
+        p.form = LAYER_BWW_TINY;
+        return p;
+    }
+    p.r = plan_bwd_weight_reg(d);
+    if (p.r.ok) {                     // the register kernels (kan_bwd_weight_reg.hip, kan_bwd_weight_dma.hip)
+        slabs(p.r.slabs, p.r.slabs, p.r.rows_per_slab);
+        p.bf = p.r.bf;
+        if (pd) {                     // exact fp32, one layer, a table row with the gather instantiation
+            if (d->groups != 1 || p.r.bf || p.r.t16 || !kv_reg_basis(d)->bww_pg) return plan_none(p, KV_PATCH_BWW_UNCOVERED);
+            p.form = LAYER_BWW_REG_PATCH;
+        } else if (p.r.t16) {
+            p.form = LAYER_BWW_REG16;
+        } else {
+            // DMA moves 16-byte pieces: the rows of x and dY must start on 16-byte boundaries (the strides and widths are multiples of
+            // four floats in every DMA-sized plan).  Rows off that grid -- a view into the middle of a tensor -- run the register ring
+            // under the SAME slab sizing: correct and slower, and the workspace does not depend on the pointers
+            p.form = (p.r.dma && !((al.x | al.dy) & 15)) ? LAYER_BWW_DMA : LAYER_BWW_REG;
+        }
+        return p;
+    }
+    if (pd) return plan_none(p, KV_PATCH_BWW_UNCOVERED);
+    // general LDS-tile kernel (kan_tile.hip), exact or with the bf16 contraction
+    p.t = plan_bwd_weight(d);
+    slabs(p.t.msplit, p.t.msplit, p.t.rows_per_split);
+    p.bf = ((d->flags & KANVIT_FLAG_BF16_MFMA) && !kv_config().no_bf16) ? 1 : 0;
+    if (is_ln(d)) return plan_none(p, "kanvit_layer_bwd_weight: KANVIT_FLAG_FUSED_LN needs the register kernel (shape)");
+    if ((long long)BW_ROWS * d->ldy >= (1LL << 30)) return plan_none(p, "kanvit_layer_bwd_weight: ldy too large for 32-bit tile offsets");
+    // (plan_bwd_weight's chunk keeps the MFMA tiles of a wave within its accumulators: KC <= 160 with three projections, <= 288 with one)
+    const int kt = (p.t.ic * gp_of(d) + 31) / 32;
+    p.lds = sizeof(float) * 2 * ((size_t)BW_ROWS * (p.t.ic | 1) * (d->family == KANVIT_RBF ? 2 : 1) + (size_t)BW_ROWS * 32 * BW_NT * p.t.nsh +
+                                 (size_t)kt * 32 * BW_AS);
+    if (p.lds > 160 * 1024) return plan_none(p, "kanvit_layer_bwd_weight: tile does not fit the LDS");
+    p.form = p.bf ? LAYER_BWW_TILE_BF16 : LAYER_BWW_TILE;
+    return p;
+}
+
 static KvTinyArgs tiny_args(const kanvit_layer_desc* d) {
     KvTinyArgs t{};
     t.M = d->M; t.ldx = d->ldx; t.ldy = d->ldy; t.bp_stride = d->bparam_stride;
@@ -517,7 +574,7 @@ int kanvit_layer_ln_fusable(const kanvit_layer_desc* d) {
     if (plan_layer_fwd(&e, nullptr, LayerAlign{}).form != (bf ? LAYER_FWD_REG_BF16 : LAYER_FWD_REG)) return 0;
     const LayerBwdInputForm bi = plan_layer_bwd_input(&e, LayerAlign{}).form;
     if (bi != LAYER_BWI_REG && bi != LAYER_BWI_REG_BF16 && bi != LAYER_BWI_REG_BF16_WIDE && bi != LAYER_BWI_RES_BF16) return 0;
-    return plan_bwd_weight_reg(&e).ok ? 1 : 0;
+    return plan_layer_bwd_weight(&e, nullptr, LayerAlign{}).r.ok ? 1 : 0;
 }
 
 // ---- fused patch embedding (model.py:111-126 patchify, :144-152 class token + position embedding) ----
@@ -580,22 +637,54 @@ int kanvit_patch_embed_fwd(const kanvit_layer_desc* d, const kanvit_patch_desc* 
 
 // Weight gradient of the patch-embedding layer with the same gather: x rows from the NCHW images, dY rows from the token-sequence
 // gradient [B][P + prepend_rows][ldy] (the class-token rows are stepped over) -- no transient patch matrix, no dY copy.
-int kanvit_patch_embed_bwd_weight_ok(const kanvit_layer_desc* d, const kanvit_patch_desc* p) {
-    if (!desc_ok(d) || !p || d->groups != 1 || d->x_group_mod != 1 || d->M < 1) return 0;
-    if (p->C < 1 || p->H < 1 || p->W < 1 || p->n_patches < 1 || p->H % p->n_patches || p->W % p->n_patches) return 0;
-    if (p->prepend_rows != 0 && p->prepend_rows != 1) return 0;
+static bool patch_bwd_weight_geometry_ok(const kanvit_layer_desc* d, const kanvit_patch_desc* p) {
+    if (!desc_ok(d) || !p || d->groups != 1 || d->x_group_mod != 1 || d->M < 1) return false;
+    if (p->C < 1 || p->H < 1 || p->W < 1 || p->n_patches < 1 || p->H % p->n_patches || p->W % p->n_patches) return false;
+    if (p->prepend_rows != 0 && p->prepend_rows != 1) return false;
     const long long P = (long long)p->n_patches * p->n_patches;
-    if (d->I != (long long)p->C * (p->H / p->n_patches) * (p->W / p->n_patches) || d->M % P) return 0;
+    if (d->I != (long long)p->C * (p->H / p->n_patches) * (p->W / p->n_patches) || d->M % P) return false;
     const long long B = d->M / P;
     // 32-bit element offsets from the image base / the dY base
-    if (B * p->C * p->H * p->W >= (1LL << 31) || (d->M + B * p->prepend_rows + 1) * d->ldy >= (1LL << 31)) return 0;
-    if (d->family == KANVIT_RBF || kv_tiny_ok(d)) return 0;
-    return kv_bwd_weight_reg_pg_ok(d, plan_bwd_weight_reg(d)) ? 1 : 0;
+    return B * p->C * p->H * p->W < (1LL << 31) && (d->M + B * p->prepend_rows + 1) * d->ldy < (1LL << 31);
+}
+
+int kanvit_patch_embed_bwd_weight_ok(const kanvit_layer_desc* d, const kanvit_patch_desc* p) {
+    return patch_bwd_weight_geometry_ok(d, p) && plan_layer_bwd_weight(d, p, LayerAlign{}).form == LAYER_BWW_REG_PATCH;
 }
 
 size_t kanvit_patch_embed_bwd_weight_workspace(const kanvit_layer_desc* d, const kanvit_patch_desc* p) {
-    if (!kanvit_patch_embed_bwd_weight_ok(d, p)) return 0;
-    return plan_bwd_weight_reg(d).ws_bytes;
+    if (!patch_bwd_weight_geometry_ok(d, p)) return 0;
+    const LayerBwdWeightPlan pl = plan_layer_bwd_weight(d, p, LayerAlign{});
+    return pl.form == LAYER_BWW_REG_PATCH ? pl.ws_bytes : 0;
+}
+
+// the forms both weight-gradient entry points launch, and the ordered sum of the partial slabs behind them
+static int launch_layer_bwd_weight(const kanvit_layer_desc* d, LayerArgs& a, const LayerBwdWeightPlan& p, float* dw, void* workspace,
+                                   hipStream_t st) {
+    if (p.form == LAYER_BWW_NONE) return kv_fail(KANVIT_EINVAL, p.why, p.why_a, p.why_b);
+    a.rows_per_split = p.rows_per_slab;
+    a.msplit = p.slabs;
+    a.slab = p.slabs > 1 ? (float*)workspace : dw;
+    int rc;
+    switch (p.form) {
+        case LAYER_BWW_TINY: {
+            KvTinyArgs t = tiny_args(d);
+            t.x = a.x; t.bp = a.bp; t.dy = a.dy;
+            t.slabs = p.slabs; t.rows_per_slab = p.rows_per_slab; t.slab = a.slab;
+            rc = kv_tiny_bwd_weight(t, st);
+            break;
+        }
+        case LAYER_BWW_DMA: rc = kv_bwd_weight_dma(a, p, st); break;
+        case LAYER_BWW_REG16:
+        case LAYER_BWW_REG:
+        case LAYER_BWW_REG_PATCH: rc = kv_bwd_weight_reg(d->family, a, p, st); break;
+        default:
+            a.IC = p.t.ic;
+            a.nchunks_n = p.t.nchunks_n;
+            rc = kv_tile_bwd_weight(d->family, a, p, st);
+    }
+    if (rc || p.slabs <= 1) return rc;
+    return kv_slab_reduce((const float*)workspace, dw, p.total, p.slabs, st);
 }
 
 int kanvit_patch_embed_bwd_weight(const kanvit_layer_desc* d, const kanvit_patch_desc* p, const float* images, const float* bparams,
@@ -609,33 +698,24 @@ int kanvit_patch_embed_bwd_weight(const kanvit_layer_desc* d, const kanvit_patch
     }
     if (!images || !dy) return kv_fail(KANVIT_EINVAL, "kanvit_patch_embed_bwd_weight: null images/dy");
     if (needs_bparams(d->family) && !bparams) return kv_fail(KANVIT_EINVAL, "kanvit_patch_embed_bwd_weight: family %d needs bparams", d->family);
-    if ((d->flags & KANVIT_FLAG_SINE_DFREQ) && !kanvit_layer_sine_dfreq_ok(d))     // as kanvit_layer_bwd_weight: never hand plain dW back as Q
+    const LayerBwdWeightPlan pl = plan_layer_bwd_weight(d, p, layer_align(images, nullptr, nullptr, nullptr, nullptr, nullptr, dy, nullptr, nullptr));
+    if ((d->flags & KANVIT_FLAG_SINE_DFREQ) && !pl.r.ok)     // as kanvit_layer_bwd_weight: never hand plain dW back as Q
         return kv_fail(KANVIT_EINVAL, "kanvit_patch_embed_bwd_weight: KANVIT_FLAG_SINE_DFREQ is not available for this layer (kanvit_layer_sine_dfreq_ok)");
-    if (!kanvit_patch_embed_bwd_weight_ok(d, p))
-        return kv_fail(KANVIT_EINVAL, "kanvit_patch_embed_bwd_weight: layer / geometry not covered by the gathering weight-gradient kernels "
-                                      "(kanvit_patch_embed_bwd_weight_ok); use patchify + kanvit_layer_bwd_weight");
-    const BwRegPlan pr = plan_bwd_weight_reg(d);
-    if (pr.ws_bytes > 0 && (!workspace || workspace_bytes < pr.ws_bytes))
-        return kv_fail(KANVIT_ENOMEM, "kanvit_patch_embed_bwd_weight: workspace %zu bytes < required %zu", workspace_bytes, pr.ws_bytes);
+    if (!patch_bwd_weight_geometry_ok(d, p) || pl.form != LAYER_BWW_REG_PATCH) return kv_fail(KANVIT_EINVAL, KV_PATCH_BWW_UNCOVERED);
+    if (pl.ws_bytes > 0 && (!workspace || workspace_bytes < pl.ws_bytes))
+        return kv_fail(KANVIT_ENOMEM, "kanvit_patch_embed_bwd_weight: workspace %zu bytes < required %zu", workspace_bytes, pl.ws_bytes);
     LayerArgs a = base_args(d);
     a.x = images;
     a.bp = bparams;
     a.dy = dy;
     patch_args(a, p, nullptr, nullptr);
-    hipStream_t st = (hipStream_t)stream;
-    const bool bf = pr.bf != 0;
-    a.rows_per_split = pr.rows_per_slab;
-    a.msplit = pr.slabs;
-    a.slab = (pr.slabs > 1) ? (float*)workspace : dw;
-    if (int rc = kv_bwd_weight_reg(d->family, a, pr, bf, st)) return rc;
-    if (pr.slabs > 1) return kv_slab_reduce((const float*)workspace, dw, (long long)a.K * d->O, pr.slabs, st);
-    return 0;
+    return launch_layer_bwd_weight(d, a, pl, dw, workspace, (hipStream_t)stream);
 }
 
+// 1 when a register weight-gradient kernel covers the layer: the forms that have the x * cos twin (KV_SINE_DF)
 int kanvit_layer_sine_dfreq_ok(const kanvit_layer_desc* d) {
     if (!desc_ok(d) || d->family != KANVIT_SINE || d->M < 1) return 0;
-    if (kv_tiny_ok(d)) return 0;
-    return plan_bwd_weight_reg(d).ok ? 1 : 0;
+    return plan_layer_bwd_weight(d, nullptr, LayerAlign{}).r.ok ? 1 : 0;
 }
 
 int64_t kanvit_layer_dparam_tiles(const kanvit_layer_desc* d) {
@@ -703,15 +783,7 @@ int kanvit_layer_bwd_input(const kanvit_layer_desc* d, const float* x, const flo
 
 size_t kanvit_layer_bwd_weight_workspace(const kanvit_layer_desc* d) {
     if (!desc_ok(d)) return 0;
-    if (kv_tiny_ok(d)) {
-        const int s = kv_tiny_slabs(d);
-        return s > 1 ? sizeof(float) * (size_t)s * d->groups * ((size_t)d->I * gp_of(d)) * d->O : 0;
-    }
-    const BwRegPlan pr = plan_bwd_weight_reg(d);
-    if (pr.ok) return pr.ws_bytes;
-    const BwPlan p = plan_bwd_weight(d);
-    if (p.msplit <= 1) return 0;
-    return sizeof(float) * (size_t)p.msplit * d->groups * ((size_t)d->I * gp_of(d)) * d->O;
+    return plan_layer_bwd_weight(d, nullptr, LayerAlign{}).ws_bytes;
 }
 
 int kanvit_layer_bwd_weight(const kanvit_layer_desc* d, const float* x, const float* u, const float* bparams,
@@ -726,24 +798,11 @@ int kanvit_layer_bwd_weight(const kanvit_layer_desc* d, const float* x, const fl
     if (needs_bparams(d->family) && !bparams) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: family %d needs bparams", d->family);
     if (d->family == KANVIT_RBF && u && d->ldu < (int64_t)d->groups * d->I)
         return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: ldu < groups*I");
-    const size_t need = kanvit_layer_bwd_weight_workspace(d);
-    if (need > 0 && (!workspace || workspace_bytes < need))
-        return kv_fail(KANVIT_ENOMEM, "kanvit_layer_bwd_weight: workspace %zu bytes < required %zu", workspace_bytes, need);
-    if ((d->flags & KANVIT_FLAG_SINE_DFREQ) && !kanvit_layer_sine_dfreq_ok(d))
+    const LayerBwdWeightPlan p = plan_layer_bwd_weight(d, nullptr, layer_align(x, u, nullptr, bparams, nullptr, nullptr, dy, nullptr, nullptr));
+    if (p.ws_bytes > 0 && (!workspace || workspace_bytes < p.ws_bytes))
+        return kv_fail(KANVIT_ENOMEM, "kanvit_layer_bwd_weight: workspace %zu bytes < required %zu", workspace_bytes, p.ws_bytes);
+    if ((d->flags & KANVIT_FLAG_SINE_DFREQ) && !p.r.ok)
         return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: KANVIT_FLAG_SINE_DFREQ needs the register weight-gradient kernel (shape)");
-    if (kv_tiny_ok(d)) {
-        hipStream_t st = (hipStream_t)stream;
-        KvTinyArgs t = tiny_args(d);
-        t.x = x; t.bp = bparams; t.dy = dy;
-        t.slabs = kv_tiny_slabs(d);
-        t.rows_per_slab = ((d->M + t.slabs - 1) / t.slabs + 63) / 64 * 64;
-        t.slabs = (int)((d->M + t.rows_per_slab - 1) / t.rows_per_slab);
-        t.slab = t.slabs > 1 ? (float*)workspace : dw;
-        if (int rc = kv_tiny_bwd_weight(t, st)) return rc;
-        if (t.slabs > 1) return kv_slab_reduce((const float*)workspace, dw, (long long)d->groups * t.K * d->O, t.slabs, st);
-        return 0;
-    }
-    const BwPlan p = plan_bwd_weight(d);
     LayerArgs a = base_args(d);
     a.x = x;
     a.u = u;
@@ -754,31 +813,7 @@ int kanvit_layer_bwd_weight(const kanvit_layer_desc* d, const float* x, const fl
         a.stats = const_cast<float*>(u);
         a.u = nullptr;
     }
-    {
-        const BwRegPlan pr = plan_bwd_weight_reg(d);
-        if (!pr.ok && a.ln) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: KANVIT_FLAG_FUSED_LN needs the register kernel (shape)");
-        if (pr.ok) {
-            hipStream_t st = (hipStream_t)stream;
-            const bool bf = pr.bf != 0;
-            a.rows_per_split = pr.rows_per_slab;
-            a.msplit = pr.slabs;
-            a.slab = (pr.slabs > 1) ? (float*)workspace : dw;
-            if (int rc = kv_bwd_weight_reg(d->family, a, pr, bf, st)) return rc;
-            if (pr.slabs > 1) return kv_slab_reduce((const float*)workspace, dw, (long long)d->groups * a.K * d->O, pr.slabs, st);
-            return 0;
-        }
-    }
-    a.IC = p.ic;
-    a.msplit = p.msplit;
-    a.nchunks_n = p.nchunks_n;
-    a.rows_per_split = p.rows_per_split;
-    a.slab = (p.msplit > 1) ? (float*)workspace : dw;
-    hipStream_t st = (hipStream_t)stream;
-    const bool bf = (d->flags & KANVIT_FLAG_BF16_MFMA) && !kv_config().no_bf16;
-    const int rc = kv_tile_bwd_weight(d->family, a, p, bf, st);
-    if (rc) return rc;
-    if (p.msplit > 1) return kv_slab_reduce((const float*)workspace, dw, (long long)d->groups * a.K * d->O, p.msplit, st);
-    return 0;
+    return launch_layer_bwd_weight(d, a, p, dw, workspace, (hipStream_t)stream);
 }
 
 // ---- per-family named entry points ---------------------------------------------------------------

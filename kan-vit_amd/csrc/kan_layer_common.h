@@ -1,13 +1,15 @@
 // Internal header of the fused KAN layer kernels (csrc/kan_*.hip): launch arguments, tile constants, the plan structs the
 // host entry points (kan_layer.hip) share with the kernel translation units, and the functions that cross between them.
 // One translation unit per kernel generation keeps a rebuild at the size of the kernel that changed:
-//     kan_layer.hip               C ABI entry points, validation, run-time switches, plan_layer_fwd / plan_layer_bwd_input
+//     kan_layer.hip               C ABI entry points, validation, run-time switches, plan_layer_fwd / _bwd_input / _bwd_weight
 //     kan_tile.hip                general LDS-tile producer/consumer kernels (every shape; fp32 and bf16 contraction)
 //     kan_fwd_reg.hip             register-form forward (fp32 exact; also the fused patch embedding)
 //     kan_fwd_reg_bf16.hip        register-form and W-stationary forward on the bf16 matrix cores
 //     kan_bwd_input_reg.hip       register-form input gradient (fp32 exact)
 //     kan_bwd_input_reg_bf16.hip  register-form input gradient on the bf16 matrix cores
 //     kan_bwd_weight_reg.hip      streaming register-form weight gradient + the ordered slab reduction
+//     kan_bwd_weight_dma.hip      the same wave unit fed through an LDS-DMA ring (ChebyKAN, three column tiles per wave)
+//     kan_tiny.hip                tiny per-head layers on the vector pipe (all three operations)
 #pragma once
 #include "kan_basis.h"
 
@@ -213,7 +215,8 @@ inline bool kv_share_ok(int family, int flags) {
 //   * the fp32 forward takes ANY basis size through its run-time-GP loop (GPC = 0); fwd_gpc only names the pipelined twins;
 //   * the bf16 forward and both input gradients exist for the listed sizes only, and the bf16 input gradient has neither
 //     SINE GP = 5 (the layer's default grid; attention.py:140 builds 4) nor FOURIER;
-//   * the weight gradient reads nt / njc (plan_bwd_weight_reg).
+//   * the weight gradient reads nt / njc (plan_bwd_weight_reg; DESIGN.md 4.5a says why these), and bww_pg names the rows whose
+//     32-row kernel is also instantiated in its patch-gather form (kv_bwd_weight_reg).
 // kan_tiny.hip keeps its own list: a different kernel family (run-time basis size on the vector pipe).
 struct RegBasis {
     int family, gp;
@@ -221,16 +224,17 @@ struct RegBasis {
     int fwd_bf16_ich;           // bf16 forward <GP, .., ICH>: features per lane half and chunk, 0 = no kernel
     int bwi_kt, bwi_bf16_kt;    // input gradient <GP, KT>: exact fp32 / bf16 matrix cores, 0 = no kernel
     int bww_nt, bww_njc;        // weight gradient: column tiles per wave unit, basis windows
+    int bww_pg;                 // weight gradient: 1 = the patch-gather instantiation exists
 };
 constexpr RegBasis KV_REG_BASES[] = {
-    {KANVIT_LINEAR, 1, {1, 0, 0}, 8, 2, 2, 6, 1},
-    {KANVIT_CHEBY, 5, {5, 0, 0}, 8, 5, 5, 3, 1},
-    {KANVIT_BSPLINE, 9, {9, 9, 0}, 8, 5, 5, 3, 2},      // 8 uniform cubic bases + the base column; ICH = 2: eight features x 9 rows x three projections overflow the W staging registers
-    {KANVIT_RBF, 9, {9, 9, 0}, 8, 5, 5, 2, 1},          // FastKAN's 8 centres + the base column
-    {KANVIT_SINE, 4, {4, 0, 0}, 8, 4, 4, 2, 1},         // the per-head mappings (attention.py:140)
-    {KANVIT_SINE, 5, {0, 0, 0}, 0, 5, 0, 2, 1},         // the layer's default grid
-    {KANVIT_SINE, 28, {0, 0, 28}, 1, 7, 7, 4, 7},       // the G = 28 patch embedding (model.py:72)
-    {KANVIT_FOURIER, 56, {0, 0, 56}, 1, 7, 0, 4, 14},
+    {KANVIT_LINEAR, 1, {1, 0, 0}, 8, 2, 2, 6, 1, 0},
+    {KANVIT_CHEBY, 5, {5, 0, 0}, 8, 5, 5, 3, 1, 1},
+    {KANVIT_BSPLINE, 9, {9, 9, 0}, 8, 5, 5, 3, 2, 0},      // 8 uniform cubic bases + the base column; ICH = 2: eight features x 9 rows x three projections overflow the W staging registers
+    {KANVIT_RBF, 9, {9, 9, 0}, 8, 5, 5, 2, 1, 0},          // FastKAN's 8 centres + the base column
+    {KANVIT_SINE, 4, {4, 0, 0}, 8, 4, 4, 2, 1, 0},         // the per-head mappings (attention.py:140)
+    {KANVIT_SINE, 5, {0, 0, 0}, 0, 5, 0, 2, 1, 0},         // the layer's default grid
+    {KANVIT_SINE, 28, {0, 0, 28}, 1, 7, 7, 4, 7, 1},       // the G = 28 patch embedding (model.py:72)
+    {KANVIT_FOURIER, 56, {0, 0, 56}, 1, 7, 0, 4, 14, 1},
 };
 
 // the families the register kernels evaluate at all: B-splines on uniform cubic knots, FastKAN's own grid (kv_rbf_reg_ok), every parameter-free one
@@ -250,6 +254,13 @@ inline const RegBasis* kv_reg_basis(int family, int gp, int has_base, int flags,
 }
 inline const RegBasis* kv_reg_basis(const kanvit_layer_desc* d) {
     return kv_reg_basis(d->family, gp_of(d), d->has_base, d->flags, d->spline_order, d->G);
+}
+
+// the weight-gradient instantiations <FAM, GP> that also exist in the patch-gather form (KV_SINE_DF is SINE's twin)
+constexpr bool kv_bww_pg(int fam, int gp) {
+    for (const RegBasis& r : KV_REG_BASES)
+        if (r.family == (fam == KV_SINE_DF ? KV_SINE : fam) && r.gp == gp) return r.bww_pg != 0;
+    return false;
 }
 
 // accumulators the fp32 register input gradient contracts: CHEBY leaves the T0 slots out (dT0/dx = 0), see kan_bwd_input_reg.hip
@@ -276,28 +287,32 @@ struct BwdRegBf16Plan {
     size_t lds, ws_bytes;
 };
 
+// shape side of the LDS-tile weight gradient (kan_tile.hip): feature chunk, grid, row split
 struct BwPlan {
     int ic, nfchunks, nchunks_n, msplit, nsh;
     long long rows_per_split;
 };
 
+// shape side of the register weight gradients (kan_bwd_weight_reg.hip, kan_bwd_weight_dma.hip): the wave-unit geometry
 struct BwRegPlan {
     bool ok;
     int gp, nt, nfb, nos, tiles_per_bg, nbg, shared, slabs, njc;
     int t16;              // 1: the 16-row-tile kernel (nt = 16-column tiles per wave, nfb = 16-feature blocks)
     int bf;               // 1: the planned kernel contracts on the bf16 matrix cores (KANVIT_FLAG_BF16_MFMA allows it; the exact kernels ignore it)
-    int dma;              // 1: the LDS-DMA form (kan_bwd_weight_dma.hip): a work-group = four row ranges of one wave unit, slabs counts WORK-GROUP slabs
+    int dma;              // 1: sized for the LDS-DMA form (a work-group = four row ranges of one wave unit, slabs counts WORK-GROUP slabs)
     long long rows_per_slab;
-    size_t ws_bytes;
 };
 
-// ---- the plan of a forward / input-gradient call (kan_layer.hip: plan_layer_fwd, plan_layer_bwd_input) ----------------
-// Pure functions of the descriptor, kv_config() and the alignment of the operands: the workspace queries, kanvit_layer_ln_fusable
-// and the launchers read the same plan, and the launchers below cannot refuse (DESIGN.md section 4.5a, table of forms).
+// ---- the plan of a forward / input-gradient / weight-gradient call (kan_layer.hip: plan_layer_fwd, plan_layer_bwd_input, -------
+// plan_layer_bwd_weight).  Pure functions of the descriptor, kv_config() and the alignment of the operands: the workspace queries,
+// kanvit_layer_ln_fusable, kanvit_layer_sine_dfreq_ok, kanvit_patch_embed_bwd_weight_ok and the launchers read the same plan, and the
+// launchers below cannot refuse (DESIGN.md section 4.5a, tables of forms).
 enum LayerFwdForm { LAYER_FWD_NONE, LAYER_FWD_TINY, LAYER_FWD_WS_BF16, LAYER_FWD_REG_BF16, LAYER_FWD_REG_BF16_PATCH, LAYER_FWD_TILE_BF16,
                     LAYER_FWD_REG, LAYER_FWD_TILE };
 enum LayerBwdInputForm { LAYER_BWI_NONE, LAYER_BWI_TINY, LAYER_BWI_RES_BF16, LAYER_BWI_REG_BF16, LAYER_BWI_REG_BF16_WIDE, LAYER_BWI_TILE_BF16,
                          LAYER_BWI_REG, LAYER_BWI_TILE };
+enum LayerBwdWeightForm { LAYER_BWW_NONE, LAYER_BWW_TINY, LAYER_BWW_DMA, LAYER_BWW_REG16, LAYER_BWW_REG, LAYER_BWW_REG_PATCH, LAYER_BWW_TILE,
+                          LAYER_BWW_TILE_BF16 };
 
 // The operand pointers whose alignment the plans look at (null pointers as 0; all 0 = aligned, the workspace queries' case)
 struct LayerAlign {
@@ -338,8 +353,23 @@ struct LayerBwdInputPlan {
     BwdRegBf16Plan rb;    // RES_BF16, REG_BF16, REG_BF16_WIDE
 };
 
+struct LayerBwdWeightPlan {
+    LayerBwdWeightForm form;
+    const char* why;
+    int why_a, why_b;
+    int bf;               // the form contracts on the bf16 matrix cores (DMA, REG, TILE_BF16)
+    int slabs;            // row ranges whose partial dW go to the workspace and are summed in order (1: the kernel writes dw itself)
+    long long rows_per_slab;
+    long long total;      // floats of one slab: groups * K * O
+    size_t lds;           // TILE forms: dynamic LDS bytes
+    size_t ws_bytes;      // kanvit_layer_bwd_weight_workspace / kanvit_patch_embed_bwd_weight_workspace
+    BwRegPlan r;          // r.ok: a register kernel covers the shape (DMA, REG16, REG, REG_PATCH run it; the patch entry may still refuse)
+    BwPlan t;             // TILE, TILE_BF16
+};
+
 LayerFwdPlan plan_layer_fwd(const kanvit_layer_desc* d, const kanvit_patch_desc* pd, const LayerAlign& al);
 LayerBwdInputPlan plan_layer_bwd_input(const kanvit_layer_desc* d, const LayerAlign& al);
+LayerBwdWeightPlan plan_layer_bwd_weight(const kanvit_layer_desc* d, const kanvit_patch_desc* pd, const LayerAlign& al);
 
 // LDS bytes of the LDS-tile kernels (kan_tile.hip) for a feature chunk of ic
 inline size_t kv_tile_fwd_lds(int family, int ic, int gp, int nt, int nsh) {
@@ -380,12 +410,10 @@ int kv_tile_bwd_input(int family, LayerArgs& a, const LayerBwdInputPlan& p, hipS
 FwdRegBf16Plan plan_fwd_reg_bf16(const kanvit_layer_desc* d);
 FwdBf16Plan plan_fwd_bf16(const kanvit_layer_desc* d);
 BwdRegBf16Plan plan_bwd_input_reg_bf16(const kanvit_layer_desc* d);
-// ---- weight gradient ----
-BwPlan plan_bwd_weight(const kanvit_layer_desc* d);
-int kv_tile_bwd_weight(int family, const LayerArgs& a, const BwPlan& p, bool bf, hipStream_t st);
-BwRegPlan plan_bwd_weight_reg(const kanvit_layer_desc* d);
-int kv_bwd_weight_reg(int family, LayerArgs& a, const BwRegPlan& p, bool bf, hipStream_t st);
+// ---- weight gradient: the shape-side pieces (members r / t of the layer plan) and the launchers of its forms ----
+BwPlan plan_bwd_weight(const kanvit_layer_desc* d);                                                       // kan_tile.hip
+BwRegPlan plan_bwd_weight_reg(const kanvit_layer_desc* d);                                                // kan_bwd_weight_reg.hip
+int kv_tile_bwd_weight(int family, const LayerArgs& a, const LayerBwdWeightPlan& p, hipStream_t st);      // TILE, TILE_BF16
+int kv_bwd_weight_reg(int family, LayerArgs& a, const LayerBwdWeightPlan& p, hipStream_t st);             // REG16, REG, REG_PATCH
+int kv_bwd_weight_dma(LayerArgs& a, const LayerBwdWeightPlan& p, hipStream_t st);                         // DMA; kan_bwd_weight_dma.hip
 int kv_slab_reduce(const float* slab, float* dw, long long total, int slabs, hipStream_t st);
-bool kv_bwd_weight_reg_pg_ok(const kanvit_layer_desc* d, const BwRegPlan& p);      // the plan's kernel exists in the patch-gather form
-int kv_bwd_weight_dma(int family, LayerArgs& a, const BwRegPlan& p, bool bf, hipStream_t st);      // kan_bwd_weight_dma.hip
-bool kv_bwd_weight_dma_aligned(const LayerArgs& a);

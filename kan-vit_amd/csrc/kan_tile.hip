@@ -1197,26 +1197,18 @@ int tile_bwd_input(LayerArgs& a, const LayerBwdInputPlan& p, hipStream_t st) {
 }
 
 template <int FAM, int NSH, bool BF>
-int launch_bwd_weight_n(const LayerArgs& a, const BwPlan& p, hipStream_t st) {
-    const int ICP = a.IC | 1;
-    const int KT = (a.IC * a.GP + 31) / 32;
-    const size_t lds = sizeof(float) * 2 * ((size_t)BW_ROWS * ICP * (FAM == KV_RBF ? 2 : 1) + (size_t)BW_ROWS * 32 * BW_NT * NSH +
-                                            (size_t)KT * 32 * BW_AS);
-    if (lds > 160 * 1024) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: tile does not fit the LDS");
-    if (KT * BW_NT * NSH > 4 * ((NSH == 1) ? BW_TPW : 8))
-        return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: internal tiling error");
+int launch_bwd_weight_n(const LayerArgs& a, const LayerBwdWeightPlan& p, hipStream_t st) {
     KV_ACT_ALLOW_LDS(FAM, a.base_act, 160 * 1024, kan_bwd_weight_kernel, kan_bwd_weight_act_kernel, (FAM, NSH, BF));
-    dim3 grid((unsigned)p.nfchunks, (unsigned)p.msplit, (unsigned)((a.groups / NSH) * p.nchunks_n));
-    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_weight_kernel, kan_bwd_weight_act_kernel, (FAM, NSH, BF), grid, dim3(NTHR), lds, st, a);
+    dim3 grid((unsigned)p.t.nfchunks, (unsigned)p.slabs, (unsigned)((a.groups / NSH) * p.t.nchunks_n));
+    KV_ACT_LAUNCH(FAM, a.base_act, kan_bwd_weight_kernel, kan_bwd_weight_act_kernel, (FAM, NSH, BF), grid, dim3(NTHR), p.lds, st, a);
     KV_LAUNCH_CHECK("kan_bwd_weight_kernel");
     return 0;
 }
 
 template <int FAM>
-int launch_bwd_weight(const LayerArgs& a, const BwPlan& p, bool bf, hipStream_t st) {
-    if ((long long)BW_ROWS * a.ldy >= (1LL << 30))
-        return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: ldy too large for 32-bit tile offsets");
-    if (p.nsh == 3) {
+int launch_bwd_weight(const LayerArgs& a, const LayerBwdWeightPlan& p, hipStream_t st) {
+    const bool bf = p.form == LAYER_BWW_TILE_BF16;
+    if (p.t.nsh == 3) {
         if constexpr (kv_shared_basis<FAM>())
             return bf ? launch_bwd_weight_n<FAM, 3, true>(a, p, st) : launch_bwd_weight_n<FAM, 3, false>(a, p, st);
     }
@@ -1298,8 +1290,8 @@ int kv_tile_bwd_input(int family, LayerArgs& a, const LayerBwdInputPlan& p, hipS
     KV_FAMILY_SWITCH(family, KV_CALL)
 #undef KV_CALL
 }
-int kv_tile_bwd_weight(int family, const LayerArgs& a, const BwPlan& p, bool bf, hipStream_t st) {
-#define KV_CALL(F) launch_bwd_weight<F>(a, p, bf, st)
+int kv_tile_bwd_weight(int family, const LayerArgs& a, const LayerBwdWeightPlan& p, hipStream_t st) {
+#define KV_CALL(F) launch_bwd_weight<F>(a, p, st)
     KV_FAMILY_SWITCH(family, KV_CALL)
 #undef KV_CALL
 }

@@ -226,13 +226,6 @@ bool kv_tiny_ok(const kanvit_layer_desc* d) {
     return d->M >= 64;                               // fewer rows: the general kernels' single tile is as good
 }
 
-int kv_tiny_slabs(const kanvit_layer_desc* d) {
-    long long s = (d->M + 127) / 128;             // 128 rows (two staged chunks) per slab: the chunks of a work-group run back to back
-    if (s > 64) s = 64;                            // behind a global-load latency each, so few chunks per group beats few partials
-    if (s < 1) s = 1;
-    return (int)s;
-}
-
 int kv_tiny_fwd(const KvTinyArgs& a, hipStream_t st) {
     const dim3 grid((unsigned)((a.M + 255) / 256), (unsigned)a.groups);
     return tiny_family(a.family, [&](auto fam) {

@@ -115,7 +115,6 @@ struct KvTinyArgs {
     int base_act;
 };
 bool kv_tiny_ok(const kanvit_layer_desc* d);
-int kv_tiny_slabs(const kanvit_layer_desc* d);
 int kv_tiny_fwd(const KvTinyArgs& a, hipStream_t st);
 int kv_tiny_bwd_input(const KvTinyArgs& a, hipStream_t st);
 int kv_tiny_bwd_weight(const KvTinyArgs& a, hipStream_t st);

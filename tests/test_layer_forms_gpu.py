@@ -12,7 +12,8 @@ the branch.  Each case asserts
   * for fp32, a second run that is bitwise equal.
 
 The shared-basis q|k|v form (row tiles x x_group_mod >= 256) and its launch tail already run at M = 2758 in
-tests/test_launch_shapes_gpu.py::test_forced_tail_ragged_launch and are not repeated."""
+tests/test_launch_shapes_gpu.py::test_forced_tail_ragged_launch and are not repeated.  The weight-gradient forms that no case here
+reaches (plan_layer_bwd_weight) are run and named in tests/test_weight_forms_gpu.py."""
 import contextlib
 
 import pytest
