@@ -123,6 +123,24 @@ typedef struct kanvit_layer_desc {
                               another family, with has_base = 0, or outside 0..5 is KANVIT_EINVAL  */
 } kanvit_layer_desc;
 
+/*
+ * Alignment and strides of kanvit_layer_fwd / kanvit_layer_bwd_input / kanvit_layer_bwd_weight (x, u, w, bparams, bias, y, dy, dx, du,
+ * dparam, dw):
+ *   - every operand pointer needs 4-byte alignment only;
+ *   - ldx, ldu, ldy and bparam_stride need only be at least the documented minimum (x_group_mod*I, groups*I, groups*O, the family's
+ *     basis-parameter count), any value; padding between rows is neither read nor written;
+ *   - the workspace of kanvit_layer_fwd and kanvit_layer_bwd_input needs 16-byte alignment (KANVIT_ENOMEM otherwise, as for one
+ *     that is too small); kanvit_layer_bwd_weight's holds partial sums accessed one float at a time: 4-byte alignment;
+ *   - the KANVIT_FLAG_FUSED_LN statistics buffer (the `u` argument) needs 8-byte alignment (KANVIT_EINVAL otherwise);
+ *   - an operand off the 16-byte grid, or an ld / bparam_stride that is not a multiple of 4 floats, selects slower kernel forms
+ *     (narrower loads, the LDS-tile kernels, the exact fp32 kernels under KANVIT_FLAG_BF16_MFMA) with the same results up to the
+ *     order of the fp32 sums.  KANVIT_FLAG_FUSED_LN has register kernels only: a call is served where one of them takes the
+ *     operands as they are (the forward with x off the grid or ldx % 4 != 0, the weight gradient with any x, dy, ldx, ldy) and is
+ *     refused with KANVIT_EINVAL otherwise (the forward with y, w, bias off the grid or ldy % 4 != 0; the input gradient with x,
+ *     dx, dy, w off the grid or ldx, ldy % 4 != 0).
+ * Packed operands from a 16-byte aligned allocation (what kanvit/ops.py passes) take the fastest form of their shape.
+ */
+
 /* base activations of the BSPLINE / RBF base column (kanvit_layer_desc.base_act): the reference's `base_activation`
  * (models/effkan.py:38, models/fastkan.py:61), whose value the base weights multiply.  Every kernel form of the two families
  * exists for each of them, so a descriptor takes the same kernels whatever its activation.                                */

@@ -200,7 +200,7 @@ void plan_fwd_reg_bf16_form(const kanvit_layer_desc* d, const kanvit_patch_desc*
 }
 
 // general LDS-tile forward (kan_tile.hip): every shape whose chunk fits the LDS
-LayerFwdPlan plan_fwd_tile(const kanvit_layer_desc* d, LayerFwdPlan p) {
+LayerFwdPlan plan_fwd_tile(const kanvit_layer_desc* d, const LayerAlign& al, LayerFwdPlan p) {
     const int fam = d->family, gp = gp_of(d);
     p.nt = d->O <= 32 ? 1 : (d->O <= 64 ? 2 : 4);
     p.nsh = (kv_share_ok(fam, d->flags) && d->groups / d->x_group_mod == 3 && p.nt <= 2) ? 3 : 1;
@@ -211,12 +211,13 @@ LayerFwdPlan plan_fwd_tile(const kanvit_layer_desc* d, LayerFwdPlan p) {
     while (ic > 1 && kv_tile_fwd_lds(fam, ic, gp, p.nt, p.nsh) > 160 * 1024) --ic;
     if (kv_tile_fwd_lds(fam, ic, gp, p.nt, p.nsh) > 160 * 1024)
         return plan_none(p, "kanvit_layer_fwd: %d generated columns per feature with O=%d does not fit the LDS", gp, d->O);
-    // fast path: power-of-two chunk dividing I, whole column tiles, 32-bit tile-local offsets
+    // fast path: power-of-two chunk dividing I, whole column tiles, 32-bit tile-local offsets, and 16-byte rows of w, bias and y (it
+    // loads W and stores its output tile as float4 without a test of its own); anything else takes the predicated variant
     int icf = 1;
     while (icf * 2 <= ic) icf *= 2;
     p.fast = (icf >= 8) && (d->I % icf == 0) && (d->O % (32 * p.nt) == 0) && ((long long)BM * d->ldx < (1LL << 30)) &&
              ((long long)BM * d->ldy < (1LL << 30)) && ((long long)BM * d->ldu < (1LL << 30)) &&
-             ((long long)d->I * gp * d->O < (1LL << 30)) && !kv_config().no_fast;
+             ((long long)d->I * gp * d->O < (1LL << 30)) && !(d->ldy & 3) && !((al.y | al.bias | al.w) & 15) && !kv_config().no_fast;
     p.ic = p.fast ? icf : ic;
     p.form = LAYER_FWD_TILE;
     p.gx = (unsigned)((d->groups / p.nsh) * ((d->O + 32 * p.nt - 1) / (32 * p.nt)));
@@ -259,7 +260,8 @@ LayerFwdPlan plan_layer_fwd(const kanvit_layer_desc* d, const kanvit_patch_desc*
             plan_fwd_reg_bf16_form(d, pd, p);
             return p;
         }
-        if (p.tb.ok && !is_ln(d)) {
+        // (its epilogue stores float4 rows of y and reads the bias as float4; a y or bias off the 16-byte grid runs exact)
+        if (p.tb.ok && !is_ln(d) && !(d->ldy & 3) && !((al.y | al.bias) & 15)) {
             p.form = LAYER_FWD_TILE_BF16;
             p.nt = p.tb.nt;
             p.nsh = p.tb.nsh;
@@ -275,7 +277,7 @@ LayerFwdPlan plan_layer_fwd(const kanvit_layer_desc* d, const kanvit_patch_desc*
     if (p.form == LAYER_FWD_REG) return p;
     if (pd) return plan_none(p, uncovered);
     if (is_ln(d)) return plan_none(p, "kanvit_layer_fwd: KANVIT_FLAG_FUSED_LN needs the register kernel (alignment / shape)");
-    return plan_fwd_tile(d, p);
+    return plan_fwd_tile(d, al, p);
 }
 
 LayerBwdInputPlan plan_layer_bwd_input(const kanvit_layer_desc* d, const LayerAlign& al) {
@@ -532,7 +534,8 @@ int kanvit_layer_fwd(const kanvit_layer_desc* d, const float* x, const float* u,
     if (needs_bparams(d->family) && !bparams) return kv_fail(KANVIT_EINVAL, "kanvit_layer_fwd: family %d needs bparams", d->family);
     if (d->family == KANVIT_RBF && u && d->ldu < (int64_t)d->groups * d->I)
         return kv_fail(KANVIT_EINVAL, "kanvit_layer_fwd: ldu < groups*I");
-    const LayerFwdPlan p = plan_layer_fwd(d, nullptr, layer_align(x, u, w, bparams, bias, y, nullptr, nullptr, nullptr));
+    const LayerAlign al = layer_align(x, u, w, bparams, bias, y, nullptr, nullptr, nullptr);
+    const LayerFwdPlan p = plan_layer_fwd(d, nullptr, al);
     if (p.form == LAYER_FWD_TINY) {
         KvTinyArgs t = tiny_args(d);
         t.x = x; t.w = w; t.bp = bparams; t.bias = bias; t.y = y;
@@ -545,6 +548,7 @@ int kanvit_layer_fwd(const kanvit_layer_desc* d, const float* x, const float* u,
     a.bp = bparams;
     a.bias = bias;
     a.y = y;
+    a.vec = al.vec();
     if (a.ln) {                       // the u slot carries the statistics buffer [M][x_group_mod][2] (written here)
         if (!u || ((uintptr_t)u & 7)) return kv_fail(KANVIT_EINVAL, "kanvit_layer_fwd: KANVIT_FLAG_FUSED_LN needs the (8-byte aligned) statistics buffer in the u argument");
         a.stats = const_cast<float*>(u);
@@ -741,7 +745,8 @@ int kanvit_layer_bwd_input(const kanvit_layer_desc* d, const float* x, const flo
         return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_input: ldu < groups*I");
     if (d->family == KANVIT_SINE && (d->groups / d->x_group_mod) * 4 * d->G > 4096)
         return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_input: SINE G too large");
-    const LayerBwdInputPlan p = plan_layer_bwd_input(d, layer_align(x, u, w, bparams, nullptr, nullptr, dy, dx, du));
+    const LayerAlign al = layer_align(x, u, w, bparams, nullptr, nullptr, dy, dx, du);
+    const LayerBwdInputPlan p = plan_layer_bwd_input(d, al);
     hipStream_t st = (hipStream_t)stream;
     if (p.form == LAYER_BWI_TINY) {
         KvTinyArgs t = tiny_args(d);
@@ -757,8 +762,9 @@ int kanvit_layer_bwd_input(const kanvit_layer_desc* d, const float* x, const flo
     a.dx = dx;
     a.du = du;
     a.dparam = dparam;
-    if (a.ln) {
-        if (!u) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_input: KANVIT_FLAG_FUSED_LN needs the statistics buffer in the u argument");
+    a.vec = al.vec();
+    if (a.ln) {                       // the kernels read a row's (mean, rstd) as one 8-byte pair
+        if (!u || ((uintptr_t)u & 7)) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_input: KANVIT_FLAG_FUSED_LN needs the (8-byte aligned) statistics buffer in the u argument");
         a.stats = const_cast<float*>(u);
         a.u = nullptr;
     }
@@ -798,7 +804,8 @@ int kanvit_layer_bwd_weight(const kanvit_layer_desc* d, const float* x, const fl
     if (needs_bparams(d->family) && !bparams) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: family %d needs bparams", d->family);
     if (d->family == KANVIT_RBF && u && d->ldu < (int64_t)d->groups * d->I)
         return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: ldu < groups*I");
-    const LayerBwdWeightPlan p = plan_layer_bwd_weight(d, nullptr, layer_align(x, u, nullptr, bparams, nullptr, nullptr, dy, nullptr, nullptr));
+    const LayerAlign al = layer_align(x, u, nullptr, bparams, nullptr, nullptr, dy, nullptr, nullptr);
+    const LayerBwdWeightPlan p = plan_layer_bwd_weight(d, nullptr, al);
     if (p.ws_bytes > 0 && (!workspace || workspace_bytes < p.ws_bytes))
         return kv_fail(KANVIT_ENOMEM, "kanvit_layer_bwd_weight: workspace %zu bytes < required %zu", workspace_bytes, p.ws_bytes);
     if ((d->flags & KANVIT_FLAG_SINE_DFREQ) && !p.r.ok)
@@ -808,8 +815,9 @@ int kanvit_layer_bwd_weight(const kanvit_layer_desc* d, const float* x, const fl
     a.u = u;
     a.bp = bparams;
     a.dy = dy;
-    if (a.ln) {
-        if (!u) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: KANVIT_FLAG_FUSED_LN needs the statistics buffer in the u argument");
+    a.vec = al.vec();
+    if (a.ln) {                       // the kernels read a row's (mean, rstd) as one 8-byte pair
+        if (!u || ((uintptr_t)u & 7)) return kv_fail(KANVIT_EINVAL, "kanvit_layer_bwd_weight: KANVIT_FLAG_FUSED_LN needs the (8-byte aligned) statistics buffer in the u argument");
         a.stats = const_cast<float*>(u);
         a.u = nullptr;
     }

@@ -65,7 +65,13 @@ struct LayerArgs {
     // fill the wave slots the last whole work-groups leave idle (forward: one projection each; input gradient: one feature chunk each)
     int tail_y0;
     int base_act;         // BSPLINE / RBF: KANVIT_BASE_* of the base column; nonzero launches the *_act_* kernels (KV_ACT_LAUNCH)
+    // KV_VEC_*: the operands the host found on the 16-byte grid (LayerAlign::vec()).  The LDS-tile kernels (kan_tile.hip) never see a
+    // plan condition on a pointer, so their 16-byte loads of w / dY are taken only with the bit set (wave-uniform, next to full_n /
+    // vec_n); without it they run the per-element branch they have for ragged columns.  The register kernels ignore it: the plans
+    // send them aligned operands only.
+    int vec;
 };
+constexpr int KV_VEC_W = 1, KV_VEC_DY = 2;
 
 // Row tiles [T1, T) of a launch of T row tiles x P work-groups per tile (two resident work-groups per CU) that should run as
 // sub-divided work-groups.  Measured on ViT-B (197 tiles x 12 heads = 9.23 work-groups per CU): a CU runs its work-groups in
@@ -318,6 +324,7 @@ enum LayerBwdWeightForm { LAYER_BWW_NONE, LAYER_BWW_TINY, LAYER_BWW_DMA, LAYER_B
 struct LayerAlign {
     uintptr_t x, u, w, bp, bias, y, dy, dx, du;
     int has_u;            // RBF: the call passes the spline-path input u (its row stride ldu counts only then)
+    int vec() const { return ((w & 15) ? 0 : KV_VEC_W) | ((dy & 15) ? 0 : KV_VEC_DY); }      // LayerArgs::vec
 };
 
 struct LayerFwdPlan {

@@ -75,7 +75,8 @@ __device__ __forceinline__ void stage_rows(float* __restrict__ dst, const float*
 template <int FAM, int NT, int NSH, bool FAST, int ACT>
 __device__ __forceinline__ void kan_fwd_kbody(const LayerArgs& a) {
     // FAST (host-checked): IC is a power of two dividing I, O % BN == 0 -- every chunk and column tile is
-    // interior, so the only remaining bounds question is the last row tile (wave-uniform flag full_m).
+    // interior, so the only remaining bounds question is the last row tile (wave-uniform flag full_m) -- and w, bias, y on the
+    // 16-byte grid with ldy % 4 == 0 (the 16-byte W loads and the float4 epilogue).
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int BN = 32 * NT;
     constexpr int WROW = NSH * BN;              // floats per W_s row
@@ -95,7 +96,8 @@ __device__ __forceinline__ void kan_fwd_kbody(const LayerArgs& a) {
     const int XS = BM * ICP, ASZ = KCP * AS, WSZ = KCP * WROW;
     const int nch = (a.I + IC - 1) / IC;
     const bool full_m = (m0 + BM <= a.M);
-    const bool full_n = FAST || ((n0 + BN <= a.O) && ((a.O & 3) == 0));
+    // 16-byte loads of W rows: whole column tile, O % 4 == 0 and w itself on the 16-byte grid (FAST: host-checked, plan_fwd_tile)
+    const bool full_n = FAST || ((n0 + BN <= a.O) && ((a.O & 3) == 0) && (a.vec & KV_VEC_W));
     const int mrem = full_m ? BM : (int)(a.M - m0);      // valid rows of this tile
 
     float* x_s = smem;                          // [2][XS]
@@ -372,7 +374,8 @@ __global__ __launch_bounds__(256) void kan_pack_w_bwd_kernel(const float* __rest
     *reinterpret_cast<u32x4*>(wb2 + e * 8) = out;
 }
 
-// Requirements (host-checked): IC is a power of two >= 8 dividing I; O % (32*NT) == 0; tile-local offsets fit 32 bits.
+// Requirements (host-checked): IC is a power of two >= 8 dividing I; O % (32*NT) == 0; tile-local offsets fit 32 bits; bias and y on
+// the 16-byte grid with ldy % 4 == 0 (the float4 epilogue; w is read by the repack kernel, one float at a time).
 template <int FAM, int NT, int NSH, int ACT>
 __device__ __forceinline__ void kan_fwd_bf16_kbody(const LayerArgs& a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -601,7 +604,8 @@ __device__ __forceinline__ void kan_bwd_input_kbody(const LayerArgs& a) {
     const int T = nci * spc;
     const bool full_m = (m0 + BM <= a.M);
     const int mrem = full_m ? BM : (int)(a.M - m0);
-    const bool vec_n = ((a.O & 3) == 0) && (a.O % BIN_NC == 0) && ((a.ldy & 3) == 0);   // float4 operand loads
+    // float4 operand loads: every dY row and every W row starts on the 16-byte grid (the bases are the host's LayerAlign::vec())
+    const bool vec_n = ((a.O & 3) == 0) && (a.O % BIN_NC == 0) && ((a.ldy & 3) == 0) && (a.vec & KV_VEC_W) && (a.vec & KV_VEC_DY);
     const int OP = a.O + 8;                         // BF: bf16 elements per dY row image (16-byte aligned, odd 16-B slot count)
     // one operand buffer, in floats: fp32 path dY_s then Wt_s; BF path dYb[BM][OP] then Wtb[O/8][KCT][8] (bf16)
     const int OPS = BF ? (BM * OP / 2 + (a.O / 8) * KCT * 4) : (BIN_NC * AS + BIN_NC * WS);
@@ -942,7 +946,7 @@ __device__ __forceinline__ void kan_bwd_weight_kbody(const LayerArgs& a) {
     const long long mend = (mbeg + a.rows_per_split < a.M) ? mbeg + a.rows_per_split : a.M;
     const int nst = (mend > mbeg) ? (int)((mend - mbeg + BW_ROWS - 1) / BW_ROWS) : 0;
     const int ldy = (int)a.ldy;
-    const bool vec_n = ((a.O & 3) == 0) && (n0 + BN <= a.O) && ((a.ldy & 3) == 0);
+    const bool vec_n = ((a.O & 3) == 0) && (n0 + BN <= a.O) && ((a.ldy & 3) == 0) && (a.vec & KV_VEC_DY);      // dY rows on the 16-byte grid
 
     auto stage_x = [&](int s, int buf) {
         stage_rows<BW_ROWS>(x_s + buf * XS, xg, a.ldx, mbeg + (long long)s * BW_ROWS, mend, i0, a.I, IC, ICP, pt);

@@ -311,8 +311,10 @@ def test_chebykan_weight_gradient_lds_dma_form(rows, amp, monkeypatch):
     """The LDS-DMA form of ChebyKAN's weight gradient (csrc/kan_bwd_weight_dma.hip: wave-private rings filled by global_load_lds,
     four row ranges per work-group summed through the LDS) against the register-ring form on the same launch: same operands and
     roundings, fp32 sums in another order.  KANVIT_BW_DMA_FORCE takes shapes that would not fill the chip through it: row ranges
-    that end inside a 16-row block, waves without rows, a single block per wave.  Bitwise reproducible; an x whose rows do not
-    start on 16-byte boundaries falls back to the register form under the same plan."""
+    that end inside a 16-row block, waves without rows, a single block per wave.  Bitwise reproducible.  The x_off leg passes a
+    sliced x whose rows do not start on 16-byte boundaries to the Python op: kanvit.ops makes every operand contiguous first, so
+    the library sees an aligned copy and the leg checks that copy path against the register form.  A misaligned x that does
+    reach the library is run in tests/test_layer_strided_gpu.py and tests/test_weight_forms_gpu.py."""
     from attention import MSA
     from kanvit import _lib, grouped
     torch.manual_seed(9)
@@ -328,7 +330,7 @@ def test_chebykan_weight_gradient_lds_dma_form(rows, amp, monkeypatch):
         return torch.cat([p.grad.flatten() for p in msa.parameters() if p.grad is not None]).clone()
 
     x = xfull[:, :256].contiguous()
-    x_off = xfull[:, 1:]                           # rows start 4 bytes off the 16-byte grid (and ldx = 257)
+    x_off = xfull[:, 1:]                           # a view 4 bytes off the 16-byte grid with row stride 257: ops copies it before the call
     monkeypatch.delenv("KANVIT_BW_NO_DMA", raising=False)      # (a run of the parity files with the round-4 forms switched off must not switch this one off)
     monkeypatch.setenv("KANVIT_BW_DMA_FORCE", "1")
     _lib.reload_config()
