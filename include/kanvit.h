@@ -254,6 +254,27 @@ int kanvit_bspline_refit_gram(const kanvit_layer_desc* d, const float* x, const 
 int kanvit_bspline_refit_solve(const kanvit_layer_desc* d, const double* N, const double* C, const float* w_old, float* w_new,
                                unsigned char* ok, void* stream);
 
+/* ---- the same fit onto a basis of ANOTHER size: the numerical half of KANLinear.extend_grid ("grid extension") ---------
+ * Train on a coarse grid, then carry every edge's function to a finer (or coarser) one.  The descriptor describes the NEW
+ * layer, G = nb_new = new_grid_size + spline_order; old_G = nb_old describes the old one; the spline order is the same on both
+ * sides, nk_old = old_G + order + 1, nk_new = G + order + 1, both nb <= 24 and both nk <= 40.  With c = g % x_group_mod:
+ *     N[c][i][j][k] = sum_m Bnew_j(x) * Bnew_k(x)        [x_group_mod][I][nb_new][nb_new]  float64
+ *     C[g][i][j][k] = sum_m Bnew_j(x) * Bold_k(x)        [groups][I][nb_new][nb_old]       float64  (rectangular)
+ *     w_new[g][i*nb_new + :][o] = N[c][i]^-1 * C[g][i] * w_old[g][i*nb_old + :][o]
+ * Everything else is kanvit_bspline_refit_*'s: the same kernels (old_G = G runs exactly the refit's arithmetic), families, flags
+ * and has_base refused alike, KANVIT_FLAG_UNIFORM_KNOTS vouching for the OLD knots only, bparam_stride the stride of old_knots
+ * (>= I * nk_old), new_knots [x_group_mod][I][nk_new], the same bands, float64 band-order reduction, Cholesky, pivot rule
+ * (KANVIT_BSPLINE_REFIT_TAU) and non-finite check.  A size over the limit is KANVIT_EINVAL and the message names the side
+ * ("old nb=25", "new nb=25").  Workspace: bands x 4 x (x_group_mod*I*nb_new^2 + groups*I*nb_new*nb_old) bytes.  ok[c][i] = 0:
+ * nothing is written to that feature's rows of w_new (the shapes differ, so the caller cannot keep the old ones: see
+ * KANLinear.extend_grid).  M = 0: ok = 0 everywhere, no launch.  (ABI 7: no struct or version change) */
+int kanvit_bspline_regrid_supported(const kanvit_layer_desc* d, int old_G);
+size_t kanvit_bspline_regrid_workspace(const kanvit_layer_desc* d, int old_G);
+int kanvit_bspline_regrid_gram(const kanvit_layer_desc* d, int old_G, const float* x, const float* old_knots, const float* new_knots,
+                               double* N, double* C, void* workspace, size_t workspace_bytes, void* stream);
+int kanvit_bspline_regrid_solve(const kanvit_layer_desc* d, int old_G, const double* N, const double* C, const float* w_old,
+                                float* w_new, unsigned char* ok, void* stream);
+
 /* ---- fused patch embedding --------------------------------------
  * The patch-embedding layer of VisionTransformer.forward (model.py:144-152) with its prologue and epilogue inside the
  * kernel: the rows of x are gathered straight from the NCHW image batch -- row m = (image m / P, patch m % P),

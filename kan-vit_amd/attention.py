@@ -148,6 +148,44 @@ class MSA(torch.nn.Module):
             m.apply_refit(new_grid[g % H], w_new[g], ok[g % H])
         return (~ok).sum()
 
+    @torch.no_grad()
+    def extend_grid(self, x, grid_size, margin=0.01):
+        """KANLinear.extend_grid for all 3*H per-head q, k and v layers on the rows of x [..., d]: every layer moves to
+        `grid_size` intervals and keeps its function.  ONE grouped launch of ops.bspline_regrid (groups = 3*H, x_group_mod = H)
+        for the fit on x and one for the fit on the fallback samples; the q, k and v layers of a head share their new knots, as in
+        update_grid.  The fallback span of a head slice is the smallest low and the largest high among its three layers' old
+        inner spans; when the three share their old span (they do unless they were loaded from differing checkpoints) every layer
+        ends bit for bit as its own extend_grid on its head's slice would leave it.  Returns the number of (head, feature) pairs
+        that took the fallback (0-d device tensor).  type='efficientkan' only."""
+        from dataclasses import replace
+        layers = list(self.q_mappings) + list(self.k_mappings) + list(self.v_mappings)
+        l0 = layers[0]
+        if not isinstance(l0, KANLinear):
+            raise NotImplementedError(f"extend_grid: MSA type '{self.type}' has no B-spline grid to extend (only 'efficientkan' has)")
+        for m in layers[1:]:
+            assert (m.grid_size, m.spline_order, m.grid_eps, m.enable_standalone_scale_spline) == \
+                (l0.grid_size, l0.spline_order, l0.grid_eps, l0.enable_standalone_scale_spline), \
+                "extend_grid: the per-head layers of one MSA must agree in grid_size, spline_order and grid_eps"
+        KANLinear.check_extension(grid_size, l0.spline_order)
+        H, dh, order = self.n_heads, self.d_head, l0.spline_order
+        nb_old = l0.grid_size + order
+        x2d = x.reshape(-1, self.d).float()
+        cfg = replace(l0.kan_cfg(layers), has_base=0, base_act=0, groups=3 * H, x_group_mod=H, G=grid_size + order)
+        sw = torch.stack([m.scaled_spline_weight for m in layers])                       # [g, O, I, nb_old]
+        w_old = sw.permute(0, 2, 3, 1).reshape(3 * H, dh * nb_old, dh)
+        grids = torch.stack([m.grid for m in layers])                                    # [g, I, nk_old]
+        old = grids.reshape(3 * H, -1)
+        new_grid = KANLinear.adapted_grid(x2d, grid_size, order, l0.grid_eps, margin).view(H, dh, -1)
+        w_new, ok = ops.bspline_regrid(x2d, w_old, cfg, nb_old, old, new_grid)
+        lo = grids[:, :, order].view(3, H * dh).min(dim=0).values
+        hi = grids[:, :, -order - 1].view(3, H * dh).max(dim=0).values
+        xf = KANLinear.span_samples(lo, hi, KANLinear.FALLBACK_SAMPLES)                  # [P, d]
+        fb_grid = KANLinear.adapted_grid(xf, grid_size, order, l0.grid_eps, margin).view(H, dh, -1)
+        w_fb, _ = ops.bspline_regrid(xf, w_old, cfg, nb_old, old, fb_grid)
+        for g, m in enumerate(layers):
+            m.apply_regrid(grid_size, new_grid[g % H], w_new[g], fb_grid[g % H], w_fb[g], ok[g % H])
+        return (~ok).sum()
+
     def forward(self, sequences):
         b, n, d = sequences.shape
         qkv = grouped.run_qkv(self.q_mappings, self.k_mappings, self.v_mappings, sequences.reshape(b * n, d))

@@ -98,6 +98,10 @@ SYMBOLS = {
     "kanvit_bspline_refit_workspace": (C.c_size_t, [C.POINTER(LayerDesc)]),
     "kanvit_bspline_refit_gram": (C.c_int, [C.POINTER(LayerDesc), _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_bspline_refit_solve": (C.c_int, [C.POINTER(LayerDesc), _P, _P, _P, _P, _P, _P]),
+    "kanvit_bspline_regrid_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
+    "kanvit_bspline_regrid_workspace": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int]),
+    "kanvit_bspline_regrid_gram": (C.c_int, [C.POINTER(LayerDesc), C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "kanvit_bspline_regrid_solve": (C.c_int, [C.POINTER(LayerDesc), C.c_int, _P, _P, _P, _P, _P, _P]),
     "kanvit_patch_embed_fwd": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(PatchDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     "kanvit_patch_embed_fwd_ws": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(PatchDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_patch_embed_bwd_weight_ok": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(PatchDesc)]),

@@ -627,6 +627,65 @@ def bspline_refit(x2d: torch.Tensor, w_old_packed: torch.Tensor, cfg: LayerCfg, 
     return w_new, ok.bool()
 
 
+@torch.no_grad()
+def bspline_regrid(x2d: torch.Tensor, w_old_packed: torch.Tensor, cfg_new: LayerCfg, old_G: int, old_knots: torch.Tensor,
+                   new_knots: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(w_new_packed [groups, I*nb_new, O], ok [x_group_mod, I] bool): bspline_refit onto a basis of another size, the numerical
+    half of KANLinear.extend_grid (kanvit_bspline_regrid_*; include/kanvit.h).  cfg_new describes the NEW layers (family BSPLINE,
+    G = nb_new = new grid_size + spline_order, has_base = 0), old_G = nb_old the old ones, the spline order is common;
+    w_old_packed [groups, I*nb_old, O], old_knots [groups, I*nk_old], new_knots [x_group_mod, I, nk_new].  The cross matrix of
+    the normal equations is rectangular, nb_new x nb_old; everything else is bspline_refit's.  ok is False for a feature whose
+    fit does not exist; its rows of w_new_packed are ZERO (there are no old rows of the new shape to keep).  Exact fp32 /
+    float64 also under autocast, deterministic, no autograd, no host synchronisation."""
+    if cfg_new.family != BSPLINE:
+        raise NotImplementedError(f"bspline_regrid: family {_lib.FAMILY_NAMES[cfg_new.family]} has no knot table to refit (bspline only)")
+    from dataclasses import replace
+    cfg = replace(cfg_new, flags=cfg_new.flags & (_lib.FLAG_UNIFORM_KNOTS | _lib.FLAG_SHARED_BPARAMS))
+    old_G = int(old_G)
+    for n, t in (("x", x2d), ("w_old", w_old_packed), ("old_knots", old_knots), ("new_knots", new_knots)):
+        _require_gpu_f32(n, t)
+    x = x2d
+    if x.dim() != 2:
+        raise KanvitError(f"bspline_regrid: x must be 2-D, got {tuple(x.shape)}")
+    if x.shape[1] != cfg.x_group_mod * cfg.I:
+        raise KanvitError(f"bspline_regrid: x has {x.shape[1]} columns, expected {cfg.x_group_mod * cfg.I}")
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):      # a column slice of a wider matrix is read in place
+        x = x.contiguous()
+    M = x.shape[0]
+    ldx = max(x.stride(0), x.shape[1]) if M > 1 else x.shape[1]
+    nb, nk = cfg.G, cfg.G + cfg.spline_order + 1
+    nbo, nko = old_G, old_G + cfg.spline_order + 1
+    w_old = w_old_packed.contiguous()
+    if tuple(w_old.shape) != (cfg.groups, cfg.I * nbo, cfg.O):
+        raise KanvitError(f"bspline_regrid: old packed weight shape {tuple(w_old.shape)} != {(cfg.groups, cfg.I * nbo, cfg.O)} "
+                          f"(old nb={nbo})")
+    if old_knots.dim() < 1 or old_knots.shape[0] != cfg.groups:
+        raise KanvitError(f"bspline_regrid: old knot table {tuple(old_knots.shape)} does not hold [{cfg.groups}][{cfg.I}*{nko}]")
+    old_knots = old_knots.reshape(cfg.groups, -1).contiguous()
+    new_knots = new_knots.contiguous()
+    if old_knots.shape[1] < cfg.I * nko:
+        raise KanvitError(f"bspline_regrid: old knot table {tuple(old_knots.shape)} does not hold [{cfg.groups}][{cfg.I}*{nko}]")
+    if tuple(new_knots.shape) != (cfg.x_group_mod, cfg.I, nk):
+        raise KanvitError(f"bspline_regrid: new knot table {tuple(new_knots.shape)} != [{cfg.x_group_mod}][{cfg.I}][{nk}]")
+    d = _desc(cfg, M, ldx, 0, cfg.groups * cfg.O, old_knots.shape[1])
+    L = _lib.lib()
+    dev = x.device
+    og = C.c_int(old_G)
+    gram_n = torch.empty(cfg.x_group_mod, cfg.I, nb, nb, device=dev, dtype=torch.float64)
+    gram_c = torch.empty(cfg.groups, cfg.I, nb, nbo, device=dev, dtype=torch.float64)
+    w_new = torch.zeros(cfg.groups, cfg.I * nb, cfg.O, device=dev, dtype=torch.float32)      # a flagged feature's rows are not written
+    ok = torch.empty(cfg.x_group_mod, cfg.I, device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        nbytes = int(L.kanvit_bspline_regrid_workspace(C.byref(d), og))
+        ws = _workspace(nbytes, dev)
+        with _timed("bspline_regrid", 2 * M * cfg.I * nb * (cfg.groups * nbo + cfg.x_group_mod * nb), 4 * (x.numel() + w_old.numel() + w_new.numel())):
+            check(L.kanvit_bspline_regrid_gram(C.byref(d), og, _ptr(x), _ptr(old_knots), _ptr(new_knots), _ptr(gram_n), _ptr(gram_c), _ptr(ws),
+                                               C.c_size_t(nbytes), _stream()), "kanvit_bspline_regrid_gram")
+            check(L.kanvit_bspline_regrid_solve(C.byref(d), og, _ptr(gram_n), _ptr(gram_c), _ptr(w_old), _ptr(w_new), _ptr(ok), _stream()),
+                  "kanvit_bspline_regrid_solve")
+    return w_new, ok.bool()
+
+
 # ------------------------------------------------------------------------------------------------
 # attention
 # ------------------------------------------------------------------------------------------------

@@ -239,6 +239,35 @@ class VisionTransformer(nn.Module):
         self._fused_embed = None
         return kept
 
+    @torch.no_grad()
+    def extend_grid(self, images, grid_size, margin=0.01):
+        """KANLinear.extend_grid for every efficient-KAN layer of the model on one image batch (grid extension: train on a coarse
+        grid, then move every layer to `grid_size` intervals with its function kept).  The walk is update_grid's: the patch
+        embedding on the patch rows, then block by block the per-head q|k|v layers on norm1 of the block's input
+        (MSA.extend_grid); a block runs after its own extension; blocks of other types in a mixed model just run.  Every
+        spline_weight of an extended layer is a NEW Parameter: an optimizer holding the old ones must be told (train.py
+        --grid-extend does).  Returns the number of features that took the fallback fit (0-d device tensor)."""
+        kan_blocks = [isinstance(blk, TransformerBlock) and isinstance(blk.attn.q_mappings[0], KANLinear) for blk in self.blocks]
+        if not isinstance(self.linear_mapper, KANLinear) and not any(kan_blocks):
+            raise NotImplementedError(f"extend_grid: model type(s) {sorted(self.layer_types())} have no KANLinear, the only layer "
+                                      "with a B-spline grid to extend ('efficientkan')")
+        for m in self.modules():                             # refuse a size a layer cannot take before any of them moves
+            if isinstance(m, KANLinear):
+                KANLinear.check_extension(grid_size, m.spline_order)
+        fell_back = torch.zeros((), dtype=torch.int64, device=images.device)
+        if isinstance(self.linear_mapper, KANLinear):
+            fell_back = fell_back + self.linear_mapper.extend_grid(self.patchify(images, self.n_patches).reshape(-1, self.input_d),
+                                                                   grid_size, margin)
+        self._fused_embed = None                             # decided for the old grid's flags and size
+        out = self._embed(images)
+        for blk, is_kan in zip(self.blocks, kan_blocks):
+            if is_kan:
+                fell_back = fell_back + blk.attn.extend_grid(blk.norm1(out), grid_size, margin)
+            if blk is not self.blocks[-1]:
+                out = blk(out)
+        self._fused_embed = None
+        return fell_back
+
     REGULARIZED_TYPES = MSA.REGULARIZED_TYPES
 
     def layer_types(self):

@@ -6,7 +6,8 @@ default, or one of ops.SUPPORTED_BASE_ACTIVATIONS, read on every forward) and bo
 contractions in one pass.  Construction-time host logic (knot vector, the least-squares
 initialisation of ``spline_weight``) is plain torch, as in the reference.  ``update_grid`` computes the new
 knots with the reference's torch expressions and refits the weights in the fused Gram-matrix kernels
-(kanvit.ops.bspline_refit)."""
+(kanvit.ops.bspline_refit); ``extend_grid`` carries the layer to another ``grid_size`` the same way
+(kanvit.ops.bspline_regrid, section 4.15)."""
 import math
 
 import torch
@@ -187,6 +188,89 @@ class KANLinear(torch.nn.Module):
         sw = w_new.view(self.in_features, nb, self.out_features).permute(2, 0, 1)
         self.grid.copy_(torch.where(ok[:, None], new_grid, self.grid))
         self.spline_weight.data.copy_(torch.where(ok[None, :, None], sw, self.spline_weight))
+
+    MAX_BASIS = 24            # basis functions per feature the refit kernels hold in registers (include/kanvit.h)
+    FALLBACK_SAMPLES = 256    # one row band of the Gram kernel
+
+    @staticmethod
+    def span_samples(lo: torch.Tensor, hi: torch.Tensor, P):
+        """[P, in]: P evenly spaced samples from lo[in] to hi[in], both ends included."""
+        t = torch.arange(P, dtype=torch.float32, device=lo.device).unsqueeze(1) / (P - 1)
+        return lo.unsqueeze(0) + (hi - lo).unsqueeze(0) * t
+
+    @staticmethod
+    def fallback_samples(old_grid: torch.Tensor, spline_order, P):
+        """[P, in]: the synthetic rows extend_grid refits a feature on when its fit on the real rows does not exist -- P evenly
+        spaced samples across the inner span [knots[order], knots[-order-1]] of the feature's old knots [in, nk], the range its
+        function was defined on.  Plain torch on old_grid's device."""
+        return KANLinear.span_samples(old_grid[:, spline_order], old_grid[:, -spline_order - 1], P)
+
+    @staticmethod
+    def check_extension(grid_size, spline_order):
+        nb = grid_size + spline_order
+        if grid_size < 1 or nb > KANLinear.MAX_BASIS:
+            raise ops.KanvitError(f"extend_grid: grid_size={grid_size} with spline_order={spline_order} gives grid_size + spline_order = "
+                                  f"{nb} basis functions per feature; supported: grid_size >= 1 and at most {KANLinear.MAX_BASIS}")
+
+    @torch.no_grad()
+    def extend_grid(self, x: torch.Tensor, grid_size, margin=0.01):
+        """Grid extension (pykan's refine): move the layer to `grid_size` intervals -- finer or coarser -- and initialise the new
+        coefficients so that every edge keeps the function it has learnt, wherever the rows of x (batch, in) sample it.  The new
+        knots are adapted_grid(x, grid_size, ...), the reference's knot rule at the new size; the new spline_weight is the
+        least-squares fit of the old spline on them, from the fused Gram-matrix kernels with a rectangular cross matrix
+        (ops.bspline_regrid).  update_grid's quirk is kept: the fit target is scaled_spline_weight, the
+        result goes into spline_weight, spline_scaler stays.  `grid` becomes a new [in, nk_new] buffer, `spline_weight` a NEW
+        Parameter [out, in, nb_new] (an optimizer holding the old one must be told), `grid_size` is updated.
+        A feature whose fit on x does not exist (a constant column, too few distinct samples) cannot keep its old knots and
+        weights, as it does in update_grid: their shapes change.  It is refitted on FALLBACK_SAMPLES evenly spaced synthetic
+        samples across its old grid's inner span (fallback_samples) and takes its knots from adapted_grid of those, so it keeps its
+        function over the range it was defined on.  Both fits always run and are combined on the device: no host sync.
+        Returns the number of features that took the fallback (0-d device tensor)."""
+        assert x.dim() == 2 and x.size(1) == self.in_features
+        self.check_extension(grid_size, self.spline_order)
+        x = x.float()
+        cfg, w_old, old = self.regrid_operands(grid_size)
+        new_grid = self.adapted_grid(x, grid_size, self.spline_order, self.grid_eps, margin)
+        w_new, ok = ops.bspline_regrid(x, w_old, cfg, self.grid_size + self.spline_order, old, new_grid.unsqueeze(0))
+        xf = self.fallback_samples(self.grid, self.spline_order, self.FALLBACK_SAMPLES)
+        fb_grid = self.adapted_grid(xf, grid_size, self.spline_order, self.grid_eps, margin)
+        w_fb, _ = ops.bspline_regrid(xf, w_old, cfg, self.grid_size + self.spline_order, old, fb_grid.unsqueeze(0))
+        self.apply_regrid(grid_size, new_grid, w_new[0], fb_grid, w_fb[0], ok[0])
+        return (~ok).sum()
+
+    def regrid_operands(self, grid_size):
+        """(cfg of the layer at `grid_size`, packed old spline weights [1, in*nb_old, out], old knots [1, in*nk_old])."""
+        from dataclasses import replace
+        cfg = replace(self.kan_cfg(), has_base=0, base_act=0, G=grid_size + self.spline_order)
+        w_old = self.scaled_spline_weight.permute(1, 2, 0).reshape(1, -1, self.out_features)
+        return cfg, w_old, self.grid.reshape(1, -1)
+
+    def apply_regrid(self, grid_size, new_grid, w_new, fb_grid, w_fb, ok):
+        """Become a layer of `grid_size` intervals: knots [in, nk_new] and packed weights [in*nb_new, out] from the fit on the
+        real rows where ok[in] is set, from the fit on the fallback samples elsewhere."""
+        nb = grid_size + self.spline_order
+        pick = torch.where(ok[:, None, None], w_new.view(self.in_features, nb, self.out_features),
+                           w_fb.view(self.in_features, nb, self.out_features))
+        self.resize_grid(grid_size, torch.where(ok[:, None], new_grid, fb_grid), pick.permute(2, 0, 1).contiguous())
+
+    def resize_grid(self, grid_size, grid, spline_weight):
+        """Replace the knot buffer and the spline_weight Parameter by tensors of another grid size."""
+        self.grid = grid                                    # a registered buffer: assignment replaces it (_grid_facts sees a new tensor)
+        self.spline_weight = torch.nn.Parameter(spline_weight, requires_grad=self.spline_weight.requires_grad)
+        self.grid_size = grid_size
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        """A checkpoint saved after extend_grid loads into a layer built at another grid_size: when the incoming grid [in, nk] and
+        spline_weight [out, in, nb] agree with each other and with this layer's spline_order (nk = gs + 2*order + 1,
+        nb = gs + order for one gs >= 1) and features, the layer adopts that grid size first.  Anything else fails as it always did."""
+        g, w = state_dict.get(prefix + "grid"), state_dict.get(prefix + "spline_weight")
+        if torch.is_tensor(g) and torch.is_tensor(w) and g.dim() == 2 and w.dim() == 3:
+            gs = w.shape[2] - self.spline_order
+            if (gs >= 1 and gs != self.grid_size and g.shape[1] == gs + 2 * self.spline_order + 1 and g.shape[0] == self.in_features
+                    and tuple(w.shape[:2]) == (self.out_features, self.in_features)):
+                self.resize_grid(gs, torch.zeros(g.shape, dtype=self.grid.dtype, device=self.grid.device),
+                                 torch.empty(w.shape, dtype=self.spline_weight.dtype, device=self.spline_weight.device))
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def edge_activation_l1(self, x: torch.Tensor, include_base=False):
         """[out, in]: the mean over the samples of |phi_{o,i}(x[.., i])|, the per-edge activation magnitude the KAN paper

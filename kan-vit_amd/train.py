@@ -11,7 +11,8 @@ train.py:31-40), running on the MI355X kernels, with optional pure data parallel
 Additions over the reference (none change a default): --synthetic / --image-size / --in-chans /
 --n-patches / --out-d (geometry), --seed, --dp, --steps-per-epoch, --amp, --graph, --no-tuned-gemms, --reg-lambda /
 --reg-activation / --reg-entropy (the sample-based KAN regulariser added to the step's loss), --grid-update-every
-(KANLinear.update_grid on the step's batch every N-th step),
+(KANLinear.update_grid on the step's batch every N-th step), --grid-extend STEP:SIZE[,...] (grid extension: at the start of
+step STEP every KANLinear moves to SIZE grid intervals with its function kept),
 --no-step-metrics (the per-step metrics stay on the device either way: one host sync per epoch instead of the
 reference's three per step, train.py:37,42-44).
 
@@ -116,8 +117,47 @@ def set_base_activation(model, model_type, name):
             m.base_activation = functions[name]
 
 
+def parse_grid_extend(text):
+    """'3:10,6:20' -> {3: 10, 6: 20}: at the start of step 3 extend to grid size 10, at step 6 to 20."""
+    plan = {}
+    for item in filter(None, (t.strip() for t in (text or "").split(","))):
+        try:
+            step, size = (int(v) for v in item.split(":"))
+        except ValueError:
+            raise SystemExit(f"--grid-extend: '{item}' is not STEP:SIZE")
+        if step < 1 or size < 1 or step in plan:
+            raise SystemExit(f"--grid-extend: '{item}': STEP and SIZE are positive and a step is named once")
+        plan[step] = size
+    return plan
+
+
+def extend_grid_and_swap(model, optimizer, x, grid_size):
+    """model.extend_grid(x, grid_size), then hand the optimizer the Parameters the extension replaced (by name): they take the old
+    ones' places in the param groups and start without state; every other parameter keeps its moments and its step count."""
+    before = dict(model.named_parameters())
+    model.extend_grid(x, grid_size)
+    swap = {id(before[n]): (before[n], p) for n, p in model.named_parameters() if before[n] is not p}
+    for group in optimizer.param_groups:
+        group["params"] = [swap[id(p)][1] if id(p) in swap else p for p in group["params"]]
+    for old, _ in swap.values():
+        optimizer.state.pop(old, None)
+    return len(swap)
+
+
 def main(args, batches=None, init_state=None):
     rank, world, local = 0, 1, 0
+    grid_extend = getattr(args, "grid_extend", None) or {}
+    if grid_extend:
+        from model import split_types
+        if args.graph:
+            raise SystemExit("--grid-extend is not combined with --graph: the captured step bakes in the parameters, the grid sizes and "
+                             "the kernel forms the grids' flags selected, and an extension replaces all three")
+        if args.dp:
+            raise SystemExit("--grid-extend is not combined with --dp: every rank would fit its own shard and the replicas "
+                             "would diverge (a gathered extension is not implemented)")
+        if "efficientkan" not in split_types(args.model_type):
+            raise SystemExit(f"--grid-extend: model type '{args.model_type}' has no KANLinear, the only layer with a B-spline "
+                             "grid to extend ('efficientkan')")
     grid_every = int(getattr(args, "grid_update_every", 0))
     if grid_every > 0:
         from model import split_types
@@ -236,7 +276,9 @@ def main(args, batches=None, init_state=None):
             if args.graph and step is eager_step:
                 step = _GraphedStep(eager_step, model, optimizer, x, y)
             n_steps += 1
-            if grid_every > 0 and n_steps % grid_every == 0:
+            if n_steps in grid_extend:             # the extension refits on this batch too: an update due on the same step is skipped
+                extend_grid_and_swap(model, optimizer, x, grid_extend[n_steps])
+            elif grid_every > 0 and n_steps % grid_every == 0:
                 model.update_grid(x)            # before the step, on the step's own batch; Adam's moments stay as they are
             loss, y_hat = step(x, y)
             step_losses.append(loss.clone() if args.graph else loss)
@@ -282,6 +324,7 @@ def main(args, batches=None, init_state=None):
         torch.distributed.barrier()             # the other ranks wait for rank 0's evaluation before the group goes away
         torch.distributed.destroy_process_group()
     history["model"] = model
+    history["optimizer"] = optimizer
     return history
 
 
@@ -323,6 +366,12 @@ def parse(argv=None):
                    help="every N-th step, before the step, move the B-spline knots of every KANLinear to that step's batch and refit "
                         "the spline weights (VisionTransformer.update_grid; 'efficientkan' model types; not with --graph or --dp). "
                         "Adam's moments of spline_weight are left as they are, as upstream practice has it; 0 (default): never")
+    p.add_argument('--grid-extend', type=parse_grid_extend, default={}, metavar='STEP:SIZE[,STEP:SIZE...]',
+                   help="grid extension -- at the start of step STEP (counted from 1 over the whole run), on "
+                        "that step's batch, move every KANLinear to SIZE grid intervals and fit the new spline coefficients so that "
+                        "every edge keeps its function (VisionTransformer.extend_grid; 'efficientkan' model types; not with --graph "
+                        "or --dp).  The replaced spline_weight parameters start with fresh Adam state, every other parameter keeps "
+                        "its own; a --grid-update-every update due on the same step is skipped.  Default: never")
     p.add_argument('--no-tuned-gemms', action='store_true', help='library-default kernel selection for the stock GEMMs')
     return p.parse_args(argv)
 
