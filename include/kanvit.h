@@ -379,6 +379,28 @@ int kanvit_attn_x_bwd(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const
                       const float* o, const float* lse, const float* d_o, float* dq, float* dk, float* dv, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---- attention probabilities: the matrix the fused kernels never materialise (attention maps, attention rollout) -----------
+ * The reference forms softmax(q k^T / sqrt(d_head)) per sample and head (attention.py:199), so a forward hook on MSA.softmax
+ * sees every head's map; kanvit_attn_fwd / kanvit_attn_x_fwd keep only o and the row log-sum-exp.  This entry writes the map:
+ *     p[b*p_stride_b + h*p_stride_h + i*p_stride_q + j] = softmax_j(scale * q[b,h,i,:] . k[b,h,j,:])      i < rows, j < e->Nk
+ * Domain and semantics are kanvit_attn_x_fwd's, so that a map describes exactly the attention the library computes: d->N =
+ * q_len, e->Nk = k_len, both >= 1 and of any size (the keys are walked in LDS chunks of 64 rows); D even and <=
+ * KANVIT_ATTN_X_MAX_D; q and k through the q / k strides of d (the packed [B][N][3][H][D] views are read in place; the v and o
+ * strides are ignored); the mask through e (required; e->mask may be NULL); `causal` needs k_len <= q_len.  A dead position gets
+ * exactly 0.0 and a query with no live key an all-zero row (the counterpart of o = 0, lse = -FLT_MAX).
+ * rows in [1, d->N]: only the first `rows` queries of every (b, h) are computed and written (rows = 1: the class-token row a ViT
+ * saliency map reads).  p_stride_q >= Nk; the innermost dimension of p is contiguous.  B, H >= 1.
+ * One mode, fp32 on the vector pipe (compensated dot products: a score carries the error of its inputs' rounding only; the row
+ * maximum subtracted before exp): d->flags must be 0, and KANVIT_FLAG_BF16_MFMA is refused by name (callers clear it: the same
+ * arithmetic under autocast).  KANVIT_EINVAL with a
+ * kanvit_last_error() text for a null d / e / q / k / p, D odd or too large, scale <= 0, rows out of range, p_stride_q < Nk, a
+ * size < 1, causal with k_len > q_len.
+ * No workspace, no atomics; the stores of p are contiguous along j.  Bitwise reproducible: row (b, h, i) has the same bits run to
+ * run, for every `rows`, whatever other samples and heads the launch holds, and whether q / k arrive packed or as separate
+ * contiguous tensors.  (ABI 7: no struct or version change) */
+int kanvit_attn_probs(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const float* q, const float* k, float* p,
+                      int64_t p_stride_b, int64_t p_stride_h, int64_t p_stride_q, int32_t rows, void* stream);
+
 /* ---- fused feed-forward for the small geometries ---------------------------------------------
  * y = relu(x W1^T + b1) W2^T + b2, the TransformerBlock's nn.Sequential(Linear, ReLU(inplace), Linear) (model.py:25-29,36),
  * x[M][D], W1[F][D], b1[F], W2[D][F], b2[D] in nn.Linear's own layouts; fp32 products and sums.  Forward: one launch;

@@ -50,6 +50,20 @@ class FlashAttention(nn.Module):
         out = FlashAttentionFunction.apply(q, k, v, mask, self.causal, qb, kb)
         return self.to_out(out.permute(0, 2, 1, 3).reshape(b, n, -1))
 
+    @torch.no_grad()
+    def attention_map(self, x, context=None, mask=None, rows=None):
+        """[B, heads, R, k_len] float32: the attention probabilities of every head for the call forward(x, context, mask) -- the
+        same projections and strided views, the module's `causal`, the mask forms forward accepts -- from kanvit.ops.attention_probs
+        (the fused forward never forms them).  `rows` = R keeps the first R queries (default all; 1 = the first token's row).
+        Not differentiable; the softmax is exact fp32 also under autocast."""
+        h = self.heads
+        context = default(context, x)
+        q = self.to_q(x)
+        k = self.to_kv(context).chunk(2, dim=-1)[0]
+        b = q.shape[0]
+        q, k = (t.view(b, t.shape[1], h, -1).permute(0, 2, 1, 3) for t in (q, k))
+        return ops.attention_probs(q, k, mask=mask, causal=self.causal, rows=rows)
+
 
 class MSA(torch.nn.Module):
     """Multi-head self-attention with one small (KAN or linear) mapping per head and per q/k/v,
@@ -185,6 +199,18 @@ class MSA(torch.nn.Module):
         for g, m in enumerate(layers):
             m.apply_regrid(grid_size, new_grid[g % H], w_new[g], fb_grid[g % H], w_fb[g], ok[g % H])
         return (~ok).sum()
+
+    @torch.no_grad()
+    def attention_map(self, x, rows=None):
+        """[B, H, R, N] float32: softmax(q k^T / sqrt(d_head)) of every head on x [B, N, d] -- what a forward hook on
+        `self.softmax` collects in the reference (attention.py:199; here that module is constructed but never called, so such a
+        hook does not fire).  q and k come from the same grouped q|k|v launch as forward's (under bf16 autocast: the autocast
+        launch's values); the softmax on top of them is exact fp32 (kanvit.ops.attention_probs_packed, forward's scale).
+        `rows` = R keeps the first R queries (default N; 1 = the class-token row).  Every MSA type.  Not differentiable."""
+        b, n, d = x.shape
+        qkv = grouped.run_qkv(self.q_mappings, self.k_mappings, self.v_mappings, x.reshape(b * n, d))
+        return ops.attention_probs_packed(qkv.view(b, n, 3, self.n_heads, self.d_head), causal=False,
+                                          scale=1.0 / (self.d_head ** 0.5), rows=rows)
 
     def forward(self, sequences):
         b, n, d = sequences.shape

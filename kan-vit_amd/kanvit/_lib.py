@@ -113,6 +113,7 @@ SYMBOLS = {
     "kanvit_attn_x_fwd": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnExt), _P, _P, _P, _P, _P, _P]),
     "kanvit_attn_x_bwd_workspace": (C.c_size_t, [C.POINTER(AttnDesc), C.POINTER(AttnExt)]),
     "kanvit_attn_x_bwd": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnExt), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "kanvit_attn_probs": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnExt), _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P]),
     "kanvit_addln_fwd": (C.c_int, [C.c_int64, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "kanvit_addln_fwd_ex": (C.c_int, [C.c_int64, C.c_int, C.c_float, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     "kanvit_addln_bwd_ex": (C.c_int, [C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),

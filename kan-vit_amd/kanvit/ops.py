@@ -886,6 +886,79 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = 
     return _AttnFn.apply(q, k, v, causal, q.shape[-1] ** -0.5 if scale is None else scale, _autocast_flags())
 
 
+def expand_attention_mask(mask: Optional[torch.Tensor], q: torch.Tensor, k: torch.Tensor) -> Optional[torch.Tensor]:
+    """The mask forms utils.FlashAttentionFunction accepts -- a [B, Nk] key-padding mask ('b n -> b 1 1 n', utils.py:156-157) or
+    anything broadcastable to [B, H, Nq, Nk], True = attend -- as a torch.bool view expanded to [B, H, Nq, Nk] (no copy)."""
+    if mask is None:
+        return None
+    if mask.dim() == 2:
+        mask = mask[:, None, None, :]
+    return mask.to(device=q.device, dtype=torch.bool).expand(q.shape[0], q.shape[1], q.shape[2], k.shape[2])
+
+
+def _attn_probs(q, k, mask, causal, scale, rows):
+    for n, t in (("q", q), ("k", k)):
+        _require_gpu_f32(n, t)
+        if t.dim() != 4:
+            raise KanvitError(f"attention_probs: {n} has shape {tuple(t.shape)}, expected [B, H, length, D]")
+    B, H, Nq, D = q.shape
+    if tuple(k.shape[:2]) != (B, H) or k.shape[3] != D:
+        raise KanvitError(f"attention_probs: q {tuple(q.shape)} and k {tuple(k.shape)} do not agree in batch, heads and head size")
+    Nk = k.shape[2]
+    q, k = (t if t.stride(3) == 1 else t.contiguous() for t in (q, k))
+    mask = expand_attention_mask(mask, q, k)
+    scale = D ** -0.5 if scale is None else scale
+    rows = Nq if rows is None else int(rows)
+    if not 1 <= rows <= Nq:
+        raise KanvitError(f"attention_probs: rows={rows} must be in [1, {Nq}]")
+    if B == 0:
+        return torch.empty(B, H, rows, Nk, device=q.device, dtype=torch.float32)
+    d = AttnDesc(B, H, Nq, D, int(bool(causal)), float(scale), 0, 0, q.stride(0), q.stride(1), q.stride(2),
+                 k.stride(0), k.stride(1), k.stride(2), 0, 0, 0, 0, 0, 0)
+    if mask is None:
+        e = _lib.AttnExt(Nk, 0, None, 0, 0, 0, 0)
+    else:               # expand_attention_mask: torch.bool on q's device, [B, H, Nq, Nk]
+        e = _lib.AttnExt(Nk, 0, mask.data_ptr(), mask.stride(0), mask.stride(1), mask.stride(2), mask.stride(3))
+    p = torch.empty(B, H, rows, Nk, device=q.device, dtype=torch.float32)
+    # three sweeps of the q.k products (max, sum, store); the map itself is the traffic
+    with torch.cuda.device(q.device), _timed("attn_probs", 6 * B * H * rows * Nk * D, 4 * B * H * (rows * Nk + rows * D + Nk * D)):
+        check(_lib.lib().kanvit_attn_probs(C.byref(d), C.byref(e), _ptr(q), _ptr(k), _ptr(p), p.stride(0), p.stride(1), p.stride(2),
+                                           rows, _stream()), "kanvit_attn_probs")
+    return p
+
+
+@torch.no_grad()
+def attention_probs(q: torch.Tensor, k: torch.Tensor, mask: Optional[torch.Tensor] = None, causal: bool = False,
+                    scale: Optional[float] = None, rows: Optional[int] = None) -> torch.Tensor:
+    """softmax(scale * q k^T) of q [B, H, Nq, D] and k [B, H, Nk, D] -> [B, H, R, Nk] float32: the attention probabilities the
+    fused kernels never materialise (kanvit_attn_probs; attention maps and rollout).  `rows` = R keeps the first R queries only
+    (default Nq; 1 = the class-token row).  `mask`: a [B, Nk] key-padding mask or anything broadcastable to [B, H, Nq, Nk],
+    True = attend; `causal` needs Nk <= Nq.  Domain and dead-position semantics are FlashAttentionFunction's: D even and <= 128,
+    any lengths, a dead position is exactly 0 and a query with no live key gives an all-zero row.  scale defaults to D ** -0.5.
+    The map is a diagnostic and is NOT differentiable: it is computed under torch.no_grad() and comes back without history.
+    One mode, fp32 with compensated dot products, also under autocast (inputs of another dtype are cast to float32).  No host synchronisation."""
+    with torch.autocast("cuda", enabled=False):
+        q, k = (t.float() if t.is_cuda and t.is_floating_point() else t for t in (q, k))
+        return _attn_probs(q, k, mask, causal, scale, rows)
+
+
+@torch.no_grad()
+def attention_probs_packed(qkv: torch.Tensor, causal: bool = False, scale: Optional[float] = None,
+                           rows: Optional[int] = None) -> torch.Tensor:
+    """attention_probs of the q and k slices of qkv[B, N, 3, H, D] (the layout the grouped q|k|v launch writes), read in place ->
+    [B, H, R, N] float32.  Bit for bit attention_probs on contiguous copies of q and k.  Not differentiable; exact fp32 also
+    under autocast."""
+    with torch.autocast("cuda", enabled=False):
+        if qkv.is_cuda and qkv.is_floating_point():
+            qkv = qkv.float()
+        _require_gpu_f32("qkv", qkv)
+        if qkv.dim() != 5 or qkv.shape[2] != 3:
+            raise KanvitError(f"attention_probs_packed: qkv has shape {tuple(qkv.shape)}, expected [B, N, 3, H, D]")
+        qkv = qkv.contiguous()
+        q, k = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(2))
+        return _attn_probs(q, k, None, causal, scale, rows)
+
+
 # ------------------------------------------------------------------------------------------------
 # residual add + LayerNorm (TransformerBlock assembly, reference model.py:31-37)
 # ------------------------------------------------------------------------------------------------

@@ -33,6 +33,12 @@ class TransformerBlock(nn.Module):
         x, f = self.run(x, None)
         return x + f
 
+    @torch.no_grad()
+    def attention_map(self, x, rows=None):
+        """[B, H, R, N]: the attention probabilities of this block's heads on the stream x the block receives
+        (MSA.attention_map of norm1(x))."""
+        return self.attn.attention_map(self.norm1(x), rows)
+
     def run(self, x, pending, reg=None):
         """The block with its residual adds fused into the LayerNorms (kanvit.ops.add_layernorm: one pass instead of an
         add kernel + a LayerNorm kernel forward, one pass instead of three + an add backward).  `pending` is the previous
@@ -267,6 +273,70 @@ class VisionTransformer(nn.Module):
                 out = blk(out)
         self._fused_embed = None
         return fell_back
+
+    def _walk_attention_maps(self, images, rows):
+        """One block's map at a time, update_grid's walk: the map of block l is taken on the block's real input, then the block
+        runs (the last one does not have to).  'flash-attn' models stack bare FlashAttention modules."""
+        out = self._embed(images)
+        for blk in self.blocks:
+            yield blk.attention_map(out, rows=rows)
+            if blk is not self.blocks[-1]:
+                out = blk(out)
+
+    @torch.no_grad()
+    def attention_maps(self, images, rows=None):
+        """[n_blocks, B, H, R, N] float32 (N = n_patches^2 + 1 tokens, the class token first): every head's attention
+        probabilities in every block on one image batch -- TransformerBlock.attention_map (FlashAttention.attention_map for a
+        'flash-attn' model) on each block's real input.  `rows` = R keeps the first R query rows (default N; 1 = the class-token
+        row).  Runs without gradients and leaves the training / eval mode as it finds it.  The stacked result grows with
+        n_blocks * B * H * N^2 (ViT-B at batch 128: 2.9 GB); attention_rollout holds one block's map at a time."""
+        return torch.stack(list(self._walk_attention_maps(images, rows)))
+
+    @staticmethod
+    def _rollout_factor(block_map, head_fusion):
+        """(fuse_h A + I) / rowsum of one block's [B, H, N, N] map, float32 with autocast off."""
+        if block_map.dim() != 4 or block_map.shape[-1] != block_map.shape[-2]:
+            raise ValueError(f"rollout needs full attention maps [.., B, H, N, N] (rows=None), got a block of shape {tuple(block_map.shape)}")
+        a = block_map.float()
+        if head_fusion == "mean":
+            a = a.mean(dim=1)
+        elif head_fusion == "max":
+            a = a.amax(dim=1)
+        elif head_fusion == "min":
+            a = a.amin(dim=1)
+        else:
+            raise ValueError(f"head_fusion must be 'mean', 'max' or 'min', got {head_fusion!r}")
+        a = a + torch.eye(a.shape[-1], dtype=a.dtype, device=a.device)
+        return a / a.sum(dim=-1, keepdim=True)
+
+    @staticmethod
+    def rollout(maps, head_fusion="mean"):
+        """Attention rollout (Abnar & Zuidema 2020) of maps [n_blocks, B, H, N, N] -> [B, N, N]: with A_l = fuse_h maps[l]
+        (head_fusion: 'mean', 'max' or 'min' over the heads) and A~_l = (A_l + I) / rowsum(A_l + I), the product
+        A~_L ... A~_1.  Pure torch, any device; float32 products with autocast off.  Needs full maps (R == N)."""
+        if maps.dim() != 5:
+            raise ValueError(f"rollout needs maps [n_blocks, B, H, N, N], got shape {tuple(maps.shape)}")
+        with torch.autocast(maps.device.type, enabled=False):
+            out = None
+            for block_map in maps:
+                f = VisionTransformer._rollout_factor(block_map, head_fusion)
+                out = f if out is None else f @ out
+        return out
+
+    @torch.no_grad()
+    def attention_rollout(self, images, head_fusion="mean"):
+        """rollout(attention_maps(images), head_fusion) -> [B, N, N] without the stacked maps: the same walk, carrying the running
+        product and one block's map.  [:, 0, 1:] is the class token's saliency over the patches (cls_saliency)."""
+        out = None
+        for block_map in self._walk_attention_maps(images, None):
+            with torch.autocast(block_map.device.type, enabled=False):
+                f = self._rollout_factor(block_map, head_fusion)
+                out = f if out is None else f @ out
+        return out
+
+    def cls_saliency(self, rollout):
+        """[B, N, N] rollout -> [B, n_patches, n_patches]: the class token's row over the patch grid."""
+        return rollout[:, 0, 1:].reshape(-1, self.n_patches, self.n_patches)
 
     REGULARIZED_TYPES = MSA.REGULARIZED_TYPES
 

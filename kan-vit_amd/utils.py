@@ -46,10 +46,7 @@ class FlashAttentionFunction(Function):
         scale = q.shape[-1] ** -0.5
         o = torch.empty(q.shape, device=q.device, dtype=q.dtype)
         general = mask is not None or k.shape[2] != q.shape[2]
-        if mask is not None:
-            if mask.dim() == 2:
-                mask = mask[:, None, None, :]                         # 'b n -> b 1 1 n' (utils.py:156-157)
-            mask = mask.to(device=q.device, dtype=torch.bool).expand(q.shape[0], q.shape[1], q.shape[2], k.shape[2])
+        mask = ops.expand_attention_mask(mask, q, k)              # 'b n -> b 1 1 n' (utils.py:156-157), then [b, h, q_len, k_len]
         if general:
             lse = ops._attn_x_fwd(q, k, v, o, mask, causal, scale)
         else:
