@@ -401,6 +401,27 @@ int kanvit_attn_x_bwd(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const
 int kanvit_attn_probs(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const float* q, const float* k, float* p,
                       int64_t p_stride_b, int64_t p_stride_h, int64_t p_stride_q, int32_t rows, void* stream);
 
+/* ---- single-query attention: one query per (batch, head) against all keys and values ------------------------------------------
+ * The classification head reads only the class token (model.py:166-169), so the last block of a ViT needs one attention row per
+ * head.  With q0 = q[b,h,:]:
+ *     s_j = scale * q0 . k[b,h,j,:]        p = softmax_j(s), the maximum subtracted        o[b,h,:] = sum_j p_j v[b,h,j,:]
+ * and from d_o[b,h,:], with dP_j = d_o . v_j and delta = sum_j p_j dP_j (= d_o . o, which is how it is formed):
+ *     ds_j = p_j (dP_j - delta)      dq0 = scale sum_j ds_j k_j      dk_j = scale ds_j q0      dv_j = p_j d_o
+ * d and e as for kanvit_attn_probs: d->N = q_len must be 1, e->Nk = k_len >= 1 of any size, D even and <= KANVIT_ATTN_X_MAX_D,
+ * any finite scale; no causal form, e->mask must be NULL, d->flags must be 0 (one mode, exact fp32 on the vector pipe; there is
+ * no matrix product left).  q, dq: [B][H][D] through q_stride_b / q_stride_h; o, d_o through o_stride_b / o_stride_h (the _n
+ * strides are ignored); k, v, dk, dv: [B][H][Nk][D] through the k / v strides -- the halves of a packed [B][Nk][2][H][D] tensor
+ * are read and written in place; p: [B][H][Nk] contiguous, written by the forward (it is scratch for the scores while the kernel
+ * runs) and read by the backward.  Innermost dimensions are contiguous; rows on the 16-byte grid with D % 4 == 0 take 16-byte
+ * loads, narrower ones otherwise, same results.  dk / dv must not alias k / v.
+ * Two streaming passes forward (K, then V), one backward (K and V read, dK and dV written): no workspace, no atomics, one fixed
+ * summation order -- bitwise reproducible.  B = 0 returns without a launch.  KANVIT_EINVAL with a kanvit_last_error() text for a
+ * null argument, q_len != 1, D odd or too large, a size < 1, causal, a mask, a flag.  (ABI 7: no struct or version change) */
+int kanvit_attn_q1_fwd(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const float* q, const float* k, const float* v,
+                       float* o, float* p, void* stream);
+int kanvit_attn_q1_bwd(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const float* q, const float* k, const float* v,
+                       const float* o, const float* p, const float* d_o, float* dq, float* dk, float* dv, void* stream);
+
 /* ---- fused feed-forward for the small geometries ---------------------------------------------
  * y = relu(x W1^T + b1) W2^T + b2, the TransformerBlock's nn.Sequential(Linear, ReLU(inplace), Linear) (model.py:25-29,36),
  * x[M][D], W1[F][D], b1[F], W2[D][F], b2[D] in nn.Linear's own layouts; fp32 products and sums.  Forward: one launch;

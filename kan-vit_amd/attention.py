@@ -217,3 +217,14 @@ class MSA(torch.nn.Module):
         qkv = grouped.run_qkv(self.q_mappings, self.k_mappings, self.v_mappings, sequences.reshape(b * n, d))
         return ops.attention_packed(qkv.view(b, n, 3, self.n_heads, self.d_head), causal=False,
                                     scale=1.0 / (self.d_head ** 0.5))
+
+    def forward_cls(self, sequences):
+        """forward(sequences)[:, 0] -> [B, d], the class-token row alone (the head of a ViT reads nothing else of its last block):
+        the q layers run on the B class rows, the k and v layers on all rows (two grouped launches with their own timer tags), and
+        every head attends with its one query (kanvit.ops.attention_q1: exact fp32, also under autocast)."""
+        b, n, d = sequences.shape
+        q0 = grouped.run_projections([self.q_mappings], sequences[:, 0], tag="qcls")
+        kv = grouped.run_projections([self.k_mappings, self.v_mappings], sequences.reshape(b * n, d), tag="kv")
+        o = ops.attention_q1(q0.view(b, self.n_heads, self.d_head), kv.view(b, n, 2, self.n_heads, self.d_head),
+                             scale=1.0 / (self.d_head ** 0.5))
+        return o.view(b, d)

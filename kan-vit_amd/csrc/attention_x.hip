@@ -936,9 +936,308 @@ int xb_launch_bwd(const AttnXArgs& a, hipStream_t st) {
     return 0;
 }
 
+// ---- single-query attention (kanvit_attn_q1_*): ONE query per (batch, head) against all Nk keys and values ------------------
+// The head of a ViT reads only the class token, so its last block needs one attention row per head.  With one query there is no
+// matrix product left: the forward is a pass over K (scores) and a pass over V (output), the backward one pass that reads K and V
+// and writes dK and dV -- plain fp32 on the vector pipe, HBM-bound.
+//   work-group  256 threads = 16 lane groups of 16 lanes for one (batch, head); lane group g takes the keys j = g, g + 16, ...
+//   lane        `sub` of a group holds the columns (t*16 + sub)*V .. + V of a row, t < ceil(D / (16 V)): one V-wide load per lane,
+//               a group reads 16*V consecutive floats of a row (V = 4: 256 bytes)
+//   sums        over d inside a group by four xor-shuffles; over the keys first inside a lane group in key order, then over the 16
+//               groups in group order through the LDS: one fixed order, no atomics, bitwise reproducible
+// V = 4 needs D % 4 == 0 and 16-byte aligned rows, V = 2 (D is even) 8-byte aligned rows, V = 1 takes anything.
+// The probabilities go through their own output p[B][H][Nk]: raw scores, then exp(s - max), then the normalised values, so any Nk
+// is served without an LDS bound.  A thread reads back only what the barrier before it has made visible.
+struct AttnQ1Args {
+    const float* q;        // [B][H][D] through qsb, qsh
+    const float* k;        // [B][H][Nk][D] through ksb, ksh, ksn
+    const float* v;
+    const float* o_in;     // backward: the forward's o, through osb, osh
+    const float* d_o;      // through osb, osh
+    float* o;
+    float* p;              // [B][H][Nk] contiguous
+    float* dq;
+    float* dk;
+    float* dv;
+    long long qsb, qsh, ksb, ksh, ksn, vsb, vsh, vsn, osb, osh;
+    int H, Nk, D;
+    float scale;
+};
+
+constexpr int Q1_THR = 256, Q1_GROUPS = Q1_THR / 16;
+
+template <int V>
+struct Q1Frag {
+    static constexpr int T = KANVIT_ATTN_X_MAX_D / (16 * V);
+    float f[T][V];
+};
+
+template <int V>
+__device__ __forceinline__ void q1_zero(Q1Frag<V>& r) {
+#pragma unroll
+    for (int t = 0; t < Q1Frag<V>::T; ++t)
+#pragma unroll
+        for (int e = 0; e < V; ++e) r.f[t][e] = 0.0f;
+}
+
+// the lane's columns of one row (zero past D)
+template <int V>
+__device__ __forceinline__ void q1_load(Q1Frag<V>& r, const float* __restrict__ row, int sub, int D) {
+#pragma unroll
+    for (int t = 0; t < Q1Frag<V>::T; ++t) {
+        const int c = (t * 16 + sub) * V;
+        if (c < D) {
+            if constexpr (V == 4) {
+                const f32x4 u = *reinterpret_cast<const f32x4*>(row + c);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) r.f[t][e] = u[e];
+            } else if constexpr (V == 2) {
+                const float2 u = *reinterpret_cast<const float2*>(row + c);
+                r.f[t][0] = u.x;
+                r.f[t][1] = u.y;
+            } else {
+                r.f[t][0] = row[c];
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < V; ++e) r.f[t][e] = 0.0f;
+        }
+    }
+}
+
+// row[c] = mul * r for the lane's columns
+template <int V>
+__device__ __forceinline__ void q1_store(float* __restrict__ row, const Q1Frag<V>& r, float mul, int sub, int D) {
+#pragma unroll
+    for (int t = 0; t < Q1Frag<V>::T; ++t) {
+        const int c = (t * 16 + sub) * V;
+        if (c < D) {
+            if constexpr (V == 4) {
+                const f32x4 u = {mul * r.f[t][0], mul * r.f[t][1], mul * r.f[t][2], mul * r.f[t][3]};
+                *reinterpret_cast<f32x4*>(row + c) = u;
+            } else if constexpr (V == 2) {
+                *reinterpret_cast<float2*>(row + c) = make_float2(mul * r.f[t][0], mul * r.f[t][1]);
+            } else {
+                row[c] = mul * r.f[t][0];
+            }
+        }
+    }
+}
+
+// sum over d of a * b, the same value in all 16 lanes of the group
+template <int V>
+__device__ __forceinline__ float q1_dot(const Q1Frag<V>& a, const Q1Frag<V>& b) {
+    float s = 0.0f;
+#pragma unroll
+    for (int t = 0; t < Q1Frag<V>::T; ++t)
+#pragma unroll
+        for (int e = 0; e < V; ++e) s = fmaf(a.f[t][e], b.f[t][e], s);
+    s += __shfl_xor(s, 8);
+    s += __shfl_xor(s, 4);
+    s += __shfl_xor(s, 2);
+    s += __shfl_xor(s, 1);
+    return s;
+}
+
+template <int V>
+__device__ __forceinline__ void q1_axpy(Q1Frag<V>& acc, float a, const Q1Frag<V>& x) {
+#pragma unroll
+    for (int t = 0; t < Q1Frag<V>::T; ++t)
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc.f[t][e] = fmaf(a, x.f[t][e], acc.f[t][e]);
+}
+
+// out[c] = mul * sum over the 16 lane groups, in group order, of their partial rows (red: [Q1_GROUPS][KANVIT_ATTN_X_MAX_D])
+template <int V>
+__device__ __forceinline__ void q1_reduce_groups(float* __restrict__ red, const Q1Frag<V>& acc, float* __restrict__ out, float mul,
+                                                 int tid, int D) {
+    const int sub = tid & 15, grp = tid >> 4;
+#pragma unroll
+    for (int t = 0; t < Q1Frag<V>::T; ++t) {
+        const int c = (t * 16 + sub) * V;
+        if (c < D) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) red[grp * KANVIT_ATTN_X_MAX_D + c + e] = acc.f[t][e];
+        }
+    }
+    __syncthreads();
+    if (tid < D) {
+        float s = 0.0f;
+#pragma unroll
+        for (int g = 0; g < Q1_GROUPS; ++g) s += red[g * KANVIT_ATTN_X_MAX_D + tid];
+        out[tid] = mul * s;
+    }
+}
+
+// maximum (IS_MAX) or sum of one value per thread over the work-group, the same bits in every thread; wred: [Q1_THR / 64]
+template <bool IS_MAX>
+__device__ __forceinline__ float q1_block_reduce(float x, float* __restrict__ wred, int tid) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float y = __shfl_xor(x, m);
+        x = IS_MAX ? fmaxf(x, y) : x + y;
+    }
+    __syncthreads();                 // the previous use of wred is over
+    if ((tid & 63) == 0) wred[tid >> 6] = x;
+    __syncthreads();
+    float r = wred[0];
+#pragma unroll
+    for (int w = 1; w < Q1_THR / 64; ++w) r = IS_MAX ? fmaxf(r, wred[w]) : r + wred[w];
+    return r;
+}
+
+template <int V>
+__global__ __launch_bounds__(Q1_THR) void attn_q1_fwd_kernel(const AttnQ1Args a) {
+    __shared__ float red[Q1_GROUPS * KANVIT_ATTN_X_MAX_D];
+    __shared__ float wred[Q1_THR / 64];
+    const int tid = threadIdx.x, sub = tid & 15, grp = tid >> 4;
+    const long long bh = blockIdx.x, bi = bh / a.H, hi = bh - bi * a.H;
+    const int D = a.D, Nk = a.Nk;
+    const float* kb = a.k + bi * a.ksb + hi * a.ksh;
+    const float* vb = a.v + bi * a.vsb + hi * a.vsh;
+    float* pb = a.p + bh * Nk;
+
+    Q1Frag<V> qf;
+    q1_load<V>(qf, a.q + bi * a.qsb + hi * a.qsh, sub, D);
+
+    // scores: s_j = scale q.k_j, kept in p; the maximum over the keys
+    float mx = -INFINITY;
+    for (int j = grp; j < Nk; j += Q1_GROUPS) {
+        Q1Frag<V> kf;
+        q1_load<V>(kf, kb + (long long)j * a.ksn, sub, D);
+        const float s = a.scale * q1_dot<V>(qf, kf);
+        if (sub == 0) pb[j] = s;
+        mx = fmaxf(mx, s);
+    }
+    mx = q1_block_reduce<true>(mx, wred, tid);      // its barriers also publish the scores
+
+    float sum = 0.0f;
+    for (int j = tid; j < Nk; j += Q1_THR) {
+        const float e = expf(pb[j] - mx);
+        pb[j] = e;
+        sum += e;
+    }
+    sum = q1_block_reduce<false>(sum, wred, tid);   // >= 1: the key of the maximum contributes exp(0)
+    const float inv = 1.0f / sum;
+
+    Q1Frag<V> oacc;
+    q1_zero<V>(oacc);
+    for (int j = grp; j < Nk; j += Q1_GROUPS) {
+        Q1Frag<V> vf;
+        q1_load<V>(vf, vb + (long long)j * a.vsn, sub, D);
+        q1_axpy<V>(oacc, pb[j] * inv, vf);
+    }
+    q1_reduce_groups<V>(red, oacc, a.o + bi * a.osb + hi * a.osh, 1.0f, tid, D);      // its barrier: every read of exp(s - max) is done
+    for (int j = tid; j < Nk; j += Q1_THR) pb[j] *= inv;                             // the thread that wrote exp(s - max)[j]
+}
+
+// one pass: dP_j = do.v_j, ds_j = p_j (dP_j - delta) with delta = sum_j p_j dP_j = do.o, dv_j = p_j do, dk_j = scale ds_j q,
+// dq = scale sum_j ds_j k_j
+template <int V>
+__global__ __launch_bounds__(Q1_THR) void attn_q1_bwd_kernel(const AttnQ1Args a) {
+    __shared__ float red[Q1_GROUPS * KANVIT_ATTN_X_MAX_D];
+    const int tid = threadIdx.x, sub = tid & 15, grp = tid >> 4;
+    const long long bh = blockIdx.x, bi = bh / a.H, hi = bh - bi * a.H;
+    const int D = a.D, Nk = a.Nk;
+    const float* kb = a.k + bi * a.ksb + hi * a.ksh;
+    const float* vb = a.v + bi * a.vsb + hi * a.vsh;
+    float* dkb = a.dk + bi * a.ksb + hi * a.ksh;
+    float* dvb = a.dv + bi * a.vsb + hi * a.vsh;
+    const float* pb = a.p + bh * Nk;
+
+    Q1Frag<V> qf, dof, of;
+    q1_load<V>(qf, a.q + bi * a.qsb + hi * a.qsh, sub, D);
+    q1_load<V>(dof, a.d_o + bi * a.osb + hi * a.osh, sub, D);
+    q1_load<V>(of, a.o_in + bi * a.osb + hi * a.osh, sub, D);
+    const float delta = q1_dot<V>(dof, of);
+
+    Q1Frag<V> dqacc;
+    q1_zero<V>(dqacc);
+    for (int j = grp; j < Nk; j += Q1_GROUPS) {
+        Q1Frag<V> kf, vf;
+        q1_load<V>(vf, vb + (long long)j * a.vsn, sub, D);
+        q1_load<V>(kf, kb + (long long)j * a.ksn, sub, D);
+        const float pj = pb[j];
+        const float ds = pj * (q1_dot<V>(dof, vf) - delta);
+        q1_store<V>(dvb + (long long)j * a.vsn, dof, pj, sub, D);
+        q1_store<V>(dkb + (long long)j * a.ksn, qf, a.scale * ds, sub, D);
+        q1_axpy<V>(dqacc, ds, kf);
+    }
+    q1_reduce_groups<V>(red, dqacc, a.dq + bi * a.qsb + hi * a.qsh, a.scale, tid, D);
+}
+
+int q1_check(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const char* who) {
+    if (!d || !e) return kv_fail(KANVIT_EINVAL, "%s: null descriptor", who);
+    if (d->B < 0 || d->H < 1 || e->Nk < 1 || d->D < 1) return kv_fail(KANVIT_EINVAL, "%s: bad sizes", who);
+    if (d->N != 1) return kv_fail(KANVIT_EINVAL, "%s: q_len=%d, this entry takes ONE query per head (kanvit_attn_x_* take any)", who, d->N);
+    if (d->D > KANVIT_ATTN_X_MAX_D || (d->D & 1)) return kv_fail(KANVIT_EINVAL, "%s: D=%d must be even and <= %d", who, d->D, KANVIT_ATTN_X_MAX_D);
+    if ((long long)d->B * d->H > 0x7fffffffLL) return kv_fail(KANVIT_EINVAL, "%s: B*H too large", who);
+    if (!(d->scale == d->scale) || d->scale - d->scale != 0.0f) return kv_fail(KANVIT_EINVAL, "%s: scale must be finite", who);
+    if (d->causal || e->mask) return kv_fail(KANVIT_EINVAL, "%s: no causal / mask form (kanvit_attn_x_* have them)", who);
+    if (d->flags) return kv_fail(KANVIT_EINVAL, "%s: flags=%d: one mode, exact fp32 (KANVIT_FLAG_BF16_MFMA is not taken; pass no flag)", who, d->flags);
+    return 0;
+}
+
+AttnQ1Args q1_args(const kanvit_attn_desc* d, const kanvit_attn_ext* e) {
+    AttnQ1Args a{};
+    a.H = d->H; a.Nk = e->Nk; a.D = d->D; a.scale = d->scale;
+    a.qsb = d->q_stride_b; a.qsh = d->q_stride_h;
+    a.ksb = d->k_stride_b; a.ksh = d->k_stride_h; a.ksn = d->k_stride_n;
+    a.vsb = d->v_stride_b; a.vsh = d->v_stride_h; a.vsn = d->v_stride_n;
+    a.osb = d->o_stride_b; a.osh = d->o_stride_h;
+    return a;
+}
+
+// widest row piece every operand allows: 4 floats (16-byte rows), 2 (D is even: 8-byte rows) or 1
+int q1_width(const AttnQ1Args& a, std::initializer_list<const void*> ptrs) {
+    long long m = a.D;
+    for (long long sd : {a.qsb, a.qsh, a.ksb, a.ksh, a.ksn, a.vsb, a.vsh, a.vsn, a.osb, a.osh}) m |= sd;
+    uintptr_t pm = 0;
+    for (const void* p : ptrs) pm |= (uintptr_t)p;
+    if (m % 4 == 0 && pm % 16 == 0) return 4;
+    if (m % 2 == 0 && pm % 8 == 0) return 2;
+    return 1;
+}
+
 }  // namespace
 
 extern "C" {
+
+int kanvit_attn_q1_fwd(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const float* q, const float* k, const float* v, float* o,
+                       float* p, void* stream) {
+    if (int rc = q1_check(d, e, "kanvit_attn_q1_fwd")) return rc;
+    if (d->B == 0) return 0;
+    if (!q || !k || !v || !o || !p) return kv_fail(KANVIT_EINVAL, "kanvit_attn_q1_fwd: null q/k/v/o/p");
+    AttnQ1Args a = q1_args(d, e);
+    a.q = q; a.k = k; a.v = v; a.o = o; a.p = p;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(d->B * d->H));
+    switch (q1_width(a, {q, k, v})) {
+        case 4: hipLaunchKernelGGL(attn_q1_fwd_kernel<4>, grid, dim3(Q1_THR), 0, st, a); break;
+        case 2: hipLaunchKernelGGL(attn_q1_fwd_kernel<2>, grid, dim3(Q1_THR), 0, st, a); break;
+        default: hipLaunchKernelGGL(attn_q1_fwd_kernel<1>, grid, dim3(Q1_THR), 0, st, a); break;
+    }
+    KV_LAUNCH_CHECK("attn_q1_fwd_kernel");
+    return 0;
+}
+
+int kanvit_attn_q1_bwd(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const float* q, const float* k, const float* v, const float* o,
+                       const float* p, const float* d_o, float* dq, float* dk, float* dv, void* stream) {
+    if (int rc = q1_check(d, e, "kanvit_attn_q1_bwd")) return rc;
+    if (d->B == 0) return 0;
+    if (!q || !k || !v || !o || !p || !d_o || !dq || !dk || !dv) return kv_fail(KANVIT_EINVAL, "kanvit_attn_q1_bwd: null argument");
+    AttnQ1Args a = q1_args(d, e);
+    a.q = q; a.k = k; a.v = v; a.o_in = o; a.p = const_cast<float*>(p); a.d_o = d_o; a.dq = dq; a.dk = dk; a.dv = dv;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(d->B * d->H));
+    switch (q1_width(a, {q, k, v, o, d_o, dq, dk, dv})) {
+        case 4: hipLaunchKernelGGL(attn_q1_bwd_kernel<4>, grid, dim3(Q1_THR), 0, st, a); break;
+        case 2: hipLaunchKernelGGL(attn_q1_bwd_kernel<2>, grid, dim3(Q1_THR), 0, st, a); break;
+        default: hipLaunchKernelGGL(attn_q1_bwd_kernel<1>, grid, dim3(Q1_THR), 0, st, a); break;
+    }
+    KV_LAUNCH_CHECK("attn_q1_bwd_kernel");
+    return 0;
+}
 
 int kanvit_attn_x_fwd(const kanvit_attn_desc* d, const kanvit_attn_ext* e, const float* q, const float* k, const float* v, float* o,
                       float* lse, void* stream) {

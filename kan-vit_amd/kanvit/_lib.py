@@ -114,6 +114,8 @@ SYMBOLS = {
     "kanvit_attn_x_bwd_workspace": (C.c_size_t, [C.POINTER(AttnDesc), C.POINTER(AttnExt)]),
     "kanvit_attn_x_bwd": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnExt), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_attn_probs": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnExt), _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P]),
+    "kanvit_attn_q1_fwd": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnExt), _P, _P, _P, _P, _P, _P]),
+    "kanvit_attn_q1_bwd": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(AttnExt), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "kanvit_addln_fwd": (C.c_int, [C.c_int64, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "kanvit_addln_fwd_ex": (C.c_int, [C.c_int64, C.c_int, C.c_float, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     "kanvit_addln_bwd_ex": (C.c_int, [C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
@@ -165,14 +167,17 @@ def py_switches() -> dict:
       no_lnff      KANVIT_NO_LNFF         separate add+LayerNorm in front of the fused small feed-forward
       no_ff_epi    KANVIT_NO_FF_EPILOGUE  stock threshold_backward + sum(0) instead of the fused ReLU-mask + bias-gradient pass
       no_dfreq_w   KANVIT_NO_DFREQ_W      SineKAN d loss / d freq always through the input-gradient kernel (ops._kan_backward)
-      no_patch_bw  KANVIT_NO_PATCH_BW     patch-embedding weight gradient on a transient patch matrix instead of gathering from the images"""
+      no_patch_bw  KANVIT_NO_PATCH_BW     patch-embedding weight gradient on a transient patch matrix instead of gathering from the images
+      no_cls_tail  KANVIT_NO_CLS_TAIL     the last block computes every row again instead of the class-token row alone
+                                          (TransformerBlock.run_cls, model.py)"""
     global _py_switches
     if _py_switches is None:
         _py_switches = {"ff": os.environ.get("KANVIT_FF", ""), "no_ff_small": int(bool(os.environ.get("KANVIT_NO_FF_SMALL"))),
                         "no_lnff": int(bool(os.environ.get("KANVIT_NO_LNFF"))),
                         "no_ff_epi": int(bool(os.environ.get("KANVIT_NO_FF_EPILOGUE"))),
                         "no_dfreq_w": int(bool(os.environ.get("KANVIT_NO_DFREQ_W"))),
-                        "no_patch_bw": int(bool(os.environ.get("KANVIT_NO_PATCH_BW")))}
+                        "no_patch_bw": int(bool(os.environ.get("KANVIT_NO_PATCH_BW"))),
+                        "no_cls_tail": int(bool(os.environ.get("KANVIT_NO_CLS_TAIL")))}
     return _py_switches
 
 
@@ -181,7 +186,7 @@ def active_config() -> str:
     library's (KvConfig) followed by the Python-side ones (py_switches)."""
     ps = py_switches()
     alt = f" lib={LIB_PATH}" if os.environ.get("KANVIT_LIB") else ""
-    return lib().kanvit_config().decode() + f" py_ff={ps['ff'] or 'default'} py_no_ff_small={ps['no_ff_small']} py_no_lnff={ps['no_lnff']} py_no_ff_epi={ps['no_ff_epi']} py_no_dfreq_w={ps['no_dfreq_w']} py_no_patch_bw={ps['no_patch_bw']}" + alt
+    return lib().kanvit_config().decode() + f" py_ff={ps['ff'] or 'default'} py_no_ff_small={ps['no_ff_small']} py_no_lnff={ps['no_lnff']} py_no_ff_epi={ps['no_ff_epi']} py_no_dfreq_w={ps['no_dfreq_w']} py_no_patch_bw={ps['no_patch_bw']}" + alt + f" py_no_cls_tail={ps['no_cls_tail']}"
 
 
 def reload_config() -> str:

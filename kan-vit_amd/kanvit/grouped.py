@@ -96,23 +96,23 @@ def run_qkv(q_layers: Sequence, k_layers: Sequence, v_layers: Sequence, x2d: tor
 
     Equivalent to the reference's per-sample, per-head loop (attention.py:188-197) because every
     layer acts row-wise."""
-    H = len(q_layers)
-    layers = list(q_layers) + list(k_layers) + list(v_layers)
-    # one grouped launch has ONE base activation (kanvit_layer_desc.base_act): layers whose activations differ (swapped after
-    # construction) run one launch each, on their own head's columns
-    acts = {ops.base_activation_code(m.base_activation) for m in layers
-            if hasattr(m, "base_activation") and getattr(m, "use_base_update", True)}
-    if len(acts) > 1:
-        dh = x2d.shape[1] // H
-        return torch.cat([run_single(m, x2d[:, (g % H) * dh:(g % H + 1) * dh]) for g, m in enumerate(layers)], dim=1)
+    return run_projections([q_layers, k_layers, v_layers], x2d)
+
+
+def pack_projections(projections: Sequence[Sequence]):
+    """(cfg, w, bparams, bias) of ONE grouped launch over P projections of H per-head layers each: groups = P*H, x_group_mod = H,
+    group g = proj*H + head.  Pure packing (differentiable torch ops on the layers' parameters), no launch."""
+    H = len(projections[0])
+    assert all(len(p) == H for p in projections), "every projection has one layer per head"
+    layers = [m for p in projections for m in p]
     if isinstance(layers[0], torch.nn.Linear):
         cfg0 = linear_cfg(layers[0])
     elif hasattr(type(layers[0]), "kan_pack_grouped") and "layers" in layers[0].kan_cfg.__code__.co_varnames:
         cfg0 = layers[0].kan_cfg(layers)          # family whose flags depend on all the layers (efficient-KAN knot tables)
     else:
         cfg0 = layers[0].kan_cfg()
-    cfg = replace(cfg0, groups=3 * H, x_group_mod=H)
-    # Pack ALL 3*H layers with one stack + one layout transform (a handful of launches) instead of a
+    cfg = replace(cfg0, groups=len(layers), x_group_mod=H)
+    # Pack ALL P*H layers with one stack + one layout transform (a handful of launches) instead of a
     # permute-copy per head (3*H launches forward and again backward: 880 tiny kernels per ViT-B step).
     if isinstance(layers[0], torch.nn.Linear):
         w = stack_params([m.weight for m in layers], perm=(1, 0))      # [g, I, O]: nn.Linear keeps [O, I]
@@ -120,11 +120,28 @@ def run_qkv(q_layers: Sequence, k_layers: Sequence, v_layers: Sequence, x2d: tor
         bias = None if layers[0].bias is None else stack_params([m.bias for m in layers])
     else:
         w, bp, bias = type(layers[0]).kan_pack_grouped(layers)
+    return cfg, w, bp, bias
+
+
+def run_projections(projections: Sequence[Sequence], x2d: torch.Tensor, tag: str = None) -> torch.Tensor:
+    """x2d[M, H*dh] -> y[M, P*H*dh] for P projections (lists of H per-head layers: [q, k, v], [k, v], [q], ...) in ONE grouped
+    launch; column block g = proj*H + head holds layer g's output.  `tag` names the launch for the kernel timer (kanvit.ops.kan_layer);
+    the q|k|v launch of run_qkv keeps the default "qkv"."""
+    H = len(projections[0])
+    layers = [m for p in projections for m in p]
+    # one grouped launch has ONE base activation (kanvit_layer_desc.base_act): layers whose activations differ (swapped after
+    # construction) run one launch each, on their own head's columns
+    acts = {ops.base_activation_code(m.base_activation) for m in layers
+            if hasattr(m, "base_activation") and getattr(m, "use_base_update", True)}
+    if len(acts) > 1:
+        dh = x2d.shape[1] // H
+        return torch.cat([run_single(m, x2d[:, (g % H) * dh:(g % H + 1) * dh]) for g, m in enumerate(layers)], dim=1)
+    cfg, w, bp, bias = pack_projections(projections)
     if hasattr(layers[0], "kan_ln") and layers[0].kan_ln() is not None and ops.ln_fusable(cfg, x2d.shape[0]):
         gamma = stack_params([l.kan_ln().weight for l in layers])
         beta = stack_params([l.kan_ln().bias for l in layers])
-        return ops.kan_layer_ln(x2d, w, cfg, torch.cat([bp, gamma, beta], dim=1), bias, layers[0].kan_ln().eps)
+        return ops.kan_layer_ln(x2d, w, cfg, torch.cat([bp, gamma, beta], dim=1), bias, layers[0].kan_ln().eps, tag=tag)
     u = None
     if hasattr(layers[0], "kan_u_grouped"):
         u = type(layers[0]).kan_u_grouped(layers, x2d, H)
-    return ops.kan_layer(x2d, w, cfg, u=u, bparams=bp, bias=bias)
+    return ops.kan_layer(x2d, w, cfg, u=u, bparams=bp, bias=bias, tag=tag)

@@ -182,7 +182,7 @@ class _KanLayerFn(torch.autograd.Function):
 
     @staticmethod
     @_fwd_f32
-    def forward(ctx, x, u, w, bparams, bias, cfg: LayerCfg):
+    def forward(ctx, x, u, w, bparams, bias, cfg: LayerCfg, tag: Optional[str] = None):
         for n, t in (("x", x), ("u", u), ("w", w), ("bparams", bparams), ("bias", bias)):
             _require_gpu_f32(n, t)
         x = x.contiguous()
@@ -199,7 +199,8 @@ class _KanLayerFn(torch.autograd.Function):
             raise KanvitError(f"u shape {tuple(u.shape)} != {(M, cfg.groups * cfg.I)}")
         y = torch.empty(M, cfg.groups * cfg.O, device=x.device, dtype=torch.float32)
         d = _desc(cfg, M, ldx, cfg.groups * cfg.I, cfg.groups * cfg.O, 0 if bparams is None else bparams.shape[1])
-        tag = ("qkv" if cfg.groups > 1 else "layer") + "_fwd" + ("_bf16" if cfg.flags & _lib.FLAG_BF16_MFMA else "")
+        ctx.tag = tag
+        tag = _tag_prefix(cfg, tag) + "_fwd" + ("_bf16" if cfg.flags & _lib.FLAG_BF16_MFMA else "")
         with torch.cuda.device(x.device):
             nbytes = int(_lib.lib().kanvit_layer_fwd_workspace(C.byref(d)))
             ws = _workspace(nbytes, x.device) if nbytes else None
@@ -218,10 +219,16 @@ class _KanLayerFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, u, w, bparams = ctx.saved_tensors
         return _kan_backward(ctx.cfg, x, u if ctx.has_u else None, w, bparams, dy.float().contiguous(), ctx.needs_input_grad[:5],
-                             ctx.has_u, ctx.has_bias) + (None,)
+                             ctx.has_u, ctx.has_bias, tag=ctx.tag) + (None, None)
 
 
-def _kan_backward(cfg: "LayerCfg", x, u, w, bparams, dy, needs, has_u, has_bias, patch=None):
+def _tag_prefix(cfg: "LayerCfg", tag: Optional[str]) -> str:
+    """The timer tag stem of a KAN launch: "qkv" for a grouped launch and "layer" for a single layer, unless the caller names
+    its launch (bench.py takes a tag's flops and bytes from its first launch: launches of another shape need their own tag)."""
+    return tag or ("qkv" if cfg.groups > 1 else "layer")
+
+
+def _kan_backward(cfg: "LayerCfg", x, u, w, bparams, dy, needs, has_u, has_bias, patch=None, tag=None):
     """Gradients of one fused KAN launch w.r.t. (x, u, w, bparams, bias): the C-ABI input-gradient and weight-gradient calls.
 
     patch = (PatchDesc, M): x is the NCHW image batch and dy the token-sequence gradient [B, P + pre, O]; the weight-gradient
@@ -234,6 +241,7 @@ def _kan_backward(cfg: "LayerCfg", x, u, w, bparams, dy, needs, has_u, has_bias,
         pd = None
         M, ldx = x.shape
     need_x, need_u, need_w, need_bp, need_b = needs
+    stem = _tag_prefix(cfg, tag)
     d = _desc(cfg, M, ldx, cfg.groups * cfg.I, cfg.groups * cfg.O, 0 if bparams is None else bparams.shape[1])
     L = _lib.lib()
 
@@ -273,7 +281,7 @@ def _kan_backward(cfg: "LayerCfg", x, u, w, bparams, dy, needs, has_u, has_bias,
                 dpart = torch.empty(tiles, cfg.groups, cfg.G, device=x.device, dtype=torch.float32)
             nb_in = int(L.kanvit_layer_bwd_input_workspace(C.byref(d)))
             ws_in = _workspace(nb_in, x.device) if nb_in else None
-            with _timed(("qkv" if cfg.groups > 1 else "layer") + "_bwd_input" + ("_bf16" if nb_in else ""),
+            with _timed(stem + "_bwd_input" + ("_bf16" if nb_in else ""),
                         *_layer_cost(cfg, M, "bwd_input")):
                 check(L.kanvit_layer_bwd_input(C.byref(d), _ptr(x), _ptr(u), _ptr(w), _ptr(bparams), _ptr(dy),
                                                _ptr(dx), _ptr(du_buf), _ptr(dpart), _ptr(ws_in), C.c_size_t(nb_in),
@@ -289,12 +297,12 @@ def _kan_backward(cfg: "LayerCfg", x, u, w, bparams, dy, needs, has_u, has_bias,
                 dbp[:, :cfg.G] = dpart.sum(0)
         if need_w:
             dw = torch.empty_like(w)
-            weight_pass(d, dw, ("qkv" if cfg.groups > 1 else "layer") + "_bwd_weight" + ("_bf16" if cfg.flags & 1 else ""))
+            weight_pass(d, dw, stem + "_bwd_weight" + ("_bf16" if cfg.flags & 1 else ""))
         if freq_via_w:
             dq = LayerDesc(*[getattr(d, f) for f, _ in LayerDesc._fields_])
             dq.flags = cfg.flags | _lib.FLAG_SINE_DFREQ
             q = torch.empty_like(w)
-            weight_pass(dq, q, ("qkv" if cfg.groups > 1 else "layer") + "_bwd_freq" + ("_bf16" if cfg.flags & 1 else ""))
+            weight_pass(dq, q, stem + "_bwd_freq" + ("_bf16" if cfg.flags & 1 else ""))
             dbp = torch.zeros_like(bparams)
             dbp[:, :cfg.G] = q.mul_(w).view(cfg.groups, cfg.I, cfg.G, cfg.O).sum((1, 3))
         if need_b and has_bias:
@@ -327,7 +335,7 @@ class _KanLayerLnFn(torch.autograd.Function):
 
     @staticmethod
     @_fwd_f32
-    def forward(ctx, x, w, bparams, bias, cfg: LayerCfg):
+    def forward(ctx, x, w, bparams, bias, cfg: LayerCfg, tag: Optional[str] = None):
         for n, t in (("x", x), ("w", w), ("bparams", bparams), ("bias", bias)):
             _require_gpu_f32(n, t)
         x, w, bparams = x.contiguous(), w.contiguous(), bparams.contiguous()
@@ -342,7 +350,8 @@ class _KanLayerLnFn(torch.autograd.Function):
         y = torch.empty(M, cfg.groups * cfg.O, device=x.device, dtype=torch.float32)
         stats = torch.empty(M, cfg.x_group_mod, 2, device=x.device, dtype=torch.float32)
         d = _desc(cfg, M, ldx, cfg.groups * cfg.I, cfg.groups * cfg.O, bparams.shape[1])
-        tag = ("qkv" if cfg.groups > 1 else "layer") + "_fwd" + ("_bf16" if cfg.flags & _lib.FLAG_BF16_MFMA else "")
+        ctx.tag = tag
+        tag = _tag_prefix(cfg, tag) + "_fwd" + ("_bf16" if cfg.flags & _lib.FLAG_BF16_MFMA else "")
         with torch.cuda.device(x.device):
             nbytes = int(_lib.lib().kanvit_layer_fwd_workspace(C.byref(d)))
             ws = _workspace(nbytes, x.device) if nbytes else None
@@ -362,7 +371,7 @@ class _KanLayerLnFn(torch.autograd.Function):
         need_x, need_w, need_bp, need_b = ctx.needs_input_grad[:4]
         need_ln = need_x or need_bp
         dx, du, dw, _, db = _kan_backward(cfg, x, stats, w, bparams, dy.float().contiguous(),
-                                          (need_ln, need_ln, need_w, False, need_b), True, ctx.has_bias)
+                                          (need_ln, need_ln, need_w, False, need_b), True, ctx.has_bias, tag=ctx.tag)
         dbp = None
         if need_ln:
             # LayerNorm backward from du and the saved statistics: dx += ..., d gamma, d beta in one pass (kanvit_layer_ln_bwd)
@@ -378,15 +387,15 @@ class _KanLayerLnFn(torch.autograd.Function):
                                                 _ptr(dgb[0]), _ptr(dgb[1]), _ptr(ws), C.c_size_t(nbytes), _stream()), "kanvit_layer_ln_bwd")
             if need_bp:
                 dbp = torch.cat([torch.zeros(cfg.groups, G, device=x.device, dtype=torch.float32), dgb[0], dgb[1]], dim=1)
-        return (dx if need_x else None), dw, dbp, db, None
+        return (dx if need_x else None), dw, dbp, db, None, None
 
 
 def kan_layer_ln(x: torch.Tensor, w: torch.Tensor, cfg: LayerCfg, bparams: torch.Tensor, bias: Optional[torch.Tensor],
-                 eps: float) -> torch.Tensor:
+                 eps: float, tag: Optional[str] = None) -> torch.Tensor:
     """kan_layer() for FastKAN with the LayerNorm fused (call only when ln_fusable(cfg, M)); bparams = [centres | gamma | beta]."""
     from dataclasses import replace
     f = cfg.flags | _lib.FLAG_FUSED_LN | (_lib.FLAG_BF16_MFMA if _autocast_flags() else 0)
-    return _KanLayerLnFn.apply(x, w, bparams, bias, replace(cfg, flags=f, ln_eps=float(eps)))
+    return _KanLayerLnFn.apply(x, w, bparams, bias, replace(cfg, flags=f, ln_eps=float(eps)), tag)
 
 
 def patchify(images: torch.Tensor, n_patches: int) -> torch.Tensor:
@@ -468,15 +477,16 @@ def patch_embed(images, w, cfg: LayerCfg, bparams, bias, cls, pos, n_patches: in
 
 
 def kan_layer(x: torch.Tensor, w: torch.Tensor, cfg: LayerCfg, u: Optional[torch.Tensor] = None,
-              bparams: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Fused basis + contraction for `cfg.groups` layers sharing the rows of x (see include/kanvit.h).
+              bparams: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, tag: Optional[str] = None) -> torch.Tensor:
+    """Fused basis + contraction for `cfg.groups` layers sharing the rows of x (see include/kanvit.h).  `tag` names the launch
+    for the kernel timer ("<tag>_fwd", "<tag>_bwd_input", ...; default "qkv" for a grouped launch, "layer" for a single layer).
 
     Under ``torch.autocast('cuda', dtype=torch.bfloat16)`` the contraction is allowed onto the bf16 matrix cores
     (KANVIT_FLAG_BF16_MFMA); without autocast it is always the exact fp32 path."""
     if torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16 and not (cfg.flags & 1):
         from dataclasses import replace
         cfg = replace(cfg, flags=cfg.flags | _lib.FLAG_BF16_MFMA)
-    return _KanLayerFn.apply(x, u, w, bparams, bias, cfg)
+    return _KanLayerFn.apply(x, u, w, bparams, bias, cfg, tag)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -884,6 +894,64 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = 
               scale: Optional[float] = None) -> torch.Tensor:
     """Self-attention on q, k, v of shape (B, H, N, D); routing and autocast behaviour as attention_packed()."""
     return _AttnFn.apply(q, k, v, causal, q.shape[-1] ** -0.5 if scale is None else scale, _autocast_flags())
+
+
+class _AttnQ1Fn(torch.autograd.Function):
+    """q0[B, H, D] and kv[B, N, 2, H, D] (the layout the grouped k|v KAN launch writes) -> o[B, H, D]: one query per head
+    (kanvit_attn_q1_*).  The probabilities p[B, H, N] are the forward's second output inside the library and all the backward
+    needs besides o; dk and dv are written into one packed tensor of kv's layout, which the KAN backward reads as it is."""
+
+    @staticmethod
+    @_fwd_f32
+    def forward(ctx, q0, kv, scale: float):
+        _require_gpu_f32("q0", q0)
+        _require_gpu_f32("kv", kv)
+        if kv.dim() != 5 or kv.shape[2] != 2 or q0.dim() != 3 or (q0.shape[0], q0.shape[1], q0.shape[2]) != (kv.shape[0], kv.shape[3], kv.shape[4]):
+            raise KanvitError(f"attention_q1: q0 {tuple(q0.shape)} and kv {tuple(kv.shape)} are not [B, H, D] and [B, N, 2, H, D]")
+        q0, kv = q0.contiguous(), kv.contiguous()
+        B, N, _, H, D = kv.shape
+        o = torch.empty(B, H, D, device=kv.device, dtype=torch.float32)
+        p = torch.empty(B, H, N, device=kv.device, dtype=torch.float32)
+        d, e = _attn_q1_desc(q0, kv, o, scale)
+        # 2 flops per element of k and of v; k and v are read once, o and p are small
+        with torch.cuda.device(kv.device), _timed("attn_q1_fwd", 4 * B * H * N * D, 4 * B * H * (2 * N * D + N + 2 * D)):
+            check(_lib.lib().kanvit_attn_q1_fwd(C.byref(d), C.byref(e), _ptr(q0), _ptr(kv[:, :, 0]), _ptr(kv[:, :, 1]), _ptr(o), _ptr(p),
+                                                _stream()), "kanvit_attn_q1_fwd")
+        ctx.save_for_backward(q0, kv, o, p)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, do):
+        q0, kv, o, p = ctx.saved_tensors
+        do = do.float().contiguous()
+        B, N, _, H, D = kv.shape
+        dq = torch.empty_like(q0)
+        dkv = torch.empty_like(kv)
+        d, e = _attn_q1_desc(q0, kv, o, ctx.scale)
+        with torch.cuda.device(kv.device), _timed("attn_q1_bwd", 8 * B * H * N * D, 4 * B * H * (4 * N * D + N + 4 * D)):
+            check(_lib.lib().kanvit_attn_q1_bwd(C.byref(d), C.byref(e), _ptr(q0), _ptr(kv[:, :, 0]), _ptr(kv[:, :, 1]), _ptr(o), _ptr(p),
+                                                _ptr(do), _ptr(dq), _ptr(dkv[:, :, 0]), _ptr(dkv[:, :, 1]), _stream()), "kanvit_attn_q1_bwd")
+        return dq, dkv, None
+
+
+def _attn_q1_desc(q0, kv, o, scale: float):
+    """Descriptor pair of kanvit_attn_q1_*: contiguous q0, o [B, H, D] and the k / v halves of a contiguous kv[B, N, 2, H, D]."""
+    B, N, _, H, D = kv.shape
+    k = kv[:, :, 0]                  # [B, N, H, D]
+    d = AttnDesc(B, H, 1, D, 0, float(scale), 0, 0, q0.stride(0), q0.stride(1), 0, k.stride(0), k.stride(2), k.stride(1),
+                 k.stride(0), k.stride(2), k.stride(1), o.stride(0), o.stride(1), 0)
+    return d, _lib.AttnExt(N, 0, None, 0, 0, 0, 0)
+
+
+def attention_q1(q0: torch.Tensor, kv: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
+    """softmax(scale q0 k^T) v for ONE query per (sample, head): q0 [B, H, D] against kv [B, N, 2, H, D], the packed output of a
+    grouped k|v launch (k = kv[:, :, 0], v = kv[:, :, 1], read in place) -> o [B, H, D].  What the last block of a ViT needs: its
+    head reads the class token only.  D even and <= 128, any N >= 1; scale defaults to D ** -0.5.  Differentiable w.r.t. q0 and
+    kv (the gradient of kv comes back packed).  One mode: exact fp32, also under autocast (inputs are cast to float32);
+    bitwise reproducible; no host synchronisation.  B = 0 gives an empty result without a launch."""
+    return _AttnQ1Fn.apply(q0, kv, kv.shape[-1] ** -0.5 if scale is None else float(scale))
 
 
 def expand_attention_mask(mask: Optional[torch.Tensor], q: torch.Tensor, k: torch.Tensor) -> Optional[torch.Tensor]:

@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from attention import MSA, FlashAttention
-from kanvit import ops
+from kanvit import _lib, ops
 from kanvit.dense import feed_forward, ff_mode, ff_small_supported, ln_feed_forward
 from kanvit.ops import add_layernorm
 from models.cheby import ChebyKANLayer
@@ -68,6 +68,33 @@ class TransformerBlock(nn.Module):
         # (the unsplit library kernel fills 36 of 256 CUs: 2.2 ms -> 0.83 ms per call).
         b, n, d = x.shape
         return x, feed_forward(h2.reshape(b * n, d), self.ff[0], self.ff[2]).view(b, n, d)   # bias + ReLU in the GEMM epilogue
+
+
+    def run_cls(self, x, pending):
+        """The class-token row [B, d] of x + MSA(LN1(x)) + FF(LN2(.)) after the pending add, i.e. forward(x + pending)[:, 0]:
+        all the head of a ViT reads of its last block (model.py:166-169).  LN1 still runs on all rows (k and v need them); the
+        q layers, the attention, the residual, LN2 and the feed-forward run on the B class rows only (MSA.forward_cls).  Under
+        bf16 autocast the grouped q|k|v launch and the attention stay what they are in run() -- all rows, on the bf16 matrix
+        cores, the rounding points the bf16 results are specified with -- and LN2 + feed-forward take the class rows."""
+        x, h1 = add_layernorm(x, pending, self.norm1)
+        ybf = (x.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+        a0 = _FirstRow.apply(self.attn(h1)) if ybf else self.attn.forward_cls(h1)
+        s, h2 = add_layernorm(_FirstRow.apply(x), a0, self.norm2, y_bf16=ybf and ff_mode() != "bf16x3")
+        return s + feed_forward(h2, self.ff[0], self.ff[2])
+
+
+class _FirstRow(torch.autograd.Function):
+    """t[:, 0] of t [B, N, d] whose backward is ONE padding launch (g in row 0, zeros below) -- the one full-size pass the
+    gradient of the class row costs on its way back into the stream."""
+
+    @staticmethod
+    def forward(ctx, t):
+        ctx.n = t.shape[1]
+        return t[:, 0].contiguous()
+
+    @staticmethod
+    def backward(ctx, g):
+        return torch.nn.functional.pad(g.unsqueeze(1), (0, 0, 0, ctx.n - 1))
 
 
 class _ClsToken(torch.autograd.Function):
@@ -365,7 +392,15 @@ class VisionTransformer(nn.Module):
                 reg = self.linear_mapper.regularization_loss(rows, **reg_kw)
         out = self._embed(images, patches)
         pending = None
+        # the head reads the class token only: the last block computes that row alone (TransformerBlock.run_cls), except for the
+        # small geometries (launch-bound: they keep the one-launch LN2 + feed-forward) and when the regulariser is asked for
+        last = self.blocks[-1] if len(self.blocks) else None
+        cls_tail = (isinstance(last, TransformerBlock) and reg_kw is None and out.is_cuda and not _lib.py_switches()["no_cls_tail"]
+                    and not ff_small_supported(last.ff[0].in_features, last.ff[0].out_features))
         for blk in self.blocks:
+            if cls_tail and blk is last:
+                out = blk.run_cls(out, pending)
+                return self.mlp_head(out)
             if isinstance(blk, TransformerBlock) and reg_kw is not None:
                 out, pending, r = blk.run(out, pending, reg_kw)
                 reg = reg + r

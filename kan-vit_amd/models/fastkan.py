@@ -123,13 +123,14 @@ class FastKANLayer(nn.Module):
     @staticmethod
     def kan_u_grouped(layers, x2d, n_heads):
         """LayerNorm of every (projection, head) slice: normalise each head slice once, then apply
-        the 3*H affine pairs -> u[M, 3*H*dh], column block g = proj*H + head."""
+        the P*H affine pairs (P = len(layers) / H projections) -> u[M, P*H*dh], column block g = proj*H + head."""
         M = x2d.shape[0]
         dh = layers[0].input_dim
         xhat = F.layer_norm(x2d.view(M, n_heads, dh), (dh,), None, None, layers[0].layernorm.eps)
-        gamma = grouped.stack_params([l.layernorm.weight for l in layers]).view(1, 3, n_heads, dh)
-        beta = grouped.stack_params([l.layernorm.bias for l in layers]).view(1, 3, n_heads, dh)
-        return torch.addcmul(beta, xhat.unsqueeze(1), gamma).reshape(M, 3 * n_heads * dh)
+        P = len(layers) // n_heads                 # projections in the launch: q|k|v, or k|v, or q alone
+        gamma = grouped.stack_params([l.layernorm.weight for l in layers]).view(1, P, n_heads, dh)
+        beta = grouped.stack_params([l.layernorm.bias for l in layers]).view(1, P, n_heads, dh)
+        return torch.addcmul(beta, xhat.unsqueeze(1), gamma).reshape(M, P * n_heads * dh)
 
     def edge_activation_l1(self, x, include_base=False):
         """[out, in]: mean over the samples of |phi_{o,i}|, phi = sum_k exp(-((LN(x)_i - c_k)/h)^2) w[o, i*G + k] (+ the base
