@@ -491,6 +491,30 @@ int kanvit_relu_bwd_bias_bf16(int64_t M, int N, const void* dy_bf16, const void*
 int kanvit_split3_bf16(int64_t M, int K, const float* x, const float* bias, int relu, const void* mask_hi, int64_t mask_ld,
                        void* out, int pattern, void* stream);
 
+/* ---- batches from a GPU-resident uint8 dataset (kanvit/data.py; csrc/augment.hip) ---------------------------------------
+ * The reference's input pipeline (train.py:100-118: RandomHorizontalFlip, RandomCrop(size, padding) on the zero-padded uint8 image,
+ * ToTensor, Normalize) as one gather over a dataset that stays in HBM:
+ *   out[b][c][y][x] = lut[c][ images[idx[b]][sy][sx][c] ],  sy = y + dy - pad_y,  sx = x + dx - pad_x,  sx <- W - 1 - sx if flipped;
+ *                     lut[c][0] where (sy, sx) is outside the image (the zero padding, normalised).
+ * images [N][H][W][C] uint8 (NHWC, as the CIFAR / MNIST arrays come); labels [N] int64 or NULL; idx [B] int64 sample indices (any
+ * order, repeats allowed; each in [0, N): the CALLER checks that, an entry outside is not dereferenced and gives padding and label
+ * -1); lut [C][256] fp32, the normalised value of every byte, built by the host with the reference's fp32 operations (the kernel
+ * does no floating-point arithmetic: the output equals the CPU transform bit for bit); out [B][C][H][W] fp32 contiguous; y_out [B]
+ * = labels[idx[b]] or NULL; params_out [B][3] = the (dy, dx, flip) used, or NULL.
+ * (dy, dx, flip) depend on (seed, epoch, idx[b]) only -- not on B, the position in the batch or the rank.  With mix() the
+ * splitmix64 step (z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ * z ^ z >> 31), all mod 2^64:
+ *   h = mix(mix(mix(seed) + epoch) + idx),  dy = (h & 0xFFFFF) % (2 pad_y + 1),  dx = ((h >> 20) & 0xFFFFF) % (2 pad_x + 1),
+ *   flip = flip_enabled ? (h >> 40) & 1 : 0.          pad = 0, flip = 0 is the evaluation transform (normalise only).
+ * Stores are 16 bytes per lane where W % 4 == 0 and out is 16-byte aligned, 4 bytes otherwise (decided on the host).  One launch,
+ * no atomics, no workspace, no synchronisation: capturable.  KANVIT_EINVAL (named in kanvit_last_error) unless N >= 1, 1 <= C <= 4,
+ * 1 <= H, W <= 2^20, 0 <= pad_y <= H, 0 <= pad_x <= W, B >= 0, flip in {0, 1}; B = 0 launches nothing.
+ * kanvit_augment_u8_supported is the same shape check as a pure host function (1 / 0).  Additive: the ABI version stays 7. */
+int kanvit_augment_u8_supported(int64_t N, int H, int W, int C, int pad_y, int pad_x);
+int kanvit_augment_u8(const uint8_t* images, const int64_t* labels, const int64_t* idx, const float* lut, float* out, int64_t* y_out,
+                      int32_t* params_out, int64_t N, int64_t B, int H, int W, int C, int pad_y, int pad_x, int flip, uint64_t seed,
+                      uint64_t epoch, void* stream);
+
 /* ---- per-family named entry points (SURVEY.md section 8b naming) ----------------------------
  * kanvit_<family>_{fwd,bwd_input,bwd_weight} are kanvit_layer_* with d->family checked;
  * kanvit_<family>_qkv_* additionally require groups == 3 * x_group_mod (one launch for all

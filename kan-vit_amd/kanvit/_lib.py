@@ -125,6 +125,9 @@ SYMBOLS = {
     "kanvit_relu_bwd_bias": (C.c_int, [C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_relu_bwd_bias_bf16": (C.c_int, [C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_split3_bf16": (C.c_int, [C.c_int64, C.c_int, _P, _P, C.c_int, _P, C.c_int64, _P, C.c_int, _P]),
+    "kanvit_augment_u8_supported": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "kanvit_augment_u8": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_uint64, C.c_uint64, _P]),
 }
 for _f in FAMILY_NAMES:
     SYMBOLS[f"kanvit_{_f}_fwd"] = (C.c_int, _LAYER_FWD)

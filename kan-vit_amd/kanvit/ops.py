@@ -1100,3 +1100,54 @@ def add_layernorm(x: torch.Tensor, delta: Optional[torch.Tensor], norm: torch.nn
         s = x if delta is None else x + delta
         return s, norm(s)
     return _AddLayerNormFn.apply(x, delta, norm.weight, norm.bias, norm.eps, bool(y_bf16))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# batches from a GPU-resident uint8 dataset (kanvit/data.py; csrc/augment.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+def augment_u8(images: torch.Tensor, labels: Optional[torch.Tensor], idx: torch.Tensor, lut: torch.Tensor, pad=0, flip: bool = False,
+               seed: int = 0, epoch: int = 0, return_params: bool = False, out: Optional[torch.Tensor] = None):
+    """One batch out of a dataset that stays on the device as uint8: gather images[idx], random crop out of the zero-padded image,
+    random horizontal flip, ToTensor + Normalize through `lut` (data.make_lut), in one launch on the current stream (the reference's
+    transforms, train.py:100-118; semantics and the per-sample hash: include/kanvit.h).
+
+    images uint8 [N, H, W, C] or [N, H, W]; labels int64 [N] or None; idx int64 [B], every entry in [0, N) -- the CALLER checks that
+    (data.GpuDataset does, on the CPU, before the list goes to the device); lut float32 [C, 256]; pad an int or (pad_y, pad_x).
+    Returns x float32 [B, C, H, W] (and y int64 [B] when labels are given, and params int32 [B, 3] = (dy, dx, flip) with
+    return_params).  `out`: write into this contiguous [B, C, H, W] float32 tensor instead of allocating one."""
+    for name, t, dt in (("images", images, torch.uint8), ("labels", labels, torch.int64), ("idx", idx, torch.int64), ("lut", lut, torch.float32),
+                        ("out", out, torch.float32)):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise KanvitError(f"augment_u8: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+        if t.device != images.device:
+            raise KanvitError(f"augment_u8: {name} is on {t.device}, images on {images.device}")
+        if t.dtype != dt:
+            raise KanvitError(f"augment_u8: {name} has dtype {t.dtype}, expected {dt}")
+        if not t.is_contiguous():
+            raise KanvitError(f"augment_u8: {name} is not contiguous")
+    if images.dim() not in (3, 4):
+        raise KanvitError(f"augment_u8: images has shape {tuple(images.shape)}, expected [N, H, W, C] or [N, H, W]")
+    N, H, W = (int(v) for v in images.shape[:3])
+    Cn = int(images.shape[3]) if images.dim() == 4 else 1
+    pad_y, pad_x = (int(pad), int(pad)) if isinstance(pad, int) else (int(pad[0]), int(pad[1]))
+    if idx.dim() != 1:
+        raise KanvitError(f"augment_u8: idx has shape {tuple(idx.shape)}, expected [B]")
+    if labels is not None and tuple(labels.shape) != (N,):
+        raise KanvitError(f"augment_u8: labels has shape {tuple(labels.shape)}, expected [{N}]")
+    if tuple(lut.shape) != (Cn, 256):
+        raise KanvitError(f"augment_u8: lut has shape {tuple(lut.shape)}, expected [{Cn}, 256]")
+    B = int(idx.shape[0])
+    if out is None:
+        out = torch.empty((B, Cn, H, W), device=images.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, Cn, H, W):
+        raise KanvitError(f"augment_u8: out has shape {tuple(out.shape)}, expected {(B, Cn, H, W)}")
+    y = torch.empty((B,), device=images.device, dtype=torch.int64) if labels is not None else None
+    params = torch.empty((B, 3), device=images.device, dtype=torch.int32) if return_params else None
+    with torch.cuda.device(images.device):
+        check(_lib.lib().kanvit_augment_u8(_ptr(images), _ptr(labels), _ptr(idx), _ptr(lut), _ptr(out), _ptr(y), _ptr(params), N, B, H, W, Cn,
+                                           pad_y, pad_x, int(bool(flip)), int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1), _stream()),
+              "kanvit_augment_u8")
+    res = (out,) + ((y,) if labels is not None else ()) + ((params,) if return_params else ())
+    return res[0] if len(res) == 1 else res

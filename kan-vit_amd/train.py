@@ -6,6 +6,7 @@ train.py:31-40), running on the MI355X kernels, with optional pure data parallel
     python train.py --model-type cheby --synthetic --epochs 1          # synthetic stream, no dataset needed
     python train.py --model-type cheby --synthetic --graph             # the whole step replayed from one HIP graph
     python train.py --model-type fast --synthetic --amp bf16           # bf16 autocast + kanvit kernels on the bf16 matrix cores
+    python train.py --model-type cheby --data-npz cifar100.npz         # real images from a GPU-resident uint8 dataset, no torchvision
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py --dp --synthetic ...
 
 Additions over the reference (none change a default): --synthetic / --image-size / --in-chans /
@@ -13,6 +14,8 @@ Additions over the reference (none change a default): --synthetic / --image-size
 --reg-activation / --reg-entropy (the sample-based KAN regulariser added to the step's loss), --grid-update-every
 (KANLinear.update_grid on the step's batch every N-th step), --grid-extend STEP:SIZE[,...] (grid extension: at the start of
 step STEP every KANLinear moves to SIZE grid intervals with its function kept),
+--data-npz / --no-augment / --crop-padding (the dataset lives on the GPU as uint8 and one kernel per batch gathers, crops, flips and
+normalises it: kanvit/data.py; the reference's transforms, train.py:100-118, without torchvision, workers or a copy per batch),
 --no-step-metrics (the per-step metrics stay on the device either way: one host sync per epoch instead of the
 reference's three per step, train.py:37,42-44).
 
@@ -22,6 +25,7 @@ carries the per-step loss trajectory."""
 import argparse
 import logging
 import os
+import time
 
 import torch
 from torch.optim import Adam
@@ -52,6 +56,40 @@ def cifar_loaders(batch, rank, world):
     mk = torch.utils.data.DataLoader
     return (mk(train, batch_size=batch, shuffle=sampler is None, sampler=sampler, num_workers=8, pin_memory=True),
             mk(test, batch_size=batch, shuffle=False, num_workers=8, pin_memory=True), sampler)
+
+
+def check_data_args(args):
+    """Contradictions among the data-source flags; parse() and main() both call it."""
+    if getattr(args, "data_npz", None) and args.synthetic:
+        raise SystemExit("--synthetic and --data-npz name two data sources; give one")
+    if getattr(args, "crop_padding", 4) < 0:
+        raise SystemExit(f"--crop-padding {args.crop_padding} is negative")
+
+
+def npz_datasets(args, device, want_test=True):
+    """--data-npz: (train, test or None) GpuDatasets.  --image-size / --in-chans left at their defaults follow the file (args is
+    updated); given values that contradict it, labels that --out-d does not cover and non-square images are refused.  Only the rank
+    that evaluates asks for the test split."""
+    from kanvit import data as kdata
+    blob = kdata.load_npz(args.data_npz)
+    x = blob["x_train"]
+    c, h, w = (x.shape[3] if x.ndim == 4 else 1), x.shape[1], x.shape[2]
+    if h != w:
+        raise SystemExit(f"--data-npz {args.data_npz}: images are {h}x{w}; the model takes square images (--image-size)")
+    for flag, name, default, have in (("--image-size", "image_size", 32, h), ("--in-chans", "in_chans", 3, c)):
+        if getattr(args, name) == default:
+            setattr(args, name, int(have))
+        elif getattr(args, name) != have:
+            raise SystemExit(f"{flag} {getattr(args, name)} contradicts --data-npz {args.data_npz}, whose images have {have}")
+    top = max(int(blob[k].max()) for k in ("y_train", "y_test") if k in blob)
+    if args.out_d <= top:
+        raise SystemExit(f"--out-d {args.out_d} does not cover the labels of --data-npz {args.data_npz} (largest: {top})")
+    augment = not args.no_augment
+    if augment and args.crop_padding > h:
+        raise SystemExit(f"--crop-padding {args.crop_padding} exceeds the image size {h}")
+    train = kdata.GpuDataset.from_arrays(blob, args.data_npz, "train", device, pad=args.crop_padding if augment else 0, flip=augment)
+    test = kdata.GpuDataset.from_arrays(blob, args.data_npz, "test", device) if want_test and "x_test" in blob else None
+    return train, test
 
 
 class _GraphedStep:
@@ -146,6 +184,7 @@ def extend_grid_and_swap(model, optimizer, x, grid_size):
 
 def main(args, batches=None, init_state=None):
     rank, world, local = 0, 1, 0
+    check_data_args(args)
     grid_extend = getattr(args, "grid_extend", None) or {}
     if grid_extend:
         from model import split_types
@@ -195,6 +234,9 @@ def main(args, batches=None, init_state=None):
         device = torch.device("cuda", torch.cuda.current_device())
     torch.cuda.set_device(device)           # the kernels launch on the model's device also with --device cuda:N
     torch.manual_seed(args.seed)
+    train_set = test_set = None
+    if batches is None and getattr(args, "data_npz", None):
+        train_set, test_set = npz_datasets(args, device, want_test=rank == 0)     # before the model: the geometry may come from the file
     chw = (args.in_chans, args.image_size, args.image_size)
     model = VisionTransformer(chw, n_patches=args.n_patches, n_blocks=args.n_blocks, d_hidden=args.d_hidden,
                               n_heads=args.n_heads, out_d=args.out_d, type=args.model_type)
@@ -255,14 +297,19 @@ def main(args, batches=None, init_state=None):
     step = eager_step
     per_rank = args.batch_size // world if args.dp else args.batch_size
     train_loader = test_loader = sampler = None
-    if batches is None and not args.synthetic:
+    if train_set is not None:
+        if test_set is not None:                # the evaluation transform: normalise only, in the file's order
+            test_loader = test_set.loader(per_rank, shuffle=False)
+    elif batches is None and not args.synthetic:
         train_loader, test_loader, sampler = cifar_loaders(per_rank, rank, world)
-    history = {"losses": [], "epoch_loss": []}
+    history = {"losses": [], "epoch_loss": [], "epoch_seconds": []}
     n_steps = 0
     model.train()
     for epoch in range(args.epochs):
         if batches is not None:
             loader, n_batches = batches, len(batches)
+        elif train_set is not None:             # order and augmentation are functions of (seed, epoch): the same on every rank
+            loader, n_batches = train_set.batches(per_rank, epoch, args.seed, rank, world), train_set.n_batches(per_rank, world)
         elif args.synthetic:
             loader = synthetic_loader(args.steps_per_epoch, per_rank, chw, args.out_d, device, args.seed + 1000 * epoch + rank)
             n_batches = args.steps_per_epoch
@@ -271,6 +318,7 @@ def main(args, batches=None, init_state=None):
                 sampler.set_epoch(epoch)            # a different shuffle per epoch, the same on every rank
             loader, n_batches = train_loader, len(train_loader)
         step_losses, ys, preds, probs = [], [], [], []
+        t_epoch = time.perf_counter()
         for x, y in loader:
             x, y = x.to(device, non_blocking=True), y.to(device, non_blocking=True)
             if args.graph and step is eager_step:
@@ -291,6 +339,7 @@ def main(args, batches=None, init_state=None):
             torch.distributed.all_reduce(losses)        # of rank means is the global-batch mean the reference would log
             losses /= world
         losses = losses.cpu()                   # the epoch's one host sync
+        history["epoch_seconds"].append(time.perf_counter() - t_epoch)     # host clock around work that ends in that sync
         history["losses"] += [float(v) for v in losses]
         train_loss = float(losses.sum() / max(n_batches, 1))
         history["epoch_loss"].append(train_loss)
@@ -373,7 +422,16 @@ def parse(argv=None):
                         "or --dp).  The replaced spline_weight parameters start with fresh Adam state, every other parameter keeps "
                         "its own; a --grid-update-every update due on the same step is skipped.  Default: never")
     p.add_argument('--no-tuned-gemms', action='store_true', help='library-default kernel selection for the stock GEMMs')
-    return p.parse_args(argv)
+    p.add_argument('--data-npz', type=str, default=None, metavar='PATH',
+                   help='train on this .npz (x_train uint8 [N,H,W,C] or [N,H,W], y_train; optional x_test, y_test, mean, std: '
+                        'kanvit/data.py), kept on the GPU as uint8; every batch is one gather + crop + flip + normalise kernel. '
+                        '--image-size and --in-chans follow the file when left at their defaults')
+    p.add_argument('--no-augment', action='store_true', help='with --data-npz: normalise only (no random crop, no flip)')
+    p.add_argument('--crop-padding', type=int, default=4,
+                   help="with --data-npz: zero padding of the random crop, the reference's RandomCrop(32, padding=4)")
+    args = p.parse_args(argv)
+    check_data_args(args)
+    return args
 
 
 if __name__ == "__main__":
