@@ -34,8 +34,14 @@ def _grid_facts(layers):
         row = g0[0].double()
         step = (row[-1] - row[0]) / (row.numel() - 1)              # the kernel derives h the same way
         ideal = row[0] + step * torch.arange(row.numel(), device=row.device, dtype=torch.float64)
-        tol = 2e-6 * (float(row.abs().max()) + 1.0)                # a few float32 ulps of the knot range
-        uniform = bool(float(step) > 0 and float((row - ideal).abs().max()) <= tol and bool((g0 == g0[0:1]).all()))
+        # The closed form evaluates the IDEAL grid row[0] + j*step, the Cox-de Boor kernels the stored knots: a knot that sits d off
+        # its ideal place moves the bases by up to ~0.65 d / step.  So the deviation is bounded RELATIVE TO THE SPACING (4e-6 of it:
+        # an eighth of the 2e-5 forward bound), and so is half a float32 ulp of the largest knot, which is what rounding makes of d on
+        # a table far from 0 for its spacing: grid_range [1000, 1001] / 5 stores knots 2.2e-4 of a spacing off and takes the
+        # Cox-de Boor kernels, grids within a few tens of spacings of 0 keep the closed form (profiles/basis_domain.md).
+        tol = 4e-6 * float(step)
+        off = max(float((row - ideal).abs().max()), float(row.abs().max()) * 2.0 ** -24)
+        uniform = bool(float(step) > 0 and off <= tol and bool((g0 == g0[0:1]).all()))
         equal = all(m.grid.shape == g0.shape and bool((m.grid == g0).all()) for m in layers[1:])
         if len(_GRID_FACTS) > 256:
             _GRID_FACTS.clear()
