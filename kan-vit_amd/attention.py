@@ -4,6 +4,8 @@ MSA keeps the reference's parameter layout ({q,k,v}_mappings.<head>.<layer keys>
 python loop over samples x heads (attention.py:188-202) by two kernel launches per block: one fused
 KAN launch that evaluates all 3*H per-head mappings on the batch-folded rows, and one attention
 launch over every (sample, head)."""
+from dataclasses import replace
+
 import torch
 from torch import nn
 
@@ -97,13 +99,32 @@ class MSA(torch.nn.Module):
 
     REGULARIZED_TYPES = ("efficientkan", "cheby", "fast")
 
+    def _qkv_layers(self, who=None):
+        """The 3*H per-head layers in the order of the grouped launch, q | k | v.  With `who` (update_grid / extend_grid) they must
+        be KANLinear layers that agree in what one grouped refit shares."""
+        layers = list(self.q_mappings) + list(self.k_mappings) + list(self.v_mappings)
+        l0 = layers[0]
+        if who is not None:
+            if not isinstance(l0, KANLinear):
+                raise NotImplementedError(f"{who}: MSA type '{self.type}' has no B-spline grid to {who.split('_')[0]} "
+                                          "(only 'efficientkan' has)")
+            for m in layers[1:]:
+                assert (m.grid_size, m.spline_order, m.grid_eps, m.enable_standalone_scale_spline) == \
+                    (l0.grid_size, l0.spline_order, l0.grid_eps, l0.enable_standalone_scale_spline), \
+                    f"{who}: the per-head layers of one MSA must agree in grid_size, spline_order and grid_eps"
+        return layers, l0
+
+    def _refit_operands(self, layers):
+        """(packed old spline weights [g, I*nb_old, O], old knots [g, I, nk_old]) of the grouped refit launches."""
+        sw = torch.stack([m.scaled_spline_weight for m in layers])                       # [g, O, I, nb_old]
+        g, o, i, nb = sw.shape
+        return sw.permute(0, 2, 3, 1).reshape(g, i * nb, o), torch.stack([m.grid for m in layers])
+
     def edge_activation_l1(self, x, include_base=False):
         """[3, H, d_head(out), d_head(in)]: the mean absolute activation of every edge of the 3*H per-head q, k and v layers on
         the rows of x [..., d] (the quantity the KAN paper regularises), from ONE grouped launch of kanvit.ops.edge_l1 with the
         packing of grouped.run_qkv.  `include_base` adds the base term of the efficient-KAN / FastKAN edge functions."""
-        from dataclasses import replace
-        layers = list(self.q_mappings) + list(self.k_mappings) + list(self.v_mappings)
-        l0 = layers[0]
+        layers, l0 = self._qkv_layers()
         if not isinstance(l0, (KANLinear, ChebyKANLayer, FastKANLayer)):
             raise NotImplementedError(f"edge_activation_l1: per-head layers of type {type(l0).__name__} have no edge-activation "
                                       f"statistic; supported MSA types: {', '.join(self.REGULARIZED_TYPES)}")
@@ -140,24 +161,13 @@ class MSA(torch.nn.Module):
         with the same constructor arguments, so they share their new knots: one table per head slice.  Every layer ends bit
         for bit as its own update_grid on its head's slice would leave it.  Returns the number of (head, feature) pairs kept
         unchanged (0-d device tensor).  type='efficientkan' only."""
-        from dataclasses import replace
-        layers = list(self.q_mappings) + list(self.k_mappings) + list(self.v_mappings)
-        l0 = layers[0]
-        if not isinstance(l0, KANLinear):
-            raise NotImplementedError(f"update_grid: MSA type '{self.type}' has no B-spline grid to update (only 'efficientkan' has)")
-        for m in layers[1:]:
-            assert (m.grid_size, m.spline_order, m.grid_eps, m.enable_standalone_scale_spline) == \
-                (l0.grid_size, l0.spline_order, l0.grid_eps, l0.enable_standalone_scale_spline), \
-                "update_grid: the per-head layers of one MSA must agree in grid_size, spline_order and grid_eps"
+        layers, l0 = self._qkv_layers("update_grid")
         H, dh = self.n_heads, self.d_head
-        nb = l0.grid_size + l0.spline_order
         x2d = x.reshape(-1, self.d).float()
         new_grid = KANLinear.adapted_grid(x2d, l0.grid_size, l0.spline_order, l0.grid_eps, margin).view(H, dh, -1)
         cfg = replace(l0.kan_cfg(layers), has_base=0, base_act=0, groups=3 * H, x_group_mod=H)
-        sw = torch.stack([m.scaled_spline_weight for m in layers])                       # [g, O, I, nb]
-        w_old = sw.permute(0, 2, 3, 1).reshape(3 * H, dh * nb, dh)
-        old = torch.stack([m.grid.reshape(-1) for m in layers])
-        w_new, ok = ops.bspline_refit(x2d, w_old, cfg, old, new_grid)
+        w_old, grids = self._refit_operands(layers)
+        w_new, ok = ops.bspline_refit(x2d, w_old, cfg, grids.reshape(3 * H, -1), new_grid)
         for g, m in enumerate(layers):
             m.apply_refit(new_grid[g % H], w_new[g], ok[g % H])
         return (~ok).sum()
@@ -171,23 +181,13 @@ class MSA(torch.nn.Module):
         inner spans; when the three share their old span (they do unless they were loaded from differing checkpoints) every layer
         ends bit for bit as its own extend_grid on its head's slice would leave it.  Returns the number of (head, feature) pairs
         that took the fallback (0-d device tensor).  type='efficientkan' only."""
-        from dataclasses import replace
-        layers = list(self.q_mappings) + list(self.k_mappings) + list(self.v_mappings)
-        l0 = layers[0]
-        if not isinstance(l0, KANLinear):
-            raise NotImplementedError(f"extend_grid: MSA type '{self.type}' has no B-spline grid to extend (only 'efficientkan' has)")
-        for m in layers[1:]:
-            assert (m.grid_size, m.spline_order, m.grid_eps, m.enable_standalone_scale_spline) == \
-                (l0.grid_size, l0.spline_order, l0.grid_eps, l0.enable_standalone_scale_spline), \
-                "extend_grid: the per-head layers of one MSA must agree in grid_size, spline_order and grid_eps"
+        layers, l0 = self._qkv_layers("extend_grid")
         KANLinear.check_extension(grid_size, l0.spline_order)
         H, dh, order = self.n_heads, self.d_head, l0.spline_order
         nb_old = l0.grid_size + order
         x2d = x.reshape(-1, self.d).float()
         cfg = replace(l0.kan_cfg(layers), has_base=0, base_act=0, groups=3 * H, x_group_mod=H, G=grid_size + order)
-        sw = torch.stack([m.scaled_spline_weight for m in layers])                       # [g, O, I, nb_old]
-        w_old = sw.permute(0, 2, 3, 1).reshape(3 * H, dh * nb_old, dh)
-        grids = torch.stack([m.grid for m in layers])                                    # [g, I, nk_old]
+        w_old, grids = self._refit_operands(layers)
         old = grids.reshape(3 * H, -1)
         new_grid = KANLinear.adapted_grid(x2d, grid_size, order, l0.grid_eps, margin).view(H, dh, -1)
         w_new, ok = ops.bspline_regrid(x2d, w_old, cfg, nb_old, old, new_grid)

@@ -11,7 +11,8 @@ contraction."""
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, ops
+from .ops import _launch, _ptr
 
 _TILE = 256
 _HALF = (torch.bfloat16, torch.float16)
@@ -96,18 +97,12 @@ class _DenseFn(torch.autograd.Function):
 def _relu_bwd_bias(dy: torch.Tensor, y: torch.Tensor):
     """(dy masked by y > 0, column sums of the result): kanvit_relu_bwd_bias -- what threshold_backward + sum(0) compute in two
     passes over [M, 4d].  The masked gradient goes to a fresh tensor (the incoming dy may be shared with other consumers)."""
-    import ctypes as C
-    from . import ops
     M, N = dy.shape
     L = _lib.lib()
     db = torch.empty(N, device=dy.device, dtype=torch.float32)
     out = torch.empty_like(dy)
     fn = L.kanvit_relu_bwd_bias_bf16 if dy.dtype == torch.bfloat16 else L.kanvit_relu_bwd_bias      # autocast: bf16 tensors, fp32 column sums
-    with torch.cuda.device(dy.device):
-        nbytes = int(L.kanvit_relu_bwd_bias_workspace(M, N))
-        ws = ops._workspace(nbytes, dy.device)
-        _lib.check(fn(M, N, ops._ptr(dy), ops._ptr(y), ops._ptr(out), ops._ptr(db), ops._ptr(ws), C.c_size_t(nbytes), ops._stream()),
-                   "kanvit_relu_bwd_bias")
+    _launch(fn, "kanvit_relu_bwd_bias", dy.device, M, N, _ptr(dy), _ptr(y), _ptr(out), _ptr(db), query=(L.kanvit_relu_bwd_bias_workspace, M, N))
     return out, db
 
 
@@ -130,16 +125,11 @@ FF_MODE = "fp32"
 
 
 def _split3(x: torch.Tensor, pattern: int, bias=None, relu=False, mask=None) -> torch.Tensor:
-    import ctypes as C
-    L = _lib.lib()
     M, K = x.shape
     out = torch.empty(M, 3 * K, device=x.device, dtype=torch.bfloat16)
     x = x.contiguous()
-    with torch.cuda.device(x.device):              # x's device and its current stream, whatever the ambient device is
-        _lib.check(L.kanvit_split3_bf16(M, K, C.c_void_p(x.data_ptr()), None if bias is None else C.c_void_p(bias.data_ptr()),
-                                        int(relu), None if mask is None else C.c_void_p(mask.data_ptr()),
-                                        0 if mask is None else mask.stride(0), C.c_void_p(out.data_ptr()), pattern,
-                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "kanvit_split3_bf16")
+    _launch(_lib.lib().kanvit_split3_bf16, "kanvit_split3_bf16", x.device, M, K, _ptr(x), _ptr(bias), int(relu), _ptr(mask),
+            0 if mask is None else mask.stride(0), _ptr(out), pattern)
     return out
 
 
@@ -195,22 +185,18 @@ class _FFSmallFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, x, w1, b1, w2, b2):
-        from . import ops
         x, w1, b1, w2, b2 = (t.contiguous() for t in (x, w1, b1, w2, b2))
         M, D = x.shape
         F_ = w1.shape[0]
         y = torch.empty(M, D, device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device), ops._timed("ff_small_fwd", 4 * M * D * F_, 4 * (2 * M * D + 2 * D * F_)):
-            _lib.check(_lib.lib().kanvit_ff_small_fwd(M, D, F_, ops._ptr(x), ops._ptr(w1), ops._ptr(b1), ops._ptr(w2), ops._ptr(b2),
-                                                      ops._ptr(y), ops._stream()), "kanvit_ff_small_fwd")
+        _launch(_lib.lib().kanvit_ff_small_fwd, "kanvit_ff_small_fwd", x.device, M, D, F_, _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(y),
+                tag="ff_small_fwd", cost=(4 * M * D * F_, 4 * (2 * M * D + 2 * D * F_)))
         ctx.save_for_backward(x, w1, b1, w2)
         return y
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, dy):
-        from . import ops
-        import ctypes as C
         x, w1, b1, w2 = ctx.saved_tensors
         M, D = x.shape
         F_ = w1.shape[0]
@@ -218,13 +204,9 @@ class _FFSmallFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         dw1, db1, dw2, db2 = torch.empty_like(w1), torch.empty_like(b1), torch.empty_like(w2), torch.empty(D, device=x.device, dtype=torch.float32)
         L = _lib.lib()
-        with torch.cuda.device(x.device):
-            nbytes = int(L.kanvit_ff_small_bwd_workspace(M, D, F_))
-            ws = ops._workspace(nbytes, x.device)
-            with ops._timed("ff_small_bwd", 8 * M * D * F_, 4 * (3 * M * D + 4 * D * F_)):
-                _lib.check(L.kanvit_ff_small_bwd(M, D, F_, ops._ptr(x), ops._ptr(w1), ops._ptr(b1), ops._ptr(w2), ops._ptr(dy), ops._ptr(dx),
-                                                 ops._ptr(dw1), ops._ptr(db1), ops._ptr(dw2), ops._ptr(db2), ops._ptr(ws), C.c_size_t(nbytes),
-                                                 ops._stream()), "kanvit_ff_small_bwd")
+        _launch(L.kanvit_ff_small_bwd, "kanvit_ff_small_bwd", x.device, M, D, F_, _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(dy), _ptr(dx),
+                _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), query=(L.kanvit_ff_small_bwd_workspace, M, D, F_),
+                tag="ff_small_bwd", cost=(8 * M * D * F_, 4 * (3 * M * D + 4 * D * F_)))
         return dx, dw1, db1, dw2, db2
 
 
@@ -236,7 +218,6 @@ class _LnFFSmallFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, x, delta, gamma, beta, w1, b1, w2, b2, eps):
-        from . import ops
         D = x.shape[-1]
         x2 = x.contiguous().view(-1, D)
         d2 = None if delta is None else delta.contiguous().view(-1, D)
@@ -246,10 +227,9 @@ class _LnFFSmallFn(torch.autograd.Function):
         y = torch.empty_like(x2)
         mean = torch.empty(M, device=x.device, dtype=torch.float32)
         rstd = torch.empty(M, device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device), ops._timed("ff_small_fwd", 4 * M * D * F_, 4 * (4 * M * D + 2 * D * F_)):
-            _lib.check(_lib.lib().kanvit_lnff_small_fwd(M, D, F_, float(eps), ops._ptr(x2), ops._ptr(d2), ops._ptr(gamma), ops._ptr(beta),
-                                                        ops._ptr(w1), ops._ptr(b1), ops._ptr(w2), ops._ptr(b2), ops._ptr(s), ops._ptr(mean),
-                                                        ops._ptr(rstd), ops._ptr(y), ops._stream()), "kanvit_lnff_small_fwd")
+        _launch(_lib.lib().kanvit_lnff_small_fwd, "kanvit_lnff_small_fwd", x.device, M, D, F_, float(eps), _ptr(x2), _ptr(d2), _ptr(gamma),
+                _ptr(beta), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(s), _ptr(mean), _ptr(rstd), _ptr(y),
+                tag="ff_small_fwd", cost=(4 * M * D * F_, 4 * (4 * M * D + 2 * D * F_)))
         ctx.save_for_backward(s, mean, rstd, gamma, beta, w1, b1, w2)
         ctx.has_delta = delta is not None
         ctx.shape = x.shape
@@ -258,8 +238,6 @@ class _LnFFSmallFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, gs, gy):
-        from . import ops
-        import ctypes as C
         s, mean, rstd, gamma, beta, w1, b1, w2 = ctx.saved_tensors
         M, D = s.shape
         F_ = w1.shape[0]
@@ -269,14 +247,9 @@ class _LnFFSmallFn(torch.autograd.Function):
         dg, db = torch.empty_like(gamma), torch.empty_like(beta)
         dw1, db1, dw2, db2 = torch.empty_like(w1), torch.empty_like(b1), torch.empty_like(w2), torch.empty(D, device=s.device, dtype=torch.float32)
         L = _lib.lib()
-        with torch.cuda.device(s.device):
-            nbytes = int(L.kanvit_ff_small_bwd_workspace(M, D, F_))
-            ws = ops._workspace(nbytes, s.device)
-            with ops._timed("ff_small_bwd", 8 * M * D * F_, 4 * (5 * M * D + 4 * D * F_)):
-                _lib.check(L.kanvit_lnff_small_bwd(M, D, F_, ops._ptr(s), ops._ptr(mean), ops._ptr(rstd), ops._ptr(gamma), ops._ptr(beta),
-                                                   ops._ptr(w1), ops._ptr(b1), ops._ptr(w2), ops._ptr(gy2), ops._ptr(gs2), ops._ptr(ds),
-                                                   ops._ptr(dg), ops._ptr(db), ops._ptr(dw1), ops._ptr(db1), ops._ptr(dw2), ops._ptr(db2),
-                                                   ops._ptr(ws), C.c_size_t(nbytes), ops._stream()), "kanvit_lnff_small_bwd")
+        _launch(L.kanvit_lnff_small_bwd, "kanvit_lnff_small_bwd", s.device, M, D, F_, _ptr(s), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta),
+                _ptr(w1), _ptr(b1), _ptr(w2), _ptr(gy2), _ptr(gs2), _ptr(ds), _ptr(dg), _ptr(db), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2),
+                query=(L.kanvit_ff_small_bwd_workspace, M, D, F_), tag="ff_small_bwd", cost=(8 * M * D * F_, 4 * (5 * M * D + 4 * D * F_)))
         ds = ds.view(ctx.shape)
         return ds, (ds if ctx.has_delta else None), dg, db, dw1, db1, dw2, db2, None
 
@@ -284,7 +257,6 @@ class _LnFFSmallFn(torch.autograd.Function):
 def ln_feed_forward(x: torch.Tensor, delta, norm: torch.nn.LayerNorm, lin1: torch.nn.Linear, lin2: torch.nn.Linear):
     """(s, f) with s = x + delta and f = lin2(relu(lin1(norm(s)))) -- model.py:36 without its final residual add.  One fused
     launch for the small geometries; otherwise add_layernorm + feed_forward (the same arithmetic as two ops)."""
-    from . import ops
     d = x.shape[-1]
     if (norm.elementwise_affine and norm.bias is not None and tuple(norm.normalized_shape) == (d,) and (delta is None or delta.shape == x.shape)
             and not _lib.py_switches()["no_lnff"] and _ff_small_ok(x.reshape(-1, d), lin1, lin2)):

@@ -7,7 +7,7 @@ kernels of libkanvit.so.  There is no fallback: CPU tensors or a missing library
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Optional, Tuple
 
 import torch
@@ -171,10 +171,65 @@ def _workspace(nbytes: int, device):
     return torch.empty(max((nbytes + 3) // 4, 4), device=device, dtype=torch.float32)
 
 
+_NO_SCRATCH = (lambda: 0,)      # a workspace "query" that answers 0 without asking the library (the fp32 patch forward)
+
+
+def _launch(fn, label, device, *args, query=None, null_ws=False, tag=None, cost=(0, 0)):
+    """One C-ABI launch on `device` and its current stream: fn(*args, [workspace, bytes,] stream), checked under `label`.
+
+    query = (workspace function, *its arguments): the entry point takes scratch -- the bytes are queried, allocated through
+    _workspace and passed as `workspace, c_size_t(bytes)` in front of the stream; null_ws passes NULL when the query answers 0
+    (entry points that refuse NULL always get an allocation).  tag: bracket the call with the kernel timer under that name and
+    `cost` = (flops, bytes); a callable tag is given the queried bytes.  No host synchronisation; HIP-graph capturable."""
+    with torch.cuda.device(device):
+        if query is None:
+            tail = (_stream(),)
+        else:
+            nbytes = int(query[0](*query[1:]))
+            ws = None if null_ws and not nbytes else _workspace(nbytes, device)
+            tail = (_ptr(ws), C.c_size_t(nbytes), _stream())
+        if tag is None or timer is None:
+            check(fn(*args, *tail), label)
+        else:
+            with _timed(tag(nbytes) if callable(tag) else tag, *cost):
+                check(fn(*args, *tail), label)
+
+
 _fwd_f32 = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _bwd = torch.amp.custom_bwd(device_type="cuda")
 # Under torch.autocast (bench.py --amp bf16: the stock FF GEMMs run on the bf16 matrix cores) the kanvit ops
 # keep computing in fp32: inputs are cast to fp32 at the boundary and autocast is off inside.
+
+
+def _bf16_tag(tag: str, flags: int) -> str:
+    return tag + "_bf16" if flags & _lib.FLAG_BF16_MFMA else tag
+
+
+def _kan_forward(cfg: LayerCfg, x, u, w, bparams, bias, tag, fused_ln=False):
+    """The kanvit_layer_fwd launch of _KanLayerFn and _KanLayerLnFn: (y, x, u, w, bparams, bias), the operands as the kernel read
+    them (contiguous).  fused_ln: bparams is [centres | gamma | beta] and the u slot carries the [M, x_group_mod, 2] statistics
+    the kernel writes, returned as u."""
+    for n, t in (("x", x), ("u", u), ("w", w), ("bparams", bparams), ("bias", bias)):
+        _require_gpu_f32(n, t)
+    x, u, w, bparams, bias = (None if t is None else t.contiguous() for t in (x, u, w, bparams, bias))
+    M, ldx = x.shape
+    if ldx != cfg.x_group_mod * cfg.I:
+        raise KanvitError(f"x has {ldx} columns, expected x_group_mod*I = {cfg.x_group_mod * cfg.I}")
+    if tuple(w.shape) != (cfg.groups, cfg.K, cfg.O):
+        raise KanvitError(f"packed weight shape {tuple(w.shape)} != {(cfg.groups, cfg.K, cfg.O)}")
+    if fused_ln:
+        if tuple(bparams.shape) != (cfg.groups, cfg.G + 2 * cfg.I):
+            raise KanvitError(f"bparams shape {tuple(bparams.shape)} != {(cfg.groups, cfg.G + 2 * cfg.I)} (centres | gamma | beta)")
+        u = torch.empty(M, cfg.x_group_mod, 2, device=x.device, dtype=torch.float32)
+    elif u is not None and tuple(u.shape) != (M, cfg.groups * cfg.I):
+        raise KanvitError(f"u shape {tuple(u.shape)} != {(M, cfg.groups * cfg.I)}")
+    y = torch.empty(M, cfg.groups * cfg.O, device=x.device, dtype=torch.float32)
+    d = _desc(cfg, M, ldx, cfg.groups * cfg.I, cfg.groups * cfg.O, 0 if bparams is None else bparams.shape[1])
+    L = _lib.lib()
+    _launch(L.kanvit_layer_fwd, "kanvit_layer_fwd", x.device, C.byref(d), _ptr(x), _ptr(u), _ptr(w), _ptr(bparams), _ptr(bias), _ptr(y),
+            query=(L.kanvit_layer_fwd_workspace, C.byref(d)), null_ws=True,
+            tag=_bf16_tag(_tag_prefix(cfg, tag) + "_fwd", cfg.flags), cost=_layer_cost(cfg, M, "fwd"))
+    return y, x, u, w, bparams, bias
 
 
 class _KanLayerFn(torch.autograd.Function):
@@ -183,30 +238,8 @@ class _KanLayerFn(torch.autograd.Function):
     @staticmethod
     @_fwd_f32
     def forward(ctx, x, u, w, bparams, bias, cfg: LayerCfg, tag: Optional[str] = None):
-        for n, t in (("x", x), ("u", u), ("w", w), ("bparams", bparams), ("bias", bias)):
-            _require_gpu_f32(n, t)
-        x = x.contiguous()
-        w = w.contiguous()
-        u = None if u is None else u.contiguous()
-        bparams = None if bparams is None else bparams.contiguous()
-        bias = None if bias is None else bias.contiguous()
-        M, ldx = x.shape
-        if ldx != cfg.x_group_mod * cfg.I:
-            raise KanvitError(f"x has {ldx} columns, expected x_group_mod*I = {cfg.x_group_mod * cfg.I}")
-        if tuple(w.shape) != (cfg.groups, cfg.K, cfg.O):
-            raise KanvitError(f"packed weight shape {tuple(w.shape)} != {(cfg.groups, cfg.K, cfg.O)}")
-        if u is not None and tuple(u.shape) != (M, cfg.groups * cfg.I):
-            raise KanvitError(f"u shape {tuple(u.shape)} != {(M, cfg.groups * cfg.I)}")
-        y = torch.empty(M, cfg.groups * cfg.O, device=x.device, dtype=torch.float32)
-        d = _desc(cfg, M, ldx, cfg.groups * cfg.I, cfg.groups * cfg.O, 0 if bparams is None else bparams.shape[1])
+        y, x, u, w, bparams, bias = _kan_forward(cfg, x, u, w, bparams, bias, tag)
         ctx.tag = tag
-        tag = _tag_prefix(cfg, tag) + "_fwd" + ("_bf16" if cfg.flags & _lib.FLAG_BF16_MFMA else "")
-        with torch.cuda.device(x.device):
-            nbytes = int(_lib.lib().kanvit_layer_fwd_workspace(C.byref(d)))
-            ws = _workspace(nbytes, x.device) if nbytes else None
-            with _timed(tag, *_layer_cost(cfg, M, "fwd")):
-                check(_lib.lib().kanvit_layer_fwd(C.byref(d), _ptr(x), _ptr(u), _ptr(w), _ptr(bparams), _ptr(bias),
-                                                  _ptr(y), _ptr(ws), C.c_size_t(nbytes), _stream()), "kanvit_layer_fwd")
         ctx.cfg = cfg
         ctx.has_u = u is not None
         ctx.has_bp = bparams is not None
@@ -245,19 +278,15 @@ def _kan_backward(cfg: "LayerCfg", x, u, w, bparams, dy, needs, has_u, has_bias,
     d = _desc(cfg, M, ldx, cfg.groups * cfg.I, cfg.groups * cfg.O, 0 if bparams is None else bparams.shape[1])
     L = _lib.lib()
 
-    def weight_pass(desc, out, tag):
+    def weight_pass(desc, out, what):
+        tag, cost = _bf16_tag(stem + what, cfg.flags), _layer_cost(cfg, M, "bwd_weight")
         if pd is not None:
-            nbytes = int(L.kanvit_patch_embed_bwd_weight_workspace(C.byref(desc), C.byref(pd)))
-            ws = torch.empty(max(nbytes // 4, 1), device=x.device, dtype=torch.float32)
-            with _timed(tag, *_layer_cost(cfg, M, "bwd_weight")):
-                check(L.kanvit_patch_embed_bwd_weight(C.byref(desc), C.byref(pd), _ptr(x), _ptr(bparams), _ptr(dy), _ptr(out),
-                                                      _ptr(ws), C.c_size_t(nbytes), _stream()), "kanvit_patch_embed_bwd_weight")
-            return
-        nbytes = int(L.kanvit_layer_bwd_weight_workspace(C.byref(desc)))
-        ws = torch.empty(max(nbytes // 4, 1), device=x.device, dtype=torch.float32)
-        with _timed(tag, *_layer_cost(cfg, M, "bwd_weight")):
-            check(L.kanvit_layer_bwd_weight(C.byref(desc), _ptr(x), _ptr(u), _ptr(bparams), _ptr(dy), _ptr(out),
-                                            _ptr(ws), C.c_size_t(nbytes), _stream()), "kanvit_layer_bwd_weight")
+            _launch(L.kanvit_patch_embed_bwd_weight, "kanvit_patch_embed_bwd_weight", x.device, C.byref(desc), C.byref(pd), _ptr(x),
+                    _ptr(bparams), _ptr(dy), _ptr(out), query=(L.kanvit_patch_embed_bwd_weight_workspace, C.byref(desc), C.byref(pd)),
+                    tag=tag, cost=cost)
+        else:
+            _launch(L.kanvit_layer_bwd_weight, "kanvit_layer_bwd_weight", x.device, C.byref(desc), _ptr(x), _ptr(u), _ptr(bparams),
+                    _ptr(dy), _ptr(out), query=(L.kanvit_layer_bwd_weight_workspace, C.byref(desc)), tag=tag, cost=cost)
 
     dx = du = dw = dbp = db = None
     sine_freq = cfg.family == SINE and need_bp
@@ -279,13 +308,10 @@ def _kan_backward(cfg: "LayerCfg", x, u, w, bparams, dy, needs, has_u, has_bias,
             if cfg.family == SINE:
                 tiles = int(L.kanvit_layer_dparam_tiles(C.byref(d)))
                 dpart = torch.empty(tiles, cfg.groups, cfg.G, device=x.device, dtype=torch.float32)
-            nb_in = int(L.kanvit_layer_bwd_input_workspace(C.byref(d)))
-            ws_in = _workspace(nb_in, x.device) if nb_in else None
-            with _timed(stem + "_bwd_input" + ("_bf16" if nb_in else ""),
-                        *_layer_cost(cfg, M, "bwd_input")):
-                check(L.kanvit_layer_bwd_input(C.byref(d), _ptr(x), _ptr(u), _ptr(w), _ptr(bparams), _ptr(dy),
-                                               _ptr(dx), _ptr(du_buf), _ptr(dpart), _ptr(ws_in), C.c_size_t(nb_in),
-                                               _stream()), "kanvit_layer_bwd_input")
+            # the tag says bf16 when the launch takes scratch (only the bf16 input-gradient kernels do), not when the flag is set
+            _launch(L.kanvit_layer_bwd_input, "kanvit_layer_bwd_input", x.device, C.byref(d), _ptr(x), _ptr(u), _ptr(w), _ptr(bparams),
+                    _ptr(dy), _ptr(dx), _ptr(du_buf), _ptr(dpart), query=(L.kanvit_layer_bwd_input_workspace, C.byref(d)), null_ws=True,
+                    tag=lambda nb_in: stem + "_bwd_input" + ("_bf16" if nb_in else ""), cost=_layer_cost(cfg, M, "bwd_input"))
             if cfg.family == RBF:
                 if has_u:
                     du = du_buf
@@ -297,12 +323,12 @@ def _kan_backward(cfg: "LayerCfg", x, u, w, bparams, dy, needs, has_u, has_bias,
                 dbp[:, :cfg.G] = dpart.sum(0)
         if need_w:
             dw = torch.empty_like(w)
-            weight_pass(d, dw, stem + "_bwd_weight" + ("_bf16" if cfg.flags & 1 else ""))
+            weight_pass(d, dw, "_bwd_weight")
         if freq_via_w:
             dq = LayerDesc(*[getattr(d, f) for f, _ in LayerDesc._fields_])
             dq.flags = cfg.flags | _lib.FLAG_SINE_DFREQ
             q = torch.empty_like(w)
-            weight_pass(dq, q, stem + "_bwd_freq" + ("_bf16" if cfg.flags & 1 else ""))
+            weight_pass(dq, q, "_bwd_freq")
             dbp = torch.zeros_like(bparams)
             dbp[:, :cfg.G] = q.mul_(w).view(cfg.groups, cfg.I, cfg.G, cfg.O).sum((1, 3))
         if need_b and has_bias:
@@ -317,8 +343,7 @@ def ln_fusable(cfg: "LayerCfg", M: int) -> bool:
     """True when the register kernels can form FastKAN's LayerNorm themselves for this launch (kanvit_layer_ln_fusable)."""
     if cfg.family != RBF:
         return False
-    f = cfg.flags | (_lib.FLAG_BF16_MFMA if _autocast_flags() else 0)
-    d = _desc(LayerCfg(**{**cfg.__dict__, "flags": f}), M, cfg.x_group_mod * cfg.I, cfg.groups * cfg.I, cfg.groups * cfg.O,
+    d = _desc(_autocast_cfg(cfg), M, cfg.x_group_mod * cfg.I, cfg.groups * cfg.I, cfg.groups * cfg.O,
               cfg.G + 2 * cfg.I)
     return bool(_lib.lib().kanvit_layer_ln_fusable(C.byref(d)))
 
@@ -336,28 +361,8 @@ class _KanLayerLnFn(torch.autograd.Function):
     @staticmethod
     @_fwd_f32
     def forward(ctx, x, w, bparams, bias, cfg: LayerCfg, tag: Optional[str] = None):
-        for n, t in (("x", x), ("w", w), ("bparams", bparams), ("bias", bias)):
-            _require_gpu_f32(n, t)
-        x, w, bparams = x.contiguous(), w.contiguous(), bparams.contiguous()
-        bias = None if bias is None else bias.contiguous()
-        M, ldx = x.shape
-        if ldx != cfg.x_group_mod * cfg.I:
-            raise KanvitError(f"x has {ldx} columns, expected x_group_mod*I = {cfg.x_group_mod * cfg.I}")
-        if tuple(w.shape) != (cfg.groups, cfg.K, cfg.O):
-            raise KanvitError(f"packed weight shape {tuple(w.shape)} != {(cfg.groups, cfg.K, cfg.O)}")
-        if tuple(bparams.shape) != (cfg.groups, cfg.G + 2 * cfg.I):
-            raise KanvitError(f"bparams shape {tuple(bparams.shape)} != {(cfg.groups, cfg.G + 2 * cfg.I)} (centres | gamma | beta)")
-        y = torch.empty(M, cfg.groups * cfg.O, device=x.device, dtype=torch.float32)
-        stats = torch.empty(M, cfg.x_group_mod, 2, device=x.device, dtype=torch.float32)
-        d = _desc(cfg, M, ldx, cfg.groups * cfg.I, cfg.groups * cfg.O, bparams.shape[1])
+        y, x, stats, w, bparams, bias = _kan_forward(cfg, x, None, w, bparams, bias, tag, fused_ln=True)
         ctx.tag = tag
-        tag = _tag_prefix(cfg, tag) + "_fwd" + ("_bf16" if cfg.flags & _lib.FLAG_BF16_MFMA else "")
-        with torch.cuda.device(x.device):
-            nbytes = int(_lib.lib().kanvit_layer_fwd_workspace(C.byref(d)))
-            ws = _workspace(nbytes, x.device) if nbytes else None
-            with _timed(tag, *_layer_cost(cfg, M, "fwd")):
-                check(_lib.lib().kanvit_layer_fwd(C.byref(d), _ptr(x), _ptr(stats), _ptr(w), _ptr(bparams), _ptr(bias),
-                                                  _ptr(y), _ptr(ws), C.c_size_t(nbytes), _stream()), "kanvit_layer_fwd")
         ctx.cfg = cfg
         ctx.has_bias = bias is not None
         ctx.save_for_backward(x, stats, w, bparams)
@@ -379,12 +384,9 @@ class _KanLayerLnFn(torch.autograd.Function):
             d = _desc(cfg, M, x.shape[1], cfg.groups * I, cfg.groups * cfg.O, bparams.shape[1])
             L = _lib.lib()
             dgb = torch.empty(2, cfg.groups, I, device=x.device, dtype=torch.float32)
-            with torch.cuda.device(x.device):
-                nbytes = int(L.kanvit_layer_ln_bwd_workspace(C.byref(d)))
-                ws = _workspace(nbytes, x.device)
-                with _timed("ln_bwd", 0, 4 * M * (cfg.groups * I + (3 if need_x else 1) * cfg.x_group_mod * I)):
-                    check(L.kanvit_layer_ln_bwd(C.byref(d), _ptr(x), _ptr(stats), _ptr(bparams), _ptr(du), _ptr(dx if need_x else None),
-                                                _ptr(dgb[0]), _ptr(dgb[1]), _ptr(ws), C.c_size_t(nbytes), _stream()), "kanvit_layer_ln_bwd")
+            _launch(L.kanvit_layer_ln_bwd, "kanvit_layer_ln_bwd", x.device, C.byref(d), _ptr(x), _ptr(stats), _ptr(bparams), _ptr(du),
+                    _ptr(dx if need_x else None), _ptr(dgb[0]), _ptr(dgb[1]), query=(L.kanvit_layer_ln_bwd_workspace, C.byref(d)),
+                    tag="ln_bwd", cost=(0, 4 * M * (cfg.groups * I + (3 if need_x else 1) * cfg.x_group_mod * I)))
             if need_bp:
                 dbp = torch.cat([torch.zeros(cfg.groups, G, device=x.device, dtype=torch.float32), dgb[0], dgb[1]], dim=1)
         return (dx if need_x else None), dw, dbp, db, None, None
@@ -393,8 +395,7 @@ class _KanLayerLnFn(torch.autograd.Function):
 def kan_layer_ln(x: torch.Tensor, w: torch.Tensor, cfg: LayerCfg, bparams: torch.Tensor, bias: Optional[torch.Tensor],
                  eps: float, tag: Optional[str] = None) -> torch.Tensor:
     """kan_layer() for FastKAN with the LayerNorm fused (call only when ln_fusable(cfg, M)); bparams = [centres | gamma | beta]."""
-    from dataclasses import replace
-    f = cfg.flags | _lib.FLAG_FUSED_LN | (_lib.FLAG_BF16_MFMA if _autocast_flags() else 0)
+    f = cfg.flags | _lib.FLAG_FUSED_LN | _autocast_flags()
     return _KanLayerLnFn.apply(x, w, bparams, bias, replace(cfg, flags=f, ln_eps=float(eps)), tag)
 
 
@@ -429,14 +430,12 @@ class _PatchEmbedFn(torch.autograd.Function):
         bp = None if bparams is None else bparams.contiguous()
         bs = None if bias is None else bias.contiguous()
         cl, po = cls.contiguous(), pos.contiguous()
-        bf = bool(cfg.flags & _lib.FLAG_BF16_MFMA)
-        with torch.cuda.device(images.device):
-            nbytes = int(_lib.lib().kanvit_layer_fwd_workspace(C.byref(d))) if bf else 0
-            ws = _workspace(nbytes, images.device) if nbytes else None
-            with _timed("layer_fwd" + ("_bf16" if bf else ""), *_layer_cost(cfg, B * P, "fwd")):
-                check(_lib.lib().kanvit_patch_embed_fwd_ws(C.byref(d), C.byref(pd), _ptr(images), _ptr(w), _ptr(bp), _ptr(bs), _ptr(cl),
-                                                            _ptr(po), _ptr(y), _ptr(ws), C.c_size_t(nbytes), _stream()),
-                      "kanvit_patch_embed_fwd")
+        L = _lib.lib()
+        # only the bf16 forward takes scratch: the query is made under the flag alone
+        _launch(L.kanvit_patch_embed_fwd_ws, "kanvit_patch_embed_fwd", images.device, C.byref(d), C.byref(pd), _ptr(images), _ptr(w), _ptr(bp),
+                _ptr(bs), _ptr(cl), _ptr(po), _ptr(y), null_ws=True,
+                query=(L.kanvit_layer_fwd_workspace, C.byref(d)) if cfg.flags & _lib.FLAG_BF16_MFMA else _NO_SCRATCH,
+                tag=_bf16_tag("layer_fwd", cfg.flags), cost=_layer_cost(cfg, B * P, "fwd"))
         ctx.cfg, ctx.n_patches = cfg, n_patches
         ctx.has_bp, ctx.has_bias = bparams is not None, bias is not None
         ctx.save_for_backward(images, w, bp)
@@ -470,10 +469,7 @@ def patch_embed(images, w, cfg: LayerCfg, bparams, bias, cls, pos, n_patches: in
     """Fused patch embedding (see _PatchEmbedFn); w is the packed weight [1, K, O], cls [O], pos [P + 1, O].  Raises
     KanvitError for shapes the fused kernel does not cover (the caller falls back to patchify + kan_layer).  Under bf16
     autocast the contraction runs on the bf16 matrix cores (KANVIT_FLAG_BF16_MFMA), as kan_layer() does."""
-    if _autocast_flags() and not (cfg.flags & _lib.FLAG_BF16_MFMA):
-        from dataclasses import replace
-        cfg = replace(cfg, flags=cfg.flags | _lib.FLAG_BF16_MFMA)
-    return _PatchEmbedFn.apply(images, w, bparams, bias, cls, pos, cfg, n_patches)
+    return _PatchEmbedFn.apply(images, w, bparams, bias, cls, pos, _autocast_cfg(cfg), n_patches)
 
 
 def kan_layer(x: torch.Tensor, w: torch.Tensor, cfg: LayerCfg, u: Optional[torch.Tensor] = None,
@@ -483,10 +479,7 @@ def kan_layer(x: torch.Tensor, w: torch.Tensor, cfg: LayerCfg, u: Optional[torch
 
     Under ``torch.autocast('cuda', dtype=torch.bfloat16)`` the contraction is allowed onto the bf16 matrix cores
     (KANVIT_FLAG_BF16_MFMA); without autocast it is always the exact fp32 path."""
-    if torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16 and not (cfg.flags & 1):
-        from dataclasses import replace
-        cfg = replace(cfg, flags=cfg.flags | _lib.FLAG_BF16_MFMA)
-    return _KanLayerFn.apply(x, u, w, bparams, bias, cfg, tag)
+    return _KanLayerFn.apply(x, u, w, bparams, bias, _autocast_cfg(cfg), tag)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -524,12 +517,9 @@ class _EdgeL1Fn(torch.autograd.Function):
         d = _edge_l1_desc(cfg, x, bparams)
         L = _lib.lib()
         A = torch.empty(cfg.groups, cfg.I, cfg.O, device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            nbytes = int(L.kanvit_edge_l1_fwd_workspace(C.byref(d)))
-            ws = _workspace(nbytes, x.device)
-            with _timed("edge_l1_fwd", 2 * x.shape[0] * cfg.K * cfg.O * cfg.groups, 4 * (x.numel() + w.numel() + A.numel())):
-                check(L.kanvit_edge_l1_fwd(C.byref(d), _ptr(x), _ptr(w), _ptr(bparams), _ptr(A), _ptr(ws), C.c_size_t(nbytes), _stream()),
-                      "kanvit_edge_l1_fwd")
+        _launch(L.kanvit_edge_l1_fwd, "kanvit_edge_l1_fwd", x.device, C.byref(d), _ptr(x), _ptr(w), _ptr(bparams), _ptr(A),
+                query=(L.kanvit_edge_l1_fwd_workspace, C.byref(d)), tag="edge_l1_fwd",
+                cost=(2 * x.shape[0] * cfg.K * cfg.O * cfg.groups, 4 * (x.numel() + w.numel() + A.numel())))
         ctx.cfg = cfg
         ctx.save_for_backward(x, w, bparams)
         return A
@@ -545,13 +535,10 @@ class _EdgeL1Fn(torch.autograd.Function):
         dw = torch.empty_like(w)
         # dx in x's own row stride (the descriptor has one ldx); NULL when nobody asks for it: the kernel then skips the derivatives
         dx = torch.empty_strided(x.shape, (d.ldx, 1), device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        with torch.cuda.device(x.device):
-            nbytes = int(L.kanvit_edge_l1_bwd_workspace(C.byref(d)))
-            ws = _workspace(nbytes, x.device)
-            with _timed("edge_l1_bwd", (6 if dx is not None else 4) * x.shape[0] * cfg.K * cfg.O * cfg.groups,
-                        4 * ((1 if dx is None else 2) * x.numel() + 2 * w.numel() + gA.numel())):
-                check(L.kanvit_edge_l1_bwd(C.byref(d), _ptr(x), _ptr(w), _ptr(bparams), _ptr(gA), _ptr(dw), _ptr(dx), _ptr(ws),
-                                           C.c_size_t(nbytes), _stream()), "kanvit_edge_l1_bwd")
+        _launch(L.kanvit_edge_l1_bwd, "kanvit_edge_l1_bwd", x.device, C.byref(d), _ptr(x), _ptr(w), _ptr(bparams), _ptr(gA), _ptr(dw), _ptr(dx),
+                query=(L.kanvit_edge_l1_bwd_workspace, C.byref(d)), tag="edge_l1_bwd",
+                cost=((6 if dx is not None else 4) * x.shape[0] * cfg.K * cfg.O * cfg.groups,
+                      4 * ((1 if dx is None else 2) * x.numel() + 2 * w.numel() + gA.numel())))
         return dx, dw, None, None
 
 
@@ -566,7 +553,6 @@ def edge_l1(x2d: torch.Tensor, w_packed: torch.Tensor, cfg: LayerCfg, bparams: O
         raise NotImplementedError(f"edge_l1: family {_lib.FAMILY_NAMES[cfg.family]} is not supported (supported: bspline, cheby, rbf)")
     keep = _lib.FLAG_UNIFORM_KNOTS | _lib.FLAG_SHARED_BPARAMS
     if cfg.flags & ~keep:
-        from dataclasses import replace
         cfg = replace(cfg, flags=cfg.flags & keep)
     return _EdgeL1Fn.apply(x2d, w_packed, bparams, cfg)
 
@@ -584,6 +570,60 @@ def l1_entropy_loss(l1: torch.Tensor, regularize_activation: float = 1.0, regula
 # ------------------------------------------------------------------------------------------------
 # B-spline refit to a new knot table (KANLinear.update_grid; csrc/kan_bspline_refit.hip)
 # ------------------------------------------------------------------------------------------------
+def _bspline_fit(who: str, x2d, w_old_packed, cfg: LayerCfg, old_G: int, old_knots, new_knots, keep_old: bool):
+    """The body of bspline_refit (old_G = cfg.G, keep_old: a flagged feature's rows of w_new are the old ones) and of
+    bspline_regrid (rows of zeros): validation under the caller's name `who`, then the kanvit_<who>_gram and _solve launches."""
+    if cfg.family != BSPLINE:
+        raise NotImplementedError(f"{who}: family {_lib.FAMILY_NAMES[cfg.family]} has no knot table to refit (bspline only)")
+    cfg = replace(cfg, flags=cfg.flags & (_lib.FLAG_UNIFORM_KNOTS | _lib.FLAG_SHARED_BPARAMS))
+    for n, t in (("x", x2d), ("w_old", w_old_packed), ("old_knots", old_knots), ("new_knots", new_knots)):
+        _require_gpu_f32(n, t)
+    x = x2d
+    if x.dim() != 2:
+        raise KanvitError(f"{who}: x must be 2-D, got {tuple(x.shape)}")
+    if x.shape[1] != cfg.x_group_mod * cfg.I:
+        raise KanvitError(f"{who}: x has {x.shape[1]} columns, expected {cfg.x_group_mod * cfg.I}")
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):      # a column slice of a wider matrix is read in place
+        x = x.contiguous()
+    M = x.shape[0]
+    ldx = max(x.stride(0), x.shape[1]) if M > 1 else x.shape[1]
+    nb, nk = cfg.G, cfg.G + cfg.spline_order + 1
+    nbo, nko = old_G, old_G + cfg.spline_order + 1
+    w_old = w_old_packed.contiguous()
+    if tuple(w_old.shape) != (cfg.groups, cfg.I * nbo, cfg.O):
+        raise KanvitError(f"{who}: packed weight shape {tuple(w_old.shape)} != {(cfg.groups, cfg.I * nbo, cfg.O)}" if keep_old else
+                          f"{who}: old packed weight shape {tuple(w_old.shape)} != {(cfg.groups, cfg.I * nbo, cfg.O)} (old nb={nbo})")
+    old_msg = "{}: old knot table {} does not hold [{}][{}*{}]"
+    if not keep_old and (old_knots.dim() < 1 or old_knots.shape[0] != cfg.groups):
+        raise KanvitError(old_msg.format(who, tuple(old_knots.shape), cfg.groups, cfg.I, nko))
+    old_knots = old_knots.reshape(cfg.groups, -1).contiguous()
+    new_knots = new_knots.contiguous()
+    bad_old, bad_new = old_knots.shape[1] < cfg.I * nko, tuple(new_knots.shape) != (cfg.x_group_mod, cfg.I, nk)
+    if keep_old and (bad_old or bad_new):
+        raise KanvitError(f"{who}: knot tables {tuple(old_knots.shape)} / {tuple(new_knots.shape)} do not hold "
+                          f"[{cfg.groups}][{cfg.I}*{nk}] / [{cfg.x_group_mod}][{cfg.I}][{nk}]")
+    if bad_old:
+        raise KanvitError(old_msg.format(who, tuple(old_knots.shape), cfg.groups, cfg.I, nko))
+    if bad_new:
+        raise KanvitError(f"{who}: new knot table {tuple(new_knots.shape)} != [{cfg.x_group_mod}][{cfg.I}][{nk}]")
+    d = _desc(cfg, M, ldx, 0, cfg.groups * cfg.O, old_knots.shape[1])
+    L = _lib.lib()
+    dev = x.device
+    lead = (C.byref(d),) if keep_old else (C.byref(d), C.c_int(old_G))         # the regrid entry points take the old basis size
+    gram_n = torch.empty(cfg.x_group_mod, cfg.I, nb, nb, device=dev, dtype=torch.float64)
+    gram_c = torch.empty(cfg.groups, cfg.I, nb, nbo, device=dev, dtype=torch.float64)
+    # the rows of a flagged feature are not written: they stay the old ones, or zero where the old rows have another shape
+    w_new = w_old.clone() if keep_old else torch.zeros(cfg.groups, cfg.I * nb, cfg.O, device=dev, dtype=torch.float32)
+    ok = torch.empty(cfg.x_group_mod, cfg.I, device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev), _timed(who, 2 * M * cfg.I * nb * (cfg.groups * nbo + cfg.x_group_mod * nb),
+                                        4 * (x.numel() + w_old.numel() + w_new.numel())):
+        _launch(getattr(L, f"kanvit_{who}_gram"), f"kanvit_{who}_gram", dev, *lead, _ptr(x), _ptr(old_knots), _ptr(new_knots), _ptr(gram_n),
+                _ptr(gram_c), query=(getattr(L, f"kanvit_{who}_workspace"), *lead))
+        _launch(getattr(L, f"kanvit_{who}_solve"), f"kanvit_{who}_solve", dev, *lead, _ptr(gram_n), _ptr(gram_c), _ptr(w_old), _ptr(w_new),
+                _ptr(ok))
+    return w_new, ok.bool()
+
+
 @torch.no_grad()
 def bspline_refit(x2d: torch.Tensor, w_old_packed: torch.Tensor, cfg: LayerCfg, old_knots: torch.Tensor,
                   new_knots: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -595,46 +635,7 @@ def bspline_refit(x2d: torch.Tensor, w_old_packed: torch.Tensor, cfg: LayerCfg, 
     column.  ok is False for a feature whose fit does not exist (constant column, fewer distinct samples than nb, ...): its rows
     of w_new_packed are w_old_packed's.  Exact fp32 / float64 also under autocast, deterministic, no autograd, no host
     synchronisation (HIP-graph capturable); workspace and matrices come from the torch allocator."""
-    if cfg.family != BSPLINE:
-        raise NotImplementedError(f"bspline_refit: family {_lib.FAMILY_NAMES[cfg.family]} has no knot table to refit (bspline only)")
-    from dataclasses import replace
-    cfg = replace(cfg, flags=cfg.flags & (_lib.FLAG_UNIFORM_KNOTS | _lib.FLAG_SHARED_BPARAMS))
-    for n, t in (("x", x2d), ("w_old", w_old_packed), ("old_knots", old_knots), ("new_knots", new_knots)):
-        _require_gpu_f32(n, t)
-    x = x2d
-    if x.dim() != 2:
-        raise KanvitError(f"bspline_refit: x must be 2-D, got {tuple(x.shape)}")
-    if x.shape[1] != cfg.x_group_mod * cfg.I:
-        raise KanvitError(f"bspline_refit: x has {x.shape[1]} columns, expected {cfg.x_group_mod * cfg.I}")
-    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):      # a column slice of a wider matrix is read in place
-        x = x.contiguous()
-    M = x.shape[0]
-    ldx = max(x.stride(0), x.shape[1]) if M > 1 else x.shape[1]
-    nb, nk = cfg.G, cfg.G + cfg.spline_order + 1
-    w_old = w_old_packed.contiguous()
-    if tuple(w_old.shape) != (cfg.groups, cfg.I * nb, cfg.O):
-        raise KanvitError(f"bspline_refit: packed weight shape {tuple(w_old.shape)} != {(cfg.groups, cfg.I * nb, cfg.O)}")
-    old_knots = old_knots.reshape(cfg.groups, -1).contiguous()
-    new_knots = new_knots.contiguous()
-    if old_knots.shape[1] < cfg.I * nk or tuple(new_knots.shape) != (cfg.x_group_mod, cfg.I, nk):
-        raise KanvitError(f"bspline_refit: knot tables {tuple(old_knots.shape)} / {tuple(new_knots.shape)} do not hold "
-                          f"[{cfg.groups}][{cfg.I}*{nk}] / [{cfg.x_group_mod}][{cfg.I}][{nk}]")
-    d = _desc(cfg, M, ldx, 0, cfg.groups * cfg.O, old_knots.shape[1])
-    L = _lib.lib()
-    dev = x.device
-    gram_n = torch.empty(cfg.x_group_mod, cfg.I, nb, nb, device=dev, dtype=torch.float64)
-    gram_c = torch.empty(cfg.groups, cfg.I, nb, nb, device=dev, dtype=torch.float64)
-    w_new = w_old.clone()                                    # the rows of a flagged feature are not written: they stay the old ones
-    ok = torch.empty(cfg.x_group_mod, cfg.I, device=dev, dtype=torch.uint8)
-    with torch.cuda.device(dev):
-        nbytes = int(L.kanvit_bspline_refit_workspace(C.byref(d)))
-        ws = _workspace(nbytes, dev)
-        with _timed("bspline_refit", 2 * M * (cfg.groups + cfg.x_group_mod) * cfg.I * nb * nb, 4 * (x.numel() + 2 * w_old.numel())):
-            check(L.kanvit_bspline_refit_gram(C.byref(d), _ptr(x), _ptr(old_knots), _ptr(new_knots), _ptr(gram_n), _ptr(gram_c), _ptr(ws),
-                                              C.c_size_t(nbytes), _stream()), "kanvit_bspline_refit_gram")
-            check(L.kanvit_bspline_refit_solve(C.byref(d), _ptr(gram_n), _ptr(gram_c), _ptr(w_old), _ptr(w_new), _ptr(ok), _stream()),
-                  "kanvit_bspline_refit_solve")
-    return w_new, ok.bool()
+    return _bspline_fit("bspline_refit", x2d, w_old_packed, cfg, cfg.G, old_knots, new_knots, keep_old=True)
 
 
 @torch.no_grad()
@@ -647,53 +648,7 @@ def bspline_regrid(x2d: torch.Tensor, w_old_packed: torch.Tensor, cfg_new: Layer
     the normal equations is rectangular, nb_new x nb_old; everything else is bspline_refit's.  ok is False for a feature whose
     fit does not exist; its rows of w_new_packed are ZERO (there are no old rows of the new shape to keep).  Exact fp32 /
     float64 also under autocast, deterministic, no autograd, no host synchronisation."""
-    if cfg_new.family != BSPLINE:
-        raise NotImplementedError(f"bspline_regrid: family {_lib.FAMILY_NAMES[cfg_new.family]} has no knot table to refit (bspline only)")
-    from dataclasses import replace
-    cfg = replace(cfg_new, flags=cfg_new.flags & (_lib.FLAG_UNIFORM_KNOTS | _lib.FLAG_SHARED_BPARAMS))
-    old_G = int(old_G)
-    for n, t in (("x", x2d), ("w_old", w_old_packed), ("old_knots", old_knots), ("new_knots", new_knots)):
-        _require_gpu_f32(n, t)
-    x = x2d
-    if x.dim() != 2:
-        raise KanvitError(f"bspline_regrid: x must be 2-D, got {tuple(x.shape)}")
-    if x.shape[1] != cfg.x_group_mod * cfg.I:
-        raise KanvitError(f"bspline_regrid: x has {x.shape[1]} columns, expected {cfg.x_group_mod * cfg.I}")
-    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):      # a column slice of a wider matrix is read in place
-        x = x.contiguous()
-    M = x.shape[0]
-    ldx = max(x.stride(0), x.shape[1]) if M > 1 else x.shape[1]
-    nb, nk = cfg.G, cfg.G + cfg.spline_order + 1
-    nbo, nko = old_G, old_G + cfg.spline_order + 1
-    w_old = w_old_packed.contiguous()
-    if tuple(w_old.shape) != (cfg.groups, cfg.I * nbo, cfg.O):
-        raise KanvitError(f"bspline_regrid: old packed weight shape {tuple(w_old.shape)} != {(cfg.groups, cfg.I * nbo, cfg.O)} "
-                          f"(old nb={nbo})")
-    if old_knots.dim() < 1 or old_knots.shape[0] != cfg.groups:
-        raise KanvitError(f"bspline_regrid: old knot table {tuple(old_knots.shape)} does not hold [{cfg.groups}][{cfg.I}*{nko}]")
-    old_knots = old_knots.reshape(cfg.groups, -1).contiguous()
-    new_knots = new_knots.contiguous()
-    if old_knots.shape[1] < cfg.I * nko:
-        raise KanvitError(f"bspline_regrid: old knot table {tuple(old_knots.shape)} does not hold [{cfg.groups}][{cfg.I}*{nko}]")
-    if tuple(new_knots.shape) != (cfg.x_group_mod, cfg.I, nk):
-        raise KanvitError(f"bspline_regrid: new knot table {tuple(new_knots.shape)} != [{cfg.x_group_mod}][{cfg.I}][{nk}]")
-    d = _desc(cfg, M, ldx, 0, cfg.groups * cfg.O, old_knots.shape[1])
-    L = _lib.lib()
-    dev = x.device
-    og = C.c_int(old_G)
-    gram_n = torch.empty(cfg.x_group_mod, cfg.I, nb, nb, device=dev, dtype=torch.float64)
-    gram_c = torch.empty(cfg.groups, cfg.I, nb, nbo, device=dev, dtype=torch.float64)
-    w_new = torch.zeros(cfg.groups, cfg.I * nb, cfg.O, device=dev, dtype=torch.float32)      # a flagged feature's rows are not written
-    ok = torch.empty(cfg.x_group_mod, cfg.I, device=dev, dtype=torch.uint8)
-    with torch.cuda.device(dev):
-        nbytes = int(L.kanvit_bspline_regrid_workspace(C.byref(d), og))
-        ws = _workspace(nbytes, dev)
-        with _timed("bspline_regrid", 2 * M * cfg.I * nb * (cfg.groups * nbo + cfg.x_group_mod * nb), 4 * (x.numel() + w_old.numel() + w_new.numel())):
-            check(L.kanvit_bspline_regrid_gram(C.byref(d), og, _ptr(x), _ptr(old_knots), _ptr(new_knots), _ptr(gram_n), _ptr(gram_c), _ptr(ws),
-                                               C.c_size_t(nbytes), _stream()), "kanvit_bspline_regrid_gram")
-            check(L.kanvit_bspline_regrid_solve(C.byref(d), og, _ptr(gram_n), _ptr(gram_c), _ptr(w_old), _ptr(w_new), _ptr(ok), _stream()),
-                  "kanvit_bspline_regrid_solve")
-    return w_new, ok.bool()
+    return _bspline_fit("bspline_regrid", x2d, w_old_packed, cfg_new, int(old_G), old_knots, new_knots, keep_old=False)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -751,31 +706,41 @@ def _attn_takes_general_kernels(q, k) -> bool:
 def _attn_fwd(q, k, v, o, causal, scale, flags=0):
     if _attn_takes_general_kernels(q, k):
         return _attn_x_fwd(q, k, v, o, None, causal, scale, flags=_attn_x_flags(flags, q.shape[3]))
-    B, H, N, _ = q.shape
+    B, H, N, D = q.shape
     lse = torch.empty(B, H, N, device=q.device, dtype=torch.float32)
     d = _attn_desc(q, k, v, o, causal, scale, flags)
-    flops, nbytes = 4 * B * H * N * N * q.shape[3], 4 * 4 * B * H * N * q.shape[3]
-    with torch.cuda.device(q.device), _timed("attn_fwd" + ("_bf16" if flags & 1 else ""), flops, nbytes):
-        check(_lib.lib().kanvit_attn_fwd(C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _stream()),
-              "kanvit_attn_fwd")
+    _launch(_lib.lib().kanvit_attn_fwd, "kanvit_attn_fwd", q.device, C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse),
+            tag=_bf16_tag("attn_fwd", flags), cost=(4 * B * H * N * N * D, 4 * 4 * B * H * N * D))
     return lse
+
+
+def _attn_backward(name, descs, q, k, v, o, lse, do, dq, dk, dv, tag, cost):
+    """The backward launch of either attention path: entry point `name` and its workspace query `name`_workspace, both led by
+    the descriptor(s) `descs`."""
+    if (do.stride() != o.stride()) or dq.stride() != q.stride() or dk.stride() != k.stride() or dv.stride() != v.stride():
+        raise KanvitError("attention backward: gradient layouts must match their forward tensors")
+    L = _lib.lib()
+    lead = tuple(C.byref(t) for t in descs)
+    _launch(getattr(L, name), name, q.device, *lead, _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _ptr(do), _ptr(dq), _ptr(dk), _ptr(dv),
+            query=(getattr(L, name + "_workspace"), *lead), tag=tag, cost=cost)
 
 
 def _attn_bwd(q, k, v, o, lse, do, dq, dk, dv, causal, scale, flags=0):
     if _attn_takes_general_kernels(q, k):
         return _attn_x_bwd(q, k, v, o, lse, do, dq, dk, dv, None, causal, scale, flags=_attn_x_flags(flags, q.shape[3]))
     d = _attn_desc(q, k, v, o, causal, scale, flags)
-    if (do.stride() != o.stride()) or dq.stride() != q.stride() or dk.stride() != k.stride() or dv.stride() != v.stride():
-        raise KanvitError("attention backward: gradient layouts must match their forward tensors")
-    L = _lib.lib()
-    nbytes = int(L.kanvit_attn_bwd_workspace(C.byref(d)))
-    ws = torch.empty(max(nbytes // 4, 1), device=q.device, dtype=torch.float32)
     B, H, N, D = q.shape
     # algorithmic work of a recompute backward: 5 products (S, dP, dV, dK, dQ) = 2.5x the forward; the two-kernel bf16 path
     # executes 7 (S and dP twice), the fp32 dS-spill path exactly 5
-    with torch.cuda.device(q.device), _timed("attn_bwd" + ("_bf16" if flags & 1 else ""), 10 * B * H * N * N * D, 4 * 9 * B * H * N * D):
-        check(L.kanvit_attn_bwd(C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _ptr(do), _ptr(dq), _ptr(dk),
-                                _ptr(dv), _ptr(ws), C.c_size_t(nbytes), _stream()), "kanvit_attn_bwd")
+    _attn_backward("kanvit_attn_bwd", (d,), q, k, v, o, lse, do, dq, dk, dv, _bf16_tag("attn_bwd", flags),
+                   (10 * B * H * N * N * D, 4 * 9 * B * H * N * D))
+
+
+def _attn_ext(Nk: int, mask) -> "_lib.AttnExt":
+    """kanvit_attn_ext of Nk keys and a mask that is None or torch.bool on the device, expanded to [B, H, Nq, Nk]."""
+    if mask is None:
+        return _lib.AttnExt(Nk, 0, None, 0, 0, 0, 0)
+    return _lib.AttnExt(Nk, 0, mask.data_ptr(), mask.stride(0), mask.stride(1), mask.stride(2), mask.stride(3))
 
 
 def _attn_x_desc(q, k, v, o, mask, causal: bool, scale: float, flags: int = 0):
@@ -785,13 +750,9 @@ def _attn_x_desc(q, k, v, o, mask, causal: bool, scale: float, flags: int = 0):
         _require_gpu_f32(n, t)
     d = _attn_build_desc(q, k, v, o, causal, scale, flags, False)
     B, H, Nq, Nk = d.B, d.H, d.N, k.shape[2]
-    if mask is None:
-        e = _lib.AttnExt(Nk, 0, None, 0, 0, 0, 0)
-    else:
-        if mask.dtype != torch.bool or not mask.is_cuda or tuple(mask.shape) != (B, H, Nq, Nk):
-            raise KanvitError(f"attention mask: need a torch.bool GPU tensor expanded to {(B, H, Nq, Nk)}, got {mask.dtype} {tuple(mask.shape)}")
-        e = _lib.AttnExt(Nk, 0, mask.data_ptr(), mask.stride(0), mask.stride(1), mask.stride(2), mask.stride(3))
-    return d, e
+    if mask is not None and (mask.dtype != torch.bool or not mask.is_cuda or tuple(mask.shape) != (B, H, Nq, Nk)):
+        raise KanvitError(f"attention mask: need a torch.bool GPU tensor expanded to {(B, H, Nq, Nk)}, got {mask.dtype} {tuple(mask.shape)}")
+    return d, _attn_ext(Nk, mask)
 
 
 def _attn_x_fwd(q, k, v, o, mask, causal, scale, flags=0):
@@ -800,25 +761,17 @@ def _attn_x_fwd(q, k, v, o, mask, causal, scale, flags=0):
     lse = torch.empty(B, H, Nq, device=q.device, dtype=torch.float32)
     d, e = _attn_x_desc(q, k, v, o, mask, causal, scale, flags)
     Nk = k.shape[2]
-    tag = "attn_x_fwd" + ("_bf16" if flags & _lib.FLAG_BF16_MFMA else "")
-    with torch.cuda.device(q.device), _timed(tag, 4 * B * H * Nq * Nk * D, 4 * 2 * B * H * (Nq + Nk) * D):
-        check(_lib.lib().kanvit_attn_x_fwd(C.byref(d), C.byref(e), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _stream()), "kanvit_attn_x_fwd")
+    _launch(_lib.lib().kanvit_attn_x_fwd, "kanvit_attn_x_fwd", q.device, C.byref(d), C.byref(e), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse),
+            tag=_bf16_tag("attn_x_fwd", flags), cost=(4 * B * H * Nq * Nk * D, 4 * 2 * B * H * (Nq + Nk) * D))
     return lse
 
 
 def _attn_x_bwd(q, k, v, o, lse, do, dq, dk, dv, mask, causal, scale, flags=0):
     d, e = _attn_x_desc(q, k, v, o, mask, causal, scale, flags)
-    if (do.stride() != o.stride()) or dq.stride() != q.stride() or dk.stride() != k.stride() or dv.stride() != v.stride():
-        raise KanvitError("attention backward: gradient layouts must match their forward tensors")
-    L = _lib.lib()
-    nbytes = int(L.kanvit_attn_x_bwd_workspace(C.byref(d), C.byref(e)))
-    ws = torch.empty(max(nbytes // 4, 1), device=q.device, dtype=torch.float32)
     B, H, Nq, D = q.shape
     Nk = k.shape[2]
-    tag = "attn_x_bwd" + ("_bf16" if flags & _lib.FLAG_BF16_MFMA else "")
-    with torch.cuda.device(q.device), _timed(tag, 14 * B * H * Nq * Nk * D, 4 * 4 * B * H * (Nq + Nk) * D):
-        check(L.kanvit_attn_x_bwd(C.byref(d), C.byref(e), _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _ptr(do), _ptr(dq), _ptr(dk),
-                                  _ptr(dv), _ptr(ws), C.c_size_t(nbytes), _stream()), "kanvit_attn_x_bwd")
+    _attn_backward("kanvit_attn_x_bwd", (d, e), q, k, v, o, lse, do, dq, dk, dv, _bf16_tag("attn_x_bwd", flags),
+                   (14 * B * H * Nq * Nk * D, 4 * 4 * B * H * (Nq + Nk) * D))
 
 
 class _AttnPackedFn(torch.autograd.Function):
@@ -882,6 +835,12 @@ def _autocast_flags() -> int:
     return _lib.FLAG_BF16_MFMA if on else 0
 
 
+def _autocast_cfg(cfg: LayerCfg) -> LayerCfg:
+    """cfg with the flag of _autocast_flags() added."""
+    f = cfg.flags | _autocast_flags()
+    return cfg if f == cfg.flags else replace(cfg, flags=f)
+
+
 def attention_packed(qkv: torch.Tensor, causal: bool = False, scale: Optional[float] = None) -> torch.Tensor:
     """Self-attention on qkv[B, N, 3, H, D] -> o[B, N, H*D].  D even and <= 128.  Heads of D <= 64 that fit one work-group run the
     ViT kernels, longer sequences the chunked general kernels; under bf16 autocast both run on the bf16 matrix cores
@@ -914,9 +873,8 @@ class _AttnQ1Fn(torch.autograd.Function):
         p = torch.empty(B, H, N, device=kv.device, dtype=torch.float32)
         d, e = _attn_q1_desc(q0, kv, o, scale)
         # 2 flops per element of k and of v; k and v are read once, o and p are small
-        with torch.cuda.device(kv.device), _timed("attn_q1_fwd", 4 * B * H * N * D, 4 * B * H * (2 * N * D + N + 2 * D)):
-            check(_lib.lib().kanvit_attn_q1_fwd(C.byref(d), C.byref(e), _ptr(q0), _ptr(kv[:, :, 0]), _ptr(kv[:, :, 1]), _ptr(o), _ptr(p),
-                                                _stream()), "kanvit_attn_q1_fwd")
+        _launch(_lib.lib().kanvit_attn_q1_fwd, "kanvit_attn_q1_fwd", kv.device, C.byref(d), C.byref(e), _ptr(q0), _ptr(kv[:, :, 0]),
+                _ptr(kv[:, :, 1]), _ptr(o), _ptr(p), tag="attn_q1_fwd", cost=(4 * B * H * N * D, 4 * B * H * (2 * N * D + N + 2 * D)))
         ctx.save_for_backward(q0, kv, o, p)
         ctx.scale = scale
         return o
@@ -930,9 +888,9 @@ class _AttnQ1Fn(torch.autograd.Function):
         dq = torch.empty_like(q0)
         dkv = torch.empty_like(kv)
         d, e = _attn_q1_desc(q0, kv, o, ctx.scale)
-        with torch.cuda.device(kv.device), _timed("attn_q1_bwd", 8 * B * H * N * D, 4 * B * H * (4 * N * D + N + 4 * D)):
-            check(_lib.lib().kanvit_attn_q1_bwd(C.byref(d), C.byref(e), _ptr(q0), _ptr(kv[:, :, 0]), _ptr(kv[:, :, 1]), _ptr(o), _ptr(p),
-                                                _ptr(do), _ptr(dq), _ptr(dkv[:, :, 0]), _ptr(dkv[:, :, 1]), _stream()), "kanvit_attn_q1_bwd")
+        _launch(_lib.lib().kanvit_attn_q1_bwd, "kanvit_attn_q1_bwd", kv.device, C.byref(d), C.byref(e), _ptr(q0), _ptr(kv[:, :, 0]),
+                _ptr(kv[:, :, 1]), _ptr(o), _ptr(p), _ptr(do), _ptr(dq), _ptr(dkv[:, :, 0]), _ptr(dkv[:, :, 1]),
+                tag="attn_q1_bwd", cost=(8 * B * H * N * D, 4 * B * H * (4 * N * D + N + 4 * D)))
         return dq, dkv, None
 
 
@@ -942,7 +900,7 @@ def _attn_q1_desc(q0, kv, o, scale: float):
     k = kv[:, :, 0]                  # [B, N, H, D]
     d = AttnDesc(B, H, 1, D, 0, float(scale), 0, 0, q0.stride(0), q0.stride(1), 0, k.stride(0), k.stride(2), k.stride(1),
                  k.stride(0), k.stride(2), k.stride(1), o.stride(0), o.stride(1), 0)
-    return d, _lib.AttnExt(N, 0, None, 0, 0, 0, 0)
+    return d, _attn_ext(N, None)
 
 
 def attention_q1(q0: torch.Tensor, kv: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
@@ -983,15 +941,11 @@ def _attn_probs(q, k, mask, causal, scale, rows):
         return torch.empty(B, H, rows, Nk, device=q.device, dtype=torch.float32)
     d = AttnDesc(B, H, Nq, D, int(bool(causal)), float(scale), 0, 0, q.stride(0), q.stride(1), q.stride(2),
                  k.stride(0), k.stride(1), k.stride(2), 0, 0, 0, 0, 0, 0)
-    if mask is None:
-        e = _lib.AttnExt(Nk, 0, None, 0, 0, 0, 0)
-    else:               # expand_attention_mask: torch.bool on q's device, [B, H, Nq, Nk]
-        e = _lib.AttnExt(Nk, 0, mask.data_ptr(), mask.stride(0), mask.stride(1), mask.stride(2), mask.stride(3))
+    e = _attn_ext(Nk, mask)     # expand_attention_mask: torch.bool on q's device, [B, H, Nq, Nk]
     p = torch.empty(B, H, rows, Nk, device=q.device, dtype=torch.float32)
     # three sweeps of the q.k products (max, sum, store); the map itself is the traffic
-    with torch.cuda.device(q.device), _timed("attn_probs", 6 * B * H * rows * Nk * D, 4 * B * H * (rows * Nk + rows * D + Nk * D)):
-        check(_lib.lib().kanvit_attn_probs(C.byref(d), C.byref(e), _ptr(q), _ptr(k), _ptr(p), p.stride(0), p.stride(1), p.stride(2),
-                                           rows, _stream()), "kanvit_attn_probs")
+    _launch(_lib.lib().kanvit_attn_probs, "kanvit_attn_probs", q.device, C.byref(d), C.byref(e), _ptr(q), _ptr(k), _ptr(p), p.stride(0),
+            p.stride(1), p.stride(2), rows, tag="attn_probs", cost=(6 * B * H * rows * Nk * D, 4 * B * H * (rows * Nk + rows * D + Nk * D)))
     return p
 
 
@@ -1055,10 +1009,9 @@ class _AddLayerNormFn(torch.autograd.Function):
         mean = torch.empty(M, device=x.device, dtype=torch.float32)
         rstd = torch.empty(M, device=x.device, dtype=torch.float32)
         g, b = gamma.float().contiguous(), beta.float().contiguous()
-        with torch.cuda.device(x.device):          # launch on x's device and ITS current stream, whatever the ambient device is
-            check(L.kanvit_addln_fwd_ex(M, D, float(eps), _ptr(x2), _ptr(d2), int(d2 is not None and d2.dtype == torch.bfloat16), _ptr(g), _ptr(b),
-                                        _ptr(s) if d2 is not None else None, _ptr(y), int(bool(y_bf16)), _ptr(mean), _ptr(rstd), _stream()),
-                  "kanvit_addln_fwd")
+        _launch(L.kanvit_addln_fwd_ex, "kanvit_addln_fwd", x.device, M, D, float(eps), _ptr(x2), _ptr(d2),
+                int(d2 is not None and d2.dtype == torch.bfloat16), _ptr(g), _ptr(b), _ptr(s) if d2 is not None else None, _ptr(y),
+                int(bool(y_bf16)), _ptr(mean), _ptr(rstd))
         ctx.save_for_backward(s, g, mean, rstd)
         ctx.delta_dtype = None if d2 is None else d2.dtype
         ctx.shape = x.shape
@@ -1081,11 +1034,8 @@ class _AddLayerNormFn(torch.autograd.Function):
         dxb = torch.empty(M, D, device=s.device, dtype=torch.bfloat16) if ctx.delta_dtype == torch.bfloat16 else None
         dg = torch.empty(D, device=s.device, dtype=torch.float32)
         db = torch.empty(D, device=s.device, dtype=torch.float32)
-        nbytes = int(L.kanvit_addln_bwd_workspace(M, D))
-        ws = _workspace(nbytes, s.device)
-        with torch.cuda.device(s.device):
-            check(L.kanvit_addln_bwd_ex(M, D, _ptr(s), _ptr(g), _ptr(mean), _ptr(rstd), _ptr(gy2), int(gy2.dtype == torch.bfloat16), _ptr(gs2),
-                                        _ptr(dx), _ptr(dxb), _ptr(dg), _ptr(db), _ptr(ws), C.c_size_t(nbytes), _stream()), "kanvit_addln_bwd")
+        _launch(L.kanvit_addln_bwd_ex, "kanvit_addln_bwd", s.device, M, D, _ptr(s), _ptr(g), _ptr(mean), _ptr(rstd), _ptr(gy2),
+                int(gy2.dtype == torch.bfloat16), _ptr(gs2), _ptr(dx), _ptr(dxb), _ptr(dg), _ptr(db), query=(L.kanvit_addln_bwd_workspace, M, D))
         dx = dx.view(ctx.shape)
         dd = None if ctx.delta_dtype is None else (dxb.view(ctx.shape) if dxb is not None else dx)
         return dx, dd, dg, db, None, None
@@ -1145,9 +1095,7 @@ def augment_u8(images: torch.Tensor, labels: Optional[torch.Tensor], idx: torch.
         raise KanvitError(f"augment_u8: out has shape {tuple(out.shape)}, expected {(B, Cn, H, W)}")
     y = torch.empty((B,), device=images.device, dtype=torch.int64) if labels is not None else None
     params = torch.empty((B, 3), device=images.device, dtype=torch.int32) if return_params else None
-    with torch.cuda.device(images.device):
-        check(_lib.lib().kanvit_augment_u8(_ptr(images), _ptr(labels), _ptr(idx), _ptr(lut), _ptr(out), _ptr(y), _ptr(params), N, B, H, W, Cn,
-                                           pad_y, pad_x, int(bool(flip)), int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1), _stream()),
-              "kanvit_augment_u8")
+    _launch(_lib.lib().kanvit_augment_u8, "kanvit_augment_u8", images.device, _ptr(images), _ptr(labels), _ptr(idx), _ptr(lut), _ptr(out), _ptr(y),
+            _ptr(params), N, B, H, W, Cn, pad_y, pad_x, int(bool(flip)), int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1))
     res = (out,) + ((y,) if labels is not None else ()) + ((params,) if return_params else ())
     return res[0] if len(res) == 1 else res

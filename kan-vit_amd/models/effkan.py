@@ -9,6 +9,7 @@ knots with the reference's torch expressions and refits the weights in the fused
 (kanvit.ops.bspline_refit); ``extend_grid`` carries the layer to another ``grid_size`` the same way
 (kanvit.ops.bspline_regrid, section 4.15)."""
 import math
+from dataclasses import replace
 
 import torch
 import torch.nn.functional as F
@@ -178,13 +179,11 @@ class KANLinear(torch.nn.Module):
         fewer distinct samples than basis functions) keeps its knots and weights, i.e. its function; the reference's answer
         there depends on the LAPACK driver.  Returns the number of features kept unchanged, a 0-d device tensor (the reference
         returns None)."""
-        from dataclasses import replace
         assert x.dim() == 2 and x.size(1) == self.in_features
         x = x.float()
         new_grid = self.adapted_grid(x, self.grid_size, self.spline_order, self.grid_eps, margin)
-        cfg = replace(self.kan_cfg(), has_base=0, base_act=0)
-        w_old = self.scaled_spline_weight.permute(1, 2, 0).reshape(1, -1, self.out_features)
-        w_new, ok = ops.bspline_refit(x, w_old, cfg, self.grid.reshape(1, -1), new_grid.unsqueeze(0))
+        cfg, w_old, old = self.regrid_operands(self.grid_size)
+        w_new, ok = ops.bspline_refit(x, w_old, cfg, old, new_grid.unsqueeze(0))
         self.apply_refit(new_grid, w_new[0], ok[0])
         return (~ok).sum()
 
@@ -246,7 +245,6 @@ class KANLinear(torch.nn.Module):
 
     def regrid_operands(self, grid_size):
         """(cfg of the layer at `grid_size`, packed old spline weights [1, in*nb_old, out], old knots [1, in*nk_old])."""
-        from dataclasses import replace
         cfg = replace(self.kan_cfg(), has_base=0, base_act=0, G=grid_size + self.spline_order)
         w_old = self.scaled_spline_weight.permute(1, 2, 0).reshape(1, -1, self.out_features)
         return cfg, w_old, self.grid.reshape(1, -1)
@@ -283,7 +281,6 @@ class KANLinear(torch.nn.Module):
         regularises and prunes by -- which the reference says it cannot form behind F.linear (models/effkan.py:244-264).  The
         fused kernel reduces over the samples as it generates the basis; the (batch, in, out) tensor never exists.  Without
         the base it is the spline path (scaled_spline_weight), with it the full edge function.  x: any leading dimensions."""
-        from dataclasses import replace
         assert x.size(-1) == self.in_features
         x2d = x if x.dim() == 2 else x.reshape(-1, self.in_features)
         cfg = self.kan_cfg()
