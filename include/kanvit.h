@@ -515,6 +515,38 @@ int kanvit_augment_u8(const uint8_t* images, const int64_t* labels, const int64_
                       int32_t* params_out, int64_t N, int64_t B, int H, int W, int C, int pad_y, int pad_x, int flip, uint64_t seed,
                       uint64_t epoch, void* stream);
 
+/* ---- epoch metrics on the device (kanvit/metrics.py; csrc/augment.hip) ---------------------------------------------------
+ * The reference appends labels, argmax and softmax of every step to host lists and runs scikit-learn on them per epoch
+ * (train.py:42-44, utils.py:13-47).  Accuracy, balanced accuracy and weighted F1 are functions of the C x C confusion matrix; the
+ * one-vs-rest ROC-AUC of class c is the Mann-Whitney statistic (2 gt_c + eq_c) / (2 P_c (N - P_c)) with
+ *   gt_c = #{(i, j): label_i = c, label_j != c, p[i][c] > p[j][c]},  eq_c = the same pairs with p[i][c] == p[j][c]
+ * (float32 compares of the stored values), P_c the samples of class c.  All of it is integer counting: exact, and the same whatever
+ * the order of the atomic adds.
+ *
+ * kanvit_metrics_update: one launch per step.  logits [B][C], float32 (logits_bf16 = 0) or bfloat16 (1, widened exactly), unit
+ * column stride, row stride ld elements; labels [B] int64.  Row b goes to slot n = n0 + b of the state buffers:
+ *   probs_t[c][n]  (float32, CLASS-major [C][cap]) = exp(z_c - max z) / sum_c exp(z_c - max z), in fp32;
+ *   preds_out[n]   (int32) = argmax_c z_c, the smallest index among equal maxima;
+ *   labels_out[n]  (int32) = labels[b], or -1 where labels[b] is outside [0, C);
+ *   confusion[labels[b]][preds_out[n]] += 1  (int64 [C][C], atomic; the caller zeroes it at the start of an epoch).
+ * A row whose label is outside [0, C) is dropped: no confusion update, and the pair counts skip a slot with label -1 both as a
+ * positive and as a negative.  A row's arithmetic does not depend on B or on its position: an epoch fed in other batch sizes gives
+ * the same bits.  KANVIT_EINVAL (named in kanvit_last_error, checked before any launch) for a null pointer, logits_bf16 outside
+ * {0, 1}, C < 2, B < 1, ld < C, n0 < 0 or n0 + B > cap, a pointer not aligned to its element.
+ *
+ * kanvit_metrics_auc_pairs: counts[c][0] = gt_c, counts[c][1] = eq_c (int64 [C][2], zeroed inside the call) over slots 0..n-1 of
+ * probs_t ([C][cap]) and labels (int32 [n], as labels_out above).  A class without positives or without negatives counts 0.  The
+ * cost is n^2 compares in total whatever C is: meant for CIFAR-sized epochs (n <= 2^28 is enforced; an ImageNet-sized epoch wants
+ * a sort-based form, which this is not).  workspace: kanvit_metrics_auc_pairs_workspace(n, C) bytes (a pure host function; 0 for
+ * arguments the call refuses), 16-byte aligned.  KANVIT_EINVAL for a null pointer, C < 2, n < 1, n > cap, n > 2^28, a short or
+ * misaligned workspace.
+ * Neither call synchronises with the host; both are capturable.  Additive: the ABI version stays 7. */
+int kanvit_metrics_update(const void* logits, int logits_bf16, int64_t ld, const int64_t* labels, int64_t B, int C, int64_t n0, int64_t cap,
+                          float* probs_t, int32_t* labels_out, int32_t* preds_out, int64_t* confusion, void* stream);
+size_t kanvit_metrics_auc_pairs_workspace(int64_t n, int C);
+int kanvit_metrics_auc_pairs(const float* probs_t, const int32_t* labels, int64_t n, int C, int64_t cap, int64_t* counts, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* ---- per-family named entry points (SURVEY.md section 8b naming) ----------------------------
  * kanvit_<family>_{fwd,bwd_input,bwd_weight} are kanvit_layer_* with d->family checked;
  * kanvit_<family>_qkv_* additionally require groups == 3 * x_group_mod (one launch for all

@@ -1099,3 +1099,75 @@ def augment_u8(images: torch.Tensor, labels: Optional[torch.Tensor], idx: torch.
             _ptr(params), N, B, H, W, Cn, pad_y, pad_x, int(bool(flip)), int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1))
     res = (out,) + ((y,) if labels is not None else ()) + ((params,) if return_params else ())
     return res[0] if len(res) == 1 else res
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# epoch metrics on the device (kanvit/metrics.py; csrc/augment.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _require_metrics_buffer(who: str, name: str, t: torch.Tensor, dtype, shape, device):
+    if not t.is_cuda:
+        raise KanvitError(f"{who}: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+    if t.device != device:
+        raise KanvitError(f"{who}: {name} is on {t.device}, expected {device}")
+    if t.dtype != dtype:
+        raise KanvitError(f"{who}: {name} has dtype {t.dtype}, expected {dtype}")
+    if not t.is_contiguous():
+        raise KanvitError(f"{who}: {name} is not contiguous")
+    if tuple(t.shape) != tuple(shape):
+        raise KanvitError(f"{who}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+
+
+def metrics_update(logits: torch.Tensor, labels: torch.Tensor, n0: int, probs_t: torch.Tensor, labels_out: torch.Tensor,
+                   preds_out: torch.Tensor, confusion: torch.Tensor) -> None:
+    """One step's rows into the epoch-metrics state, in one launch on the current stream (semantics: include/kanvit.h): the fp32
+    softmax of logits [B, C] (float32 or bfloat16, unit column stride; a padded row stride is taken as it is) goes class-major to
+    probs_t [C, cap] at columns n0 .. n0 + B - 1, labels (int64 [B]) and the first argmax to labels_out / preds_out (int32 [cap]),
+    and confusion (int64 [C, C]) gains one count per row.  A row whose label is outside [0, C) is stored with label -1 and counted
+    nowhere.  No host synchronisation."""
+    who = "metrics_update"
+    if not logits.is_cuda:
+        raise KanvitError(f"{who}: logits is on {logits.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise KanvitError(f"{who}: logits has dtype {logits.dtype}, expected torch.float32 or torch.bfloat16")
+    if logits.dim() != 2:
+        raise KanvitError(f"{who}: logits has shape {tuple(logits.shape)}, expected [B, C]")
+    B, Cn = (int(v) for v in logits.shape)
+    if B < 1 or Cn < 2:
+        raise KanvitError(f"{who}: logits has shape {tuple(logits.shape)}: at least one row and two classes")
+    if logits.stride(1) != 1 or logits.stride(0) < Cn:
+        raise KanvitError(f"{who}: logits has strides {tuple(logits.stride())}: unit column stride and a row stride of at least C = {Cn}")
+    cap = int(probs_t.shape[1]) if probs_t.dim() == 2 else -1
+    _require_metrics_buffer(who, "labels", labels, torch.int64, (B,), logits.device)
+    _require_metrics_buffer(who, "probs_t", probs_t, torch.float32, (Cn, cap), logits.device)
+    _require_metrics_buffer(who, "labels_out", labels_out, torch.int32, (cap,), logits.device)
+    _require_metrics_buffer(who, "preds_out", preds_out, torch.int32, (cap,), logits.device)
+    _require_metrics_buffer(who, "confusion", confusion, torch.int64, (Cn, Cn), logits.device)
+    if n0 < 0 or n0 + B > cap:
+        raise KanvitError(f"{who}: rows {n0} .. {n0 + B - 1} do not fit the capacity {cap}")
+    _launch(_lib.lib().kanvit_metrics_update, "kanvit_metrics_update", logits.device, _ptr(logits), int(logits.dtype == torch.bfloat16),
+            int(logits.stride(0)), _ptr(labels), B, Cn, int(n0), cap, _ptr(probs_t), _ptr(labels_out), _ptr(preds_out), _ptr(confusion),
+            tag="metrics_update", cost=(0, B * Cn * (logits.element_size() + 4)))
+
+
+def metrics_auc_pairs(probs_t: torch.Tensor, labels: torch.Tensor, n: int, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The Mann-Whitney pair counts of the one-vs-rest ROC-AUC over the first n slots of the epoch-metrics state: counts[c] =
+    (gt_c, eq_c), int64 [C, 2] (include/kanvit.h), written into `counts` when given.  probs_t float32 [C, cap] class-major, labels
+    int32 [cap] (-1 = a dropped row).  n * n compares in all; no host synchronisation."""
+    who = "metrics_auc_pairs"
+    if not probs_t.is_cuda:
+        raise KanvitError(f"{who}: probs_t is on {probs_t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+    if probs_t.dim() != 2:
+        raise KanvitError(f"{who}: probs_t has shape {tuple(probs_t.shape)}, expected [C, cap]")
+    Cn, cap = (int(v) for v in probs_t.shape)
+    _require_metrics_buffer(who, "probs_t", probs_t, torch.float32, (Cn, cap), probs_t.device)
+    _require_metrics_buffer(who, "labels", labels, torch.int32, (cap,), probs_t.device)
+    if counts is None:
+        counts = torch.empty((Cn, 2), device=probs_t.device, dtype=torch.int64)
+    _require_metrics_buffer(who, "counts", counts, torch.int64, (Cn, 2), probs_t.device)
+    n = int(n)
+    if n < 1 or n > cap or Cn < 2:
+        raise KanvitError(f"{who}: n = {n} of capacity {cap}, C = {Cn}: at least one sample, at most the capacity, at least two classes")
+    L = _lib.lib()
+    _launch(L.kanvit_metrics_auc_pairs, "kanvit_metrics_auc_pairs", probs_t.device, _ptr(probs_t), _ptr(labels), n, Cn, cap, _ptr(counts),
+            query=(L.kanvit_metrics_auc_pairs_workspace, n, Cn), tag="metrics_auc", cost=(0, 4 * n * Cn))
+    return counts

@@ -17,7 +17,9 @@ step STEP every KANLinear moves to SIZE grid intervals with its function kept),
 --data-npz / --no-augment / --crop-padding (the dataset lives on the GPU as uint8 and one kernel per batch gathers, crops, flips and
 normalises it: kanvit/data.py; the reference's transforms, train.py:100-118, without torchvision, workers or a copy per batch),
 --no-step-metrics (the per-step metrics stay on the device either way: one host sync per epoch instead of the
-reference's three per step, train.py:37,42-44).
+reference's three per step, train.py:37,42-44), --device-metrics (the epoch's four metrics from integer tables counted on the GPU,
+kanvit/metrics.py: one kernel per step, one pair-counting pass per epoch, C*C + 2*C integers to the host -- instead of three lists,
+an [N, C] copy and scikit-learn on one CPU thread).
 
 `main(args, batches=None, init_state=None)` also serves the parity tests: `batches` (a list of (x, y) tensors) replaces
 the data stream, `init_state` (a reference-layout state dict) replaces the random initialisation, and the returned dict
@@ -302,7 +304,9 @@ def main(args, batches=None, init_state=None):
             test_loader = test_set.loader(per_rank, shuffle=False)
     elif batches is None and not args.synthetic:
         train_loader, test_loader, sampler = cifar_loaders(per_rank, rank, world)
-    history = {"losses": [], "epoch_loss": [], "epoch_seconds": []}
+    history = {"losses": [], "epoch_loss": [], "epoch_seconds": [], "train_metrics": [], "metrics_seconds": []}
+    device_metrics = bool(getattr(args, "device_metrics", False)) and not args.no_step_metrics and rank == 0
+    epoch_metrics = None            # --device-metrics: rank 0's shard, as the lists below are; sized at the first epoch, reset per epoch
     n_steps = 0
     model.train()
     for epoch in range(args.epochs):
@@ -318,6 +322,12 @@ def main(args, batches=None, init_state=None):
                 sampler.set_epoch(epoch)            # a different shuffle per epoch, the same on every rank
             loader, n_batches = train_loader, len(train_loader)
         step_losses, ys, preds, probs = [], [], [], []
+        if device_metrics:
+            if epoch_metrics is None:
+                from kanvit.metrics import EpochMetrics
+                rows = sum(int(b[1].shape[0]) for b in batches) if batches is not None else n_batches * per_rank
+                epoch_metrics = history["epoch_metrics"] = EpochMetrics(args.out_d, max(rows, 1), device)
+            epoch_metrics.reset()
         t_epoch = time.perf_counter()
         for x, y in loader:
             x, y = x.to(device, non_blocking=True), y.to(device, non_blocking=True)
@@ -330,7 +340,9 @@ def main(args, batches=None, init_state=None):
                 model.update_grid(x)            # before the step, on the step's own batch; Adam's moments stay as they are
             loss, y_hat = step(x, y)
             step_losses.append(loss.clone() if args.graph else loss)
-            if not args.no_step_metrics:
+            if device_metrics:
+                epoch_metrics.update(y_hat, y)      # eagerly after the step, also under --graph (y_hat is then the graph's output buffer)
+            elif not args.no_step_metrics:
                 ys.append(y)
                 preds.append(y_hat.argmax(dim=1))
                 probs.append(torch.softmax(y_hat.float(), dim=1))
@@ -345,9 +357,15 @@ def main(args, batches=None, init_state=None):
         history["epoch_loss"].append(train_loss)
         if rank == 0:
             logging.info(f"Epoch {epoch + 1}/{args.epochs}\n  Train Loss: {train_loss:.4f}")
-            if ys:
-                acc, bal, f1, auc = calculate_metrics(torch.cat(ys).cpu().numpy(), torch.cat(preds).cpu().numpy(),
-                                                      torch.cat(probs).cpu().numpy(), num_classes=args.out_d)
+            if ys or (device_metrics and epoch_metrics.n):
+                t_metrics = time.perf_counter()             # host clock around work that ends with the four numbers on the host
+                if device_metrics:
+                    acc, bal, f1, auc = epoch_metrics.compute()
+                else:
+                    acc, bal, f1, auc = calculate_metrics(torch.cat(ys).cpu().numpy(), torch.cat(preds).cpu().numpy(),
+                                                          torch.cat(probs).cpu().numpy(), num_classes=args.out_d)
+                history["train_metrics"].append((acc, bal, f1, auc))
+                history["metrics_seconds"].append(time.perf_counter() - t_metrics)
                 logging.info(f"  Train Accuracy: {acc:.4f}\n  Train Balanced Accuracy: {bal:.4f}\n"
                              f"  Train F1 Score: {f1:.4f}\n  Train ROC AUC: {auc:.4f}")
                 if epoch == args.epochs - 1:
@@ -358,15 +376,26 @@ def main(args, batches=None, init_state=None):
         model.eval()
         with torch.no_grad():
             tl, ys, preds, probs = [], [], [], []
+            test_metrics = None
+            if bool(getattr(args, "device_metrics", False)):
+                from kanvit.metrics import EpochMetrics
+                test_metrics = EpochMetrics(args.out_d, max(len(test_loader) * per_rank, 1), device)
             for x, y in test_loader:
                 x, y = x.to(device), y.to(device)
                 with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
                     y_hat = model(x)
                 tl.append(criterion(y_hat.float(), y))
-                ys.append(y), preds.append(y_hat.argmax(dim=1)), probs.append(torch.softmax(y_hat.float(), dim=1))
+                if test_metrics is not None:
+                    test_metrics.update(y_hat, y)
+                else:
+                    ys.append(y), preds.append(y_hat.argmax(dim=1)), probs.append(torch.softmax(y_hat.float(), dim=1))
             test_loss = float(torch.stack(tl).sum() / len(test_loader))
-            acc, bal, f1, auc = calculate_metrics(torch.cat(ys).cpu().numpy(), torch.cat(preds).cpu().numpy(),
-                                                  torch.cat(probs).cpu().numpy(), num_classes=args.out_d)
+            if test_metrics is not None:
+                acc, bal, f1, auc = test_metrics.compute()
+            else:
+                acc, bal, f1, auc = calculate_metrics(torch.cat(ys).cpu().numpy(), torch.cat(preds).cpu().numpy(),
+                                                      torch.cat(probs).cpu().numpy(), num_classes=args.out_d)
+            history["test_metrics"] = (acc, bal, f1, auc)
             logging.info(f"Test Results:\n  Test Loss: {test_loss:.4f}\n  Test Accuracy: {acc:.4f}")
             save_metrics(metrics_file, args.epochs, "Test", test_loss, acc, bal, f1, auc, flag=1)
     if args.dp:
@@ -400,6 +429,10 @@ def parse(argv=None):
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--dp', action='store_true', help='data parallel: one process per GPU (launch with torch.distributed.run)')
     p.add_argument('--no-step-metrics', action='store_true', help='skip per-step metric accumulation')
+    p.add_argument('--device-metrics', action='store_true',
+                   help='count the epoch metrics on the GPU (kanvit/metrics.py: confusion matrix and exact ROC-AUC pair counts; only '
+                        'C*C + 2*C integers go to the host) instead of scikit-learn on host copies; the pair counts cost N^2 compares '
+                        'per epoch, so this is for CIFAR-sized epochs; --no-step-metrics still switches the train metrics off')
     p.add_argument('--amp', choices=['off', 'bf16'], default='off',
                    help='bf16: autocast for the stock dense ops and the kanvit kernels on the bf16 matrix cores (fp32 I/O and '
                         'accumulation); off (default): the reference\'s fp32 arithmetic')
