@@ -515,6 +515,39 @@ int kanvit_augment_u8(const uint8_t* images, const int64_t* labels, const int64_
                       int32_t* params_out, int64_t N, int64_t B, int H, int W, int C, int pad_y, int pad_x, int flip, uint64_t seed,
                       uint64_t epoch, void* stream);
 
+/* ---- Mixup / CutMix on the same pass (kanvit/data.py: mix_table; csrc/augment.hip) ---------------------------------------
+ * kanvit_augment_u8 with a second source.  Three tables indexed by the DATASET index s (not by the position in the batch):
+ * partner [N] int64 (the sample mixed into s, or -1), weight [N] fp32 (the weight w of s's own label; 1 where partner is -1) and box
+ * [N][4] int32 = (y0, y1, x0, x1), half open, in OUTPUT coordinates.  With s = idx[b], j = partner[s],
+ *   a(b,c,y,x) = kanvit_augment_u8's value for s,   p(b,c,y,x) = kanvit_augment_u8's value for j -- with j's OWN (dy, dx, flip),
+ *   out = a                                           j outside [0, N)  (-1: not mixed; anything else is never dereferenced)
+ *   out = (y0 <= y < y1 && x0 <= x < x1) ? p : a      y0 < y1 and x0 < x1  (CutMix: look-ups only, bit-exact)
+ *   out = fadd(fmul(w, a), fmul(1 - w, p))            otherwise  (Mixup: three fp32 roundings to nearest, 1 - w one more; never an
+ *                                                     fma, so the same four operations on the host give the same bits)
+ *   y_out[b] = labels[s],  y2_out[b] = labels[j] (labels[s] where not mixed),  w_out[b] = weight[s]   (each may be NULL).
+ * A sample's pixels depend on (seed, epoch, s) and its table row only.  Stores, the staged table, the launch (one, no atomics, no
+ * workspace, capturable) and the checks are kanvit_augment_u8's; the three tables are required; B = 0 launches nothing.  The
+ * CALLER checks partner against [-1, N) when it uploads the table.  Additive: the ABI version stays 7. */
+int kanvit_mix_u8(const uint8_t* images, const int64_t* labels, const int64_t* idx, const float* lut, const int64_t* partner,
+                  const float* weight, const int32_t* box, float* out, int64_t* y_out, int64_t* y2_out, float* w_out, int64_t N, int64_t B,
+                  int H, int W, int C, int pad_y, int pad_x, int flip, uint64_t seed, uint64_t epoch, void* stream);
+
+/* ---- soft-target cross-entropy, loss and gradient in one pass (ops.soft_cross_entropy; csrc/augment.hip) -----------------
+ * The training loss for Mixup / CutMix pairs and label smoothing.  logits [B][C] fp32, unit column stride, row stride ld >= C;
+ * y1 [B] int64; y2 [B] int64 and w [B] fp32 together or both NULL (NULL: w = 1); eps in [0, 1).
+ *   t_c    = (1 - eps) (w [c == y1] + (1 - w) [c == y2]) + eps / C
+ *   loss_b = lse(z_b) - sum_c t_c z_bc,  computed as log(sum_c exp(z_c - m)) + sum_c t_c (m - z_c) with m = max_c z_c
+ *   dz_bc  = (softmax(z_b)_c - t_c) / B,      loss = (1/B) sum_b loss_b
+ * loss_rows [B], dlogits [B][C] contiguous, loss [1], all fp32.  One wave per row, fixed lane assignment and shuffle tree: a row's
+ * loss_rows entry does not depend on B or on its position, and its gradient only through the factor 1/B (rounded once on the
+ * host, one multiply per element).  The mean is an ordered sum in a second, one-work-group launch: no floating-point atomics, the
+ * same bits on every run.  A row whose y1 or y2 is outside [0, C) gets loss 0 and a zero gradient row and is never used as an index;
+ * the divisor stays B.  No host synchronisation; capturable.  KANVIT_EINVAL (named in kanvit_last_error, before any launch) for
+ * C < 2, B < 1, ld < C, eps outside [0, 1), a null logits / y1 / output pointer, exactly one of y2 and w, a misaligned pointer.
+ * Additive: the ABI version stays 7. */
+int kanvit_soft_ce(const float* logits, int64_t ld, const int64_t* y1, const int64_t* y2, const float* w, int64_t B, int C, float eps,
+                   float* loss_rows, float* dlogits, float* loss, void* stream);
+
 /* ---- epoch metrics on the device (kanvit/metrics.py; csrc/augment.hip) ---------------------------------------------------
  * The reference appends labels, argmax and softmax of every step to host lists and runs scikit-learn on them per epoch
  * (train.py:42-44, utils.py:13-47).  Accuracy, balanced accuracy and weighted F1 are functions of the C x C confusion matrix; the

@@ -14,8 +14,9 @@
 // W/VEC * C lanes of one image row read one contiguous W*C-byte stretch of the NHWC source between them, and every lane stores
 // VEC * 4 bytes (16 in the vector form) of a contiguous output row.
 //
-// The training loop's other off-model kernels live here too: the epoch metrics (softmax / argmax / confusion update per step, and
-// the pair counts of the one-vs-rest ROC-AUC per epoch), further down.
+// The training loop's other off-model kernels live here too: the Mixup / CutMix form of the same pass (mix_u8_kernel), the fused
+// soft-target cross-entropy (loss and gradient in one walk over a logits row) and the epoch metrics (softmax / argmax / confusion
+// update per step, and the pair counts of the one-vs-rest ROC-AUC per epoch), further down.
 #include "../../include/kanvit.h"
 #include "kanvit_common.h"
 
@@ -89,6 +90,193 @@ __global__ __launch_bounds__(256) void augment_u8_kernel(const AugArgs a) {
             o[0] = v[0];
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Mixup / CutMix on the same pass (kanvit/data.py: mix_table).  The epoch's table names, per DATASET index s, a partner j (or -1), the
+// weight w of s's own label and a box in output coordinates.  a = augment_u8's value for s, p = augment_u8's value for j with j's
+// OWN crop and flip (the hash of (seed, epoch, j)), so both operands -- and with them the output -- are functions of (seed, epoch, s)
+// and the table row alone, never of the batch:
+//     out = a                                         j < 0
+//     out = inside the box ? p : a                    box non-empty  (CutMix: look-ups only)
+//     out = fadd(fmul(w, a), fmul(1 - w, p))          otherwise      (Mixup: three roundings, never contracted into an fma, so a
+//                                                                     float32 restatement on the host gives the same bits)
+// Same work item as augment_u8_kernel (VEC consecutive x of one (b, y, c) row), up to twice its reads for the same stores.
+struct MixArgs {
+    AugArgs g;
+    const long long* partner;
+    const float* weight;
+    const int* box;
+    long long* y2_out;
+    float* w_out;
+};
+
+// aug_params / aug_fetch restate augment_u8_kernel's gather for one sample, so that the mix kernel can take it twice.  augment_u8_kernel
+// keeps its own body: routed through them it compiles to 5 % more instructions, and it is the kernel every --data-npz step runs.
+struct AugParams {
+    int dy, dx, fl;
+};
+
+__device__ __forceinline__ AugParams aug_params(const AugArgs& a, long long s) {
+    const unsigned long long h = aug_mix(a.seed_epoch + (unsigned long long)s);
+    AugParams p;
+    p.dy = (int)((unsigned)(h & 0xFFFFFu) % (unsigned)(2 * a.pad_y + 1));
+    p.dx = (int)((unsigned)((h >> 20) & 0xFFFFFu) % (unsigned)(2 * a.pad_x + 1));
+    p.fl = a.flip ? (int)((h >> 40) & 1u) : 0;
+    return p;
+}
+
+// augment_u8's values of sample s (valid: s in [0, N)) at row y, channel c, columns x0 .. x0 + VEC - 1
+template <int VEC>
+__device__ __forceinline__ void aug_fetch(const AugArgs& a, const float* l, long long s, bool valid, int y, int c, int x0, float* v) {
+    const AugParams q = aug_params(a, s);
+    const int sy = y + q.dy - a.pad_y;
+    const bool row_ok = valid && sy >= 0 && sy < a.H;
+    const unsigned char* src = a.images + (((valid ? s : 0) * a.H + (row_ok ? sy : 0)) * a.W) * a.C + c;       // not read when !row_ok
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        const int sx = x0 + e + q.dx - a.pad_x;
+        const bool ok = row_ok && sx >= 0 && sx < a.W;
+        const int fx = q.fl ? a.W - 1 - sx : sx;
+        v[e] = l[ok ? (int)src[(long long)fx * a.C] : 0];
+    }
+}
+
+__device__ __forceinline__ float mix_blend(float w, float w1, float a, float p) {
+#pragma clang fp contract(off)
+    const float wa = __fmul_rn(w, a);
+    const float wp = __fmul_rn(w1, p);
+    return __fadd_rn(wa, wp);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void mix_u8_kernel(const MixArgs m) {
+    __shared__ float lut[4 * 256];
+    const AugArgs& a = m.g;
+    for (int i = threadIdx.x; i < a.C * 256; i += 256) lut[i] = a.lut[i];
+    __syncthreads();
+    const int WV = a.W / VEC, H = a.H, W = a.W, C = a.C;
+    const long long total = a.B * H * C * WV;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+        const long long row = t / WV;                    // (b, y, c)
+        const int x0 = (int)(t - row * WV) * VEC;
+        const long long by = row / C;
+        const int c = (int)(row - by * C);
+        const long long b = by / H;
+        const int y = (int)(by - b * H);
+        const long long s = a.idx[b];
+        const bool sample_ok = s >= 0 && s < a.N;        // as augment_u8: the caller validates idx and the table
+        const long long j = sample_ok ? m.partner[s] : -1;
+        const bool mixed = j >= 0 && j < a.N;            // a partner outside the dataset is never dereferenced: the row stays unmixed
+        const float w = sample_ok ? m.weight[s] : 1.f;
+        if (c == 0 && y == 0 && x0 == 0) {
+            const long long lab = (sample_ok && a.labels) ? a.labels[s] : -1;
+            if (a.y_out) a.y_out[b] = lab;
+            if (m.y2_out) m.y2_out[b] = (mixed && a.labels) ? a.labels[j] : lab;
+            if (m.w_out) m.w_out[b] = w;
+        }
+        const float* l = lut + c * 256;
+        float v[VEC];
+        aug_fetch<VEC>(a, l, s, sample_ok, y, c, x0, v);
+        if (mixed) {
+            const int* bx = m.box + 4 * s;
+            const int y0 = bx[0], y1 = bx[1], bx0 = bx[2], bx1 = bx[3];
+            const bool cut = y0 < y1 && bx0 < bx1;
+            if (!cut || (y >= y0 && y < y1 && x0 < bx1 && x0 + VEC > bx0)) {     // CutMix rows and columns outside the box keep a
+                float p[VEC];
+                aug_fetch<VEC>(a, l, j, true, y, c, x0, p);
+                const float w1 = 1.f - w;
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) {
+                    if (cut)
+                        v[e] = (x0 + e >= bx0 && x0 + e < bx1) ? p[e] : v[e];
+                    else
+                        v[e] = mix_blend(w, w1, v[e], p[e]);
+                }
+            }
+        }
+        float* o = a.out + ((b * C + c) * H + y) * W + x0;
+        if constexpr (VEC == 4) {
+            *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
+        } else {
+            o[0] = v[0];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Soft-target cross-entropy, forward and gradient in one walk (ops.soft_cross_entropy): the target of row b is
+//     t_c = (1 - eps) (w [c == y1] + (1 - w) [c == y2]) + eps / C        (label smoothing eps; Mixup / CutMix pair (y1, y2, w))
+// and with m = max z, s = sum exp(z - m), p = exp(z - m) / s:
+//     loss_b = log s + sum_c t_c (m - z_c)        (= lse(z) - t.z because sum t = 1; every term is >= 0: nothing cancels)
+//     dz_bc  = (p_c - t_c) * (1 / B)
+// One wave per row with the lane on the class index, as metrics_update_kernel walks it: max, then sum exp and sum (m - z) together,
+// then the gradient.  A row's bits depend on the row alone (fixed lane assignment, fixed xor-shuffle tree); 1 / B is rounded once on
+// the host.  The mean is soft_ce_mean_kernel: one work-group, thread t adds rows t, t + 256, ... in order, then a fixed LDS tree.
+constexpr int SC_ROWS = 4, SC_THREADS = 64 * SC_ROWS;
+
+struct SoftCeArgs {
+    const float* logits;
+    const long long* y1;
+    const long long* y2;
+    const float* w;
+    float* loss_rows;
+    float* dlogits;
+    float* loss;
+    long long ld, B;
+    int C;
+    float eps, inv_B;
+};
+
+__global__ __launch_bounds__(SC_THREADS) void soft_ce_kernel(const SoftCeArgs a) {
+    const int lane = threadIdx.x & 63, C = a.C;
+    const long long row = (long long)blockIdx.x * SC_ROWS + (threadIdx.x >> 6);
+    if (row >= a.B) return;                              // a whole wave at once; the kernel has no barrier
+    const float* z = a.logits + row * a.ld;
+    float* dz = a.dlogits + row * C;
+    const long long l1 = a.y1[row], l2 = a.y2 ? a.y2[row] : l1;
+    const float w = a.w ? a.w[row] : 1.f;
+    if (l1 < 0 || l1 >= C || l2 < 0 || l2 >= C) {        // a label outside [0, C) is never an index: the row counts 0, its gradient is 0
+        for (int c = lane; c < C; c += 64) dz[c] = 0.f;
+        if (lane == 0) a.loss_rows[row] = 0.f;
+        return;
+    }
+    float m = -INFINITY;
+    for (int c = lane; c < C; c += 64) m = fmaxf(m, z[c]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    float s = 0.f, d = 0.f;
+    for (int c = lane; c < C; c += 64) {
+        const float zc = z[c];
+        s += expf(zc - m);
+        d += m - zc;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o);
+        d += __shfl_xor(d, o);
+    }
+    const float keep = 1.f - a.eps, u = a.eps / (float)C;
+    const float t1 = keep * w, t2 = keep * (1.f - w);
+    if (lane == 0) a.loss_rows[row] = logf(s) + (t1 * (m - z[l1]) + t2 * (m - z[l2])) + u * d;
+    const float inv_s = 1.f / s;
+    for (int c = lane; c < C; c += 64) {
+        const float t = u + (c == l1 ? t1 : 0.f) + (c == l2 ? t2 : 0.f);
+        dz[c] = (expf(z[c] - m) * inv_s - t) * a.inv_B;
+    }
+}
+
+__global__ __launch_bounds__(256) void soft_ce_mean_kernel(const SoftCeArgs a) {
+    __shared__ float part[256];
+    float s = 0.f;
+    for (long long r = threadIdx.x; r < a.B; r += 256) s += a.loss_rows[r];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.loss[0] = part[0] / (float)a.B;
 }
 
 int aug_check_shape(const char* who, int64_t N, int H, int W, int C, int pad_y, int pad_x) {
@@ -393,6 +581,76 @@ int kanvit_augment_u8(const uint8_t* images, const int64_t* labels, const int64_
     else
         hipLaunchKernelGGL(augment_u8_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     KV_LAUNCH_CHECK("augment_u8_kernel");
+    return 0;
+}
+
+int kanvit_mix_u8(const uint8_t* images, const int64_t* labels, const int64_t* idx, const float* lut, const int64_t* partner,
+                  const float* weight, const int32_t* box, float* out, int64_t* y_out, int64_t* y2_out, float* w_out, int64_t N, int64_t B,
+                  int H, int W, int C, int pad_y, int pad_x, int flip, uint64_t seed, uint64_t epoch, void* stream) {
+    if (int rc = aug_check_shape("kanvit_mix_u8", N, H, W, C, pad_y, pad_x)) return rc;
+    if (B < 0) return kv_fail(KANVIT_EINVAL, "kanvit_mix_u8: B=%lld is negative", (long long)B);
+    if (flip != 0 && flip != 1) return kv_fail(KANVIT_EINVAL, "kanvit_mix_u8: flip=%d is 0 (never) or 1 (with probability 1/2)", flip);
+    if (B == 0) return 0;
+    if (!images || !idx || !lut || !out) return kv_fail(KANVIT_EINVAL, "kanvit_mix_u8: null images/idx/lut/out");
+    if (!partner || !weight || !box) return kv_fail(KANVIT_EINVAL, "kanvit_mix_u8: null partner/weight/box (the three tables come together)");
+    if ((y_out || y2_out) && !labels) return kv_fail(KANVIT_EINVAL, "kanvit_mix_u8: y_out / y2_out without labels");
+    if ((uintptr_t)out & 3 || (uintptr_t)lut & 3 || (uintptr_t)idx & 7 || (uintptr_t)labels & 7 || (uintptr_t)y_out & 7 || (uintptr_t)y2_out & 7 ||
+        (uintptr_t)partner & 7 || (uintptr_t)weight & 3 || (uintptr_t)box & 3 || (uintptr_t)w_out & 3)
+        return kv_fail(KANVIT_EINVAL, "kanvit_mix_u8: a pointer is not aligned to its element size");
+    MixArgs m;
+    AugArgs& a = m.g;
+    a.images = images;
+    a.labels = (const long long*)labels;
+    a.idx = (const long long*)idx;
+    a.lut = lut;
+    a.out = out;
+    a.y_out = (long long*)y_out;
+    a.params_out = nullptr;
+    a.N = N, a.B = B, a.H = H, a.W = W, a.C = C, a.pad_y = pad_y, a.pad_x = pad_x, a.flip = flip;
+    a.seed_epoch = aug_mix(aug_mix(seed) + epoch);
+    m.partner = (const long long*)partner;
+    m.weight = weight;
+    m.box = box;
+    m.y2_out = (long long*)y2_out;
+    m.w_out = w_out;
+    const bool vec = (W % 4 == 0) && ((uintptr_t)out & 15) == 0;        // as kanvit_augment_u8 decides it
+    const long long total = (long long)B * H * C * (vec ? W / 4 : W);
+    long long blocks = (total + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (vec)
+        hipLaunchKernelGGL(mix_u8_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m);
+    else
+        hipLaunchKernelGGL(mix_u8_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m);
+    KV_LAUNCH_CHECK("mix_u8_kernel");
+    return 0;
+}
+
+int kanvit_soft_ce(const float* logits, int64_t ld, const int64_t* y1, const int64_t* y2, const float* w, int64_t B, int C, float eps,
+                   float* loss_rows, float* dlogits, float* loss, void* stream) {
+    if (C < 2) return kv_fail(KANVIT_EINVAL, "kanvit_soft_ce: C=%d: at least two classes", C);
+    if (B < 1) return kv_fail(KANVIT_EINVAL, "kanvit_soft_ce: B=%lld: at least one row", (long long)B);
+    if (ld < C) return kv_fail(KANVIT_EINVAL, "kanvit_soft_ce: row stride ld=%lld is below C=%d", (long long)ld, C);
+    if (!(eps >= 0.f && eps < 1.f)) return kv_fail(KANVIT_EINVAL, "kanvit_soft_ce: eps=%g must be in [0, 1)", (double)eps);
+    if (!logits || !y1 || !loss_rows || !dlogits || !loss) return kv_fail(KANVIT_EINVAL, "kanvit_soft_ce: null logits/y1/loss_rows/dlogits/loss");
+    if ((y2 == nullptr) != (w == nullptr))
+        return kv_fail(KANVIT_EINVAL, "kanvit_soft_ce: %s without %s (y2 and w come together)", y2 ? "y2" : "w", y2 ? "w" : "y2");
+    if ((B + SC_ROWS - 1) / SC_ROWS > 0x7fffffffll) return kv_fail(KANVIT_EINVAL, "kanvit_soft_ce: B=%lld: too many rows for one launch", (long long)B);
+    if ((uintptr_t)logits & 3 || (uintptr_t)y1 & 7 || (uintptr_t)y2 & 7 || (uintptr_t)w & 3 || (uintptr_t)loss_rows & 3 || (uintptr_t)dlogits & 3 ||
+        (uintptr_t)loss & 3)
+        return kv_fail(KANVIT_EINVAL, "kanvit_soft_ce: a pointer is not aligned to its element size");
+    SoftCeArgs a;
+    a.logits = logits;
+    a.y1 = (const long long*)y1;
+    a.y2 = (const long long*)y2;
+    a.w = w;
+    a.loss_rows = loss_rows;
+    a.dlogits = dlogits;
+    a.loss = loss;
+    a.ld = ld, a.B = B, a.C = C, a.eps = eps, a.inv_B = 1.f / (float)B;
+    hipLaunchKernelGGL(soft_ce_kernel, dim3((unsigned)((B + SC_ROWS - 1) / SC_ROWS)), dim3(SC_THREADS), 0, (hipStream_t)stream, a);
+    KV_LAUNCH_CHECK("soft_ce_kernel");
+    hipLaunchKernelGGL(soft_ce_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    KV_LAUNCH_CHECK("soft_ce_mean_kernel");
     return 0;
 }
 

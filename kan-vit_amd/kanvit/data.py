@@ -10,11 +10,17 @@ The crop offsets and the flip of a sample are a pure function of (seed, epoch, s
 order is a permutation drawn from a CPU generator seeded by (seed, epoch): a run is reproducible across batch sizes and
 data-parallel layouts, and needs no RNG state on the device.
 
+Mixup and CutMix ride on the same pass: mix_table draws one table per epoch from (seed, epoch), indexed by dataset index, and
+batches(mix=...) hands it to ops.mix_u8, which blends or pastes the partner under the partner's own crop and flip -- a sample's pixels
+and soft targets stay a function of (seed, epoch, sample index).
+
 The file format is an .npz: x_train uint8 [N, H, W, C] (or [N, H, W] for one channel), y_train of any integer type, optionally
 x_test / y_test, optionally mean / std ([C], on the 0-1 scale; computed from x_train when absent).  tools/cifar_to_npz.py writes
 one from an unpacked CIFAR python-pickle directory.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -63,6 +69,59 @@ def epoch_indices(n: int, epoch: int, seed: int, rank: int = 0, world: int = 1, 
     if total > n:
         perm = perm.repeat(-(-total // n))[:total]
     return perm[rank::world].contiguous().to(device)
+
+
+class MixTable(NamedTuple):
+    """One epoch's Mixup / CutMix decisions, CPU tensors indexed by the DATASET index: partner int64 [n] (-1: not mixed), weight
+    float32 [n] (of the sample's own label; 1 where not mixed), box int32 [n, 4] = (y0, y1, x0, x1), half open, output coordinates
+    (empty -- all zero -- for Mixup and unmixed rows)."""
+    partner: torch.Tensor
+    weight: torch.Tensor
+    box: torch.Tensor
+
+
+_MIX_TABLE_KEY = 0x6D69785F7461626C     # "mix_tabl": keeps the table's generator apart from the permutation's
+
+
+def mix_table(n: int, epoch: int, seed: int, hw, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, prob: float = 1.0,
+              switch_prob: float = 0.5) -> MixTable:
+    """The Mixup / CutMix table of `epoch` for a dataset of n images of size hw = (H, W) (the recipe of DeiT / timm's Mixup, per
+    sample).  Every draw comes from ONE CPU generator (NumPy's PCG64) seeded by (seed, epoch), and all n rows are drawn, in index
+    order: the table depends on nothing else -- not on the batch size, the rank or the world size -- so what ops.mix_u8 makes of
+    sample i is a function of (seed, epoch, i) like the crop and the flip.
+
+    With probability `prob` a sample is mixed, with a partner uniform over [0, n) (it may draw itself).  CutMix is chosen with
+    probability `switch_prob` when both alphas are positive, otherwise the mode whose alpha is positive; lam ~ Beta(alpha, alpha).
+    Mixup: weight = float32(lam), empty box.  CutMix is timm's rand_bbox: r = sqrt(1 - lam), a box of int(H r) x int(W r) around a
+    centre uniform in [0, H) x [0, W), clipped to the image; weight = 1 - area / (H W), in float64, rounded to float32; a box clipped
+    to nothing leaves the row unmixed.  Both alphas 0 is a ValueError (not a table of -1)."""
+    H, W = int(hw[0]), int(hw[1])
+    ma, ca = float(mixup_alpha), float(cutmix_alpha)
+    if n < 1 or H < 1 or W < 1:
+        raise ValueError(f"mix_table: n={n}, hw={tuple(hw)}")
+    if ma < 0 or ca < 0 or not 0.0 <= prob <= 1.0 or not 0.0 <= switch_prob <= 1.0:
+        raise ValueError(f"mix_table: mixup_alpha={ma}, cutmix_alpha={ca}, prob={prob}, switch_prob={switch_prob}: alphas are not "
+                         "negative and probabilities lie in [0, 1]")
+    if ma == 0 and ca == 0:
+        raise ValueError("mix_table: mixup_alpha and cutmix_alpha are both 0: nothing to mix (leave `mix` out instead)")
+    g = np.random.Generator(np.random.PCG64(_mix(_mix((_mix(int(seed) & _M64) + int(epoch)) & _M64) ^ _MIX_TABLE_KEY)))
+    mixed = g.random(n) < prob                       # each column is drawn for all n rows, in index order, whatever the flags
+    switch = g.random(n) < switch_prob
+    partner = g.integers(0, n, n)
+    lam_mix = g.beta(ma, ma, n) if ma > 0 else np.zeros(n)
+    lam_cut = g.beta(ca, ca, n) if ca > 0 else np.zeros(n)
+    cy, cx = g.integers(0, H, n), g.integers(0, W, n)
+    cut = switch if (ma > 0 and ca > 0) else np.full(n, ca > 0)
+    r = np.sqrt(1.0 - lam_cut)
+    ch, cw = (H * r).astype(np.int64), (W * r).astype(np.int64)
+    y0, y1 = np.clip(cy - ch // 2, 0, H), np.clip(cy + ch // 2, 0, H)
+    x0, x1 = np.clip(cx - cw // 2, 0, W), np.clip(cx + cw // 2, 0, W)
+    area = (y1 - y0) * (x1 - x0)
+    mixed &= ~cut | (area > 0)
+    cut &= mixed
+    weight = np.where(cut, 1.0 - area / float(H * W), np.where(mixed, lam_mix, 1.0)).astype(np.float32)
+    box = np.where(cut[:, None], np.stack([y0, y1, x0, x1], 1), 0).astype(np.int32)
+    return MixTable(torch.from_numpy(np.where(mixed, partner, -1).astype(np.int64)), torch.from_numpy(weight), torch.from_numpy(box))
 
 
 def _fail(path, key, what):
@@ -173,14 +232,27 @@ class GpuDataset:
     def loader(self, batch_size, epoch=0, seed=0, rank=0, world=1, shuffle=True):
         return Batches(self, batch_size, epoch, seed, rank, world, shuffle)
 
-    def batches(self, batch_size, epoch, seed, rank=0, world=1, shuffle=True):
+    def batches(self, batch_size, epoch, seed, rank=0, world=1, shuffle=True, mix=None):
         """Generator of (x, y) device tensors for one epoch: x float32 [b, C, H, W], y int64 [b]; the last batch is short (a DataLoader
-        with drop_last=False).  The index list is checked against [0, N) on the CPU and goes to the device once per epoch."""
+        with drop_last=False).  The index list is checked against [0, N) on the CPU and goes to the device once per epoch.
+
+        mix: the keyword arguments of mix_table after hw (mixup_alpha, cutmix_alpha, prob, switch_prob) as a dict -- Mixup / CutMix.
+        The epoch's table is drawn and checked on the CPU and uploaded once, next to the index list, and every batch is one
+        ops.mix_u8 launch yielding (x, y, y2, w): y2 int64 [b] the partner's label (y where the sample is not mixed), w float32 [b]
+        the weight of y.  Without `mix` nothing changes: (x, y) through ops.augment_u8."""
         if batch_size < 1:
             raise ValueError(f"GpuDataset.batches: batch_size={batch_size}")
         idx = epoch_indices(len(self), epoch, seed, rank, world, shuffle)
         if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= len(self)):
             raise IndexError(f"GpuDataset.batches: an index outside [0, {len(self)})")
         idx = idx.to(self.device)
+        if mix is None:
+            for i in range(0, idx.numel(), batch_size):
+                yield ops.augment_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, self.pad, self.flip, seed, epoch)
+            return
+        table = mix_table(len(self), epoch, seed, self.chw[1:], **mix)
+        if tuple(table.partner.shape) != (len(self),) or int(table.partner.min()) < -1 or int(table.partner.max()) >= len(self):
+            raise IndexError(f"GpuDataset.batches: the mix table names a partner outside [-1, {len(self)}) or is not of length {len(self)}")
+        partner, weight, box = (t.contiguous().to(self.device) for t in table)
         for i in range(0, idx.numel(), batch_size):
-            yield ops.augment_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, self.pad, self.flip, seed, epoch)
+            yield ops.mix_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, partner, weight, box, self.pad, self.flip, seed, epoch)

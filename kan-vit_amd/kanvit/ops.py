@@ -1101,6 +1101,113 @@ def augment_u8(images: torch.Tensor, labels: Optional[torch.Tensor], idx: torch.
     return res[0] if len(res) == 1 else res
 
 
+def mix_u8(images: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor, lut: torch.Tensor, partner: torch.Tensor, weight: torch.Tensor,
+           box: torch.Tensor, pad=0, flip: bool = False, seed: int = 0, epoch: int = 0, out: Optional[torch.Tensor] = None):
+    """augment_u8 with Mixup / CutMix in the same launch (semantics: include/kanvit.h).  partner int64 [N], weight float32 [N] and box
+    int32 [N, 4] = (y0, y1, x0, x1) are the epoch's table (data.mix_table) on the device, indexed by the DATASET index: sample s =
+    idx[b] is blended with (Mixup, empty box) or gets the box of (CutMix) sample partner[s] under that sample's own crop and flip;
+    partner -1 leaves it as augment_u8 gives it.  Every partner lies in [-1, N): the CALLER checks that before the upload, as for idx.
+    Returns (x float32 [B, C, H, W], y int64 [B] = labels[s], y2 int64 [B] = the partner's label (y where not mixed), w float32 [B] =
+    weight[s])."""
+    N = int(images.shape[0]) if images.dim() in (3, 4) else -1
+    for name, t, dt in (("images", images, torch.uint8), ("labels", labels, torch.int64), ("idx", idx, torch.int64), ("lut", lut, torch.float32),
+                        ("partner", partner, torch.int64), ("weight", weight, torch.float32), ("box", box, torch.int32), ("out", out, torch.float32)):
+        if t is None:
+            if name == "out":
+                continue
+            raise KanvitError(f"mix_u8: {name} is None")
+        if not t.is_cuda:
+            raise KanvitError(f"mix_u8: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+        if t.device != images.device:
+            raise KanvitError(f"mix_u8: {name} is on {t.device}, images on {images.device}")
+        if t.dtype != dt:
+            raise KanvitError(f"mix_u8: {name} has dtype {t.dtype}, expected {dt}")
+        if not t.is_contiguous():
+            raise KanvitError(f"mix_u8: {name} is not contiguous")
+    if N < 0:
+        raise KanvitError(f"mix_u8: images has shape {tuple(images.shape)}, expected [N, H, W, C] or [N, H, W]")
+    H, W = int(images.shape[1]), int(images.shape[2])
+    Cn = int(images.shape[3]) if images.dim() == 4 else 1
+    pad_y, pad_x = (int(pad), int(pad)) if isinstance(pad, int) else (int(pad[0]), int(pad[1]))
+    if idx.dim() != 1:
+        raise KanvitError(f"mix_u8: idx has shape {tuple(idx.shape)}, expected [B]")
+    for name, t, shape in (("labels", labels, (N,)), ("lut", lut, (Cn, 256)), ("partner", partner, (N,)), ("weight", weight, (N,)),
+                           ("box", box, (N, 4))):
+        if tuple(t.shape) != shape:
+            raise KanvitError(f"mix_u8: {name} has shape {tuple(t.shape)}, expected {list(shape)}")
+    B = int(idx.shape[0])
+    if out is None:
+        out = torch.empty((B, Cn, H, W), device=images.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, Cn, H, W):
+        raise KanvitError(f"mix_u8: out has shape {tuple(out.shape)}, expected {(B, Cn, H, W)}")
+    y = torch.empty((B,), device=images.device, dtype=torch.int64)
+    y2 = torch.empty((B,), device=images.device, dtype=torch.int64)
+    w = torch.empty((B,), device=images.device, dtype=torch.float32)
+    _launch(_lib.lib().kanvit_mix_u8, "kanvit_mix_u8", images.device, _ptr(images), _ptr(labels), _ptr(idx), _ptr(lut), _ptr(partner),
+            _ptr(weight), _ptr(box), _ptr(out), _ptr(y), _ptr(y2), _ptr(w), N, B, H, W, Cn, pad_y, pad_x, int(bool(flip)),
+            int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1), tag="mix_u8", cost=(0, B * Cn * H * W * 6))
+    return out, y, y2, w
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# soft-target cross-entropy: loss and gradient in one pass over the logits (csrc/augment.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+def soft_ce(logits: torch.Tensor, y: torch.Tensor, y2: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None,
+            label_smoothing: float = 0.0):
+    """The kernel call behind soft_cross_entropy, without autograd: (loss float32 [], loss_rows float32 [B], dlogits float32 [B, C]) for
+    logits float32 [B, C] (unit column stride; a padded row stride is taken as it is), y int64 [B], and y2 int64 [B] with w float32 [B]
+    or neither (semantics: include/kanvit.h).  One launch plus the one-work-group mean; no host synchronisation."""
+    who = "soft_cross_entropy"
+    if not logits.is_cuda:
+        raise KanvitError(f"{who}: logits is on {logits.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+    if logits.dtype != torch.float32:
+        raise KanvitError(f"{who}: logits has dtype {logits.dtype}, expected torch.float32 (train.py hands the loss y_hat.float())")
+    if logits.dim() != 2:
+        raise KanvitError(f"{who}: logits has shape {tuple(logits.shape)}, expected [B, C]")
+    B, Cn = (int(v) for v in logits.shape)
+    if B < 1 or Cn < 2:
+        raise KanvitError(f"{who}: logits has shape {tuple(logits.shape)}: at least one row and two classes")
+    if logits.stride(1) != 1 or logits.stride(0) < Cn:
+        raise KanvitError(f"{who}: logits has strides {tuple(logits.stride())}: unit column stride and a row stride of at least C = {Cn}")
+    if (y2 is None) != (w is None):
+        raise KanvitError(f"{who}: y2 and w come together")
+    if not 0.0 <= float(label_smoothing) < 1.0:
+        raise KanvitError(f"{who}: label_smoothing={label_smoothing} must be in [0, 1)")
+    for name, t, dt in (("y", y, torch.int64), ("y2", y2, torch.int64), ("w", w, torch.float32)):
+        if t is not None:
+            _require_metrics_buffer(who, name, t, dt, (B,), logits.device)
+    out = torch.empty((B * Cn + B + 1,), device=logits.device, dtype=torch.float32)
+    dlogits, loss_rows, loss = out[:B * Cn].view(B, Cn), out[B * Cn:B * Cn + B], out[B * Cn + B:].view(())
+    _launch(_lib.lib().kanvit_soft_ce, "kanvit_soft_ce", logits.device, _ptr(logits), int(logits.stride(0)), _ptr(y), _ptr(y2), _ptr(w), B, Cn,
+            C.c_float(float(label_smoothing)), _ptr(loss_rows), _ptr(dlogits), _ptr(loss), tag="soft_ce", cost=(0, B * Cn * 16))
+    return loss, loss_rows, dlogits
+
+
+class _SoftCeFn(torch.autograd.Function):
+    @staticmethod
+    @_fwd_f32
+    def forward(ctx, logits, y, y2, w, label_smoothing):
+        loss, _, dlogits = soft_ce(logits, y, y2, w, label_smoothing)
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad_output):
+        dlogits, = ctx.saved_tensors
+        return dlogits * grad_output, None, None, None, None
+
+
+def soft_cross_entropy(logits: torch.Tensor, y: torch.Tensor, y2: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None,
+                       label_smoothing: float = 0.0) -> torch.Tensor:
+    """Mean cross-entropy of logits [B, C] against the soft targets t = (1 - eps) (w onehot(y) + (1 - w) onehot(y2)) + eps / C (eps =
+    label_smoothing; y2 and w absent: plain or smoothed cross-entropy), as torch's cross_entropy with probability targets gives it.
+    The forward launch computes the gradient (softmax - t) / B as well and keeps it: backward is one element-wise multiply by the
+    upstream gradient, with no second pass over the logits.  A row with a label outside [0, C) contributes 0 to the sum (the divisor
+    stays B) and gets a zero gradient."""
+    return _SoftCeFn.apply(logits, y, y2, w, float(label_smoothing))
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # epoch metrics on the device (kanvit/metrics.py; csrc/augment.hip)
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -19,7 +19,10 @@ normalises it: kanvit/data.py; the reference's transforms, train.py:100-118, wit
 --no-step-metrics (the per-step metrics stay on the device either way: one host sync per epoch instead of the
 reference's three per step, train.py:37,42-44), --device-metrics (the epoch's four metrics from integer tables counted on the GPU,
 kanvit/metrics.py: one kernel per step, one pair-counting pass per epoch, C*C + 2*C integers to the host -- instead of three lists,
-an [N, C] copy and scikit-learn on one CPU thread).
+an [N, C] copy and scikit-learn on one CPU thread), --mixup / --cutmix / --mix-prob / --mix-switch-prob (Mixup and CutMix inside the
+batch kernel, from a per-epoch table that is a function of (seed, epoch) alone: kanvit/data.py mix_table, ops.mix_u8),
+--label-smoothing and --fused-loss (the training loss and its gradient from one fused soft-target cross-entropy launch:
+ops.soft_cross_entropy).
 
 `main(args, batches=None, init_state=None)` also serves the parity tests: `batches` (a list of (x, y) tensors) replaces
 the data stream, `init_state` (a reference-layout state dict) replaces the random initialisation, and the returned dict
@@ -66,6 +69,28 @@ def check_data_args(args):
         raise SystemExit("--synthetic and --data-npz name two data sources; give one")
     if getattr(args, "crop_padding", 4) < 0:
         raise SystemExit(f"--crop-padding {args.crop_padding} is negative")
+    mixup, cutmix = float(getattr(args, "mixup", 0.0)), float(getattr(args, "cutmix", 0.0))
+    if mixup < 0 or cutmix < 0:
+        raise SystemExit(f"--mixup {mixup} / --cutmix {cutmix}: a Beta parameter is not negative")
+    for flag, name in (("--mix-prob", "mix_prob"), ("--mix-switch-prob", "mix_switch_prob")):
+        if not 0.0 <= float(getattr(args, name, 1.0)) <= 1.0:
+            raise SystemExit(f"{flag} {getattr(args, name)} is not a probability")
+    if not 0.0 <= float(getattr(args, "label_smoothing", 0.0)) < 1.0:
+        raise SystemExit(f"--label-smoothing {args.label_smoothing} must be in [0, 1)")
+    if mixup > 0 or cutmix > 0:
+        if not getattr(args, "data_npz", None):
+            raise SystemExit("--mixup / --cutmix mix inside the kernel that reads the GPU-resident dataset; give --data-npz")
+        if getattr(args, "no_augment", False):
+            raise SystemExit("--mixup / --cutmix are augmentations; they are not combined with --no-augment")
+
+
+def mix_config(args):
+    """The `mix` argument of GpuDataset.batches from the flags, or None when neither --mixup nor --cutmix is given."""
+    mixup, cutmix = float(getattr(args, "mixup", 0.0)), float(getattr(args, "cutmix", 0.0))
+    if mixup <= 0 and cutmix <= 0:
+        return None
+    return dict(mixup_alpha=mixup, cutmix_alpha=cutmix, prob=float(getattr(args, "mix_prob", 1.0)),
+                switch_prob=float(getattr(args, "mix_switch_prob", 0.5)))
 
 
 def npz_datasets(args, device, want_test=True):
@@ -103,14 +128,15 @@ class _GraphedStep:
     side stream first; parameters are then restored and the Adam moments / step counters zeroed, which is exactly the state
     of a fresh optimizer -- the replayed trajectory equals the eager one."""
 
-    def __init__(self, eager_step, model, optimizer, x, y):
+    def __init__(self, eager_step, model, optimizer, x, y, y2=None, w=None):
         self.eager = eager_step
         self.sx, self.sy = x.clone(), y.clone()
+        self.pair = () if y2 is None else (y2.clone(), w.clone())      # Mixup / CutMix: static buffers like x and y
         saved = [p.detach().clone() for p in model.parameters()]
         side = torch.cuda.Stream(device=x.device)
         side.wait_stream(torch.cuda.current_stream(x.device))
         with torch.cuda.stream(side):
-            eager_step(self.sx, self.sy)
+            eager_step(self.sx, self.sy, *self.pair)
         torch.cuda.current_stream(x.device).wait_stream(side)
         with torch.no_grad():
             for p, s in zip(model.parameters(), saved):
@@ -123,13 +149,16 @@ class _GraphedStep:
         optimizer.zero_grad(set_to_none=True)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.loss, self.logits = eager_step(self.sx, self.sy)
+            self.loss, self.logits = eager_step(self.sx, self.sy, *self.pair)
 
-    def __call__(self, x, y):
+    def __call__(self, x, y, y2=None, w=None):
         if x.shape != self.sx.shape:
-            return self.eager(x, y)
+            return self.eager(x, y, y2, w)
         self.sx.copy_(x, non_blocking=True)
         self.sy.copy_(y, non_blocking=True)
+        if self.pair:
+            self.pair[0].copy_(y2, non_blocking=True)
+            self.pair[1].copy_(w, non_blocking=True)
         self.graph.replay()
         return self.loss, self.logits
 
@@ -248,6 +277,18 @@ def main(args, batches=None, init_state=None):
     model = model.to(device)
     kdp.broadcast_parameters(model)
     criterion = torch.nn.CrossEntropyLoss()
+    mix = mix_config(args) if train_set is not None else None
+    label_smoothing = float(getattr(args, "label_smoothing", 0.0))
+    soft_loss = mix is not None or label_smoothing > 0 or bool(getattr(args, "fused_loss", False))
+    if soft_loss:
+        from kanvit import ops as kops
+
+    def step_loss(logits, y, y2, w):
+        """The training loss: the reference's criterion, or with any of --mixup / --cutmix / --label-smoothing / --fused-loss the
+        fused soft-target cross-entropy (ops.soft_cross_entropy: loss and gradient in one launch).  The test loop keeps the criterion."""
+        if not soft_loss:
+            return criterion(logits, y)
+        return kops.soft_cross_entropy(logits, y, y2, w, label_smoothing)
     if not args.no_tuned_gemms:
         from kanvit import tuned
         tuned.enable_tuned_gemms()          # recorded kernel selections for the stock FF GEMMs (no run-time tuning)
@@ -262,12 +303,12 @@ def main(args, batches=None, init_state=None):
     if reg_lambda > 0 and not model.layer_types() <= set(VisionTransformer.REGULARIZED_TYPES):
         raise SystemExit(f"--reg-lambda: the edge-activation regulariser covers the model types {', '.join(VisionTransformer.REGULARIZED_TYPES)}")
 
-    def eager_step(x, y):
+    def eager_step(x, y, y2=None, w=None):
         if reg_lambda > 0:
-            return regularized_step(x, y)
+            return regularized_step(x, y, y2, w)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
             y_hat = model(x)
-            loss = criterion(y_hat.float(), y)
+            loss = step_loss(y_hat.float(), y, y2, w)
         if reducer is not None:
             reducer.zero_grad()
             reducer.scale_loss(loss).backward()     # mean over ranks inside the collective (RCCL AVG) or the loss: kanvit/dp.py
@@ -278,13 +319,13 @@ def main(args, batches=None, init_state=None):
         optimizer.step()
         return loss.detach(), y_hat.detach()
 
-    def regularized_step(x, y):
+    def regularized_step(x, y, y2=None, w=None):
         """The step with the KAN paper's sample-based regulariser: loss = CE + lambda * reg, reg from the same forward (exact fp32
         also under --amp bf16).  The returned (logged) loss stays the CE term, so trajectories with and without it compare."""
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
             y_hat, reg = model(x, return_regularization=True, regularize_activation=float(getattr(args, "reg_activation", 1.0)),
                                regularize_entropy=float(getattr(args, "reg_entropy", 1.0)))
-            loss = criterion(y_hat.float(), y)
+            loss = step_loss(y_hat.float(), y, y2, w)
         total = loss + reg_lambda * reg.float()
         if reducer is not None:
             reducer.zero_grad()
@@ -313,7 +354,9 @@ def main(args, batches=None, init_state=None):
         if batches is not None:
             loader, n_batches = batches, len(batches)
         elif train_set is not None:             # order and augmentation are functions of (seed, epoch): the same on every rank
-            loader, n_batches = train_set.batches(per_rank, epoch, args.seed, rank, world), train_set.n_batches(per_rank, world)
+            loader = train_set.batches(per_rank, epoch, args.seed, rank, world) if mix is None else \
+                train_set.batches(per_rank, epoch, args.seed, rank, world, mix=mix)     # yields (x, y, y2, w): one table per epoch
+            n_batches = train_set.n_batches(per_rank, world)
         elif args.synthetic:
             loader = synthetic_loader(args.steps_per_epoch, per_rank, chw, args.out_d, device, args.seed + 1000 * epoch + rank)
             n_batches = args.steps_per_epoch
@@ -329,16 +372,18 @@ def main(args, batches=None, init_state=None):
                 epoch_metrics = history["epoch_metrics"] = EpochMetrics(args.out_d, max(rows, 1), device)
             epoch_metrics.reset()
         t_epoch = time.perf_counter()
-        for x, y in loader:
+        for x, y, *pair in loader:
             x, y = x.to(device, non_blocking=True), y.to(device, non_blocking=True)
             if args.graph and step is eager_step:
-                step = _GraphedStep(eager_step, model, optimizer, x, y)
+                step = _GraphedStep(eager_step, model, optimizer, x, y, *pair)
             n_steps += 1
             if n_steps in grid_extend:             # the extension refits on this batch too: an update due on the same step is skipped
                 extend_grid_and_swap(model, optimizer, x, grid_extend[n_steps])
             elif grid_every > 0 and n_steps % grid_every == 0:
                 model.update_grid(x)            # before the step, on the step's own batch; Adam's moments stay as they are
-            loss, y_hat = step(x, y)
+            loss, y_hat = step(x, y, *pair)
+            if pair:                            # the metrics count a mixed sample against its majority label
+                y = torch.where(pair[1] >= 0.5, y, pair[0])
             step_losses.append(loss.clone() if args.graph else loss)
             if device_metrics:
                 epoch_metrics.update(y_hat, y)      # eagerly after the step, also under --graph (y_hat is then the graph's output buffer)
@@ -462,6 +507,22 @@ def parse(argv=None):
     p.add_argument('--no-augment', action='store_true', help='with --data-npz: normalise only (no random crop, no flip)')
     p.add_argument('--crop-padding', type=int, default=4,
                    help="with --data-npz: zero padding of the random crop, the reference's RandomCrop(32, padding=4)")
+    p.add_argument('--mixup', type=float, default=0.0, metavar='ALPHA',
+                   help='with --data-npz: Mixup -- blend every sample with a partner, lam ~ Beta(ALPHA, ALPHA), inside the batch kernel '
+                        '(kanvit/data.py: mix_table, ops.mix_u8); the loss becomes the fused soft-target cross-entropy and the train '
+                        'metrics count a mixed sample against its majority label (the one whose weight is at least 0.5).  0 (default): off')
+    p.add_argument('--cutmix', type=float, default=0.0, metavar='ALPHA',
+                   help="with --data-npz: CutMix -- paste a box of the partner, area ~ 1 - Beta(ALPHA, ALPHA) (timm's rand_bbox); the "
+                        'same loss and the same majority-label rule for the train metrics as --mixup.  0 (default): off')
+    p.add_argument('--mix-prob', type=float, default=1.0, metavar='P', help='probability that a sample is mixed at all (--mixup / --cutmix)')
+    p.add_argument('--mix-switch-prob', type=float, default=0.5, metavar='P',
+                   help='probability of CutMix for a mixed sample when both --mixup and --cutmix are given')
+    p.add_argument('--label-smoothing', type=float, default=0.0, metavar='EPS',
+                   help='label smoothing of the training loss, in [0, 1) (through the fused soft-target cross-entropy; the test loss '
+                        'stays plain).  0 (default): off')
+    p.add_argument('--fused-loss', action='store_true',
+                   help='the fused cross-entropy kernel (ops.soft_cross_entropy: loss and gradient in one launch) also for the plain '
+                        'training loss; opt-in, the default stays torch.nn.CrossEntropyLoss')
     args = p.parse_args(argv)
     check_data_args(args)
     return args
