@@ -532,6 +532,41 @@ int kanvit_mix_u8(const uint8_t* images, const int64_t* labels, const int64_t* i
                   const float* weight, const int32_t* box, float* out, int64_t* y_out, int64_t* y2_out, float* w_out, int64_t N, int64_t B,
                   int H, int W, int C, int pad_y, int pad_x, int flip, uint64_t seed, uint64_t epoch, void* stream);
 
+/* ---- bilinear resize / RandomResizedCrop on the same pass (kanvit/data.py: crop_table; csrc/augment.hip) ------------------
+ * kanvit_augment_u8 / kanvit_mix_u8 at an output size of their own: out [B][C][OH][OW] fp32 contiguous; images, labels, idx and
+ * lut as kanvit_augment_u8's.  crop [N][5] int32, indexed by the DATASET index s = idx[b] (as the mix tables are), or NULL.  A row
+ * (y0, x0, bh, bw, flip) is a box of bh x bw source pixels with its top-left corner at (y0, x0), in the coordinates of the possibly
+ * flipped image extended by zero padding on all sides; it may lie partly or wholly outside the image; NULL means (0, 0, H, W, 0)
+ * for every sample (the evaluation transform).  The tap at box-local (r, u) reads row sy = y0 + r, column sx = x0 + u:
+ *   t(r, u) = lut[c][0]                                      where (sy, sx) is outside [0, H) x [0, W)
+ *           = lut[c][ images[s][sy][flip ? W-1-sx : sx][c] ]  otherwise
+ * -- kanvit_augment_u8's rule: the row (dy - pad_y, dx - pad_x, H, W, flip) describes its crop.  The output is the bilinear resize
+ * of the box with half-pixel centres and the taps clamped to the box (F.interpolate(crop, size, mode="bilinear",
+ * align_corners=False, antialias=False): no antialiasing, so meant for upsampling and mild downsampling).  The fp32 operation
+ * sequence is fixed, every operation rounded to nearest, none contracted into an fma, the division correctly rounded:
+ *   scale_y = float(bh) / float(OH);   src = max(scale_y * (float(oy) + 0.5f) - 0.5f, 0.f)
+ *   r0 = min(int(src), bh - 1);  r1 = min(r0 + 1, bh - 1);  wy1 = src - float(r0);  wy0 = 1.f - wy1
+ *   (the same along x with bw, OW, ox  ->  u0, u1, wx0, wx1)
+ *   top = wx0 * t(r0,u0) + wx1 * t(r0,u1);   bot = wx0 * t(r1,u0) + wx1 * t(r1,u1);   a = wy0 * top + wy1 * bot
+ * so the same operations in float32 on the host give the same bits, and at bh == OH, bw == OW they give t(r0, u0) exactly: the
+ * call reproduces kanvit_augment_u8 bit for bit at the identity size.  A row with bh < 1 or bw < 1 reads nothing and gives
+ * lut[c][0] (no arithmetic).
+ * partner / weight / box: kanvit_mix_u8's tables with its three rules (unmixed / CutMix look-up / Mixup fadd(fmul(w, a),
+ * fmul(1 - w, p))), all three or all NULL (no mixing; y2_out and w_out must then be NULL).  box is in OUTPUT coordinates
+ * (OH x OW); p is the resampled value of sample j = partner[s] under j's OWN crop row.  y_out, y2_out, w_out as there.  A
+ * sample's pixels depend on its own and its partner's table rows only -- never on B, the position in the batch or the rank.
+ * An idx or partner outside [0, N) is never dereferenced; no tap outside the image is loaded; the CALLER validates the tables on
+ * the CPU before the upload.  Stores are 16 bytes per lane where OW % 4 == 0 and out is 16-byte aligned, 4 bytes otherwise
+ * (decided on the host).  One launch, no atomics, no workspace, no synchronisation: capturable.  KANVIT_EINVAL (named in
+ * kanvit_last_error, before any device call) unless N >= 1, 1 <= C <= 4, 1 <= H, W, OH, OW <= 2^20, B >= 0 (B = 0 returns 0 and
+ * launches nothing); for a null images / idx / lut / out, mix tables not given together, y_out / y2_out without labels, a
+ * misaligned pointer.  kanvit_resample_u8_supported is the shape check as a pure host function (1 / 0).  Additive: the ABI
+ * version stays 7. */
+int kanvit_resample_u8_supported(int64_t N, int H, int W, int C, int OH, int OW);
+int kanvit_resample_u8(const uint8_t* images, const int64_t* labels, const int64_t* idx, const float* lut, const int32_t* crop,
+                       const int64_t* partner, const float* weight, const int32_t* box, float* out, int64_t* y_out, int64_t* y2_out,
+                       float* w_out, int64_t N, int64_t B, int H, int W, int C, int OH, int OW, void* stream);
+
 /* ---- soft-target cross-entropy, loss and gradient in one pass (ops.soft_cross_entropy; csrc/augment.hip) -----------------
  * The training loss for Mixup / CutMix pairs and label smoothing.  logits [B][C] fp32, unit column stride, row stride ld >= C;
  * y1 [B] int64; y2 [B] int64 and w [B] fp32 together or both NULL (NULL: w = 1); eps in [0, 1).

@@ -14,11 +14,14 @@
 // W/VEC * C lanes of one image row read one contiguous W*C-byte stretch of the NHWC source between them, and every lane stores
 // VEC * 4 bytes (16 in the vector form) of a contiguous output row.
 //
-// The training loop's other off-model kernels live here too: the Mixup / CutMix form of the same pass (mix_u8_kernel), the fused
+// The training loop's other off-model kernels live here too: the Mixup / CutMix form of the same pass (mix_u8_kernel), its resampling
+// form (resample_u8_kernel: bilinear resize of a per-sample box to the model's size, RandomResizedCrop from a table), the fused
 // soft-target cross-entropy (loss and gradient in one walk over a logits row) and the epoch metrics (softmax / argmax / confusion
 // update per step, and the pair counts of the one-vs-rest ROC-AUC per epoch), further down.
 #include "../../include/kanvit.h"
 #include "kanvit_common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -205,6 +208,269 @@ __global__ __launch_bounds__(256) void mix_u8_kernel(const MixArgs m) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// Bilinear resize / RandomResizedCrop to the model's size on the same pass (kanvit/data.py: crop_table).  The epoch's crop table
+// names, per DATASET index s, a box (y0, x0, bh, bw, flip) of source pixels in the coordinates of the possibly flipped, zero-padded
+// image; the output [OH][OW] is the bilinear resize of that box with half-pixel centres and the taps clamped to the box
+// (F.interpolate(crop, size, mode="bilinear", align_corners=False, antialias=False)).  A tap's value is augment_u8's: lut[c][byte],
+// lut[c][0] outside the image.  The fp32 operations are fixed and never contracted (include/kanvit.h states the sequence), so a float32
+// restatement on the host gives the same bits, and at bh == OH, bw == OW the second weights are 0 and the output is the tap itself.
+//
+// The kernel is bound by the instructions it issues, not by its stores, so the work item is shaped to share them:
+// VEC consecutive ox by RES_ROWS consecutive oy of one (b, c) plane.  What depends on the sample and the columns alone -- the index and
+// table rows, the two divisions, the x taps and weights, the source byte offsets -- is computed once per item (ResCols::init), and a
+// row costs its own y taps, its loads and the blend (ResCols::row); lanes that are neighbours in x store neighbouring 16 bytes of one
+// output row.  Where the VEC = 4 outputs span at most RES_WIN source columns (always at 3x upsampling and beyond: four outputs then
+// lie within 1 1/3 source pixels) each of the two source rows is fetched as a window of RES_WIN columns -- 6 byte loads and 6 table
+// look-ups instead of 16 -- the eight taps are picked out of it with selects, and a window is kept for the next output row, which at
+// 7x upsampling reads the same source rows six times out of seven.  Loads are unconditional at addresses clamped into the image, the
+// padding rule is a select on the table index: no branch per tap.
+// A thread walks the items t0, t0 + stride, ... with its position kept as the mixed-radix number (b, c, og, xg) and advanced by the
+// stride's digits with carries: t0 and the stride are below 2^19 (2048 work-groups at the most), so the only divisions are 32-bit
+// ones, once per thread.
+constexpr int RES_WIN = 3, RES_ROWS = 4;
+
+struct ResArgs {
+    const unsigned char* images;
+    const long long* labels;
+    const long long* idx;
+    const float* lut;
+    const int* crop;            // [N][5] or null: (0, 0, H, W, 0) for every sample
+    const long long* partner;   // the three mix tables: the <*, true> kernels only
+    const float* weight;
+    const int* box;
+    float* out;
+    long long* y_out;
+    long long* y2_out;
+    float* w_out;
+    long long N, B, total;      // total work items
+    int H, W, C, OH, OW;
+};
+
+struct ResAxis {
+    int t0, t1;                 // the two taps, box-local
+    float w0, w1;
+};
+
+// one axis of the resize: output coordinate o of an axis that maps n source pixels (scale = n / outputs)
+__device__ __forceinline__ ResAxis res_axis(float scale, int o, int n) {
+#pragma clang fp contract(off)
+    const float src = fmaxf(__fsub_rn(__fmul_rn(scale, __fadd_rn((float)o, 0.5f)), 0.5f), 0.f);
+    ResAxis r;
+    r.t0 = min((int)src, n - 1);
+    r.t1 = min(r.t0 + 1, n - 1);
+    r.w1 = __fsub_rn(src, (float)r.t0);
+    r.w0 = __fsub_rn(1.f, r.w1);
+    return r;
+}
+
+// m ? hi : lo for m all ones or zero, as one bit-select on the vector unit: a mask kept in a vector register, where a lane mask per
+// output would cost a scalar register pair each (the mixing form holds two ResCols and runs out of them)
+__device__ __forceinline__ float res_select(unsigned m, float hi, float lo) {
+    return __uint_as_float((m & __float_as_uint(hi)) | (~m & __float_as_uint(lo)));
+}
+
+__device__ __forceinline__ float res_blend(const ResAxis& x, const ResAxis& y, float t00, float t01, float t10, float t11) {
+#pragma clang fp contract(off)
+    const float top = __fadd_rn(__fmul_rn(x.w0, t00), __fmul_rn(x.w1, t01));
+    const float bot = __fadd_rn(__fmul_rn(x.w0, t10), __fmul_rn(x.w1, t11));
+    return __fadd_rn(__fmul_rn(y.w0, top), __fmul_rn(y.w1, bot));
+}
+
+// What the RES_ROWS rows of one work item share: sample s (valid: s in [0, N)) under ITS crop row at channel c, output columns
+// x0 .. x0 + VEC - 1.
+template <int VEC>
+struct ResCols {
+    bool ok;                    // a sample and a non-empty box: otherwise every value is padding and nothing is read
+    bool win;                   // row<true> serves: the item's first taps are columns ub = rx[0].t0 and ub + 1 at the most (see init), or !ok
+    int y0, x0, bh, bw, fl;
+    int at0, at1;               // w0 / w1 hold the windows of source rows at0 / at1 (at first of row INT_MIN, which is all padding)
+    float scale_y;
+    const unsigned char* img;   // the sample's channel c
+    ResAxis rx[VEC];
+    int off[RES_WIN];           // byte offsets of the window's columns in a source row, clamped into it
+    int keep[RES_WIN];          // ... and 0xFF where the column lies inside the image, 0 where it is padding (byte & keep: the table index)
+    unsigned up[VEC];           // all ones where the output's first tap is column ub + 1, zero where it is ub
+    float w0[RES_WIN], w1[RES_WIN];
+
+    // box-local column u -> byte offset in a source row (clamped into the row: a load there is always inside the image) and the mask
+    // of its byte.  Unsigned sum: a table row the caller did not validate wraps instead of overflowing.
+    __device__ __forceinline__ int column(const ResArgs& a, int u, int& mask) const {
+        const int sx = (int)((unsigned)x0 + (unsigned)u);
+        mask = (sx >= 0 && sx < a.W) ? 0xFF : 0;
+        const int fx = fl ? a.W - 1 - sx : sx;
+        return min(max(fx, 0), a.W - 1) * a.C;
+    }
+
+    __device__ __forceinline__ void init(const ResArgs& a, const float* l, long long s, bool valid, int c, int ox0) {
+        y0 = 0, x0 = 0, bh = a.H, bw = a.W, fl = 0;
+        if (a.crop && valid) {
+            const int* q = a.crop + 5 * s;
+            y0 = q[0], x0 = q[1], bh = q[2], bw = q[3], fl = q[4];
+        }
+        ok = valid && bh >= 1 && bw >= 1;
+        win = VEC == 4;
+        if (!ok) return;
+        scale_y = __fdiv_rn((float)bh, (float)a.OH);
+        const float scale_x = __fdiv_rn((float)bw, (float)a.OW);
+        img = a.images + s * a.H * a.W * a.C + c;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) rx[e] = res_axis(scale_x, ox0 + e, bw);
+        if constexpr (VEC == 4) {
+            // The taps do not decrease along x.  If the last output's first tap is ub or ub + 1, every output's taps are (ub, ub + 1) or
+            // (ub + 1, ub + 2) with each column clamped to bw - 1 -- t1 = min(t0 + 1, bw - 1) -- so the window of columns
+            // min(ub + k, bw - 1), k = 0, 1, 2, holds all eight taps of a source row, and an output picks its pair by t0 != ub.
+            static_assert(RES_WIN == 3, "the window is the columns ub, ub + 1, ub + 2");
+            const int ub = rx[0].t0;
+            win = rx[3].t0 - ub <= 1;
+            if (win) {
+#pragma unroll
+                for (int k = 0; k < RES_WIN; ++k) {
+                    off[k] = column(a, min(ub + k, bw - 1), keep[k]);
+                    w0[k] = w1[k] = l[0];
+                }
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) up[e] = rx[e].t0 != ub ? ~0u : 0u;
+                at0 = at1 = INT_MIN;                     // y0 + a tap reaches it only from an unvalidated table, and that row is padding too
+            }
+        }
+    }
+
+    // The values of output row oy.  WIN: through the windows, for an item with `win` (VEC == 4); otherwise tap by tap.  The two are
+    // separate so that the kernel can run them in separate row loops: what either keeps across rows is live in its own loop only.
+    template <bool WIN>
+    __device__ __forceinline__ void row(const ResArgs& a, const float* l, int oy, float* v) {
+        if (!ok) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) v[e] = l[0];
+            return;
+        }
+        const ResAxis ry = res_axis(scale_y, oy, bh);
+        const int sy0 = (int)((unsigned)y0 + (unsigned)ry.t0), sy1 = (int)((unsigned)y0 + (unsigned)ry.t1);
+        const int keep0 = (sy0 >= 0 && sy0 < a.H) ? 0xFF : 0, keep1 = (sy1 >= 0 && sy1 < a.H) ? 0xFF : 0;
+        const long long pitch = (long long)a.W * a.C;
+        const unsigned char* row0 = img + min(max(sy0, 0), a.H - 1) * pitch;       // clamped like the columns
+        const unsigned char* row1 = img + min(max(sy1, 0), a.H - 1) * pitch;
+        if constexpr (WIN) {
+            if (at0 != sy0) {
+#pragma unroll
+                for (int k = 0; k < RES_WIN; ++k) w0[k] = l[(int)row0[off[k]] & keep0 & keep[k]];
+                at0 = sy0;
+            }
+            if (at1 != sy1) {
+#pragma unroll
+                for (int k = 0; k < RES_WIN; ++k) w1[k] = l[(int)row1[off[k]] & keep1 & keep[k]];
+                at1 = sy1;
+            }
+#pragma unroll
+            for (int e = 0; e < VEC; ++e)
+                v[e] = res_blend(rx[e], ry, res_select(up[e], w0[1], w0[0]), res_select(up[e], w0[2], w0[1]), res_select(up[e], w1[1], w1[0]),
+                                 res_select(up[e], w1[2], w1[1]));
+            return;
+        }
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            int m0, m1;
+            const int o0 = column(a, rx[e].t0, m0), o1 = column(a, rx[e].t1, m1);
+            v[e] = res_blend(rx[e], ry, l[(int)row0[o0] & keep0 & m0], l[(int)row0[o1] & keep0 & m1], l[(int)row1[o0] & keep1 & m0],
+                             l[(int)row1[o1] & keep1 & m1]);
+        }
+    }
+};
+
+template <int VEC, bool MIX>
+__global__ __launch_bounds__(256) void resample_u8_kernel(const ResArgs a) {
+    __shared__ float lut[4 * 256];
+    for (int i = threadIdx.x; i < a.C * 256; i += 256) lut[i] = a.lut[i];
+    __syncthreads();
+    const unsigned WV = (unsigned)a.OW / VEC, OG = ((unsigned)a.OH + RES_ROWS - 1) / RES_ROWS, C = (unsigned)a.C;
+    const unsigned t0 = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
+    unsigned xg = t0 % WV, r = t0 / WV;                  // the item's digits (b, c, og, xg) ...
+    unsigned og = r % OG;
+    r /= OG;
+    unsigned c = r % C;
+    long long b = r / C;
+    const unsigned s_xg = stride % WV, s_r = stride / WV, s_og = s_r % OG, s_c = (s_r / OG) % C, s_b = s_r / OG / C;      // ... and the stride's
+    for (long long t = t0; t < a.total; t += stride) {
+        const long long s = a.idx[b];
+        const bool sample_ok = s >= 0 && s < a.N;        // the caller validates idx and the tables; nothing outside them is dereferenced
+        const int x0 = (int)xg * VEC;
+        const float* l = lut + c * 256;
+        ResCols<VEC> own;
+        own.init(a, l, s, sample_ok, (int)c, x0);
+        const bool first = c == 0 && og == 0 && xg == 0;
+        long long lab = -1;
+        if (first) {
+            if (sample_ok && a.labels) lab = a.labels[s];
+            if (a.y_out) a.y_out[b] = lab;
+        }
+        [[maybe_unused]] ResCols<VEC> par;                // the partner under ITS crop row
+        [[maybe_unused]] bool mixed = false, cut = false;
+        [[maybe_unused]] int by0 = 0, by1 = 0, bx0 = 0, bx1 = 0;
+        [[maybe_unused]] float w = 1.f, w1 = 0.f;
+        if constexpr (MIX) {
+            const long long j = sample_ok ? a.partner[s] : -1;
+            mixed = j >= 0 && j < a.N;                   // a partner outside the dataset is never dereferenced: the row stays unmixed
+            w = sample_ok ? a.weight[s] : 1.f;
+            w1 = 1.f - w;
+            if (first) {
+                if (a.y2_out) a.y2_out[b] = (mixed && a.labels) ? a.labels[j] : lab;
+                if (a.w_out) a.w_out[b] = w;
+            }
+            if (mixed) {
+                const int* bx = a.box + 4 * s;
+                by0 = bx[0], by1 = bx[1], bx0 = bx[2], bx1 = bx[3];
+                cut = by0 < by1 && bx0 < bx1;
+                mixed = !cut || (x0 < bx1 && x0 + VEC > bx0);       // CutMix columns outside the box keep a
+                if (mixed) par.init(a, l, j, true, (int)c, x0);
+            }
+        }
+        const int oy0 = (int)og * RES_ROWS, oy_end = min(oy0 + RES_ROWS, a.OH);
+        float* const o0 = a.out + ((b * C + c) * a.OH + oy0) * a.OW + x0;
+        auto rows = [&](auto through_windows) {
+            constexpr bool WIN = decltype(through_windows)::value;
+            float* o = o0;
+#pragma unroll 1
+            for (int oy = oy0; oy < oy_end; ++oy, o += a.OW) {
+                float v[VEC];
+                own.template row<WIN>(a, l, oy, v);
+                if constexpr (MIX) {
+                    if (mixed && (!cut || (oy >= by0 && oy < by1))) {        // CutMix rows outside the box keep a
+                        float p[VEC];
+                        par.template row<WIN>(a, l, oy, p);
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) {
+                            if (cut)
+                                v[e] = (x0 + e >= bx0 && x0 + e < bx1) ? p[e] : v[e];
+                            else
+                                v[e] = mix_blend(w, w1, v[e], p[e]);
+                        }
+                    }
+                }
+                if constexpr (VEC == 4) {
+                    *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
+                } else {
+                    o[0] = v[0];
+                }
+            }
+        };
+        if (VEC == 4 && own.win && (!mixed || par.win))
+            rows(std::integral_constant<bool, VEC == 4>{});
+        else
+            rows(std::false_type{});
+        xg += s_xg;                                      // every digit and its stride digit are below the radix: one carry each
+        unsigned k = xg >= WV ? 1u : 0u;
+        xg -= k ? WV : 0u;
+        og += s_og + k;
+        k = og >= OG ? 1u : 0u;
+        og -= k ? OG : 0u;
+        c += s_c + k;
+        k = c >= C ? 1u : 0u;
+        c -= k ? C : 0u;
+        b += s_b + k;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // Soft-target cross-entropy, forward and gradient in one walk (ops.soft_cross_entropy): the target of row b is
 //     t_c = (1 - eps) (w [c == y1] + (1 - w) [c == y2]) + eps / C        (label smoothing eps; Mixup / CutMix pair (y1, y2, w))
 // and with m = max z, s = sum exp(z - m), p = exp(z - m) / s:
@@ -285,6 +551,14 @@ int aug_check_shape(const char* who, int64_t N, int H, int W, int C, int pad_y, 
     if (H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20)) return kv_fail(KANVIT_EINVAL, "%s: H=%d, W=%d must be in 1..2^20", who, H, W);
     if (pad_y < 0 || pad_y > H) return kv_fail(KANVIT_EINVAL, "%s: pad_y=%d must be in 0..H=%d", who, pad_y, H);
     if (pad_x < 0 || pad_x > W) return kv_fail(KANVIT_EINVAL, "%s: pad_x=%d must be in 0..W=%d", who, pad_x, W);
+    return 0;
+}
+
+int res_check_shape(const char* who, int64_t N, int H, int W, int C, int OH, int OW) {
+    if (N < 1) return kv_fail(KANVIT_EINVAL, "%s: N=%lld: the dataset holds at least one image", who, (long long)N);
+    if (C < 1 || C > 4) return kv_fail(KANVIT_EINVAL, "%s: C=%d must be in 1..4 (the look-up table is staged as C x 1 KB)", who, C);
+    if (H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20)) return kv_fail(KANVIT_EINVAL, "%s: H=%d, W=%d must be in 1..2^20", who, H, W);
+    if (OH < 1 || OW < 1 || OH > (1 << 20) || OW > (1 << 20)) return kv_fail(KANVIT_EINVAL, "%s: OH=%d, OW=%d must be in 1..2^20", who, OH, OW);
     return 0;
 }
 
@@ -622,6 +896,59 @@ int kanvit_mix_u8(const uint8_t* images, const int64_t* labels, const int64_t* i
     else
         hipLaunchKernelGGL(mix_u8_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m);
     KV_LAUNCH_CHECK("mix_u8_kernel");
+    return 0;
+}
+
+int kanvit_resample_u8_supported(int64_t N, int H, int W, int C, int OH, int OW) {
+    return res_check_shape("kanvit_resample_u8_supported", N, H, W, C, OH, OW) == 0 ? 1 : 0;
+}
+
+int kanvit_resample_u8(const uint8_t* images, const int64_t* labels, const int64_t* idx, const float* lut, const int32_t* crop,
+                       const int64_t* partner, const float* weight, const int32_t* box, float* out, int64_t* y_out, int64_t* y2_out,
+                       float* w_out, int64_t N, int64_t B, int H, int W, int C, int OH, int OW, void* stream) {
+    if (int rc = res_check_shape("kanvit_resample_u8", N, H, W, C, OH, OW)) return rc;
+    if (B < 0) return kv_fail(KANVIT_EINVAL, "kanvit_resample_u8: B=%lld is negative", (long long)B);
+    if (B == 0) return 0;
+    if (B > (1ll << 62) / ((long long)C * OH * OW)) return kv_fail(KANVIT_EINVAL, "kanvit_resample_u8: B=%lld: too many output pixels for one launch", (long long)B);
+    if (!images || !idx || !lut || !out) return kv_fail(KANVIT_EINVAL, "kanvit_resample_u8: null images/idx/lut/out");
+    const bool mix = partner || weight || box;
+    if (mix && (!partner || !weight || !box))
+        return kv_fail(KANVIT_EINVAL, "kanvit_resample_u8: null %s (the three mix tables partner/weight/box come together or not at all)",
+                       !partner ? "partner" : !weight ? "weight" : "box");
+    if ((y2_out || w_out) && !mix) return kv_fail(KANVIT_EINVAL, "kanvit_resample_u8: y2_out / w_out without the mix tables");
+    if ((y_out || y2_out) && !labels) return kv_fail(KANVIT_EINVAL, "kanvit_resample_u8: y_out / y2_out without labels");
+    if ((uintptr_t)out & 3 || (uintptr_t)lut & 3 || (uintptr_t)idx & 7 || (uintptr_t)labels & 7 || (uintptr_t)crop & 3 || (uintptr_t)y_out & 7 ||
+        (uintptr_t)y2_out & 7 || (uintptr_t)partner & 7 || (uintptr_t)weight & 3 || (uintptr_t)box & 3 || (uintptr_t)w_out & 3)
+        return kv_fail(KANVIT_EINVAL, "kanvit_resample_u8: a pointer is not aligned to its element size");
+    ResArgs a;
+    a.images = images;
+    a.labels = (const long long*)labels;
+    a.idx = (const long long*)idx;
+    a.lut = lut;
+    a.crop = crop;
+    a.partner = (const long long*)partner;
+    a.weight = weight;
+    a.box = box;
+    a.out = out;
+    a.y_out = (long long*)y_out;
+    a.y2_out = (long long*)y2_out;
+    a.w_out = w_out;
+    a.N = N, a.B = B, a.H = H, a.W = W, a.C = C, a.OH = OH, a.OW = OW;
+    const bool vec = (OW % 4 == 0) && ((uintptr_t)out & 15) == 0;       // as kanvit_augment_u8 decides it, on the output's width
+    a.total = (long long)B * C * ((OH + RES_ROWS - 1) / RES_ROWS) * (vec ? OW / 4 : OW);       // items of RES_ROWS rows by 4 (or 1) columns
+    long long blocks = (a.total + 255) / 256;
+    if (blocks > 2048) blocks = 2048;           // the kernel's 32-bit index arithmetic relies on this cap: t0 and the stride stay below 2^19
+    const dim3 grid((unsigned)blocks), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec && mix)
+        hipLaunchKernelGGL((resample_u8_kernel<4, true>), grid, block, 0, st, a);
+    else if (vec)
+        hipLaunchKernelGGL((resample_u8_kernel<4, false>), grid, block, 0, st, a);
+    else if (mix)
+        hipLaunchKernelGGL((resample_u8_kernel<1, true>), grid, block, 0, st, a);
+    else
+        hipLaunchKernelGGL((resample_u8_kernel<1, false>), grid, block, 0, st, a);
+    KV_LAUNCH_CHECK("resample_u8_kernel");
     return 0;
 }
 

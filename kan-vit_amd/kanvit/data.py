@@ -14,6 +14,10 @@ Mixup and CutMix ride on the same pass: mix_table draws one table per epoch from
 batches(mix=...) hands it to ops.mix_u8, which blends or pastes the partner under the partner's own crop and flip -- a sample's pixels
 and soft targets stay a function of (seed, epoch, sample index).
 
+Another output size and RandomResizedCrop ride on it too: GpuDataset(out_size=..., crop="rrc") produces every batch with
+ops.resample_u8, the bilinear resize of a per-sample box named by crop_table -- again one table per epoch drawn from (seed, epoch) and
+indexed by dataset index.  With the stored size and the padded crop nothing changes.
+
 The file format is an .npz: x_train uint8 [N, H, W, C] (or [N, H, W] for one channel), y_train of any integer type, optionally
 x_test / y_test, optionally mean / std ([C], on the 0-1 scale; computed from x_train when absent).  tools/cifar_to_npz.py writes
 one from an unpacked CIFAR python-pickle directory.
@@ -124,6 +128,78 @@ def mix_table(n: int, epoch: int, seed: int, hw, mixup_alpha: float = 0.0, cutmi
     return MixTable(torch.from_numpy(np.where(mixed, partner, -1).astype(np.int64)), torch.from_numpy(weight), torch.from_numpy(box))
 
 
+_CROP_TABLE_KEY = 0x63726F705F74626C    # "crop_tbl": the crop table's generator, apart from the permutation's and the mix table's
+_RRC_ATTEMPTS = 10                      # torchvision's RandomResizedCrop.get_params tries ten boxes before it falls back
+
+
+def _mix_u64(z: np.ndarray) -> np.ndarray:
+    """_mix on a uint64 array (arithmetic mod 2^64 is what the dtype does)."""
+    z = z + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def crop_table(n: int, epoch: int, seed: int, hw, mode: str, pad=(0, 0), flip: bool = True, scale=(0.08, 1.0),
+               ratio=(3.0 / 4.0, 4.0 / 3.0)) -> torch.Tensor:
+    """The crop table of `epoch` for ops.resample_u8: int32 [n, 5] on the CPU, row s = (y0, x0, bh, bw, flip) for DATASET index s -- a
+    box of bh x bw source pixels at (y0, x0) in the coordinates of the possibly flipped, zero-padded image of size hw = (H, W).  Like
+    mix_table it is a function of its arguments alone: not of the batch size, the rank or the world size.
+
+    mode "pad": ops.augment_u8's crop.  (dy, dx, fl) are the per-sample hash of include/kanvit.h (mix(mix(mix(seed) + epoch) + s),
+    here on a uint64 array) and the row is (dy - pad_y, dx - pad_x, H, W, fl); `scale` and `ratio` are not used.
+
+    mode "rrc": torchvision's RandomResizedCrop.get_params; `pad` is not used.  The draws come from ONE NumPy PCG64 generator seeded
+    by (seed, epoch) under a key of its own; every column is a g.random(n) in float64 for all n rows in index order: ten area
+    fractions a_k (area = H W (lo + (hi - lo) a_k) over `scale`), then ten ratios r_k = exp(log lo + (log hi - log lo) u_k) over
+    `ratio`, then one row position, one column position and one flip (u < 0.5).  Attempt k gives w = rint(sqrt(area r)),
+    h = rint(sqrt(area / r)); the first with 1 <= w <= W and 1 <= h <= H is taken and placed at floor(u (H - h + 1)),
+    floor(u (W - w + 1)).  If none fits: the centred whole image clipped to the ratio bounds (W / H below ratio[0]: w = W,
+    h = rint(W / ratio[0]); above ratio[1]: h = H, w = rint(H ratio[1])).  Every box lies inside the image.
+
+    flip=False zeroes the flip column.  Bad arguments are a ValueError."""
+    H, W = int(hw[0]), int(hw[1])
+    if n < 1 or H < 1 or W < 1:
+        raise ValueError(f"crop_table: n={n}, hw={tuple(hw)}")
+    if mode not in ("pad", "rrc"):
+        raise ValueError(f"crop_table: mode '{mode}' is 'pad' or 'rrc'")
+    base = _mix((_mix(int(seed) & _M64) + int(epoch)) & _M64)
+    if mode == "pad":
+        pad_y, pad_x = (int(pad), int(pad)) if isinstance(pad, int) else (int(pad[0]), int(pad[1]))
+        if not 0 <= pad_y <= H or not 0 <= pad_x <= W:
+            raise ValueError(f"crop_table: pad=({pad_y}, {pad_x}) must be in 0..H={H}, 0..W={W}")
+        h = _mix_u64(np.uint64(base) + np.arange(n, dtype=np.uint64))
+        m20 = np.uint64(0xFFFFF)
+        dy = ((h & m20) % np.uint64(2 * pad_y + 1)).astype(np.int64)
+        dx = (((h >> np.uint64(20)) & m20) % np.uint64(2 * pad_x + 1)).astype(np.int64)
+        fl = ((h >> np.uint64(40)) & np.uint64(1)).astype(np.int64)
+        rows = np.stack([dy - pad_y, dx - pad_x, np.full(n, H), np.full(n, W), fl if flip else np.zeros(n, np.int64)], 1)
+        return torch.from_numpy(rows.astype(np.int32))
+    s_lo, s_hi, r_lo, r_hi = float(scale[0]), float(scale[1]), float(ratio[0]), float(ratio[1])
+    if not 0 < s_lo <= s_hi or not 0 < r_lo <= r_hi or not all(np.isfinite([s_hi, r_hi])):
+        raise ValueError(f"crop_table: scale={tuple(scale)} and ratio={tuple(ratio)} are (lo, hi) with 0 < lo <= hi")
+    g = np.random.Generator(np.random.PCG64(_mix(base ^ _CROP_TABLE_KEY)))
+    area = [H * W * (s_lo + (s_hi - s_lo) * g.random(n)) for _ in range(_RRC_ATTEMPTS)]
+    rat = [np.exp(np.log(r_lo) + (np.log(r_hi) - np.log(r_lo)) * g.random(n)) for _ in range(_RRC_ATTEMPTS)]
+    uy, ux, fl = g.random(n), g.random(n), g.random(n) < 0.5
+    bh, bw = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    for a, r in zip(area, rat):
+        w, h = np.rint(np.sqrt(a * r)).astype(np.int64), np.rint(np.sqrt(a / r)).astype(np.int64)
+        take = (bh == 0) & (w >= 1) & (w <= W) & (h >= 1) & (h <= H)
+        bh, bw = np.where(take, h, bh), np.where(take, w, bw)
+    found = bh > 0
+    y0 = np.floor(uy * (H - bh + 1)).astype(np.int64)
+    x0 = np.floor(ux * (W - bw + 1)).astype(np.int64)
+    fh, fw = H, W                                   # the fallback: one box for the whole table
+    if W / H < r_lo:
+        fh = min(max(int(np.rint(W / r_lo)), 1), H)
+    elif W / H > r_hi:
+        fw = min(max(int(np.rint(H * r_hi)), 1), W)
+    rows = np.stack([np.where(found, y0, (H - fh) // 2), np.where(found, x0, (W - fw) // 2), np.where(found, bh, fh),
+                     np.where(found, bw, fw), fl.astype(np.int64) if flip else np.zeros(n, np.int64)], 1)
+    return torch.from_numpy(rows.astype(np.int32))
+
+
 def _fail(path, key, what):
     raise ValueError(f"{path}: '{key}' {what}")
 
@@ -190,7 +266,11 @@ class Batches:
 class GpuDataset:
     """Images (uint8, NHWC) and labels (int64) resident on `device`; batches() yields normalised, augmented float32 NCHW batches."""
 
-    def __init__(self, images, labels, mean, std, device, pad=0, flip=False):
+    def __init__(self, images, labels, mean, std, device, pad=0, flip=False, out_size=None, crop="pad", rrc_scale=(0.08, 1.0),
+                 rrc_ratio=(3.0 / 4.0, 4.0 / 3.0)):
+        """out_size (an int or (OH, OW)): the size of the batches, resized from the stored images by ops.resample_u8; None: the stored
+        size.  crop: "pad" (the random crop out of the zero-padded image, `pad` and `flip`) or "rrc" (RandomResizedCrop over rrc_scale /
+        rrc_ratio, with `flip`; `pad` is then unused).  With the stored size and crop="pad" nothing changes: ops.augment_u8 / ops.mix_u8."""
         images = torch.as_tensor(images)
         labels = torch.as_tensor(labels)
         if images.dtype != torch.uint8 or images.dim() not in (3, 4):
@@ -203,25 +283,34 @@ class GpuDataset:
             raise ValueError(f"GpuDataset: mean/std have {self.lut_cpu.shape[0]} entries, the images {self.chw[0]} channels")
         self.pad = (int(pad), int(pad)) if isinstance(pad, int) else (int(pad[0]), int(pad[1]))
         self.flip = bool(flip)
+        if crop not in ("pad", "rrc"):
+            raise ValueError(f"GpuDataset: crop '{crop}' is 'pad' or 'rrc'")
+        self.crop, self.rrc_scale, self.rrc_ratio = crop, tuple(rrc_scale), tuple(rrc_ratio)
+        self.out_hw = self.chw[1:] if out_size is None else \
+            (int(out_size), int(out_size)) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
+        if min(self.out_hw) < 1:
+            raise ValueError(f"GpuDataset: out_size={out_size} must be positive")
+        self.resample = crop != "pad" or self.out_hw != self.chw[1:]     # False: today's path, call for call
         self.device = torch.device(device)
         self.images = images.contiguous().to(self.device)
         self.labels = labels.to(torch.int64).contiguous().to(self.device)
         self.lut = self.lut_cpu.to(self.device)
 
     @classmethod
-    def from_npz(cls, path, split, device, pad=0, flip=False):
+    def from_npz(cls, path, split, device, pad=0, flip=False, **resample):
         """The `split` ('train' or 'test') of an .npz in this module's layout; mean / std from the file, else from x_train."""
         if split not in ("train", "test"):
             raise ValueError(f"GpuDataset.from_npz: split '{split}' is 'train' or 'test'")
-        return cls.from_arrays(load_npz(path), path, split, device, pad=pad, flip=flip)
+        return cls.from_arrays(load_npz(path), path, split, device, pad=pad, flip=flip, **resample)
 
     @classmethod
-    def from_arrays(cls, blob, path, split, device, pad=0, flip=False):
+    def from_arrays(cls, blob, path, split, device, pad=0, flip=False, **resample):
+        """`resample`: out_size, crop, rrc_scale, rrc_ratio, as the constructor takes them."""
         if f"x_{split}" not in blob:
             _fail(path, f"x_{split}", "is missing")
         mean, std = (blob["mean"], blob["std"]) if "mean" in blob else channel_stats(blob["x_train"])
         return cls(torch.from_numpy(blob[f"x_{split}"]), torch.from_numpy(blob[f"y_{split}"].astype(np.int64)), mean.astype(np.float32),
-                   std.astype(np.float32), device, pad=pad, flip=flip)
+                   std.astype(np.float32), device, pad=pad, flip=flip, **resample)
 
     def __len__(self):
         return int(self.images.shape[0])
@@ -239,20 +328,43 @@ class GpuDataset:
         mix: the keyword arguments of mix_table after hw (mixup_alpha, cutmix_alpha, prob, switch_prob) as a dict -- Mixup / CutMix.
         The epoch's table is drawn and checked on the CPU and uploaded once, next to the index list, and every batch is one
         ops.mix_u8 launch yielding (x, y, y2, w): y2 int64 [b] the partner's label (y where the sample is not mixed), w float32 [b]
-        the weight of y.  Without `mix` nothing changes: (x, y) through ops.augment_u8."""
+        the weight of y.  Without `mix` nothing changes: (x, y) through ops.augment_u8.
+
+        A dataset with an out_size of its own or crop="rrc" yields x float32 [b, C, OH, OW] from one ops.resample_u8 launch per batch
+        instead: the epoch's crop table (crop_table) is drawn, checked and uploaded once, like the mix table, which is then drawn
+        at hw = out_size; the evaluation transform (crop="pad", pad 0, no flip) passes no table at all."""
         if batch_size < 1:
             raise ValueError(f"GpuDataset.batches: batch_size={batch_size}")
         idx = epoch_indices(len(self), epoch, seed, rank, world, shuffle)
         if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= len(self)):
             raise IndexError(f"GpuDataset.batches: an index outside [0, {len(self)})")
         idx = idx.to(self.device)
+        if self.resample:
+            yield from self._resampled(idx, batch_size, epoch, seed, mix)
+            return
         if mix is None:
             for i in range(0, idx.numel(), batch_size):
                 yield ops.augment_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, self.pad, self.flip, seed, epoch)
             return
-        table = mix_table(len(self), epoch, seed, self.chw[1:], **mix)
-        if tuple(table.partner.shape) != (len(self),) or int(table.partner.min()) < -1 or int(table.partner.max()) >= len(self):
-            raise IndexError(f"GpuDataset.batches: the mix table names a partner outside [-1, {len(self)}) or is not of length {len(self)}")
-        partner, weight, box = (t.contiguous().to(self.device) for t in table)
+        partner, weight, box = self._mix_tables(epoch, seed, self.chw[1:], mix)
         for i in range(0, idx.numel(), batch_size):
             yield ops.mix_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, partner, weight, box, self.pad, self.flip, seed, epoch)
+
+    def _mix_tables(self, epoch, seed, hw, mix):
+        """The epoch's mix table at output size hw, checked on the CPU, on the device."""
+        table = mix_table(len(self), epoch, seed, hw, **mix)
+        if tuple(table.partner.shape) != (len(self),) or int(table.partner.min()) < -1 or int(table.partner.max()) >= len(self):
+            raise IndexError(f"GpuDataset.batches: the mix table names a partner outside [-1, {len(self)}) or is not of length {len(self)}")
+        return tuple(t.contiguous().to(self.device) for t in table)
+
+    def _resampled(self, idx, batch_size, epoch, seed, mix):
+        """batches() through ops.resample_u8: (x, y), or (x, y, y2, w) with `mix`."""
+        n, crop = len(self), None
+        if self.crop != "pad" or self.pad != (0, 0) or self.flip:
+            crop = crop_table(n, epoch, seed, self.chw[1:], self.crop, pad=self.pad, flip=self.flip, scale=self.rrc_scale, ratio=self.rrc_ratio)
+            if tuple(crop.shape) != (n, 5) or crop.dtype != torch.int32 or int(crop[:, 2:4].min()) < 1:
+                raise ValueError(f"GpuDataset.batches: the crop table is not int32 [{n}, 5] or holds an empty box")
+            crop = crop.contiguous().to(self.device)
+        tables = self._mix_tables(epoch, seed, self.out_hw, mix) if mix is not None else ()
+        for i in range(0, idx.numel(), batch_size):
+            yield ops.resample_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, self.out_hw, crop, *tables)

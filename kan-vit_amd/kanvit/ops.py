@@ -1149,6 +1149,66 @@ def mix_u8(images: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor, lut: t
     return out, y, y2, w
 
 
+def resample_u8(images: torch.Tensor, labels: Optional[torch.Tensor], idx: torch.Tensor, lut: torch.Tensor, out_size, crop: Optional[torch.Tensor] = None,
+                partner: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None, box: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None):
+    """augment_u8 / mix_u8 at an output size of their own, in one launch: the bilinear resize (half-pixel centres, no antialiasing) of
+    a per-sample box of the zero-padded, possibly flipped image to out_size = (OH, OW) (semantics and the fixed fp32 operation sequence:
+    include/kanvit.h).  crop int32 [N, 5] = (y0, x0, bh, bw, flip) is the epoch's table (data.crop_table) on the device, indexed by the
+    DATASET index; None is the whole image, unflipped, for every sample.  partner / weight / box are mix_u8's tables, all three or
+    none, with box in OUTPUT coordinates; the partner is resampled under its own crop row.  Every idx and partner lies inside the
+    dataset: the CALLER checks that before the upload.
+    Returns (x float32 [B, C, OH, OW], y int64 [B]) -- x alone when labels is None -- or (x, y, y2, w) with the mix tables."""
+    N = int(images.shape[0]) if images.dim() in (3, 4) else -1
+    tables = (partner, weight, box)
+    mixing = any(t is not None for t in tables)
+    if mixing and any(t is None for t in tables):
+        raise KanvitError("resample_u8: partner, weight and box come together (all three or none)")
+    if mixing and labels is None:
+        raise KanvitError("resample_u8: labels is None: the mix tables yield (x, y, y2, w)")
+    for name, t, dt in (("images", images, torch.uint8), ("labels", labels, torch.int64), ("idx", idx, torch.int64), ("lut", lut, torch.float32),
+                        ("crop", crop, torch.int32), ("partner", partner, torch.int64), ("weight", weight, torch.float32), ("box", box, torch.int32),
+                        ("out", out, torch.float32)):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise KanvitError(f"resample_u8: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+        if t.device != images.device:
+            raise KanvitError(f"resample_u8: {name} is on {t.device}, images on {images.device}")
+        if t.dtype != dt:
+            raise KanvitError(f"resample_u8: {name} has dtype {t.dtype}, expected {dt}")
+        if not t.is_contiguous():
+            raise KanvitError(f"resample_u8: {name} is not contiguous")
+    if N < 0:
+        raise KanvitError(f"resample_u8: images has shape {tuple(images.shape)}, expected [N, H, W, C] or [N, H, W]")
+    H, W = int(images.shape[1]), int(images.shape[2])
+    Cn = int(images.shape[3]) if images.dim() == 4 else 1
+    try:
+        OH, OW = (int(out_size), int(out_size)) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
+    except (TypeError, IndexError):
+        raise KanvitError(f"resample_u8: out_size={out_size!r} is an int or (OH, OW)") from None
+    if idx.dim() != 1:
+        raise KanvitError(f"resample_u8: idx has shape {tuple(idx.shape)}, expected [B]")
+    for name, t, shape in (("labels", labels, (N,)), ("lut", lut, (Cn, 256)), ("crop", crop, (N, 5)), ("partner", partner, (N,)),
+                           ("weight", weight, (N,)), ("box", box, (N, 4))):
+        if t is not None and tuple(t.shape) != shape:
+            raise KanvitError(f"resample_u8: {name} has shape {tuple(t.shape)}, expected {list(shape)}")
+    B = int(idx.shape[0])
+    if out is None:
+        out = torch.empty((B, Cn, max(OH, 0), max(OW, 0)), device=images.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, Cn, OH, OW):
+        raise KanvitError(f"resample_u8: out has shape {tuple(out.shape)}, expected {(B, Cn, OH, OW)}")
+    y = torch.empty((B,), device=images.device, dtype=torch.int64) if labels is not None else None
+    y2 = torch.empty((B,), device=images.device, dtype=torch.int64) if mixing else None
+    w = torch.empty((B,), device=images.device, dtype=torch.float32) if mixing else None
+    _launch(_lib.lib().kanvit_resample_u8, "kanvit_resample_u8", images.device, _ptr(images), _ptr(labels), _ptr(idx), _ptr(lut), _ptr(crop),
+            _ptr(partner), _ptr(weight), _ptr(box), _ptr(out), _ptr(y), _ptr(y2), _ptr(w), N, B, H, W, Cn, OH, OW,
+            tag="resample_u8", cost=(0, B * Cn * OH * OW * 4))
+    if mixing:
+        return out, y, y2, w
+    return (out, y) if labels is not None else out
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # soft-target cross-entropy: loss and gradient in one pass over the logits (csrc/augment.hip)
 # ---------------------------------------------------------------------------------------------------------------------------

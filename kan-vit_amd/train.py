@@ -22,7 +22,10 @@ kanvit/metrics.py: one kernel per step, one pair-counting pass per epoch, C*C + 
 an [N, C] copy and scikit-learn on one CPU thread), --mixup / --cutmix / --mix-prob / --mix-switch-prob (Mixup and CutMix inside the
 batch kernel, from a per-epoch table that is a function of (seed, epoch) alone: kanvit/data.py mix_table, ops.mix_u8),
 --label-smoothing and --fused-loss (the training loss and its gradient from one fused soft-target cross-entropy launch:
-ops.soft_cross_entropy).
+ops.soft_cross_entropy), --resize S / --random-resized-crop / --rrc-scale / --rrc-ratio (the batch kernel resamples: every batch
+comes out at S x S, bilinear, from the stored images -- `--data-npz cifar100.npz --resize 224 --n-patches 14` trains the ViT-B/16
+geometry on 32 x 32 images -- and RandomResizedCrop boxes come from a per-epoch table, a function of (seed, epoch) alone:
+kanvit/data.py crop_table, ops.resample_u8; --image-size stays the size of the stored images).
 
 `main(args, batches=None, init_state=None)` also serves the parity tests: `batches` (a list of (x, y) tensors) replaces
 the data stream, `init_state` (a reference-layout state dict) replaces the random initialisation, and the returned dict
@@ -82,6 +85,17 @@ def check_data_args(args):
             raise SystemExit("--mixup / --cutmix mix inside the kernel that reads the GPU-resident dataset; give --data-npz")
         if getattr(args, "no_augment", False):
             raise SystemExit("--mixup / --cutmix are augmentations; they are not combined with --no-augment")
+    resize, rrc = int(getattr(args, "resize", 0)), bool(getattr(args, "random_resized_crop", False))
+    if resize < 0:
+        raise SystemExit(f"--resize {resize} is negative (0: off)")
+    if (resize > 0 or rrc) and not getattr(args, "data_npz", None):
+        raise SystemExit("--resize / --random-resized-crop resample inside the kernel that reads the GPU-resident dataset; give --data-npz")
+    if rrc and getattr(args, "no_augment", False):
+        raise SystemExit("--random-resized-crop is an augmentation; it is not combined with --no-augment")
+    for flag, name, default in (("--rrc-scale", "rrc_scale", (0.08, 1.0)), ("--rrc-ratio", "rrc_ratio", (3.0 / 4.0, 4.0 / 3.0))):
+        lo, hi = (float(v) for v in getattr(args, name, default))
+        if not 0 < lo <= hi or hi == float("inf"):
+            raise SystemExit(f"{flag} {lo} {hi}: LO and HI are positive and LO is not above HI")
 
 
 def mix_config(args):
@@ -96,7 +110,8 @@ def mix_config(args):
 def npz_datasets(args, device, want_test=True):
     """--data-npz: (train, test or None) GpuDatasets.  --image-size / --in-chans left at their defaults follow the file (args is
     updated); given values that contradict it, labels that --out-d does not cover and non-square images are refused.  Only the rank
-    that evaluates asks for the test split."""
+    that evaluates asks for the test split.  --resize S gives both splits out_size = (S, S) (--image-size stays the file's size) and
+    --random-resized-crop gives the train split crop="rrc": their batches then come from ops.resample_u8."""
     from kanvit import data as kdata
     blob = kdata.load_npz(args.data_npz)
     x = blob["x_train"]
@@ -114,8 +129,13 @@ def npz_datasets(args, device, want_test=True):
     augment = not args.no_augment
     if augment and args.crop_padding > h:
         raise SystemExit(f"--crop-padding {args.crop_padding} exceeds the image size {h}")
-    train = kdata.GpuDataset.from_arrays(blob, args.data_npz, "train", device, pad=args.crop_padding if augment else 0, flip=augment)
-    test = kdata.GpuDataset.from_arrays(blob, args.data_npz, "test", device) if want_test and "x_test" in blob else None
+    resize, rrc = int(getattr(args, "resize", 0)), bool(getattr(args, "random_resized_crop", False))
+    out_size = (resize, resize) if resize > 0 else None          # --resize: both splits come out at the model's size
+    train = kdata.GpuDataset.from_arrays(blob, args.data_npz, "train", device, pad=args.crop_padding if augment else 0, flip=augment,
+                                         out_size=out_size, crop="rrc" if rrc else "pad",
+                                         rrc_scale=tuple(getattr(args, "rrc_scale", (0.08, 1.0))),
+                                         rrc_ratio=tuple(getattr(args, "rrc_ratio", (3.0 / 4.0, 4.0 / 3.0))))
+    test = kdata.GpuDataset.from_arrays(blob, args.data_npz, "test", device, out_size=out_size) if want_test and "x_test" in blob else None
     return train, test
 
 
@@ -268,7 +288,8 @@ def main(args, batches=None, init_state=None):
     train_set = test_set = None
     if batches is None and getattr(args, "data_npz", None):
         train_set, test_set = npz_datasets(args, device, want_test=rank == 0)     # before the model: the geometry may come from the file
-    chw = (args.in_chans, args.image_size, args.image_size)
+    size = int(getattr(args, "resize", 0)) or args.image_size       # --resize S: --image-size stays the file's, the model sees S x S
+    chw = (args.in_chans, size, size)
     model = VisionTransformer(chw, n_patches=args.n_patches, n_blocks=args.n_blocks, d_hidden=args.d_hidden,
                               n_heads=args.n_heads, out_d=args.out_d, type=args.model_type)
     set_base_activation(model, args.model_type, getattr(args, "base_activation", "silu"))
@@ -506,7 +527,20 @@ def parse(argv=None):
                         '--image-size and --in-chans follow the file when left at their defaults')
     p.add_argument('--no-augment', action='store_true', help='with --data-npz: normalise only (no random crop, no flip)')
     p.add_argument('--crop-padding', type=int, default=4,
-                   help="with --data-npz: zero padding of the random crop, the reference's RandomCrop(32, padding=4)")
+                   help="with --data-npz: zero padding of the random crop, the reference's RandomCrop(32, padding=4); unused with "
+                        "--random-resized-crop")
+    p.add_argument('--resize', type=int, default=0, metavar='S',
+                   help='with --data-npz: resize every batch to S x S inside the batch kernel (bilinear, half-pixel centres, no '
+                        'antialiasing: meant for upsampling and mild downsampling; ops.resample_u8) and build the model at S x S; the '
+                        'test split is resized too.  --image-size keeps its meaning, the size of the stored images.  0 (default): off')
+    p.add_argument('--random-resized-crop', action='store_true',
+                   help="with --data-npz: torchvision's RandomResizedCrop in place of the padded random crop (--crop-padding is then "
+                        'unused; the flip stays), from a per-epoch table that is a function of (seed, epoch) alone (kanvit/data.py: '
+                        'crop_table); the output size is --resize S, else the stored size')
+    p.add_argument('--rrc-scale', type=float, nargs=2, default=(0.08, 1.0), metavar=('LO', 'HI'),
+                   help='--random-resized-crop: the range of the box area as a fraction of the image')
+    p.add_argument('--rrc-ratio', type=float, nargs=2, default=(3.0 / 4.0, 4.0 / 3.0), metavar=('LO', 'HI'),
+                   help='--random-resized-crop: the range of the box aspect ratio (log-uniform)')
     p.add_argument('--mixup', type=float, default=0.0, metavar='ALPHA',
                    help='with --data-npz: Mixup -- blend every sample with a partner, lam ~ Beta(ALPHA, ALPHA), inside the batch kernel '
                         '(kanvit/data.py: mix_table, ops.mix_u8); the loss becomes the fused soft-target cross-entropy and the train '
