@@ -18,6 +18,9 @@
 // weight gradients (contraction over the 32 rows).  dW1, dW2^T, db1, db2 accumulate in registers over the tiles a
 // work-group walks, go to one partial per work-group and are summed in fixed order by ff_small_reduce_kernel
 // (deterministic; no atomics).
+// Every per-row result (y, s, mean, rstd, dx / ds) depends on the row and on its position in the 32-row tile alone, not on the
+// work-group or the step of the walk that computes the tile; only the parameter-gradient sums change their order with the grid
+// (tests/test_ff_walk_gpu.py holds the first bitwise, and both bit for bit against float64 on integer data).
 #include "../../include/kanvit.h"
 #include "kanvit_common.h"
 
@@ -58,6 +61,17 @@ __device__ __forceinline__ void ff_load_row(float (&r)[N], const float* p) {
         r[4 * i + 2] = v[2];
         r[4 * i + 3] = v[3];
     }
+}
+
+// sum of v[0..N) as a balanced tree, N a power of two (v is overwritten): log2 N roundings on any path instead of N - 1
+template <int N>
+__device__ __forceinline__ float ff_tree_sum(float (&v)[N]) {
+    static_assert(N > 0 && (N & (N - 1)) == 0, "balanced tree");
+#pragma unroll
+    for (int w = N / 2; w > 0; w >>= 1)
+#pragma unroll
+        for (int i = 0; i < w; ++i) v[i] += v[i + w];
+    return v[0];
 }
 
 __device__ __forceinline__ f32x16 ff_zero16() {
@@ -105,14 +119,18 @@ __global__ __launch_bounds__(64 * NW) void ff_small_fwd_kernel(const FfArgs a) {
                     *reinterpret_cast<f32x4*>(a.s + mr * D + hf * DH + 4 * i) = v;
                 }
             }
-            float sum = 0.0f;
+            // Row sums as a pairwise tree (ff_tree_sum), not one running sum: a row that holds one repeated value c only ever
+            // doubles, so its mean is c exactly, its variance 0 and LN(s) = beta.  A running sum is off by up to ~8 ulp of c
+            // there, and rstd = 1 / sqrt(eps) = 316 turns that into 4e-4 of the LayerNorm output.
+            float tr[DH];
 #pragma unroll
-            for (int i = 0; i < DH; ++i) sum += xr[i];
+            for (int i = 0; i < DH; ++i) tr[i] = xr[i];
+            float sum = ff_tree_sum<DH>(tr);
             sum += __shfl_xor(sum, 32);
             const float mu = sum * (1.0f / D);
-            float sq = 0.0f;
 #pragma unroll
-            for (int i = 0; i < DH; ++i) sq += (xr[i] - mu) * (xr[i] - mu);       // two-pass: no E[x^2] - E[x]^2 cancellation
+            for (int i = 0; i < DH; ++i) tr[i] = (xr[i] - mu) * (xr[i] - mu);       // two-pass: no E[x^2] - E[x]^2 cancellation
+            float sq = ff_tree_sum<DH>(tr);
             sq += __shfl_xor(sq, 32);
             const float rs = rsqrtf(sq * (1.0f / D) + a.eps);
             if (owner && hf == 0) {

@@ -1,7 +1,14 @@
 """The fused small-geometry feed-forward (csrc/ff_small.hip) against the float64 statement of the
 reference's block feed-forward, model.py:25-29,36: nn.Sequential(Linear(d, 4d), ReLU(inplace), Linear(4d, d)) -- forward,
 dx and all four parameter gradients, ragged row counts (tiles of 32 rows with a partial last tile), determinism, and that the
-TransformerBlock really takes this route at d = 64.  Tolerance 1e-4 normwise (BASELINE.json), observed ~1e-6."""
+TransformerBlock really takes this route at d = 64.  Tolerance 1e-4 normwise (BASELINE.json), observed ~1e-6.
+
+What is NOT here: the plain variant walks its tiles at 16384 and 40001 rows, the LayerNorm variant (at most 200 tiles) never does,
+KANVIT_FF_GRID is not set, and every input is randn under a normwise bound.  tests/test_ff_walk_gpu.py has the rest: both variants
+past the forward cap (1024 work-groups) and the backward cap (256, or KANVIT_FF_GRID = 1 / 7 / 64) on integer-lattice data where the
+result equals float64 bit for bit (ReLU ties at +0 / -0 included), the LayerNorm variant at 32805 and 65536 rows, bitwise row
+independence of a walked launch, the fused LayerNorm's edges (constant rows, eps, a large mean, gamma <= 0), the workspace contract
+and the refusals; kanvit_split3_bf16 bitwise.  tests/_ff_ref.py holds the float64 closed forms, tests/test_ff_ref_cpu.py checks them."""
 import pytest
 import torch
 
