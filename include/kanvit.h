@@ -615,6 +615,54 @@ size_t kanvit_metrics_auc_pairs_workspace(int64_t n, int C);
 int kanvit_metrics_auc_pairs(const float* probs_t, const int32_t* labels, int64_t n, int C, int64_t cap, int64_t* counts, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ---- fused AdamW step: global-norm clipping, schedule table, weight EMA (kanvit/optim.py; csrc/augment.hip) ---------------
+ * Multi-tensor launches over fp32 tensors: up to KANVIT_OPTIM_MAX_TENSORS (the host query returns it) per call, passed BY VALUE in
+ * the kernel arguments -- no device-side pointer table, and the pointers a HIP-graph capture records are the tensors' own.  A
+ * work-group takes one chunk of KANVIT_OPTIM_CHUNK elements of one tensor.  The arrays params / grads / offsets / numel / decay are
+ * HOST arrays of n entries; a tensor with numel = 0 may have null pointers and gets no work-group; n = 0 launches nothing.
+ *
+ * Sum of squares: the partials of tensor i's chunks follow those of tensor i - 1 in `workspace` (float64, one per chunk;
+ * kanvit_optim_sumsq_workspace(n, numel) bytes, a pure host function, 0 for arguments the call refuses).  A chunk's partial is the
+ * float64 sum of the float64 squares (exact products): thread t of 256 adds elements 4 (256 r + t) + k in the order r = 0..3,
+ * k = 0..3, then part[t] += part[t + o] for o = 128, 64, .., 1.  No atomics: the same bits on every run, whatever the alignment.
+ * Several calls fill one workspace side by side (the caller advances the pointer).
+ *
+ * Begin: one work-group.  S = the float64 sum of partials[0 .. n_partials) (thread t adds t, t + 256, .. in order, then the same
+ * tree); norm_coef[0] = (float)sqrt(S); norm_coef[1] = (float)min(1, max_norm / (sqrt(S) + 1e-6)) evaluated in float64 and rounded
+ * once -- torch's clip_grad_norm_ rule -- or 1 when max_norm <= 0 (no clipping); step[0] += 1 (int64).  partials = NULL with
+ * n_partials = 0 and max_norm <= 0: the norm is not taken and norm_coef[0] = NaN.  A non-finite norm is not special-cased: a NaN
+ * sum gives a NaN coefficient, as torch's clamp does.
+ *
+ * Update: with t = step[0] (already counted by the begin call) and row = table[min(t, table_rows) - 1] of the [table_rows][4]
+ * float table (1 - lr_t wd, lr_t / (1 - b1^t), sqrt(1 - b2^t), 1 - d^t), every element runs this sequence, each operation one
+ * fp32 rounding, none contracted into an fma, denormals kept, division and square root correctly rounded:
+ *   g   = fmul(g, coef)                                  (norm_coef != NULL only; coef = norm_coef[1])
+ *   p   = fmul(p, row[0])                                (has_wd != 0 and decay[i] != 0 only)
+ *   m   = fadd(fmul(b1, m), fmul(ob1, g))
+ *   v   = fadd(fmul(b2, v), fmul(fmul(ob2, g), g))
+ *   den = fadd(fdiv(fsqrt(v), row[2]), eps)           (fsqrt: the correctly rounded square root, sqrtf -- not HIP's __fsqrt_rn)
+ *   p   = fsub(p, fmul(row[1], fdiv(m, den)))
+ *   e   = fadd(fmul(d, e), fmul(od, p))                  (ema != NULL only)
+ * so a float32 restatement on the host gives the same bits.  m / v / e of tensor i are exp_avg / exp_avg_sq / ema + offsets[i]:
+ * offsets are multiples of 4 elements and the three buffers 16-byte aligned, state_numel elements long.  p and g need 4-byte
+ * alignment only; a tensor whose p and g are both 16-byte aligned moves as 16-byte accesses, any other as 4-byte ones, with
+ * identical results.  row[3] debiases the EMA on read (weights = e / row[3]); the kernel does not use it.
+ *
+ * None of the calls synchronises with the host; all are capturable.  KANVIT_EINVAL (named in kanvit_last_error, checked before any
+ * launch) for n outside 0..KANVIT_OPTIM_MAX_TENSORS, a null array or pointer, a negative numel, a pointer off its alignment, a
+ * state slice outside the buffers or off a multiple of 4, a short workspace, table_rows < 1, a NaN max_norm, max_norm > 0 without
+ * partials.  Additive: the ABI version stays 7. */
+#define KANVIT_OPTIM_MAX_TENSORS 80
+#define KANVIT_OPTIM_CHUNK 4096
+int kanvit_optim_max_tensors(void);
+size_t kanvit_optim_sumsq_workspace(int n, const int64_t* numel);
+int kanvit_optim_sumsq(int n, const void* const* grads, const int64_t* numel, void* workspace, size_t workspace_bytes, void* stream);
+int kanvit_optim_begin(const void* partials, int64_t n_partials, double max_norm, int64_t* step, float* norm_coef, void* stream);
+int kanvit_optim_adamw(int n, void* const* params, const void* const* grads, const int64_t* offsets, const int64_t* numel,
+                       const int32_t* decay, float* exp_avg, float* exp_avg_sq, float* ema, int64_t state_numel, const float* table,
+                       int64_t table_rows, const int64_t* step, const float* norm_coef, int has_wd, float b1, float ob1, float b2, float ob2,
+                       float eps, float d, float od, void* stream);
+
 /* ---- per-family named entry points (SURVEY.md section 8b naming) ----------------------------
  * kanvit_<family>_{fwd,bwd_input,bwd_weight} are kanvit_layer_* with d->family checked;
  * kanvit_<family>_qkv_* additionally require groups == 3 * x_group_mod (one launch for all

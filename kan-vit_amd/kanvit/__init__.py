@@ -2,7 +2,7 @@
 
 `ops` holds the autograd wrappers, `grouped` the helpers that launch one fused kernel for a
 single KAN layer or for all heads' q|k|v mappings at once, `dp` the data-parallel gradient
-reducer.  Importing this package does not load the shared library; the first op does, and
-fails loudly if it is missing.
+reducer, `optim` the fused AdamW step (clipping, schedule table, weight EMA).  Importing this
+package does not load the shared library; the first op does, and fails loudly if it is missing.
 """
 from ._lib import KanvitError  # noqa: F401

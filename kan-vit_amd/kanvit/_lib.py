@@ -135,7 +135,13 @@ SYMBOLS = {
     "kanvit_metrics_update": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int64, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
     "kanvit_metrics_auc_pairs_workspace": (C.c_size_t, [C.c_int64, C.c_int]),
     "kanvit_metrics_auc_pairs": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "kanvit_optim_max_tensors": (C.c_int, []),
+    "kanvit_optim_sumsq_workspace": (C.c_size_t, [C.c_int, _P]),
+    "kanvit_optim_sumsq": (C.c_int, [C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "kanvit_optim_begin": (C.c_int, [_P, C.c_int64, C.c_double, _P, _P, _P]),
+    "kanvit_optim_adamw": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int] + [C.c_float] * 7 + [_P]),
 }
+OPTIM_CHUNK = 4096      # KANVIT_OPTIM_CHUNK: the elements one work-group of the optimizer kernels takes
 for _f in FAMILY_NAMES:
     SYMBOLS[f"kanvit_{_f}_fwd"] = (C.c_int, _LAYER_FWD)
     SYMBOLS[f"kanvit_{_f}_bwd_input"] = (C.c_int, _LAYER_BWD_IN)

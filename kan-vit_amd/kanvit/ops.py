@@ -1338,3 +1338,111 @@ def metrics_auc_pairs(probs_t: torch.Tensor, labels: torch.Tensor, n: int, count
     _launch(L.kanvit_metrics_auc_pairs, "kanvit_metrics_auc_pairs", probs_t.device, _ptr(probs_t), _ptr(labels), n, Cn, cap, _ptr(counts),
             query=(L.kanvit_metrics_auc_pairs_workspace, n, Cn), tag="metrics_auc", cost=(0, 4 * n * Cn))
     return counts
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# fused AdamW step: global-norm clipping, schedule table, weight EMA (kanvit/optim.py; csrc/augment.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _require_optim_tensor(who: str, name: str, t: torch.Tensor, device=None):
+    if not t.is_cuda:
+        raise KanvitError(f"{who}: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+    if device is not None and t.device != device:
+        raise KanvitError(f"{who}: {name} is on {t.device}, expected {device}")
+    if t.dtype != torch.float32:
+        raise KanvitError(f"{who}: {name} has dtype {t.dtype}; the optimizer kernels compute in float32")
+    if not t.is_contiguous():
+        raise KanvitError(f"{who}: {name} with shape {tuple(t.shape)} and strides {tuple(t.stride())} is not contiguous")
+
+
+def _optim_ptrs(tensors):
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def optim_max_tensors() -> int:
+    """Tensors one optimizer launch takes in its kernel arguments (KANVIT_OPTIM_MAX_TENSORS)."""
+    return int(_lib.lib().kanvit_optim_max_tensors())
+
+
+def optim_grad_sumsq(grads, partials: torch.Tensor) -> int:
+    """The float64 partial sums of squares of the float32 tensors `grads` into partials (float64, one entry per chunk of
+    _lib.OPTIM_CHUNK elements, tensor after tensor; semantics: include/kanvit.h): ceil(len(grads) / optim_max_tensors()) launches, no
+    atomics, no host synchronisation.  Returns the number of partials written; optim_begin adds them up."""
+    who = "optim_grad_sumsq"
+    if not partials.is_cuda:
+        raise KanvitError(f"{who}: partials is on {partials.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+    _require_metrics_buffer(who, "partials", partials, torch.float64, (partials.numel(),), partials.device)
+    grads = list(grads)
+    for k, g in enumerate(grads):
+        _require_optim_tensor(who, f"grads[{k}]", g, partials.device)
+    L, done, cap = _lib.lib(), 0, optim_max_tensors()
+    for lo in range(0, len(grads), cap):
+        part = grads[lo:lo + cap]
+        numel = (C.c_int64 * len(part))(*[g.numel() for g in part])
+        need = int(L.kanvit_optim_sumsq_workspace(len(part), numel)) // 8
+        if done + need > partials.numel():
+            raise KanvitError(f"{who}: partials holds {partials.numel()} entries, {done + need} needed so far")
+        if need:
+            _launch(L.kanvit_optim_sumsq, "kanvit_optim_sumsq", partials.device, len(part), _optim_ptrs(part), numel,
+                    C.c_void_p(partials.data_ptr() + 8 * done), C.c_size_t(8 * need), tag="optim_sumsq", cost=(0, 4 * sum(g.numel() for g in part)))
+        done += need
+    return done
+
+
+def optim_begin(partials: Optional[torch.Tensor], n_partials: int, max_norm: float, step: torch.Tensor, norm_coef: torch.Tensor) -> None:
+    """Open an optimizer step in one one-work-group launch (include/kanvit.h): norm_coef (float32 [2]) = (global gradient norm from the
+    first n_partials of optim_grad_sumsq's partials, clip coefficient min(1, max_norm / (norm + 1e-6)) evaluated in float64; max_norm
+    <= 0: no clipping, the coefficient is 1), and step (int64 [1]) += 1.  partials = None: the norm is not taken (NaN)."""
+    who = "optim_begin"
+    if not step.is_cuda:
+        raise KanvitError(f"{who}: step is on {step.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+    _require_metrics_buffer(who, "step", step, torch.int64, (1,), step.device)
+    _require_metrics_buffer(who, "norm_coef", norm_coef, torch.float32, (2,), step.device)
+    if partials is not None:
+        _require_metrics_buffer(who, "partials", partials, torch.float64, (partials.numel(),), step.device)
+        if not 0 <= int(n_partials) <= partials.numel():
+            raise KanvitError(f"{who}: n_partials = {n_partials} of {partials.numel()} entries")
+    elif n_partials:
+        raise KanvitError(f"{who}: n_partials = {n_partials} without partials")
+    _launch(_lib.lib().kanvit_optim_begin, "kanvit_optim_begin", step.device, _ptr(partials), int(n_partials), C.c_double(float(max_norm)),
+            _ptr(step), _ptr(norm_coef), tag="optim_begin")
+
+
+def optim_adamw(params, grads, offsets, decay, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, ema: Optional[torch.Tensor],
+                table: torch.Tensor, step: torch.Tensor, norm_coef: Optional[torch.Tensor], has_wd: bool, consts) -> None:
+    """The fused AdamW update of the float32 tensors `params` from `grads` (include/kanvit.h states the fp32 sequence): tensor k's
+    moments are exp_avg / exp_avg_sq [offsets[k] : offsets[k] + numel], its weight EMA the same slice of `ema` (None: no EMA), it is
+    decayed where decay[k] and has_wd; the step's coefficients are row min(step, T) - 1 of table (float32 [T, 4]); norm_coef (float32
+    [2], from optim_begin) scales the gradients by its clip coefficient, None: no clipping.  consts = (b1, 1 - b1, b2, 1 - b2, eps, d,
+    1 - d), each already rounded to float32.  ceil(len(params) / optim_max_tensors()) launches; no host synchronisation."""
+    who = "optim_adamw"
+    params, grads = list(params), list(grads)
+    if not (len(params) == len(grads) == len(offsets) == len(decay)):
+        raise KanvitError(f"{who}: {len(params)} params, {len(grads)} grads, {len(offsets)} offsets, {len(decay)} decay flags")
+    if not exp_avg.is_cuda:
+        raise KanvitError(f"{who}: exp_avg is on {exp_avg.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+    dev, S = exp_avg.device, exp_avg.numel()
+    for name, t in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("ema", ema)):
+        if t is not None:
+            _require_metrics_buffer(who, name, t, torch.float32, (S,), dev)
+    if table.dim() != 2 or table.shape[1] != 4 or table.shape[0] < 1:
+        raise KanvitError(f"{who}: table has shape {tuple(table.shape)}, expected [T, 4]")
+    _require_metrics_buffer(who, "table", table, torch.float32, tuple(table.shape), dev)
+    _require_metrics_buffer(who, "step", step, torch.int64, (1,), dev)
+    if norm_coef is not None:
+        _require_metrics_buffer(who, "norm_coef", norm_coef, torch.float32, (2,), dev)
+    for k, (p, g) in enumerate(zip(params, grads)):
+        _require_optim_tensor(who, f"params[{k}]", p, dev)
+        _require_optim_tensor(who, f"grads[{k}]", g, dev)
+        if g.numel() != p.numel():
+            raise KanvitError(f"{who}: grads[{k}] has {g.numel()} elements, params[{k}] {p.numel()}")
+    if len(consts) != 7:
+        raise KanvitError(f"{who}: consts = (b1, 1 - b1, b2, 1 - b2, eps, d, 1 - d)")
+    L, cap = _lib.lib(), optim_max_tensors()
+    for lo in range(0, len(params), cap):
+        ps, gs = params[lo:lo + cap], grads[lo:lo + cap]
+        n = len(ps)
+        moved = sum(p.numel() for p in ps)
+        _launch(L.kanvit_optim_adamw, "kanvit_optim_adamw", dev, n, _optim_ptrs(ps), _optim_ptrs(gs), (C.c_int64 * n)(*offsets[lo:lo + cap]),
+                (C.c_int64 * n)(*[p.numel() for p in ps]), (C.c_int32 * n)(*[int(bool(f)) for f in decay[lo:lo + cap]]), _ptr(exp_avg),
+                _ptr(exp_avg_sq), _ptr(ema), S, _ptr(table), int(table.shape[0]), _ptr(step), _ptr(norm_coef), int(bool(has_wd)),
+                *[C.c_float(float(c)) for c in consts], tag="optim_adamw", cost=(0, moved * (36 if ema is not None else 28)))

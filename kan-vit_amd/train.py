@@ -25,12 +25,15 @@ batch kernel, from a per-epoch table that is a function of (seed, epoch) alone: 
 ops.soft_cross_entropy), --resize S / --random-resized-crop / --rrc-scale / --rrc-ratio (the batch kernel resamples: every batch
 comes out at S x S, bilinear, from the stored images -- `--data-npz cifar100.npz --resize 224 --n-patches 14` trains the ViT-B/16
 geometry on 32 x 32 images -- and RandomResizedCrop boxes come from a per-epoch table, a function of (seed, epoch) alone:
-kanvit/data.py crop_table, ops.resample_u8; --image-size stays the size of the stored images).
+kanvit/data.py crop_table, ops.resample_u8; --image-size stays the size of the stored images), --optimizer kanvit-adamw with --weight-decay /
+--clip-grad-norm / --warmup-steps / --lr-schedule / --min-lr / --ema-decay (AdamW with global-norm clipping, a schedule table and a weight
+EMA in the project's own fused step, kanvit/optim.py; the default --optimizer adam is the reference's step).
 
 `main(args, batches=None, init_state=None)` also serves the parity tests: `batches` (a list of (x, y) tensors) replaces
 the data stream, `init_state` (a reference-layout state dict) replaces the random initialisation, and the returned dict
 carries the per-step loss trajectory."""
 import argparse
+import contextlib
 import logging
 import os
 import time
@@ -96,6 +99,29 @@ def check_data_args(args):
         lo, hi = (float(v) for v in getattr(args, name, default))
         if not 0 < lo <= hi or hi == float("inf"):
             raise SystemExit(f"{flag} {lo} {hi}: LO and HI are positive and LO is not above HI")
+
+
+RECIPE_FLAGS = (("--weight-decay", "weight_decay", 0.0), ("--clip-grad-norm", "clip_grad_norm", 0.0), ("--warmup-steps", "warmup_steps", 0),
+                ("--lr-schedule", "lr_schedule", "constant"), ("--min-lr", "min_lr", 0.0), ("--ema-decay", "ema_decay", 0.0))
+
+
+def check_optimizer_args(args):
+    """Contradictions among the optimizer flags; parse() and main() both call it.  The recipe flags belong to --optimizer kanvit-adamw:
+    given without it they are refused, not ignored."""
+    fused = getattr(args, "optimizer", "adam") == "kanvit-adamw"
+    given = [flag for flag, name, default in RECIPE_FLAGS if getattr(args, name, default) != default]
+    if given and not fused:
+        raise SystemExit(f"{' / '.join(given)}: the recipe flags are implemented by --optimizer kanvit-adamw; the default Adam has none of them")
+    if not fused:
+        return
+    if getattr(args, "grid_extend", None):
+        raise SystemExit("--grid-extend is not combined with --optimizer kanvit-adamw: its flat moment buffers cannot take the "
+                         "parameters of a new shape that an extension creates")
+    for flag, name, default in RECIPE_FLAGS:
+        if name != "lr_schedule" and float(getattr(args, name, default)) < 0:
+            raise SystemExit(f"{flag} {getattr(args, name)} is negative")
+    if not float(getattr(args, "ema_decay", 0.0)) < 1.0:
+        raise SystemExit(f"--ema-decay {args.ema_decay} must be in [0, 1)")
 
 
 def mix_config(args):
@@ -236,6 +262,7 @@ def extend_grid_and_swap(model, optimizer, x, grid_size):
 def main(args, batches=None, init_state=None):
     rank, world, local = 0, 1, 0
     check_data_args(args)
+    check_optimizer_args(args)
     grid_extend = getattr(args, "grid_extend", None) or {}
     if grid_extend:
         from model import split_types
@@ -313,8 +340,28 @@ def main(args, batches=None, init_state=None):
     if not args.no_tuned_gemms:
         from kanvit import tuned
         tuned.enable_tuned_gemms()          # recorded kernel selections for the stock FF GEMMs (no run-time tuning)
-    # fused=True: same update rule as the reference's Adam, one multi-tensor kernel per parameter chunk instead of ~8 per step
-    optimizer = Adam(model.parameters(), lr=args.learning_rate, fused=True, capturable=bool(args.graph))
+    recipe = getattr(args, "optimizer", "adam") == "kanvit-adamw"
+    ema_decay = float(getattr(args, "ema_decay", 0.0)) if recipe else 0.0
+    if not recipe:
+        # fused=True: same update rule as the reference's Adam, one multi-tensor kernel per parameter chunk instead of ~8 per step
+        optimizer = Adam(model.parameters(), lr=args.learning_rate, fused=True, capturable=bool(args.graph))
+    else:
+        # --optimizer kanvit-adamw: clipping, decay, schedule and weight EMA in the project's own step (kanvit/optim.py); the schedule
+        # spans the run, epochs x batches per epoch, and a step past it keeps the last row
+        from kanvit.optim import KanvitAdamW
+        if batches is not None:
+            per_epoch = len(batches)
+        elif train_set is not None:
+            per_epoch = train_set.n_batches(args.batch_size // world if args.dp else args.batch_size, world)
+        elif args.synthetic:
+            per_epoch = args.steps_per_epoch
+        else:
+            per_epoch = -(-50000 // args.batch_size)            # CIFAR-100's train split, as cifar_loaders serves it
+        total = max(args.epochs * per_epoch, 1)
+        optimizer = KanvitAdamW(model.parameters(), lr=args.learning_rate, weight_decay=float(getattr(args, "weight_decay", 0.0)),
+                                max_grad_norm=float(getattr(args, "clip_grad_norm", 0.0)) or None, ema_decay=ema_decay, total_steps=total,
+                                warmup_steps=min(int(getattr(args, "warmup_steps", 0)), total),
+                                schedule=getattr(args, "lr_schedule", "constant"), min_lr=float(getattr(args, "min_lr", 0.0)))
     reducer = kdp.GradReducer(model.parameters()) if world > 1 else None
     metrics_file = setup_logging(args.log_dir) if rank == 0 else None
     logging.info(f"Using device: {device} ({torch.cuda.get_device_name(device)}), world {world}, amp {args.amp}, "
@@ -438,9 +485,13 @@ def main(args, batches=None, init_state=None):
                     save_metrics(metrics_file, epoch + 1, "Train", train_loss, acc, bal, f1, auc, flag=0)
                     history["metrics_file"] = metrics_file
 
+    if recipe:
+        history["grad_norm"] = float(optimizer.grad_norm)       # the last step's global norm (NaN without --clip-grad-norm: not taken)
     if test_loader is not None and rank == 0:
         model.eval()
-        with torch.no_grad():
+        if recipe:
+            history["ema_eval"] = ema_decay > 0                 # --ema-decay: the test pass runs on the averaged weights
+        with torch.no_grad(), (optimizer.ema_weights(model) if ema_decay > 0 else contextlib.nullcontext()):
             tl, ys, preds, probs = [], [], [], []
             test_metrics = None
             if bool(getattr(args, "device_metrics", False)):
@@ -557,8 +608,26 @@ def parse(argv=None):
     p.add_argument('--fused-loss', action='store_true',
                    help='the fused cross-entropy kernel (ops.soft_cross_entropy: loss and gradient in one launch) also for the plain '
                         'training loss; opt-in, the default stays torch.nn.CrossEntropyLoss')
+    p.add_argument('--optimizer', choices=['adam', 'kanvit-adamw'], default='adam',
+                   help="adam (default): the reference's torch Adam at a constant learning rate.  kanvit-adamw: AdamW in the project's own "
+                        'fused step (kanvit/optim.py) -- global-norm clipping, decoupled weight decay, warm-up / cosine schedule from a '
+                        'device table and a weight EMA in one pass over the parameters; the flags below belong to it and are refused '
+                        'without it; not with --grid-extend')
+    p.add_argument('--weight-decay', type=float, default=0.0,
+                   help='kanvit-adamw: decoupled weight decay of the weight matrices; biases, LayerNorm parameters, the class token and other '
+                        'tensors that are vectors up to leading dimensions of size 1 are not decayed')
+    p.add_argument('--clip-grad-norm', type=float, default=0.0, metavar='MAX',
+                   help="kanvit-adamw: clip the global gradient norm to MAX (clip_grad_norm_'s rule); 0 (default): off")
+    p.add_argument('--warmup-steps', type=int, default=0, help='kanvit-adamw: linear warm-up of the learning rate over this many steps')
+    p.add_argument('--lr-schedule', choices=['constant', 'cosine'], default='constant',
+                   help='kanvit-adamw: after the warm-up, a constant rate or cosine decay to --min-lr at the last step of the run')
+    p.add_argument('--min-lr', type=float, default=0.0, help='kanvit-adamw: where --lr-schedule cosine ends')
+    p.add_argument('--ema-decay', type=float, default=0.0, metavar='D',
+                   help='kanvit-adamw: keep an exponential moving average of the weights (decay D, debiased) and run the test pass on it; '
+                        '0 (default): off')
     args = p.parse_args(argv)
     check_data_args(args)
+    check_optimizer_args(args)
     return args
 
 
