@@ -469,6 +469,38 @@ int kanvit_addln_bwd_ex(int64_t M, int D, const float* xsum, const float* gamma,
                         const void* dy, int dy_bf16, const float* dres, float* dx, void* dx_bf16, float* dgamma, float* dbeta, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- stochastic depth (DropPath): a per-sample scale of the branch inside the residual add + LayerNorm pass -----------------
+ * The reference model has no regulariser (model.py:31-37 adds every branch as it is); the DeiT recipe drops each residual branch per
+ * sample with a rate that grows with the depth.  Stock PyTorch spends a bernoulli_, a divide, a broadcast multiply over [B, N, D] and
+ * that multiply's backward per branch; here the scale rides in the pass that adds the branch anyway.
+ *
+ * kanvit_depth_scales: the keep decisions of all n_branch <= KANVIT_DEPTH_MAX_BRANCHES branches of one forward, ONE launch of ONE
+ * work-group.  keep[n_branch] is a HOST array of fp32 keep probabilities in (0, 1]; they, their reciprocals inv_j = float32(1) /
+ * float32(keep_j) (divided on the host) and the thresholds T_j = round(keep_j * 2^24) (to nearest, ties to even) travel by value in the
+ * kernel argument, so a captured graph bakes them in and nothing is uploaded.  With mix() the splitmix64 step stated at
+ * kanvit_augment_u8 and c the value of *counter when the kernel starts,
+ *   h = mix(mix(mix(seed) + c) + ((uint64)j << 32) + b),      scales[j][b] = (h >> 40) < T_j ? inv_j : 0.0f,
+ * scales being [n_branch][B] fp32 on the device.  keep = 1 gives T = 2^24: always kept, scale exactly 1.0.  Every thread reads
+ * *counter, the work-group synchronises, then one thread stores c + 1: consecutive launches (and replays of a captured launch) walk
+ * c, c + 1, ... with no RNG state and nothing from the host.  counter is a device uint64, 8-byte aligned.  KANVIT_EINVAL (named in
+ * kanvit_last_error, before the device is touched) for n_branch outside 1..64, B < 0, a keep outside (0, 1] or a null pointer.
+ *
+ * kanvit_addln_sd_fwd / _bwd: kanvit_addln_fwd_ex / _bwd_ex with  s = x + row_scale[r / rows_per_sample] * delta  for row r -- the
+ * product and the sum are two fp32 roundings, never contracted (bit for bit torch's x + scale * delta in fp32; a bf16 delta is widened
+ * first); y, mean, rstd as before.  Backward: dx as before; the gradient of delta is its own tensor now, ddelta = row_scale[.] * dx,
+ * written by the same pass -- fp32 [M][D], or bf16 rounded to nearest even when ddelta_bf16 != 0; it may not be dx.  dgamma / dbeta and
+ * the workspace are those of kanvit_addln_bwd (kanvit_addln_bwd_workspace).  delta and row_scale (fp32 [M / rows_per_sample], on the
+ * device) are required; KANVIT_EINVAL unless rows_per_sample >= 1 divides M, besides the width and alignment conditions above.
+ * Additive: the ABI version stays 7. */
+#define KANVIT_DEPTH_MAX_BRANCHES 64
+int kanvit_depth_scales(int64_t B, int n_branch, const float* keep, uint64_t seed, uint64_t* counter, float* scales, void* stream);
+int kanvit_addln_sd_fwd(int64_t M, int D, float eps, const float* x, const void* delta, int delta_bf16, const float* gamma, const float* beta,
+                        float* xsum, void* y, int y_bf16, float* mean, float* rstd, const float* row_scale, int64_t rows_per_sample,
+                        void* stream);
+int kanvit_addln_sd_bwd(int64_t M, int D, const float* xsum, const float* gamma, const float* mean, const float* rstd,
+                        const void* dy, int dy_bf16, const float* dres, float* dx, void* ddelta, int ddelta_bf16, float* dgamma, float* dbeta,
+                        const float* row_scale, int64_t rows_per_sample, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- ReLU backward + bias gradient of the feed-forward's first Linear in one pass ----------------
  * The TransformerBlock's nn.Sequential(Linear, ReLU(inplace), Linear) (model.py:25-29): what autograd runs for the ReLU and
  * for the first Linear's bias -- threshold_backward on the saved activation y, then a column sum of the result --

@@ -5,6 +5,9 @@
 //   backward:  dx = LayerNorm backward of dy w.r.t. s  (+ dres, the gradient arriving on the residual stream);
 //              dgamma = sum_rows dy * xhat,  dbeta = sum_rows dy
 //
+// Stochastic depth (kanvit_addln_sd_*, the SD flag of the two kernels): s = x + row_scale[sample] * delta in the same forward pass, and
+// the backward pass writes the branch's gradient row_scale[sample] * dx beside dx; kanvit_depth_scales draws the scales (further down).
+//
 // HBM-bound row kernels: one wave per row, D <= 1024 columns held in registers (float4 per lane, lane + 64 v), two-pass
 // variance in registers (no E[x^2] - E[x]^2 cancellation), wave reductions by DPP/shuffle.  The backward keeps per-lane
 // partial sums of dgamma / dbeta over all rows a wave processes; the waves of a work-group meet in LDS and write ONE
@@ -13,6 +16,7 @@
 #include "../../include/kanvit.h"
 #include "kanvit_common.h"
 
+#include <cmath>
 #include <type_traits>
 
 namespace {
@@ -45,6 +49,32 @@ struct LnArgs {
     float eps;
 };
 
+// per-sample branch scale (the *_sd kernels; stochastic depth): an argument struct of their own, LnArgs stays what it was
+struct LnSdArgs : LnArgs {
+    const float* row_scale;       // [M / rps]: row r takes row_scale[r / rps]
+    float* dd;                    // gradient of delta, scale * dx: fp32 ...
+    unsigned short* dd_bf16;      // ... or rounded to bf16 (a bf16 delta); exactly one of the two is set
+    long long rps;                // rows per sample
+    long long step_q, step_r;     // the rows a wave advances per iteration, gridDim.x * LN_WAVES = step_q * rps + step_r
+};
+
+// The sample a wave's row belongs to, carried along the row walk: one division per wave instead of one per row
+struct LnSample {
+    long long b = 0, rem = 0;
+    __device__ __forceinline__ void start(const LnSdArgs& a, long long r0) {
+        b = r0 / a.rps;
+        rem = r0 - b * a.rps;
+    }
+    __device__ __forceinline__ void next(const LnSdArgs& a) {
+        b += a.step_q;
+        rem += a.step_r;
+        if (rem >= a.rps) {
+            rem -= a.rps;
+            ++b;
+        }
+    }
+};
+
 // bf16 tensors at the boundary (torch.autocast: the feed-forward's output / input / input gradient are bf16): 4 values = 8 bytes
 typedef unsigned short ln_u16x4 __attribute__((ext_vector_type(4)));
 template <bool BF>
@@ -62,9 +92,25 @@ __device__ __forceinline__ ln_u16x4 ln_to_bf16(const f32x4& v) {               /
     const ln_bf16x4 b = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
     return __builtin_bit_cast(ln_u16x4, b);
 }
+// x + sc * d as two fp32 roundings, never contracted into an fma: what torch's `x + sc * d` computes (include/kanvit.h)
+__device__ __forceinline__ f32x4 ln_scaled_add(const f32x4& x, float sc, const f32x4& d) {
+#pragma clang fp contract(off)
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = __fadd_rn(x[e], __fmul_rn(sc, d[e]));
+    return o;
+}
+__device__ __forceinline__ f32x4 ln_scaled(float sc, const f32x4& d) {
+#pragma clang fp contract(off)
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = __fmul_rn(sc, d[e]);
+    return o;
+}
 
-template <int NV, bool DB = false, bool YB = false>      // DB: delta is bf16; YB: y is written as bf16
-__global__ __launch_bounds__(64 * LN_WAVES) void addln_fwd_kernel(const LnArgs a) {
+// DB: delta is bf16; YB: y is written as bf16; SD: s = x + row_scale[sample] * delta (delta is then never NULL)
+template <int NV, bool DB = false, bool YB = false, bool SD = false>
+__global__ __launch_bounds__(64 * LN_WAVES) void addln_fwd_kernel(const std::conditional_t<SD, LnSdArgs, LnArgs> a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long wid = (long long)blockIdx.x * LN_WAVES + wave, nw = (long long)gridDim.x * LN_WAVES;
     const int D = a.D;
@@ -78,16 +124,24 @@ __global__ __launch_bounds__(64 * LN_WAVES) void addln_fwd_kernel(const LnArgs a
         g[v] = ok[v] ? *reinterpret_cast<const f32x4*>(a.gamma + c) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         bt[v] = ok[v] ? *reinterpret_cast<const f32x4*>(a.beta + c) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
+    LnSample smp;
+    if constexpr (SD) smp.start(a, wid);
     for (long long r = wid; r < a.M; r += nw) {
         f32x4 s[NV];
         float sum = 0.0f;
+        float sc = 1.0f;
+        if constexpr (SD) {
+            sc = a.row_scale[smp.b];
+            smp.next(a);
+        }
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
             const int c = 4 * (lane + 64 * v);
             f32x4 t = {0.0f, 0.0f, 0.0f, 0.0f};
             if (ok[v]) {
                 t = *reinterpret_cast<const f32x4*>(a.x + r * D + c);
-                if (a.delta) t += ln_ld4<DB>(a.delta, r * D + c);
+                if constexpr (SD) t = ln_scaled_add(t, sc, ln_ld4<DB>(a.delta, r * D + c));
+                else if (a.delta) t += ln_ld4<DB>(a.delta, r * D + c);
                 if (a.xsum) *reinterpret_cast<f32x4*>(a.xsum + r * D + c) = t;
             }
             s[v] = t;
@@ -123,8 +177,9 @@ __global__ __launch_bounds__(64 * LN_WAVES) void addln_fwd_kernel(const LnArgs a
     }
 }
 
-template <int NV, bool GB = false>      // GB: dy is bf16
-__global__ __launch_bounds__(64 * LN_WAVES) void addln_bwd_kernel(const LnArgs a) {
+// GB: dy is bf16; SD: also writes the gradient of delta, row_scale[sample] * dx, to its own buffer (fp32 or bf16)
+template <int NV, bool GB = false, bool SD = false>
+__global__ __launch_bounds__(64 * LN_WAVES) void addln_bwd_kernel(const std::conditional_t<SD, LnSdArgs, LnArgs> a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long wid = (long long)blockIdx.x * LN_WAVES + wave, nw = (long long)gridDim.x * LN_WAVES;
     const int D = a.D;
@@ -139,8 +194,15 @@ __global__ __launch_bounds__(64 * LN_WAVES) void addln_bwd_kernel(const LnArgs a
         dg[v] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         db[v] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
+    LnSample smp;
+    if constexpr (SD) smp.start(a, wid);
     for (long long r = wid; r < a.M; r += nw) {
         const float mu = a.mean[r], rs = a.rstd[r];
+        float sc = 1.0f;
+        if constexpr (SD) {
+            sc = a.row_scale[smp.b];
+            smp.next(a);
+        }
         f32x4 xh[NV], gy[NV];
         float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
@@ -172,7 +234,13 @@ __global__ __launch_bounds__(64 * LN_WAVES) void addln_bwd_kernel(const LnArgs a
                 for (int e = 0; e < 4; ++e) o[e] = rs * (gy[v][e] - m1 - xh[v][e] * m2);
                 if (a.dres) o += *reinterpret_cast<const f32x4*>(a.dres + r * D + c);
                 *reinterpret_cast<f32x4*>(a.dx + r * D + c) = o;
-                if (a.dx_bf16) *reinterpret_cast<ln_u16x4*>(a.dx_bf16 + r * D + c) = ln_to_bf16(o);
+                if constexpr (SD) {
+                    const f32x4 dd = ln_scaled(sc, o);
+                    if (a.dd_bf16) *reinterpret_cast<ln_u16x4*>(a.dd_bf16 + r * D + c) = ln_to_bf16(dd);
+                    else *reinterpret_cast<f32x4*>(a.dd + r * D + c) = dd;
+                } else {
+                    if (a.dx_bf16) *reinterpret_cast<ln_u16x4*>(a.dx_bf16 + r * D + c) = ln_to_bf16(o);
+                }
             }
         }
     }
@@ -398,6 +466,59 @@ int ln_check(const char* who, long long M, int D) {
     return 0;
 }
 
+// ---- stochastic depth: the per-sample keep decisions of every residual branch of one forward, in one launch --------------------------
+// scales[j][b] = h(seed, counter, j, b) >> 40 < thr[j] ? inv[j] : 0 with the splitmix64 hash the batch kernels use (include/kanvit.h
+// states it): no RNG state, nothing read from the host per step.  The probabilities travel by value in the kernel argument (a captured
+// graph bakes them in); the only state is the device counter, which the ONE work-group reads, then bumps: every thread holds the old
+// value in a register before thread 0 stores the new one.
+constexpr int SD_THREADS = 256;
+
+__host__ __device__ __forceinline__ unsigned long long sd_mix(unsigned long long z) {     // one splitmix64 step
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+struct DepthArgs {
+    float inv[KANVIT_DEPTH_MAX_BRANCHES];         // float32(1) / float32(keep), divided on the host
+    unsigned thr[KANVIT_DEPTH_MAX_BRANCHES];      // round(keep * 2^24): kept iff the hash's top 24 bits are below it
+    unsigned long long seed_mixed;                // mix(seed)
+    unsigned long long* counter;
+    float* scales;                                // [n_branch][B]
+    long long B;
+    int n_branch;
+};
+
+__global__ __launch_bounds__(SD_THREADS) void depth_scales_kernel(const DepthArgs a) {
+    const unsigned long long c = *a.counter;
+    __syncthreads();
+    if (threadIdx.x == 0) *a.counter = c + 1ull;
+    const unsigned long long base = sd_mix(a.seed_mixed + c);
+    for (int j = 0; j < a.n_branch; ++j) {
+        const float inv = a.inv[j];
+        const unsigned thr = a.thr[j];
+        const unsigned long long bj = base + ((unsigned long long)j << 32);
+        for (long long b = threadIdx.x; b < a.B; b += SD_THREADS) {
+            const unsigned long long h = sd_mix(bj + (unsigned long long)b);
+            a.scales[(long long)j * a.B + b] = (unsigned)(h >> 40) < thr ? inv : 0.0f;
+        }
+    }
+}
+
+int ln_sd_check(const char* who, long long M, long long rps) {
+    if (rps < 1 || M % rps != 0) return kv_fail(KANVIT_EINVAL, "%s: rows_per_sample=%lld must be >= 1 and divide M=%lld", who, rps, M);
+    return 0;
+}
+
+void ln_sd_fill(LnSdArgs& a, const float* row_scale, long long rps, int grid) {
+    const long long nw = (long long)grid * LN_WAVES;
+    a.row_scale = row_scale;
+    a.rps = rps;
+    a.step_q = nw / rps;
+    a.step_r = nw % rps;
+}
+
 template <typename F>
 int ln_dispatch(int D, F&& f) {
     const int nv = (D + 255) / 256;
@@ -484,6 +605,99 @@ int kanvit_addln_bwd_ex(int64_t M, int D, const float* xsum, const float* gamma,
     if (rc) return rc;
     hipLaunchKernelGGL(addln_reduce_kernel, dim3((2 * D + 31) / 32), dim3(256), 0, st, (const float*)workspace, dgamma, dbeta, D, grid);
     KV_LAUNCH_CHECK("addln_reduce_kernel");
+    return 0;
+}
+
+int kanvit_addln_sd_fwd(int64_t M, int D, float eps, const float* x, const void* delta, int delta_bf16, const float* gamma, const float* beta,
+                        float* xsum, void* y, int y_bf16, float* mean, float* rstd, const float* row_scale, int64_t rows_per_sample,
+                        void* stream) {
+    if (int rc = ln_check("kanvit_addln_sd_fwd", M, D)) return rc;
+    if (int rc = ln_sd_check("kanvit_addln_sd_fwd", M, rows_per_sample)) return rc;
+    if (M == 0) return 0;
+    if (!x || !delta || !row_scale || !gamma || !beta || !y || !mean || !rstd)
+        return kv_fail(KANVIT_EINVAL, "kanvit_addln_sd_fwd: null argument (delta and row_scale are required)");
+    if ((((uintptr_t)x | (uintptr_t)delta | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)xsum | (uintptr_t)y) & 15) || ((uintptr_t)row_scale & 3))
+        return kv_fail(KANVIT_EINVAL, "kanvit_addln_sd_fwd: pointers must be 16-byte aligned (row_scale: 4)");
+    LnSdArgs a{};
+    a.x = x; a.delta = (const float*)delta; a.gamma = gamma; a.beta = beta; a.xsum = xsum; a.y = (float*)y; a.mean = mean; a.rstd = rstd;
+    a.M = M; a.D = D; a.eps = eps;
+    const int wgs = ln_grid(M);
+    ln_sd_fill(a, row_scale, rows_per_sample, wgs);
+    hipStream_t st = (hipStream_t)stream;
+    const bool db = delta_bf16 != 0, yb = y_bf16 != 0;
+    return ln_dispatch(D, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        const dim3 grid(wgs), block(64 * LN_WAVES);
+        if (db && yb) hipLaunchKernelGGL((addln_fwd_kernel<NV, true, true, true>), grid, block, 0, st, a);
+        else if (db) hipLaunchKernelGGL((addln_fwd_kernel<NV, true, false, true>), grid, block, 0, st, a);
+        else if (yb) hipLaunchKernelGGL((addln_fwd_kernel<NV, false, true, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((addln_fwd_kernel<NV, false, false, true>), grid, block, 0, st, a);
+        KV_LAUNCH_CHECK("addln_fwd_kernel (scaled)");
+        return 0;
+    });
+}
+
+int kanvit_addln_sd_bwd(int64_t M, int D, const float* xsum, const float* gamma, const float* mean, const float* rstd,
+                        const void* dy, int dy_bf16, const float* dres, float* dx, void* ddelta, int ddelta_bf16, float* dgamma, float* dbeta,
+                        const float* row_scale, int64_t rows_per_sample, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = ln_check("kanvit_addln_sd_bwd", M, D)) return rc;
+    if (int rc = ln_sd_check("kanvit_addln_sd_bwd", M, rows_per_sample)) return rc;
+    if (!dgamma || !dbeta) return kv_fail(KANVIT_EINVAL, "kanvit_addln_sd_bwd: null dgamma/dbeta");
+    hipStream_t st = (hipStream_t)stream;
+    if (M == 0) {
+        KV_HIP_CHECK(hipMemsetAsync(dgamma, 0, sizeof(float) * D, st));
+        KV_HIP_CHECK(hipMemsetAsync(dbeta, 0, sizeof(float) * D, st));
+        return 0;
+    }
+    if (!xsum || !gamma || !mean || !rstd || !dy || !dx || !ddelta || !row_scale)
+        return kv_fail(KANVIT_EINVAL, "kanvit_addln_sd_bwd: null argument (ddelta and row_scale are required)");
+    if ((void*)dx == ddelta) return kv_fail(KANVIT_EINVAL, "kanvit_addln_sd_bwd: dx and ddelta must be two buffers");
+    if ((((uintptr_t)xsum | (uintptr_t)gamma | (uintptr_t)dy | (uintptr_t)dres | (uintptr_t)dx | (uintptr_t)workspace | (uintptr_t)ddelta) & 15) ||
+        ((uintptr_t)row_scale & 3))
+        return kv_fail(KANVIT_EINVAL, "kanvit_addln_sd_bwd: pointers must be 16-byte aligned (row_scale: 4)");
+    const size_t need = kanvit_addln_bwd_workspace(M, D);
+    if (!workspace || workspace_bytes < need)
+        return kv_fail(KANVIT_ENOMEM, "kanvit_addln_sd_bwd: workspace %zu bytes < required %zu", workspace_bytes, need);
+    LnSdArgs a{};
+    a.x = xsum; a.gamma = gamma; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd);
+    a.dy = (const float*)dy; a.dres = dres; a.dx = dx; a.part = (float*)workspace; a.M = M; a.D = D;
+    if (ddelta_bf16) a.dd_bf16 = (unsigned short*)ddelta;
+    else a.dd = (float*)ddelta;
+    const int grid = ln_grid(M);
+    ln_sd_fill(a, row_scale, rows_per_sample, grid);
+    int rc = ln_dispatch(D, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        if (dy_bf16) hipLaunchKernelGGL((addln_bwd_kernel<NV, true, true>), dim3(grid), dim3(64 * LN_WAVES), sizeof(float) * LN_WAVES * 2 * D, st, a);
+        else hipLaunchKernelGGL((addln_bwd_kernel<NV, false, true>), dim3(grid), dim3(64 * LN_WAVES), sizeof(float) * LN_WAVES * 2 * D, st, a);
+        KV_LAUNCH_CHECK("addln_bwd_kernel (scaled)");
+        return 0;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(addln_reduce_kernel, dim3((2 * D + 31) / 32), dim3(256), 0, st, (const float*)workspace, dgamma, dbeta, D, grid);
+    KV_LAUNCH_CHECK("addln_reduce_kernel");
+    return 0;
+}
+
+int kanvit_depth_scales(int64_t B, int n_branch, const float* keep, uint64_t seed, uint64_t* counter, float* scales, void* stream) {
+    if (n_branch < 1 || n_branch > KANVIT_DEPTH_MAX_BRANCHES)
+        return kv_fail(KANVIT_EINVAL, "kanvit_depth_scales: n_branch=%d: one launch takes 1..%d branches", n_branch, KANVIT_DEPTH_MAX_BRANCHES);
+    if (B < 0) return kv_fail(KANVIT_EINVAL, "kanvit_depth_scales: B=%lld is negative", (long long)B);
+    if (!keep || !counter || (B > 0 && !scales)) return kv_fail(KANVIT_EINVAL, "kanvit_depth_scales: null keep/counter/scales");
+    if (((uintptr_t)counter & 7) || ((uintptr_t)scales & 3)) return kv_fail(KANVIT_EINVAL, "kanvit_depth_scales: counter/scales is not aligned to its element size");
+    DepthArgs a = {};
+    for (int j = 0; j < n_branch; ++j) {
+        const float k = keep[j];
+        if (!(k > 0.0f && k <= 1.0f)) return kv_fail(KANVIT_EINVAL, "kanvit_depth_scales: keep[%d]=%g is outside (0, 1]", j, (double)k);
+        a.inv[j] = 1.0f / k;
+        a.thr[j] = (unsigned)llrint((double)k * 16777216.0);
+    }
+    a.seed_mixed = sd_mix(seed);
+    a.counter = (unsigned long long*)counter;
+    a.scales = scales;
+    a.B = B;
+    a.n_branch = n_branch;
+    hipLaunchKernelGGL(depth_scales_kernel, dim3(1), dim3(SD_THREADS), 0, (hipStream_t)stream, a);
+    KV_LAUNCH_CHECK("depth_scales_kernel");
     return 0;
 }
 

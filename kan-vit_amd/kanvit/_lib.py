@@ -121,6 +121,9 @@ SYMBOLS = {
     "kanvit_addln_bwd_ex": (C.c_int, [C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_addln_bwd_workspace": (C.c_size_t, [C.c_int64, C.c_int]),
     "kanvit_addln_bwd": (C.c_int, [C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "kanvit_depth_scales": (C.c_int, [C.c_int64, C.c_int, _P, C.c_uint64, _P, _P, _P]),
+    "kanvit_addln_sd_fwd": (C.c_int, [C.c_int64, C.c_int, C.c_float, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int64, _P]),
+    "kanvit_addln_sd_bwd": (C.c_int, [C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_size_t, _P]),
     "kanvit_relu_bwd_bias_workspace": (C.c_size_t, [C.c_int64, C.c_int]),
     "kanvit_relu_bwd_bias": (C.c_int, [C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_relu_bwd_bias_bf16": (C.c_int, [C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
@@ -142,6 +145,7 @@ SYMBOLS = {
     "kanvit_optim_adamw": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int] + [C.c_float] * 7 + [_P]),
 }
 OPTIM_CHUNK = 4096      # KANVIT_OPTIM_CHUNK: the elements one work-group of the optimizer kernels takes
+DEPTH_MAX_BRANCHES = 64      # KANVIT_DEPTH_MAX_BRANCHES: the residual branches one kanvit_depth_scales launch draws for
 for _f in FAMILY_NAMES:
     SYMBOLS[f"kanvit_{_f}_fwd"] = (C.c_int, _LAYER_FWD)
     SYMBOLS[f"kanvit_{_f}_bwd_input"] = (C.c_int, _LAYER_BWD_IN)

@@ -1041,15 +1041,125 @@ class _AddLayerNormFn(torch.autograd.Function):
         return dx, dd, dg, db, None, None
 
 
-def add_layernorm(x: torch.Tensor, delta: Optional[torch.Tensor], norm: torch.nn.LayerNorm, y_bf16: bool = False):
+class _AddLayerNormScaledFn(torch.autograd.Function):
+    """(x, delta, row_scale[B], gamma, beta) -> (s = x + row_scale[sample] * delta, LayerNorm(s)): _AddLayerNormFn with the per-sample
+    scale of stochastic depth inside the same pass (kanvit_addln_sd_*).  Rows r * N .. r * N + N - 1 belong to sample r.  The gradient
+    of delta, row_scale * dx, is a tensor of its own written by the backward pass (fp32, or bf16 for a bf16 delta); row_scale gets none."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, x, delta, row_scale, rows_per_sample, gamma, beta, eps, y_bf16):
+        if not x.is_cuda:
+            raise KanvitError(f"x is on {x.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+        _require_gpu_f32("row_scale", row_scale)
+        L = _lib.lib()
+        D = x.shape[-1]
+        x2 = x.float().contiguous().view(-1, D)
+        d2 = (delta if delta.dtype in (torch.float32, torch.bfloat16) else delta.float()).contiguous().view(-1, D)
+        M, N = x2.shape[0], int(rows_per_sample)
+        sc = row_scale.contiguous().view(-1)
+        if d2.shape != x2.shape or N < 1 or M % N or sc.numel() * N != M:
+            raise KanvitError(f"add_layernorm(row_scale): x has {M} rows, delta {tuple(delta.shape)}, {sc.numel()} scales x {N} rows per sample")
+        y = torch.empty(M, D, device=x.device, dtype=torch.bfloat16 if y_bf16 else torch.float32)
+        s = torch.empty_like(x2)
+        mean = torch.empty(M, device=x.device, dtype=torch.float32)
+        rstd = torch.empty(M, device=x.device, dtype=torch.float32)
+        g, b = gamma.float().contiguous(), beta.float().contiguous()
+        _launch(L.kanvit_addln_sd_fwd, "kanvit_addln_sd_fwd", x.device, M, D, float(eps), _ptr(x2), _ptr(d2), int(d2.dtype == torch.bfloat16),
+                _ptr(g), _ptr(b), _ptr(s), _ptr(y), int(bool(y_bf16)), _ptr(mean), _ptr(rstd), _ptr(sc), N)
+        ctx.save_for_backward(s, g, mean, rstd, sc)
+        ctx.delta_dtype = d2.dtype
+        ctx.n = N
+        ctx.shape = x.shape
+        return s.view(x.shape), y.view(x.shape)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, gs, gy):
+        s, g, mean, rstd, sc = ctx.saved_tensors
+        L = _lib.lib()
+        M, D = s.shape
+        if gy is None:
+            gy2 = torch.zeros_like(s)
+        else:
+            gy2 = gy.contiguous().view(M, D)
+            if gy2.dtype != torch.bfloat16:
+                gy2 = gy2.float()
+        gs2 = None if gs is None else gs.contiguous().view(M, D).float()
+        dx = torch.empty_like(s)
+        dd = torch.empty(M, D, device=s.device, dtype=ctx.delta_dtype)
+        dg = torch.empty(D, device=s.device, dtype=torch.float32)
+        db = torch.empty(D, device=s.device, dtype=torch.float32)
+        _launch(L.kanvit_addln_sd_bwd, "kanvit_addln_sd_bwd", s.device, M, D, _ptr(s), _ptr(g), _ptr(mean), _ptr(rstd), _ptr(gy2),
+                int(gy2.dtype == torch.bfloat16), _ptr(gs2), _ptr(dx), _ptr(dd), int(dd.dtype == torch.bfloat16), _ptr(dg), _ptr(db),
+                _ptr(sc), ctx.n, query=(L.kanvit_addln_bwd_workspace, M, D))
+        return dx.view(ctx.shape), dd.view(ctx.shape), None, None, dg, db, None, None
+
+
+def add_layernorm(x: torch.Tensor, delta: Optional[torch.Tensor], norm: torch.nn.LayerNorm, y_bf16: bool = False,
+                  row_scale: Optional[torch.Tensor] = None, rows_per_sample: Optional[int] = None):
     """(x + delta, norm(x + delta)) -- delta None gives (x, norm(x)).  Shapes the kernel does not cover (last dim not a
     multiple of 4 or > 1024, non-affine norms) take the stock ops; like every kanvit op it needs CUDA tensors.
-    y_bf16: write norm(...) as bfloat16 (the caller feeds it to bf16 GEMMs under autocast: no cast pass in between)."""
+    y_bf16: write norm(...) as bfloat16 (the caller feeds it to bf16 GEMMs under autocast: no cast pass in between).
+    row_scale (float32 [B], stochastic depth: depth_scales): s = x + row_scale[sample] * delta in the same pass, sample = row //
+    rows_per_sample; x is [B, N, d] (rows_per_sample = N) or 2-D with rows_per_sample given.  None is the unscaled path."""
     D = x.shape[-1]
+    if row_scale is not None:
+        if delta is None:
+            raise ValueError("add_layernorm: row_scale scales delta, and delta is None")
+        if x.dim() == 3 and rows_per_sample in (None, x.shape[1]):
+            rows_per_sample = x.shape[1]
+        elif x.dim() != 2 or rows_per_sample is None:
+            raise ValueError(f"add_layernorm(row_scale): x is [B, N, d], or 2-D with rows_per_sample; got {tuple(x.shape)}, rows_per_sample={rows_per_sample}")
     if norm.weight is None or norm.bias is None or len(norm.normalized_shape) != 1 or D % 4 or D > 1024 or D < 4:
+        if row_scale is not None:
+            delta = (row_scale.repeat_interleave(int(rows_per_sample)).view(*x.shape[:-1], 1) * delta).to(delta.dtype)
         s = x if delta is None else x + delta
         return s, norm(s)
+    if row_scale is not None:
+        return _AddLayerNormScaledFn.apply(x, delta, row_scale, int(rows_per_sample), norm.weight, norm.bias, norm.eps, bool(y_bf16))
     return _AddLayerNormFn.apply(x, delta, norm.weight, norm.bias, norm.eps, bool(y_bf16))
+
+
+def depth_scales(B: int, keep, seed: int, counter: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The stochastic-depth scales of one forward: float32 [n_branch, B], entry (j, b) = 1 / keep[j] if sample b keeps branch j, else 0
+    (kanvit_depth_scales; the hash and the threshold are stated in include/kanvit.h, depth_keep below restates them on the CPU).
+    keep: a sequence of n_branch <= 64 probabilities in (0, 1] -- host values, baked into the launch; seed: any integer (taken mod
+    2^64); counter: a one-element int64 tensor on the device, read and then incremented by the launch, so consecutive calls -- and
+    replays of a captured call -- draw different masks without RNG state and without anything from the host.  One launch, capturable."""
+    keep = [float(k) for k in keep]
+    n = len(keep)
+    if not torch.is_tensor(counter) or not counter.is_cuda or counter.dtype != torch.int64 or counter.numel() != 1:
+        raise KanvitError("depth_scales: counter is a one-element int64 tensor on the GPU")
+    B = int(B)
+    if out is None:
+        out = torch.empty(n, max(B, 0), device=counter.device, dtype=torch.float32)
+    elif not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (n, B) or not out.is_contiguous():
+        raise KanvitError(f"depth_scales: out is a contiguous float32 [{n}, {B}] tensor on the GPU")
+    host = (C.c_float * max(n, 1))(*keep)
+    _launch(_lib.lib().kanvit_depth_scales, "kanvit_depth_scales", counter.device, B, n, C.cast(host, C.c_void_p),
+            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(counter), _ptr(out))
+    return out
+
+
+def depth_keep(B: int, keep, seed: int, counter: int) -> torch.Tensor:
+    """depth_scales restated in Python integers and NumPy float32 on the CPU (the tests compare the kernel with it bit for bit):
+    h = mix(mix(mix(seed) + counter) + (j << 32) + b); kept iff (h >> 40) < round(keep_j * 2^24); scale float32(1) / float32(keep_j)."""
+    import numpy as np
+    from .data import _mix
+    m64 = 0xFFFFFFFFFFFFFFFF
+    base = _mix((_mix(int(seed) & m64) + int(counter)) & m64)
+    out = np.zeros((len(keep), int(B)), dtype=np.float32)
+    for j, k in enumerate(keep):
+        k32 = np.float32(k)
+        if not 0.0 < float(k32) <= 1.0:
+            raise ValueError(f"depth_keep: keep[{j}]={k} is outside (0, 1]")
+        thr = int(np.rint(np.float64(k32) * 16777216.0))
+        inv = np.float32(1.0) / k32
+        for b in range(int(B)):
+            if (_mix((base + (j << 32) + b) & m64) >> 40) < thr:
+                out[j, b] = inv
+    return torch.from_numpy(out)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -39,28 +39,37 @@ class TransformerBlock(nn.Module):
         (MSA.attention_map of norm1(x))."""
         return self.attn.attention_map(self.norm1(x), rows)
 
-    def run(self, x, pending, reg=None):
+    def run(self, x, pending, reg=None, drop=None):
         """The block with its residual adds fused into the LayerNorms (kanvit.ops.add_layernorm: one pass instead of an
         add kernel + a LayerNorm kernel forward, one pass instead of three + an add backward).  `pending` is the previous
         block's feed-forward output that has not been added to the stream yet (None for the first block); returns
         (stream after the attention add, this block's feed-forward output) -- same arithmetic as model.py:31-37:
             x = x + MSA(LN1(x));  x = x + FF(LN2(x)).
         reg (a dict of MSA.regularization_loss keywords, or None): also return, as a third value, the sample-based KAN
-        regulariser of the per-head q|k|v layers on the rows they read, LN1(x) -- the tensor this forward already holds."""
-        x, h1 = add_layernorm(x, pending, self.norm1)
+        regulariser of the per-head q|k|v layers on the rows they read, LN1(x) -- the tensor this forward already holds.
+        drop (stochastic depth, VisionTransformer.set_drop_path; None = off): (the [B] scale row of the branch `pending` is -- the
+        previous block's feed-forward -- or None, the [B] scale row of this block's attention branch).  Each fused add takes the row
+        of the branch it adds; the returned feed-forward output is unscaled, like `pending`."""
+        if drop is None:
+            x, h1 = add_layernorm(x, pending, self.norm1)
+        else:
+            x, h1 = add_layernorm(x, pending, self.norm1, row_scale=None if pending is None else drop[0])
         if reg is not None:
-            return self._rest(x, h1) + (self.attn.regularization_loss(h1, **reg),)
-        return self._rest(x, h1)
+            return self._rest(x, h1, drop) + (self.attn.regularization_loss(h1, **reg),)
+        return self._rest(x, h1, drop)
 
-    def _rest(self, x, h1):
-        if x.dim() == 3 and ff_small_supported(self.ff[0].in_features, self.ff[0].out_features):
+    def _rest(self, x, h1, drop=None):
+        if drop is None and x.dim() == 3 and ff_small_supported(self.ff[0].in_features, self.ff[0].out_features):
             # small geometries: residual add + LN2 + feed-forward in one launch (SURVEY 8(f)1); ln_feed_forward itself falls
             # back to add_layernorm + feed_forward for inputs the fused kernel refuses (dtype, autocast, row count)
             return ln_feed_forward(x, self.attn(h1), self.norm2, self.ff[0], self.ff[2])
         # under bf16 autocast the stock feed-forward GEMMs take bf16 operands: LN2 writes its output as bf16 directly, and the bf16
         # feed-forward output comes back into the next block's add_layernorm as it is (no cast passes in either direction)
         ybf = (x.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16 and ff_mode() != "bf16x3")
-        x, h2 = add_layernorm(x, self.attn(h1), self.norm2, y_bf16=ybf)
+        if drop is None:
+            x, h2 = add_layernorm(x, self.attn(h1), self.norm2, y_bf16=ybf)
+        else:             # also the small geometries: the one-launch LN2 + feed-forward has no scaled form (DESIGN 4.23)
+            x, h2 = add_layernorm(x, self.attn(h1), self.norm2, y_bf16=ybf, row_scale=drop[1])
         # Same three ops as self.ff (Linear -> ReLU(inplace) -> Linear, model.py:25-29), applied to the 2-D
         # (B*N, d) tensor: nn.Linear on 3-D input returns a VIEW, and an in-place ReLU on a view makes autograd
         # insert CopySlices (two full [B*N, 4d] copies per block in backward: 12 ms/step at ViT-B, B=128).
@@ -70,17 +79,25 @@ class TransformerBlock(nn.Module):
         return x, feed_forward(h2.reshape(b * n, d), self.ff[0], self.ff[2]).view(b, n, d)   # bias + ReLU in the GEMM epilogue
 
 
-    def run_cls(self, x, pending):
+    def run_cls(self, x, pending, drop=None):
         """The class-token row [B, d] of x + MSA(LN1(x)) + FF(LN2(.)) after the pending add, i.e. forward(x + pending)[:, 0]:
         all the head of a ViT reads of its last block (model.py:166-169).  LN1 still runs on all rows (k and v need them); the
         q layers, the attention, the residual, LN2 and the feed-forward run on the B class rows only (MSA.forward_cls).  Under
         bf16 autocast the grouped q|k|v launch and the attention stay what they are in run() -- all rows, on the bf16 matrix
-        cores, the rounding points the bf16 results are specified with -- and LN2 + feed-forward take the class rows."""
-        x, h1 = add_layernorm(x, pending, self.norm1)
+        cores, the rounding points the bf16 results are specified with -- and LN2 + feed-forward take the class rows.
+        drop (stochastic depth; None = off): run()'s pair and, third, the scale row of this block's feed-forward branch.  The pending
+        add takes its row inside the fused pass; the two [B, d] class-row branches are scaled by a plain multiply."""
+        if drop is None:
+            x, h1 = add_layernorm(x, pending, self.norm1)
+        else:
+            x, h1 = add_layernorm(x, pending, self.norm1, row_scale=None if pending is None else drop[0])
         ybf = (x.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16)
         a0 = _FirstRow.apply(self.attn(h1)) if ybf else self.attn.forward_cls(h1)
+        if drop is not None:
+            a0 = a0 * drop[1].unsqueeze(1)
         s, h2 = add_layernorm(_FirstRow.apply(x), a0, self.norm2, y_bf16=ybf and ff_mode() != "bf16x3")
-        return s + feed_forward(h2, self.ff[0], self.ff[2])
+        f = feed_forward(h2, self.ff[0], self.ff[2])
+        return s + (f if drop is None else f * drop[2].unsqueeze(1))
 
 
 class _FirstRow(torch.autograd.Function):
@@ -178,6 +195,42 @@ class VisionTransformer(nn.Module):
                                                           attn_type=self.block_types[l]) for l in range(n_blocks)])
         self.mlp_head = nn.Sequential(nn.LayerNorm(d_hidden), nn.Linear(d_hidden, out_d))
         self._fused_embed = None       # None = not tried yet, else {bf16 autocast?: the fused patch-embedding kernel covers this model}
+        self._drop_path = None         # set_drop_path: None = off, else (keep probabilities of the 2 * n_blocks branches, seed)
+        self.drop_path_rates = []
+
+    def set_drop_path(self, rate, seed=0, schedule="linear"):
+        """Stochastic depth (DropPath, Huang et al. 2016, as the DeiT recipe uses it): in train() mode every residual branch of
+        block l is dropped per sample with probability rates[l] and scaled by 1 / (1 - rates[l]) otherwise; rates[l] = rate * l /
+        (L - 1) for schedule 'linear' (rate itself with L = 1), rate everywhere for 'constant'.  Set after construction, like a
+        base activation (the constructor stays the reference's, whose model has no such option); rate 0 removes it again, and
+        eval() ignores it.  The keep decisions come from one kanvit.ops.depth_scales launch per forward -- a hash of (seed, a
+        device call counter, branch, position in the batch), no RNG state -- and ride as per-sample scales in the fused residual
+        add + LayerNorm passes.  The counter is a non-persistent buffer: state_dict() is unchanged.  Returns the per-block rates."""
+        if schedule not in ("linear", "constant"):
+            raise ValueError(f"set_drop_path: schedule must be 'linear' or 'constant', got {schedule!r}")
+        rate = float(rate)
+        if not 0.0 <= rate < 1.0:
+            raise ValueError(f"set_drop_path: rate {rate} must be in [0, 1)")
+        if rate == 0.0:
+            self._drop_path = None
+            self.drop_path_rates = []
+            if "drop_path_counter" in self._buffers:
+                del self._buffers["drop_path_counter"]
+                self._non_persistent_buffers_set.discard("drop_path_counter")
+            return self.drop_path_rates
+        if not all(isinstance(blk, TransformerBlock) for blk in self.blocks):
+            raise NotImplementedError("set_drop_path: 'flash-attn' models stack bare FlashAttention modules (model.py:113-117), which "
+                                      "have no residual branches to drop")
+        n = len(self.blocks)
+        if 2 * n > _lib.DEPTH_MAX_BRANCHES:
+            raise NotImplementedError(f"set_drop_path: {n} blocks have {2 * n} branches; one depth_scales launch takes {_lib.DEPTH_MAX_BRANCHES}")
+        self.drop_path_rates = [rate if schedule == "constant" or n == 1 else rate * l / (n - 1) for l in range(n)]
+        self._drop_path = ([1.0 - r for r in self.drop_path_rates for _ in range(2)], int(seed))      # branch 2l: attention, 2l + 1: feed-forward
+        if "drop_path_counter" not in self._buffers:
+            self.register_buffer("drop_path_counter", torch.zeros(1, dtype=torch.int64, device=self.v_class.device), persistent=False)
+        else:
+            self.drop_path_counter.zero_()
+        return self.drop_path_rates
 
     def patchify(self, images, n_patches):
         """(B, C, H, W) -> (B, n_patches^2, C*ph*pw): patches row-major, each flattened in (C, ph, pw)
@@ -397,18 +450,26 @@ class VisionTransformer(nn.Module):
         last = self.blocks[-1] if len(self.blocks) else None
         cls_tail = (isinstance(last, TransformerBlock) and reg_kw is None and out.is_cuda and not _lib.py_switches()["no_cls_tail"]
                     and not ff_small_supported(last.ff[0].in_features, last.ff[0].out_features))
-        for blk in self.blocks:
+        # stochastic depth (set_drop_path), train() mode only: one launch draws every branch's per-sample scales, rows 2l (attention)
+        # and 2l + 1 (feed-forward) of block l; the add that takes a branch in takes its row
+        scales = None
+        if self._drop_path is not None and self.training:
+            scales = ops.depth_scales(out.shape[0], self._drop_path[0], self._drop_path[1], self.drop_path_counter)
+        for l, blk in enumerate(self.blocks):
+            drop = None if scales is None else (scales[2 * l - 1] if l else None, scales[2 * l], scales[2 * l + 1])
             if cls_tail and blk is last:
-                out = blk.run_cls(out, pending)
+                out = blk.run_cls(out, pending) if drop is None else blk.run_cls(out, pending, drop)
                 return self.mlp_head(out)
             if isinstance(blk, TransformerBlock) and reg_kw is not None:
-                out, pending, r = blk.run(out, pending, reg_kw)
+                out, pending, r = blk.run(out, pending, reg_kw) if drop is None else blk.run(out, pending, reg_kw, drop)
                 reg = reg + r
             elif isinstance(blk, TransformerBlock):
-                out, pending = blk.run(out, pending)
+                out, pending = blk.run(out, pending) if drop is None else blk.run(out, pending, drop=drop)
             else:                                     # 'flash-attn' models stack bare FlashAttention modules (model.py:113-117)
                 out = blk(out)
-        if pending is not None:
+        if pending is not None and scales is not None:    # the class rows of the stream and of the last, still pending branch
+            out = _FirstRow.apply(out) + _FirstRow.apply(pending) * scales[-1].unsqueeze(1)
+        elif pending is not None:
             out = _ClsToken.apply(out, pending)   # only the class token feeds the head (model.py:166-169)
         else:
             out = out[:, 0]

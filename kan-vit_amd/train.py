@@ -27,7 +27,9 @@ comes out at S x S, bilinear, from the stored images -- `--data-npz cifar100.npz
 geometry on 32 x 32 images -- and RandomResizedCrop boxes come from a per-epoch table, a function of (seed, epoch) alone:
 kanvit/data.py crop_table, ops.resample_u8; --image-size stays the size of the stored images), --optimizer kanvit-adamw with --weight-decay /
 --clip-grad-norm / --warmup-steps / --lr-schedule / --min-lr / --ema-decay (AdamW with global-norm clipping, a schedule table and a weight
-EMA in the project's own fused step, kanvit/optim.py; the default --optimizer adam is the reference's step).
+EMA in the project's own fused step, kanvit/optim.py; the default --optimizer adam is the reference's step), --drop-path RATE /
+--drop-path-schedule (stochastic depth as a per-sample scale inside the fused residual add + LayerNorm passes, masks from a hash of
+--seed and a device step counter: VisionTransformer.set_drop_path; the test pass runs without it).
 
 `main(args, batches=None, init_state=None)` also serves the parity tests: `batches` (a list of (x, y) tensors) replaces
 the data stream, `init_state` (a reference-layout state dict) replaces the random initialisation, and the returned dict
@@ -171,14 +173,16 @@ class _GraphedStep:
     microsecond kernels.  Batches are copied into static buffers; a batch of another shape (the last, short one) runs eagerly.
 
     Capturing needs lazily created state (optimizer moments, library workspaces) to exist, so one throw-away step runs on a
-    side stream first; parameters are then restored and the Adam moments / step counters zeroed, which is exactly the state
-    of a fresh optimizer -- the replayed trajectory equals the eager one."""
+    side stream first; parameters are then restored, the Adam moments / step counters zeroed, which is exactly the state
+    of a fresh optimizer, and the model's drop-path counter (--drop-path) put back -- the replayed trajectory equals the eager one."""
 
     def __init__(self, eager_step, model, optimizer, x, y, y2=None, w=None):
         self.eager = eager_step
         self.sx, self.sy = x.clone(), y.clone()
         self.pair = () if y2 is None else (y2.clone(), w.clone())      # Mixup / CutMix: static buffers like x and y
         saved = [p.detach().clone() for p in model.parameters()]
+        counter = getattr(model, "drop_path_counter", None)          # --drop-path: the throw-away step must not use up a mask
+        count = None if counter is None else counter.clone()
         side = torch.cuda.Stream(device=x.device)
         side.wait_stream(torch.cuda.current_stream(x.device))
         with torch.cuda.stream(side):
@@ -192,6 +196,8 @@ class _GraphedStep:
                 for v in st.values():
                     if torch.is_tensor(v):
                         v.zero_()
+            if counter is not None:
+                counter.copy_(count)
         optimizer.zero_grad(set_to_none=True)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
@@ -320,6 +326,18 @@ def main(args, batches=None, init_state=None):
     model = VisionTransformer(chw, n_patches=args.n_patches, n_blocks=args.n_blocks, d_hidden=args.d_hidden,
                               n_heads=args.n_heads, out_d=args.out_d, type=args.model_type)
     set_base_activation(model, args.model_type, getattr(args, "base_activation", "silu"))
+    drop_path = float(getattr(args, "drop_path", 0.0))
+    if not 0.0 <= drop_path < 1.0:
+        raise SystemExit(f"--drop-path {drop_path} must be in [0, 1)")
+    if drop_path > 0:
+        # --drop-path: the masks are a hash of (seed, step counter, branch, position in the rank's batch); under --dp the rank is mixed
+        # into the seed, or every rank would drop the same positions of its shard
+        from kanvit.data import _mix
+        try:
+            model.set_drop_path(drop_path, seed=args.seed if world == 1 else _mix(_mix(args.seed) + rank),
+                                schedule=getattr(args, "drop_path_schedule", "linear"))
+        except NotImplementedError as e:
+            raise SystemExit(f"--drop-path: {e}")
     if init_state is not None:
         model.load_state_dict(init_state)
     model = model.to(device)
@@ -625,7 +643,16 @@ def parse(argv=None):
     p.add_argument('--ema-decay', type=float, default=0.0, metavar='D',
                    help='kanvit-adamw: keep an exponential moving average of the weights (decay D, debiased) and run the test pass on it; '
                         '0 (default): off')
+    p.add_argument('--drop-path', type=float, default=0.0, metavar='RATE',
+                   help='stochastic depth (DropPath): in training, drop every residual branch per sample with a probability that grows '
+                        'to RATE at the last block and scale the kept ones by 1 / (1 - p), inside the fused residual add + LayerNorm '
+                        'passes (VisionTransformer.set_drop_path; masks from a hash of --seed and a device step counter, so --graph '
+                        "works); not for 'flash-attn'; the test pass runs without it.  0 (default): off")
+    p.add_argument('--drop-path-schedule', choices=['linear', 'constant'], default='linear',
+                   help='--drop-path: the rate of block l of L is RATE * l / (L - 1) (linear, the DeiT / timm rule) or RATE in every block')
     args = p.parse_args(argv)
+    if not 0.0 <= args.drop_path < 1.0:
+        raise SystemExit(f"--drop-path {args.drop_path} must be in [0, 1)")
     check_data_args(args)
     check_optimizer_args(args)
     return args
