@@ -523,7 +523,7 @@ int kanvit_relu_bwd_bias_bf16(int64_t M, int N, const void* dy_bf16, const void*
 int kanvit_split3_bf16(int64_t M, int K, const float* x, const float* bias, int relu, const void* mask_hi, int64_t mask_ld,
                        void* out, int pattern, void* stream);
 
-/* ---- batches from a GPU-resident uint8 dataset (kanvit/data.py; csrc/augment.hip) ---------------------------------------
+/* ---- batches from a GPU-resident uint8 dataset (kanvit/data.py; csrc/batch_u8.hip) --------------------------------------
  * The reference's input pipeline (train.py:100-118: RandomHorizontalFlip, RandomCrop(size, padding) on the zero-padded uint8 image,
  * ToTensor, Normalize) as one gather over a dataset that stays in HBM:
  *   out[b][c][y][x] = lut[c][ images[idx[b]][sy][sx][c] ],  sy = y + dy - pad_y,  sx = x + dx - pad_x,  sx <- W - 1 - sx if flipped;
@@ -547,7 +547,7 @@ int kanvit_augment_u8(const uint8_t* images, const int64_t* labels, const int64_
                       int32_t* params_out, int64_t N, int64_t B, int H, int W, int C, int pad_y, int pad_x, int flip, uint64_t seed,
                       uint64_t epoch, void* stream);
 
-/* ---- Mixup / CutMix on the same pass (kanvit/data.py: mix_table; csrc/augment.hip) ---------------------------------------
+/* ---- Mixup / CutMix on the same pass (kanvit/data.py: mix_table; csrc/batch_u8.hip) --------------------------------------
  * kanvit_augment_u8 with a second source.  Three tables indexed by the DATASET index s (not by the position in the batch):
  * partner [N] int64 (the sample mixed into s, or -1), weight [N] fp32 (the weight w of s's own label; 1 where partner is -1) and box
  * [N][4] int32 = (y0, y1, x0, x1), half open, in OUTPUT coordinates.  With s = idx[b], j = partner[s],
@@ -564,7 +564,7 @@ int kanvit_mix_u8(const uint8_t* images, const int64_t* labels, const int64_t* i
                   const float* weight, const int32_t* box, float* out, int64_t* y_out, int64_t* y2_out, float* w_out, int64_t N, int64_t B,
                   int H, int W, int C, int pad_y, int pad_x, int flip, uint64_t seed, uint64_t epoch, void* stream);
 
-/* ---- bilinear resize / RandomResizedCrop on the same pass (kanvit/data.py: crop_table; csrc/augment.hip) ------------------
+/* ---- bilinear resize / RandomResizedCrop on the same pass (kanvit/data.py: crop_table; csrc/batch_u8.hip) -----------------
  * kanvit_augment_u8 / kanvit_mix_u8 at an output size of their own: out [B][C][OH][OW] fp32 contiguous; images, labels, idx and
  * lut as kanvit_augment_u8's.  crop [N][5] int32, indexed by the DATASET index s = idx[b] (as the mix tables are), or NULL.  A row
  * (y0, x0, bh, bw, flip) is a box of bh x bw source pixels with its top-left corner at (y0, x0), in the coordinates of the possibly
@@ -599,7 +599,7 @@ int kanvit_resample_u8(const uint8_t* images, const int64_t* labels, const int64
                        const int64_t* partner, const float* weight, const int32_t* box, float* out, int64_t* y_out, int64_t* y2_out,
                        float* w_out, int64_t N, int64_t B, int H, int W, int C, int OH, int OW, void* stream);
 
-/* ---- soft-target cross-entropy, loss and gradient in one pass (ops.soft_cross_entropy; csrc/augment.hip) -----------------
+/* ---- soft-target cross-entropy, loss and gradient in one pass (ops.soft_cross_entropy; csrc/soft_ce.hip) -----------------
  * The training loss for Mixup / CutMix pairs and label smoothing.  logits [B][C] fp32, unit column stride, row stride ld >= C;
  * y1 [B] int64; y2 [B] int64 and w [B] fp32 together or both NULL (NULL: w = 1); eps in [0, 1).
  *   t_c    = (1 - eps) (w [c == y1] + (1 - w) [c == y2]) + eps / C
@@ -615,7 +615,7 @@ int kanvit_resample_u8(const uint8_t* images, const int64_t* labels, const int64
 int kanvit_soft_ce(const float* logits, int64_t ld, const int64_t* y1, const int64_t* y2, const float* w, int64_t B, int C, float eps,
                    float* loss_rows, float* dlogits, float* loss, void* stream);
 
-/* ---- epoch metrics on the device (kanvit/metrics.py; csrc/augment.hip) ---------------------------------------------------
+/* ---- epoch metrics on the device (kanvit/metrics.py; csrc/metrics.hip) ---------------------------------------------------
  * The reference appends labels, argmax and softmax of every step to host lists and runs scikit-learn on them per epoch
  * (train.py:42-44, utils.py:13-47).  Accuracy, balanced accuracy and weighted F1 are functions of the C x C confusion matrix; the
  * one-vs-rest ROC-AUC of class c is the Mann-Whitney statistic (2 gt_c + eq_c) / (2 P_c (N - P_c)) with
@@ -647,7 +647,7 @@ size_t kanvit_metrics_auc_pairs_workspace(int64_t n, int C);
 int kanvit_metrics_auc_pairs(const float* probs_t, const int32_t* labels, int64_t n, int C, int64_t cap, int64_t* counts, void* workspace,
                              size_t workspace_bytes, void* stream);
 
-/* ---- fused AdamW step: global-norm clipping, schedule table, weight EMA (kanvit/optim.py; csrc/augment.hip) ---------------
+/* ---- fused AdamW step: global-norm clipping, schedule table, weight EMA (kanvit/optim.py; csrc/optim.hip) -----------------
  * Multi-tensor launches over fp32 tensors: up to KANVIT_OPTIM_MAX_TENSORS (the host query returns it) per call, passed BY VALUE in
  * the kernel arguments -- no device-side pointer table, and the pointers a HIP-graph capture records are the tensors' own.  A
  * work-group takes one chunk of KANVIT_OPTIM_CHUNK elements of one tensor.  The arrays params / grads / offsets / numel / decay are

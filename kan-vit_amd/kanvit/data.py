@@ -1,7 +1,7 @@
 """Training and evaluation batches from a dataset that stays on the GPU as uint8.
 
 CIFAR-100's training set is 154 MB as uint8 and MNIST's 47 MB: they fit in HBM thousands of times over.  GpuDataset keeps the images
-(NHWC, as the arrays come) and the labels on the device and produces every batch with ONE kernel (ops.augment_u8, csrc/augment.hip):
+(NHWC, as the arrays come) and the labels on the device and produces every batch with ONE kernel (ops.augment_u8, csrc/batch_u8.hip):
 gather by index, random crop out of the zero-padded image, random horizontal flip, ToTensor and Normalize -- the reference's
 transforms (train.py:100-118) without its DataLoader workers, its PIL round trip, its host-to-device copy per batch, and without
 torchvision.  Per batch the device reads B*H*W*C bytes and writes 4*B*C*H*W.

@@ -1163,8 +1163,67 @@ def depth_keep(B: int, keep, seed: int, counter: int) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# batches from a GPU-resident uint8 dataset (kanvit/data.py; csrc/augment.hip)
+# the training loop's off-model kernels, from here to the end of the file: one operand check
 # ---------------------------------------------------------------------------------------------------------------------------
+def _require_tensor(who: str, name: str, t: torch.Tensor, dtype, shape=None, device=None, contiguous: bool = True, hint: str = ""):
+    """The one place the ops below test an operand: on a GPU (`device`: on that one; None: any), of `dtype` (one, or a tuple to choose
+    from; `hint` is added to that refusal), contiguous, and of `shape` where one is given."""
+    if not t.is_cuda:
+        raise KanvitError(f"{who}: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+    if device is not None and t.device != device:
+        raise KanvitError(f"{who}: {name} is on {t.device}, expected {device}")
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    if t.dtype not in dtypes:
+        raise KanvitError(f"{who}: {name} has dtype {t.dtype}, expected {' or '.join(str(d) for d in dtypes)}{hint}")
+    if contiguous and not t.is_contiguous():
+        raise KanvitError(f"{who}: {name} with shape {tuple(t.shape)} and strides {tuple(t.stride())} is not contiguous")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise KanvitError(f"{who}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# batches from a GPU-resident uint8 dataset (kanvit/data.py; csrc/batch_u8.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+_BATCH_TABLES = (("crop", torch.int32, (5,)), ("partner", torch.int64, ()), ("weight", torch.float32, ()), ("box", torch.int32, (4,)))
+
+
+def _batch_operands(who: str, images, labels, idx, lut, out, name: str, pair, **tables):
+    """What augment_u8 / mix_u8 / resample_u8 share, checked: the sizes (N, B, H, W, C), `pair` (an int or two; `name` is "pad", or
+    "out_size": the output then has that size instead of the images') as two ints, and the tensors the launch writes: `out` (the
+    caller's, or a new one), y where labels are given, y2 and w where the mix tables are.  tables: crop / partner / weight / box,
+    each or None."""
+    _require_tensor(who, "images", images, torch.uint8)
+    if images.dim() not in (3, 4):
+        raise KanvitError(f"{who}: images has shape {tuple(images.shape)}, expected [N, H, W, C] or [N, H, W]")
+    dev = images.device
+    N, H, W = (int(v) for v in images.shape[:3])
+    Cn = int(images.shape[3]) if images.dim() == 4 else 1
+    try:
+        pair = (int(pair), int(pair)) if isinstance(pair, int) else (int(pair[0]), int(pair[1]))
+    except (TypeError, IndexError):
+        raise KanvitError(f"{who}: {name}={pair!r} is an int or a pair of ints") from None
+    OH, OW = pair if name == "out_size" else (H, W)
+    _require_tensor(who, "idx", idx, torch.int64, None, dev)
+    if idx.dim() != 1:
+        raise KanvitError(f"{who}: idx has shape {tuple(idx.shape)}, expected [B]")
+    B = int(idx.shape[0])
+    if labels is not None:
+        _require_tensor(who, "labels", labels, torch.int64, (N,), dev)
+    _require_tensor(who, "lut", lut, torch.float32, (Cn, 256), dev)
+    for table, dt, tail in _BATCH_TABLES:
+        if tables.get(table) is not None:
+            _require_tensor(who, table, tables[table], dt, (N,) + tail, dev)
+    if out is None:
+        out = torch.empty((B, Cn, max(OH, 0), max(OW, 0)), device=dev, dtype=torch.float32)
+    else:
+        _require_tensor(who, "out", out, torch.float32, (B, Cn, OH, OW), dev)
+    mixing = tables.get("partner") is not None
+    y = torch.empty((B,), device=dev, dtype=torch.int64) if labels is not None else None
+    y2 = torch.empty((B,), device=dev, dtype=torch.int64) if mixing else None
+    w = torch.empty((B,), device=dev, dtype=torch.float32) if mixing else None
+    return (N, B, H, W, Cn), pair, (out, y, y2, w)
+
+
 def augment_u8(images: torch.Tensor, labels: Optional[torch.Tensor], idx: torch.Tensor, lut: torch.Tensor, pad=0, flip: bool = False,
                seed: int = 0, epoch: int = 0, return_params: bool = False, out: Optional[torch.Tensor] = None):
     """One batch out of a dataset that stays on the device as uint8: gather images[idx], random crop out of the zero-padded image,
@@ -1175,38 +1234,10 @@ def augment_u8(images: torch.Tensor, labels: Optional[torch.Tensor], idx: torch.
     (data.GpuDataset does, on the CPU, before the list goes to the device); lut float32 [C, 256]; pad an int or (pad_y, pad_x).
     Returns x float32 [B, C, H, W] (and y int64 [B] when labels are given, and params int32 [B, 3] = (dy, dx, flip) with
     return_params).  `out`: write into this contiguous [B, C, H, W] float32 tensor instead of allocating one."""
-    for name, t, dt in (("images", images, torch.uint8), ("labels", labels, torch.int64), ("idx", idx, torch.int64), ("lut", lut, torch.float32),
-                        ("out", out, torch.float32)):
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise KanvitError(f"augment_u8: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
-        if t.device != images.device:
-            raise KanvitError(f"augment_u8: {name} is on {t.device}, images on {images.device}")
-        if t.dtype != dt:
-            raise KanvitError(f"augment_u8: {name} has dtype {t.dtype}, expected {dt}")
-        if not t.is_contiguous():
-            raise KanvitError(f"augment_u8: {name} is not contiguous")
-    if images.dim() not in (3, 4):
-        raise KanvitError(f"augment_u8: images has shape {tuple(images.shape)}, expected [N, H, W, C] or [N, H, W]")
-    N, H, W = (int(v) for v in images.shape[:3])
-    Cn = int(images.shape[3]) if images.dim() == 4 else 1
-    pad_y, pad_x = (int(pad), int(pad)) if isinstance(pad, int) else (int(pad[0]), int(pad[1]))
-    if idx.dim() != 1:
-        raise KanvitError(f"augment_u8: idx has shape {tuple(idx.shape)}, expected [B]")
-    if labels is not None and tuple(labels.shape) != (N,):
-        raise KanvitError(f"augment_u8: labels has shape {tuple(labels.shape)}, expected [{N}]")
-    if tuple(lut.shape) != (Cn, 256):
-        raise KanvitError(f"augment_u8: lut has shape {tuple(lut.shape)}, expected [{Cn}, 256]")
-    B = int(idx.shape[0])
-    if out is None:
-        out = torch.empty((B, Cn, H, W), device=images.device, dtype=torch.float32)
-    elif tuple(out.shape) != (B, Cn, H, W):
-        raise KanvitError(f"augment_u8: out has shape {tuple(out.shape)}, expected {(B, Cn, H, W)}")
-    y = torch.empty((B,), device=images.device, dtype=torch.int64) if labels is not None else None
-    params = torch.empty((B, 3), device=images.device, dtype=torch.int32) if return_params else None
+    sizes, pads, (out, y, _, _) = _batch_operands("augment_u8", images, labels, idx, lut, out, "pad", pad)
+    params = torch.empty((sizes[1], 3), device=images.device, dtype=torch.int32) if return_params else None
     _launch(_lib.lib().kanvit_augment_u8, "kanvit_augment_u8", images.device, _ptr(images), _ptr(labels), _ptr(idx), _ptr(lut), _ptr(out), _ptr(y),
-            _ptr(params), N, B, H, W, Cn, pad_y, pad_x, int(bool(flip)), int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1))
+            _ptr(params), *sizes, *pads, int(bool(flip)), int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1))
     res = (out,) + ((y,) if labels is not None else ()) + ((params,) if return_params else ())
     return res[0] if len(res) == 1 else res
 
@@ -1219,43 +1250,13 @@ def mix_u8(images: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor, lut: t
     partner -1 leaves it as augment_u8 gives it.  Every partner lies in [-1, N): the CALLER checks that before the upload, as for idx.
     Returns (x float32 [B, C, H, W], y int64 [B] = labels[s], y2 int64 [B] = the partner's label (y where not mixed), w float32 [B] =
     weight[s])."""
-    N = int(images.shape[0]) if images.dim() in (3, 4) else -1
-    for name, t, dt in (("images", images, torch.uint8), ("labels", labels, torch.int64), ("idx", idx, torch.int64), ("lut", lut, torch.float32),
-                        ("partner", partner, torch.int64), ("weight", weight, torch.float32), ("box", box, torch.int32), ("out", out, torch.float32)):
+    for name, t in (("labels", labels), ("partner", partner), ("weight", weight), ("box", box)):
         if t is None:
-            if name == "out":
-                continue
             raise KanvitError(f"mix_u8: {name} is None")
-        if not t.is_cuda:
-            raise KanvitError(f"mix_u8: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
-        if t.device != images.device:
-            raise KanvitError(f"mix_u8: {name} is on {t.device}, images on {images.device}")
-        if t.dtype != dt:
-            raise KanvitError(f"mix_u8: {name} has dtype {t.dtype}, expected {dt}")
-        if not t.is_contiguous():
-            raise KanvitError(f"mix_u8: {name} is not contiguous")
-    if N < 0:
-        raise KanvitError(f"mix_u8: images has shape {tuple(images.shape)}, expected [N, H, W, C] or [N, H, W]")
-    H, W = int(images.shape[1]), int(images.shape[2])
-    Cn = int(images.shape[3]) if images.dim() == 4 else 1
-    pad_y, pad_x = (int(pad), int(pad)) if isinstance(pad, int) else (int(pad[0]), int(pad[1]))
-    if idx.dim() != 1:
-        raise KanvitError(f"mix_u8: idx has shape {tuple(idx.shape)}, expected [B]")
-    for name, t, shape in (("labels", labels, (N,)), ("lut", lut, (Cn, 256)), ("partner", partner, (N,)), ("weight", weight, (N,)),
-                           ("box", box, (N, 4))):
-        if tuple(t.shape) != shape:
-            raise KanvitError(f"mix_u8: {name} has shape {tuple(t.shape)}, expected {list(shape)}")
-    B = int(idx.shape[0])
-    if out is None:
-        out = torch.empty((B, Cn, H, W), device=images.device, dtype=torch.float32)
-    elif tuple(out.shape) != (B, Cn, H, W):
-        raise KanvitError(f"mix_u8: out has shape {tuple(out.shape)}, expected {(B, Cn, H, W)}")
-    y = torch.empty((B,), device=images.device, dtype=torch.int64)
-    y2 = torch.empty((B,), device=images.device, dtype=torch.int64)
-    w = torch.empty((B,), device=images.device, dtype=torch.float32)
+    sizes, pads, (out, y, y2, w) = _batch_operands("mix_u8", images, labels, idx, lut, out, "pad", pad, partner=partner, weight=weight, box=box)
     _launch(_lib.lib().kanvit_mix_u8, "kanvit_mix_u8", images.device, _ptr(images), _ptr(labels), _ptr(idx), _ptr(lut), _ptr(partner),
-            _ptr(weight), _ptr(box), _ptr(out), _ptr(y), _ptr(y2), _ptr(w), N, B, H, W, Cn, pad_y, pad_x, int(bool(flip)),
-            int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1), tag="mix_u8", cost=(0, B * Cn * H * W * 6))
+            _ptr(weight), _ptr(box), _ptr(out), _ptr(y), _ptr(y2), _ptr(w), *sizes, *pads, int(bool(flip)),
+            int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1), tag="mix_u8", cost=(0, out.numel() * 6))
     return out, y, y2, w
 
 
@@ -1269,69 +1270,28 @@ def resample_u8(images: torch.Tensor, labels: Optional[torch.Tensor], idx: torch
     none, with box in OUTPUT coordinates; the partner is resampled under its own crop row.  Every idx and partner lies inside the
     dataset: the CALLER checks that before the upload.
     Returns (x float32 [B, C, OH, OW], y int64 [B]) -- x alone when labels is None -- or (x, y, y2, w) with the mix tables."""
-    N = int(images.shape[0]) if images.dim() in (3, 4) else -1
     tables = (partner, weight, box)
     mixing = any(t is not None for t in tables)
     if mixing and any(t is None for t in tables):
         raise KanvitError("resample_u8: partner, weight and box come together (all three or none)")
     if mixing and labels is None:
         raise KanvitError("resample_u8: labels is None: the mix tables yield (x, y, y2, w)")
-    for name, t, dt in (("images", images, torch.uint8), ("labels", labels, torch.int64), ("idx", idx, torch.int64), ("lut", lut, torch.float32),
-                        ("crop", crop, torch.int32), ("partner", partner, torch.int64), ("weight", weight, torch.float32), ("box", box, torch.int32),
-                        ("out", out, torch.float32)):
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise KanvitError(f"resample_u8: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
-        if t.device != images.device:
-            raise KanvitError(f"resample_u8: {name} is on {t.device}, images on {images.device}")
-        if t.dtype != dt:
-            raise KanvitError(f"resample_u8: {name} has dtype {t.dtype}, expected {dt}")
-        if not t.is_contiguous():
-            raise KanvitError(f"resample_u8: {name} is not contiguous")
-    if N < 0:
-        raise KanvitError(f"resample_u8: images has shape {tuple(images.shape)}, expected [N, H, W, C] or [N, H, W]")
-    H, W = int(images.shape[1]), int(images.shape[2])
-    Cn = int(images.shape[3]) if images.dim() == 4 else 1
-    try:
-        OH, OW = (int(out_size), int(out_size)) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
-    except (TypeError, IndexError):
-        raise KanvitError(f"resample_u8: out_size={out_size!r} is an int or (OH, OW)") from None
-    if idx.dim() != 1:
-        raise KanvitError(f"resample_u8: idx has shape {tuple(idx.shape)}, expected [B]")
-    for name, t, shape in (("labels", labels, (N,)), ("lut", lut, (Cn, 256)), ("crop", crop, (N, 5)), ("partner", partner, (N,)),
-                           ("weight", weight, (N,)), ("box", box, (N, 4))):
-        if t is not None and tuple(t.shape) != shape:
-            raise KanvitError(f"resample_u8: {name} has shape {tuple(t.shape)}, expected {list(shape)}")
-    B = int(idx.shape[0])
-    if out is None:
-        out = torch.empty((B, Cn, max(OH, 0), max(OW, 0)), device=images.device, dtype=torch.float32)
-    elif tuple(out.shape) != (B, Cn, OH, OW):
-        raise KanvitError(f"resample_u8: out has shape {tuple(out.shape)}, expected {(B, Cn, OH, OW)}")
-    y = torch.empty((B,), device=images.device, dtype=torch.int64) if labels is not None else None
-    y2 = torch.empty((B,), device=images.device, dtype=torch.int64) if mixing else None
-    w = torch.empty((B,), device=images.device, dtype=torch.float32) if mixing else None
+    sizes, size, (out, y, y2, w) = _batch_operands("resample_u8", images, labels, idx, lut, out, "out_size", out_size, crop=crop, partner=partner,
+                                                   weight=weight, box=box)
     _launch(_lib.lib().kanvit_resample_u8, "kanvit_resample_u8", images.device, _ptr(images), _ptr(labels), _ptr(idx), _ptr(lut), _ptr(crop),
-            _ptr(partner), _ptr(weight), _ptr(box), _ptr(out), _ptr(y), _ptr(y2), _ptr(w), N, B, H, W, Cn, OH, OW,
-            tag="resample_u8", cost=(0, B * Cn * OH * OW * 4))
+            _ptr(partner), _ptr(weight), _ptr(box), _ptr(out), _ptr(y), _ptr(y2), _ptr(w), *sizes, *size,
+            tag="resample_u8", cost=(0, out.numel() * 4))
     if mixing:
         return out, y, y2, w
     return (out, y) if labels is not None else out
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# soft-target cross-entropy: loss and gradient in one pass over the logits (csrc/augment.hip)
+# soft-target cross-entropy: loss and gradient in one pass over the logits (csrc/soft_ce.hip)
 # ---------------------------------------------------------------------------------------------------------------------------
-def soft_ce(logits: torch.Tensor, y: torch.Tensor, y2: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None,
-            label_smoothing: float = 0.0):
-    """The kernel call behind soft_cross_entropy, without autograd: (loss float32 [], loss_rows float32 [B], dlogits float32 [B, C]) for
-    logits float32 [B, C] (unit column stride; a padded row stride is taken as it is), y int64 [B], and y2 int64 [B] with w float32 [B]
-    or neither (semantics: include/kanvit.h).  One launch plus the one-work-group mean; no host synchronisation."""
-    who = "soft_cross_entropy"
-    if not logits.is_cuda:
-        raise KanvitError(f"{who}: logits is on {logits.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
-    if logits.dtype != torch.float32:
-        raise KanvitError(f"{who}: logits has dtype {logits.dtype}, expected torch.float32 (train.py hands the loss y_hat.float())")
+def _logits_2d(who: str, logits: torch.Tensor, dtypes, hint: str = ""):
+    """(B, C) of the logits soft_ce and metrics_update walk: on the GPU, of one of `dtypes`, [B >= 1, C >= 2], unit column stride."""
+    _require_tensor(who, "logits", logits, dtypes, contiguous=False, hint=hint)
     if logits.dim() != 2:
         raise KanvitError(f"{who}: logits has shape {tuple(logits.shape)}, expected [B, C]")
     B, Cn = (int(v) for v in logits.shape)
@@ -1339,13 +1299,23 @@ def soft_ce(logits: torch.Tensor, y: torch.Tensor, y2: Optional[torch.Tensor] = 
         raise KanvitError(f"{who}: logits has shape {tuple(logits.shape)}: at least one row and two classes")
     if logits.stride(1) != 1 or logits.stride(0) < Cn:
         raise KanvitError(f"{who}: logits has strides {tuple(logits.stride())}: unit column stride and a row stride of at least C = {Cn}")
+    return B, Cn
+
+
+def soft_ce(logits: torch.Tensor, y: torch.Tensor, y2: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None,
+            label_smoothing: float = 0.0):
+    """The kernel call behind soft_cross_entropy, without autograd: (loss float32 [], loss_rows float32 [B], dlogits float32 [B, C]) for
+    logits float32 [B, C] (unit column stride; a padded row stride is taken as it is), y int64 [B], and y2 int64 [B] with w float32 [B]
+    or neither (semantics: include/kanvit.h).  One launch plus the one-work-group mean; no host synchronisation."""
+    who = "soft_cross_entropy"
+    B, Cn = _logits_2d(who, logits, torch.float32, hint=" (train.py hands the loss y_hat.float())")
     if (y2 is None) != (w is None):
         raise KanvitError(f"{who}: y2 and w come together")
     if not 0.0 <= float(label_smoothing) < 1.0:
         raise KanvitError(f"{who}: label_smoothing={label_smoothing} must be in [0, 1)")
     for name, t, dt in (("y", y, torch.int64), ("y2", y2, torch.int64), ("w", w, torch.float32)):
         if t is not None:
-            _require_metrics_buffer(who, name, t, dt, (B,), logits.device)
+            _require_tensor(who, name, t, dt, (B,), logits.device)
     out = torch.empty((B * Cn + B + 1,), device=logits.device, dtype=torch.float32)
     dlogits, loss_rows, loss = out[:B * Cn].view(B, Cn), out[B * Cn:B * Cn + B], out[B * Cn + B:].view(())
     _launch(_lib.lib().kanvit_soft_ce, "kanvit_soft_ce", logits.device, _ptr(logits), int(logits.stride(0)), _ptr(y), _ptr(y2), _ptr(w), B, Cn,
@@ -1379,21 +1349,8 @@ def soft_cross_entropy(logits: torch.Tensor, y: torch.Tensor, y2: Optional[torch
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# epoch metrics on the device (kanvit/metrics.py; csrc/augment.hip)
+# epoch metrics on the device (kanvit/metrics.py; csrc/metrics.hip)
 # ---------------------------------------------------------------------------------------------------------------------------
-def _require_metrics_buffer(who: str, name: str, t: torch.Tensor, dtype, shape, device):
-    if not t.is_cuda:
-        raise KanvitError(f"{who}: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
-    if t.device != device:
-        raise KanvitError(f"{who}: {name} is on {t.device}, expected {device}")
-    if t.dtype != dtype:
-        raise KanvitError(f"{who}: {name} has dtype {t.dtype}, expected {dtype}")
-    if not t.is_contiguous():
-        raise KanvitError(f"{who}: {name} is not contiguous")
-    if tuple(t.shape) != tuple(shape):
-        raise KanvitError(f"{who}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-
-
 def metrics_update(logits: torch.Tensor, labels: torch.Tensor, n0: int, probs_t: torch.Tensor, labels_out: torch.Tensor,
                    preds_out: torch.Tensor, confusion: torch.Tensor) -> None:
     """One step's rows into the epoch-metrics state, in one launch on the current stream (semantics: include/kanvit.h): the fp32
@@ -1402,23 +1359,13 @@ def metrics_update(logits: torch.Tensor, labels: torch.Tensor, n0: int, probs_t:
     and confusion (int64 [C, C]) gains one count per row.  A row whose label is outside [0, C) is stored with label -1 and counted
     nowhere.  No host synchronisation."""
     who = "metrics_update"
-    if not logits.is_cuda:
-        raise KanvitError(f"{who}: logits is on {logits.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
-    if logits.dtype not in (torch.float32, torch.bfloat16):
-        raise KanvitError(f"{who}: logits has dtype {logits.dtype}, expected torch.float32 or torch.bfloat16")
-    if logits.dim() != 2:
-        raise KanvitError(f"{who}: logits has shape {tuple(logits.shape)}, expected [B, C]")
-    B, Cn = (int(v) for v in logits.shape)
-    if B < 1 or Cn < 2:
-        raise KanvitError(f"{who}: logits has shape {tuple(logits.shape)}: at least one row and two classes")
-    if logits.stride(1) != 1 or logits.stride(0) < Cn:
-        raise KanvitError(f"{who}: logits has strides {tuple(logits.stride())}: unit column stride and a row stride of at least C = {Cn}")
+    B, Cn = _logits_2d(who, logits, (torch.float32, torch.bfloat16))
     cap = int(probs_t.shape[1]) if probs_t.dim() == 2 else -1
-    _require_metrics_buffer(who, "labels", labels, torch.int64, (B,), logits.device)
-    _require_metrics_buffer(who, "probs_t", probs_t, torch.float32, (Cn, cap), logits.device)
-    _require_metrics_buffer(who, "labels_out", labels_out, torch.int32, (cap,), logits.device)
-    _require_metrics_buffer(who, "preds_out", preds_out, torch.int32, (cap,), logits.device)
-    _require_metrics_buffer(who, "confusion", confusion, torch.int64, (Cn, Cn), logits.device)
+    _require_tensor(who, "labels", labels, torch.int64, (B,), logits.device)
+    _require_tensor(who, "probs_t", probs_t, torch.float32, (Cn, cap), logits.device)
+    _require_tensor(who, "labels_out", labels_out, torch.int32, (cap,), logits.device)
+    _require_tensor(who, "preds_out", preds_out, torch.int32, (cap,), logits.device)
+    _require_tensor(who, "confusion", confusion, torch.int64, (Cn, Cn), logits.device)
     if n0 < 0 or n0 + B > cap:
         raise KanvitError(f"{who}: rows {n0} .. {n0 + B - 1} do not fit the capacity {cap}")
     _launch(_lib.lib().kanvit_metrics_update, "kanvit_metrics_update", logits.device, _ptr(logits), int(logits.dtype == torch.bfloat16),
@@ -1431,16 +1378,14 @@ def metrics_auc_pairs(probs_t: torch.Tensor, labels: torch.Tensor, n: int, count
     (gt_c, eq_c), int64 [C, 2] (include/kanvit.h), written into `counts` when given.  probs_t float32 [C, cap] class-major, labels
     int32 [cap] (-1 = a dropped row).  n * n compares in all; no host synchronisation."""
     who = "metrics_auc_pairs"
-    if not probs_t.is_cuda:
-        raise KanvitError(f"{who}: probs_t is on {probs_t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+    _require_tensor(who, "probs_t", probs_t, torch.float32)
     if probs_t.dim() != 2:
         raise KanvitError(f"{who}: probs_t has shape {tuple(probs_t.shape)}, expected [C, cap]")
     Cn, cap = (int(v) for v in probs_t.shape)
-    _require_metrics_buffer(who, "probs_t", probs_t, torch.float32, (Cn, cap), probs_t.device)
-    _require_metrics_buffer(who, "labels", labels, torch.int32, (cap,), probs_t.device)
+    _require_tensor(who, "labels", labels, torch.int32, (cap,), probs_t.device)
     if counts is None:
         counts = torch.empty((Cn, 2), device=probs_t.device, dtype=torch.int64)
-    _require_metrics_buffer(who, "counts", counts, torch.int64, (Cn, 2), probs_t.device)
+    _require_tensor(who, "counts", counts, torch.int64, (Cn, 2), probs_t.device)
     n = int(n)
     if n < 1 or n > cap or Cn < 2:
         raise KanvitError(f"{who}: n = {n} of capacity {cap}, C = {Cn}: at least one sample, at most the capacity, at least two classes")
@@ -1451,19 +1396,8 @@ def metrics_auc_pairs(probs_t: torch.Tensor, labels: torch.Tensor, n: int, count
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# fused AdamW step: global-norm clipping, schedule table, weight EMA (kanvit/optim.py; csrc/augment.hip)
+# fused AdamW step: global-norm clipping, schedule table, weight EMA (kanvit/optim.py; csrc/optim.hip)
 # ---------------------------------------------------------------------------------------------------------------------------
-def _require_optim_tensor(who: str, name: str, t: torch.Tensor, device=None):
-    if not t.is_cuda:
-        raise KanvitError(f"{who}: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
-    if device is not None and t.device != device:
-        raise KanvitError(f"{who}: {name} is on {t.device}, expected {device}")
-    if t.dtype != torch.float32:
-        raise KanvitError(f"{who}: {name} has dtype {t.dtype}; the optimizer kernels compute in float32")
-    if not t.is_contiguous():
-        raise KanvitError(f"{who}: {name} with shape {tuple(t.shape)} and strides {tuple(t.stride())} is not contiguous")
-
-
 def _optim_ptrs(tensors):
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
@@ -1478,12 +1412,10 @@ def optim_grad_sumsq(grads, partials: torch.Tensor) -> int:
     _lib.OPTIM_CHUNK elements, tensor after tensor; semantics: include/kanvit.h): ceil(len(grads) / optim_max_tensors()) launches, no
     atomics, no host synchronisation.  Returns the number of partials written; optim_begin adds them up."""
     who = "optim_grad_sumsq"
-    if not partials.is_cuda:
-        raise KanvitError(f"{who}: partials is on {partials.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
-    _require_metrics_buffer(who, "partials", partials, torch.float64, (partials.numel(),), partials.device)
+    _require_tensor(who, "partials", partials, torch.float64, (partials.numel(),))
     grads = list(grads)
     for k, g in enumerate(grads):
-        _require_optim_tensor(who, f"grads[{k}]", g, partials.device)
+        _require_tensor(who, f"grads[{k}]", g, torch.float32, None, partials.device)
     L, done, cap = _lib.lib(), 0, optim_max_tensors()
     for lo in range(0, len(grads), cap):
         part = grads[lo:lo + cap]
@@ -1503,12 +1435,10 @@ def optim_begin(partials: Optional[torch.Tensor], n_partials: int, max_norm: flo
     first n_partials of optim_grad_sumsq's partials, clip coefficient min(1, max_norm / (norm + 1e-6)) evaluated in float64; max_norm
     <= 0: no clipping, the coefficient is 1), and step (int64 [1]) += 1.  partials = None: the norm is not taken (NaN)."""
     who = "optim_begin"
-    if not step.is_cuda:
-        raise KanvitError(f"{who}: step is on {step.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
-    _require_metrics_buffer(who, "step", step, torch.int64, (1,), step.device)
-    _require_metrics_buffer(who, "norm_coef", norm_coef, torch.float32, (2,), step.device)
+    _require_tensor(who, "step", step, torch.int64, (1,))
+    _require_tensor(who, "norm_coef", norm_coef, torch.float32, (2,), step.device)
     if partials is not None:
-        _require_metrics_buffer(who, "partials", partials, torch.float64, (partials.numel(),), step.device)
+        _require_tensor(who, "partials", partials, torch.float64, (partials.numel(),), step.device)
         if not 0 <= int(n_partials) <= partials.numel():
             raise KanvitError(f"{who}: n_partials = {n_partials} of {partials.numel()} entries")
     elif n_partials:
@@ -1528,21 +1458,20 @@ def optim_adamw(params, grads, offsets, decay, exp_avg: torch.Tensor, exp_avg_sq
     params, grads = list(params), list(grads)
     if not (len(params) == len(grads) == len(offsets) == len(decay)):
         raise KanvitError(f"{who}: {len(params)} params, {len(grads)} grads, {len(offsets)} offsets, {len(decay)} decay flags")
-    if not exp_avg.is_cuda:
-        raise KanvitError(f"{who}: exp_avg is on {exp_avg.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+    _require_tensor(who, "exp_avg", exp_avg, torch.float32, (exp_avg.numel(),))
     dev, S = exp_avg.device, exp_avg.numel()
-    for name, t in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("ema", ema)):
+    for name, t in (("exp_avg_sq", exp_avg_sq), ("ema", ema)):
         if t is not None:
-            _require_metrics_buffer(who, name, t, torch.float32, (S,), dev)
+            _require_tensor(who, name, t, torch.float32, (S,), dev)
     if table.dim() != 2 or table.shape[1] != 4 or table.shape[0] < 1:
         raise KanvitError(f"{who}: table has shape {tuple(table.shape)}, expected [T, 4]")
-    _require_metrics_buffer(who, "table", table, torch.float32, tuple(table.shape), dev)
-    _require_metrics_buffer(who, "step", step, torch.int64, (1,), dev)
+    _require_tensor(who, "table", table, torch.float32, None, dev)
+    _require_tensor(who, "step", step, torch.int64, (1,), dev)
     if norm_coef is not None:
-        _require_metrics_buffer(who, "norm_coef", norm_coef, torch.float32, (2,), dev)
+        _require_tensor(who, "norm_coef", norm_coef, torch.float32, (2,), dev)
     for k, (p, g) in enumerate(zip(params, grads)):
-        _require_optim_tensor(who, f"params[{k}]", p, dev)
-        _require_optim_tensor(who, f"grads[{k}]", g, dev)
+        _require_tensor(who, f"params[{k}]", p, torch.float32, None, dev)
+        _require_tensor(who, f"grads[{k}]", g, torch.float32, None, dev)
         if g.numel() != p.numel():
             raise KanvitError(f"{who}: grads[{k}] has {g.numel()} elements, params[{k}] {p.numel()}")
     if len(consts) != 7:

@@ -1,4 +1,4 @@
-"""KanvitAdamW: the optimizer half of the DeiT / timm recipe in the project's own kernels (csrc/augment.hip, include/kanvit.h).
+"""KanvitAdamW: the optimizer half of the DeiT / timm recipe in the project's own kernels (csrc/optim.hip, include/kanvit.h).
 
 One step is: the gradients' sum of squares (only when clipping is on), one one-work-group launch that turns it into the global norm
 and the clip coefficient and counts the step, and one multi-tensor update that clips, decays, runs AdamW with the step's learning
@@ -99,7 +99,7 @@ class KanvitAdamW(torch.optim.Optimizer):
         if not params:
             raise KanvitError("KanvitAdamW: no parameter requires a gradient")
         for k, p in enumerate(params):
-            ops._require_optim_tensor("KanvitAdamW", f"params[{k}]", p, params[0].device)
+            ops._require_tensor("KanvitAdamW", f"params[{k}]", p, torch.float32, None, params[0].device)
         if (table is None) == (total_steps is None):
             raise KanvitError("KanvitAdamW: give table= (a step_table) or total_steps= (with warmup_steps, schedule, min_lr), one of them")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:

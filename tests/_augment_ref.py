@@ -1,4 +1,4 @@
-"""Reference for the GPU-resident data path (kanvit/data.py, csrc/augment.hip): the per-sample hash of include/kanvit.h in Python
+"""Reference for the GPU-resident data path (kanvit/data.py, csrc/batch_u8.hip): the per-sample hash of include/kanvit.h in Python
 integers, and the reference's transform order (train.py:100-118: RandomHorizontalFlip, RandomCrop(size, padding) with zero padding
 on the uint8 image, ToTensor, Normalize) in CPU torch with the parameters the hash gives."""
 import torch

@@ -1,4 +1,4 @@
-"""numpy brute force for the epoch-metrics tests: the tables the kernels of csrc/augment.hip count, straight from their definitions."""
+"""numpy brute force for the epoch-metrics tests: the tables the kernels of csrc/metrics.hip count, straight from their definitions."""
 import numpy as np
 
 

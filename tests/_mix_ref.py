@@ -1,5 +1,5 @@
-"""NumPy restatements for the Mixup / CutMix batch kernel and the fused soft-target cross-entropy (csrc/augment.hip: mix_u8_kernel,
-soft_ce_kernel).  The batch side builds on tests/_augment_ref.augment and states the kernel's arithmetic in float32, operation by
+"""NumPy restatements for the Mixup / CutMix batch kernel and the fused soft-target cross-entropy (csrc/batch_u8.hip: mix_u8_kernel;
+csrc/soft_ce.hip: soft_ce_kernel).  The batch side builds on tests/_augment_ref.augment and states the kernel's arithmetic in float32, operation by
 operation, so the comparison is bitwise; the loss side is float64, the common yardstick for the kernel and for torch's own fp32
 cross_entropy."""
 import numpy as np

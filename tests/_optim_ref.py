@@ -1,4 +1,4 @@
-"""Host restatements of the optimizer kernels (include/kanvit.h, csrc/augment.hip) for tests/test_optim_*.py.
+"""Host restatements of the optimizer kernels (include/kanvit.h, csrc/optim.hip) for tests/test_optim_*.py.
 
 adamw_f32      the update as NumPy float32 operations, one rounding each, in the kernel's order: equals the device bit for bit.
 sumsq_partials / total_sumsq / norm_and_coef    the float64 norm in the kernels' own order of additions, and clip_grad_norm_'s rule.

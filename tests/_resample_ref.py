@@ -1,4 +1,4 @@
-"""NumPy float32 restatement of the resampling batch kernel (csrc/augment.hip: resample_u8_kernel; the operation sequence of
+"""NumPy float32 restatement of the resampling batch kernel (csrc/batch_u8.hip: resample_u8_kernel; the operation sequence of
 include/kanvit.h), operation by operation so that the comparison is bitwise, on tests/_augment_ref's look-up arithmetic (byte / 255,
 minus mean, over std, in fp32) and padding rule (a tap outside the image is the normalised zero); and a plain per-sample loop
 restating kanvit.data.crop_table(mode="rrc") from columns it draws itself.  Mixing reuses tests/_mix_ref.mix, which takes any

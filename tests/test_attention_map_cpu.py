@@ -28,7 +28,7 @@ def test_export_and_abi_version(lib):
                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, P]
     assert lib.kanvit_abi_version() == 7
     from kanvit import build
-    assert "attention_probs.hip" in build.SOURCES and len(build.SOURCES) == 19
+    assert "attention_probs.hip" in build.SOURCES and len(build.SOURCES) == 22
 
 
 def _call(lib, d=None, e=None, q=8, k=8, p=8, stride_q=None, rows=1, **kw):

@@ -1,4 +1,4 @@
-"""CPU-only checks of Mixup / CutMix and the fused soft-target loss (kanvit/data.py: mix_table; csrc/augment.hip: kanvit_mix_u8,
+"""CPU-only checks of Mixup / CutMix and the fused soft-target loss (kanvit/data.py: mix_table; csrc/batch_u8.hip: kanvit_mix_u8; csrc/soft_ce.hip:
 kanvit_soft_ce; train.py --mixup / --cutmix / --label-smoothing / --fused-loss): the per-epoch table and what it may depend on, the new
 symbols and their host-side refusals, the resources of the new kernels, the wrappers without a GPU and the command-line flags."""
 import ctypes

@@ -1,4 +1,4 @@
-"""ops.mix_u8 (csrc/augment.hip: mix_u8_kernel) on the GPU against the float32 restatement of tests/_mix_ref.py -- BITWISE: CutMix
+"""ops.mix_u8 (csrc/batch_u8.hip: mix_u8_kernel) on the GPU against the float32 restatement of tests/_mix_ref.py -- BITWISE: CutMix
 only looks values up, and Mixup is three roundings the compiler may not contract, which NumPy's float32 operations repeat.  A
 hand-built table holds every kind of row (tests/_mix_ref.hand_table); the shapes cover both store forms (W = 8, 12: 16 bytes per lane;
 W = 6: the scalar form) and every channel count the table is staged for on both sides of three channels."""

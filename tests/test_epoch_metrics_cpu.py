@@ -1,4 +1,4 @@
-"""CPU-only checks of the device epoch metrics (kanvit/metrics.py, csrc/augment.hip, train.py --device-metrics): the host formulas
+"""CPU-only checks of the device epoch metrics (kanvit/metrics.py, csrc/metrics.hip, train.py --device-metrics): the host formulas
 on brute-force tables against the reference's own calculate_metrics output and against scikit-learn, the new symbols and their
 argument lists, the host-side refusals of both entry points, and the new command-line flag."""
 import ctypes

@@ -1,4 +1,4 @@
-"""The device epoch metrics on the GPU (csrc/augment.hip: kanvit_metrics_update, kanvit_metrics_auc_pairs; kanvit/metrics.py;
+"""The device epoch metrics on the GPU (csrc/metrics.hip: kanvit_metrics_update, kanvit_metrics_auc_pairs; kanvit/metrics.py;
 train.py --device-metrics) against the numpy brute force of tests/_metrics_ref.py, scikit-learn and the default metrics path."""
 import re
 

@@ -1,4 +1,4 @@
-"""CPU-only checks of the GPU-resident data path (kanvit/data.py, csrc/augment.hip, train.py --data-npz): the per-sample hash
+"""CPU-only checks of the GPU-resident data path (kanvit/data.py, csrc/batch_u8.hip, train.py --data-npz): the per-sample hash
 against its check vectors, the coverage of offsets the GPU parity test relies on, the look-up table against the reference's
 operations, the epoch's index lists, host-side validation of the entry point, the .npz layout and the new command-line flags."""
 import ctypes

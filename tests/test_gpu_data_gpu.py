@@ -1,4 +1,4 @@
-"""GPU tests of the GPU-resident data path: ops.augment_u8 (csrc/augment.hip) against the CPU transform of tests/_augment_ref.py --
+"""GPU tests of the GPU-resident data path: ops.augment_u8 (csrc/batch_u8.hip) against the CPU transform of tests/_augment_ref.py --
 BITWISE, since the kernel only looks values up in a table the host built with the reference's operations -- at the smallest shapes
 that reach each form and edge; GpuDataset.batches; and train.main --data-npz against train.main fed the same batches."""
 import re

@@ -1,4 +1,4 @@
-"""CPU-only checks of the resampling batch kernel's surroundings (csrc/augment.hip: kanvit_resample_u8; kanvit/data.py: crop_table;
+"""CPU-only checks of the resampling batch kernel's surroundings (csrc/batch_u8.hip: kanvit_resample_u8; kanvit/data.py: crop_table;
 train.py --resize / --random-resized-crop): the float32 restatement the GPU tests compare with, anchored to torch's own bilinear
 interpolation; the per-epoch crop table and what it may depend on; the new symbols and their host-side refusals; the resources of
 the new kernels; the wrapper without a GPU and the command-line flags."""

@@ -1,4 +1,4 @@
-"""ops.resample_u8 (csrc/augment.hip: resample_u8_kernel) on the GPU against the float32 restatement of tests/_resample_ref.py --
+"""ops.resample_u8 (csrc/batch_u8.hip: resample_u8_kernel) on the GPU against the float32 restatement of tests/_resample_ref.py --
 BITWISE: the kernel's fp32 operation sequence is fixed and never contracted, and NumPy's float32 operations repeat it.  The shapes
 are the smallest that reach each form and edge: 8x8x3 -> 20x20 (16-byte stores, boxes over every edge), 7x9x1 -> 12x10 (the scalar
 form), a hand-made table of degenerate boxes, a downscale, the identity size against ops.augment_u8 / ops.mix_u8, mixing with the

@@ -1,4 +1,4 @@
-"""ops.soft_cross_entropy (csrc/augment.hip: soft_ce_kernel) on the GPU against the float64 restatement of tests/_mix_ref.py.
+"""ops.soft_cross_entropy (csrc/soft_ce.hip: soft_ce_kernel) on the GPU against the float64 restatement of tests/_mix_ref.py.
 
 The bound is relative to torch's own fp32 cross_entropy on the same device and the same inputs (probability targets plus
 label_smoothing, forward and backward), measured against the same float64 values: with e_t its largest error of a case, the kernel may

@@ -1,4 +1,4 @@
-"""What the GPU-resident data path (kanvit/data.py, csrc/augment.hip) delivers, on the GPU, for train.py's default geometry
+"""What the GPU-resident data path (kanvit/data.py, csrc/batch_u8.hip) delivers, on the GPU, for train.py's default geometry
 (32x32x3 images, batch 128, random crop with padding 4, random flip) on a generated dataset of CIFAR's size (50 000 images):
 
   (a) GpuDataset.batches alone: images/s of whole epochs (host loop, allocation and launch included; device events around each
