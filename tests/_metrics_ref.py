@@ -47,3 +47,21 @@ def tie_logits(rng, B, C):
     for i in range(2, B, 3):
         z[i] = z[i - 1]
     return z.astype(np.float32)
+
+
+HIST_LAP = 2048 * 256               # metrics_hist_kernel / metrics_scatter_kernel: at most 2048 work-groups of 256 threads, one sample each per lap
+
+
+def past_cap_case(seed=0, C=3, head=900, tail=700):
+    """(labels int64 [n], proba float32 [n, C]) with n = HIST_LAP + tail: past the first lap of the histogram and the scatter.  Every
+    row is dropped (label -1) but `head` rows scattered over the first HIST_LAP and all `tail` rows behind them.  The valid rows hold
+    tied probabilities (softmax64 of tie_logits); the dropped rows hold -1.0, below any probability, so a dropped row taken for a
+    negative adds to gt."""
+    rng = np.random.default_rng(seed)
+    n = HIST_LAP + tail
+    valid = np.concatenate([np.sort(rng.choice(HIST_LAP, head, replace=False)), np.arange(HIST_LAP, n)])
+    y = np.full(n, -1, dtype=np.int64)
+    y[valid] = rng.integers(0, C, valid.size)
+    p = np.full((n, C), -1.0, dtype=np.float32)
+    p[valid] = softmax64(tie_logits(rng, valid.size, C)).astype(np.float32)
+    return y, p

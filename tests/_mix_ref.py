@@ -101,3 +101,21 @@ def soft_ce(z, y1, y2=None, w=None, eps=0.0):
     rows = np.where(ok, np.log(s[:, 0]) + (t * (m - z)).sum(1), 0.0)
     dz = np.where(ok[:, None], (e / s - t) / B, 0.0)
     return rows.sum() / B, rows, dz
+
+
+def mean_rows_f32(rows, threads=256):
+    """soft_ce_mean_kernel in NumPy float32: thread t adds rows t, t + 256, ... in order, then part[:o] += part[o:2o] for o = 128 .. 1,
+    then one float32 division by float32(B).  Every operation rounds once, as the device's do (its division is the IEEE sequence)."""
+    rows = np.asarray(rows)
+    assert rows.dtype == np.float32 and rows.ndim == 1 and rows.size >= 1
+    part = np.zeros(threads, np.float32)
+    for lo in range(0, rows.size, threads):
+        blk = rows[lo:lo + threads]
+        part[:blk.size] = part[:blk.size] + blk
+    o = threads // 2
+    while o:
+        part[:o] = part[:o] + part[o:2 * o]
+        o //= 2
+    out = part[0] / np.float32(rows.size)
+    assert out.dtype == np.float32
+    return out

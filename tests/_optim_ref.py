@@ -108,6 +108,13 @@ def tiny_numels(n):
     return [(1, 2, 3, 5, 8)[k % 5] for k in range(n)]
 
 
+# the begin kernel's second lap: 81 + 261 + 1 = 343 partials (threads 0..86 add two) over 83 tensors, so two launches; the second
+# launch holds tiny tensor 80, the 261-chunk tensor (chunks from first[1] = 1, partials from offset 80 of the workspace) and a 9-element
+# one.  Tensor 81 is the large one: 81 % 4 = 1 puts its misaligned gradient 4 bytes off the 16-byte grid
+LAP_NUMELS = tiny_numels(81) + [260 * CHUNK + 5, 9]
+LAP_STEPS = 2                       # the sequential float64 order is a Python loop over 1.07 M elements: about a second per step
+
+
 def case_params(numels, seed=0):
     rng = np.random.default_rng([seed, len(numels)])
     return [rng.standard_normal(n).astype(np.float32) for n in numels]
@@ -138,15 +145,17 @@ HUGE = (5000, 1e25, 1.0)            # (numel, value, max_norm): squares that ove
 
 
 def clip_cases(max_tensors):
-    """Every synthetic clipping case tests/test_optim_gpu.py runs, as (name, numels, max_norm, none): the edge list under each clipping
-    config with the None gradients, the edge list without them (graph replay against eager), MAX and MAX + 1 tiny tensors."""
+    """Every synthetic clipping case tests/test_optim_gpu.py runs, as (name, numels, max_norm, none, steps): the edge list under each
+    clipping config with the None gradients, the edge list without them (graph replay against eager), MAX and MAX + 1 tiny tensors,
+    the list whose partials take the begin kernel past its first lap."""
     for name, (_, max_norm, _) in CONFIGS.items():
         if max_norm is not None:
-            yield f"{name}/edge", EDGE_NUMELS, max_norm, NONE_GRAD
+            yield f"{name}/edge", EDGE_NUMELS, max_norm, NONE_GRAD, STEPS
     max_norm = CONFIGS["ema_clip"][1]
-    yield "ema_clip/edge, every gradient", EDGE_NUMELS, max_norm, frozenset()
+    yield "ema_clip/edge, every gradient", EDGE_NUMELS, max_norm, frozenset(), STEPS
     for n in (max_tensors, max_tensors + 1):
-        yield f"ema_clip/{n} tiny", tiny_numels(n), max_norm, frozenset()
+        yield f"ema_clip/{n} tiny", tiny_numels(n), max_norm, frozenset(), STEPS
+    yield "ema_clip/lap", LAP_NUMELS, max_norm, frozenset(), LAP_STEPS
 
 
 def coefficient_in_three_orders(grads, max_norm):

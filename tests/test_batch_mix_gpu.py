@@ -45,11 +45,11 @@ def _idx(B):
     return np.concatenate([rng.permutation(N), rng.permutation(N)[:B - N]]).tolist()
 
 
-def _run(c, idx, pad, flip, table=None, seed=SEED, epoch=EPOCH):
+def _run(c, idx, pad, flip, table=None, seed=SEED, epoch=EPOCH, out=None):
     from kanvit import ops
     d = c["dev"]
     return ops.mix_u8(d["images"], d["labels"], torch.tensor(idx, dtype=torch.int64, device=DEV), d["lut"], *(table or d["table"]),
-                      pad=pad, flip=flip, seed=seed, epoch=epoch)
+                      pad=pad, flip=flip, seed=seed, epoch=epoch, out=out)
 
 
 def _bits(t):
@@ -71,6 +71,53 @@ def test_batch_is_bitwise_the_restatement(shape, pad, flip, B):
     assert np.array_equal(_bits(w), want_w.view(np.uint32))
     if B == 64:
         assert set(idx) == set(range(N))                            # every kind of row of the hand-built table was there
+
+
+GRID_ITEMS = 2048 * 256             # BATCH_MAX_GROUPS work-groups of 256 threads: past that many work items a thread takes a second one
+# name -> ((H, W, C), B, pixels per work item, out= one element off the 16-byte grid)
+LAP_CASES = {"vec 8x8x3": ((8, 8, 3), 11000, 4, False), "vec 8x12x4": ((8, 12, 4), 5500, 4, False),
+             "scalar 6x6x1": ((6, 6, 1), 14600, 1, False), "scalar by alignment 8x8x3": ((8, 8, 3), 2750, 1, True)}
+
+
+def _lap_idx(B):
+    """The N samples repeated in a shuffled order, ending on a whole permutation."""
+    rng = np.random.default_rng(B)
+    return np.concatenate([rng.permutation(N) for _ in range(-(-B // N))])[-B:]
+
+
+def _kinds(c, samples):
+    """The kinds of table row among `samples`: unmixed, Mixup (a partner and an empty box), CutMix."""
+    partner, _, box = c["table"]
+    area = (box[:, 1] - box[:, 0]).clip(0) * (box[:, 3] - box[:, 2]).clip(0)
+    return {"unmixed" if partner[s] < 0 else "cutmix" if area[s] > 0 else "mixup" for s in samples}
+
+
+@pytest.mark.parametrize("name", list(LAP_CASES))
+def test_batch_past_the_grid_cap_wraps_the_stride_loop(name):
+    """More work items than a full grid has threads: the end of the batch -- pixels, and y, y2 and w of its last samples, which the
+    thread of a sample's first item writes -- comes from a thread's second lap, and that lap holds unmixed, Mixup and CutMix rows.  A
+    sample's output does not depend on its place, so the reference is the restatement of the N samples, gathered."""
+    (H, W, C), B, vec, off = LAP_CASES[name]
+    per_sample = H * C * (W // vec)
+    assert B * per_sample > GRID_ITEMS and (vec == 4) == (W % 4 == 0 and not off)
+    pad, flip = (2, 2), True
+    c, idx = _case((H, W, C), pad, flip), _lap_idx(B)
+    second_lap = idx[-(-GRID_ITEMS // per_sample):]                 # the samples that lie in the second lap whole
+    assert len(second_lap) >= 16 and _kinds(c, second_lap) == {"unmixed", "mixup", "cutmix"}
+    n = B * C * H * W
+    buf = torch.full((n + 5,), float("nan"), device=DEV)
+    view = buf[off:n + off].view(B, C, H, W)
+    assert view.data_ptr() % 16 == 4 * off and view.is_contiguous()
+    x, y, y2, w = _run(c, idx.tolist(), pad, flip, out=view)
+    assert x.data_ptr() == view.data_ptr()
+    got, rest = view.cpu().numpy(), buf.cpu()
+    assert not np.isnan(got).any()
+    assert torch.isnan(rest[:off]).all() and torch.isnan(rest[n + off:]).all()           # nothing written outside the view
+    want_x, want_y, want_y2, want_w = mr.mix(c["aug"], c["labels"].numpy(), list(range(N)), *c["table"])
+    assert np.array_equal(got.view(np.uint32), want_x[idx].view(np.uint32))
+    assert np.array_equal(y.cpu().numpy(), want_y[idx]) and np.array_equal(y2.cpu().numpy(), want_y2[idx])
+    assert np.array_equal(_bits(w), want_w[idx].view(np.uint32))
+    assert (want_y[idx] != want_y2[idx]).any() and len(set(want_w[second_lap].tolist())) > 3
 
 
 def test_the_table_holds_every_kind_of_row_and_mixing_changes_them():

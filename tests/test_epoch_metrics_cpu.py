@@ -68,6 +68,22 @@ def test_a_missing_class_gives_nan_auc_and_leaves_the_rest():
     assert np.abs(np.array(got[:3]) - np.array(want[:3])).max() <= 1e-12, (got, want)
 
 
+def test_the_past_cap_case_has_valid_rows_on_both_sides_and_a_first_lap_that_counts_less():
+    """What tests/test_epoch_metrics_gpu.py's past-the-cap case relies on: valid rows before and behind sample 2048 * 256, and pair
+    counts over the first lap's rows alone that differ from the full ones in every class, so a histogram or a scatter that stops after
+    its first lap cannot give the full counts.  The dropped rows hold -1.0, below every valid probability: one of them counted as a
+    negative would add the class's positives to its gt."""
+    y, p = mr.past_cap_case()
+    lap, C = mr.HIST_LAP, 3
+    assert lap == 2048 * 256 and len(y) == lap + 700 and p.shape == (len(y), C) and p.dtype == np.float32
+    ok = y >= 0
+    assert ok[:lap].sum() == 900 and ok[lap:].all() and set(y[ok].tolist()) == set(range(C)) and (y[~ok] == -1).all()
+    assert (p[~ok] == -1.0).all() and (p[ok] > 0.0).all()
+    gt, eq = mr.pair_counts(y, p, C)
+    gt1, eq1 = mr.pair_counts(y[:lap], p[:lap], C)
+    assert (gt != gt1).all() and (eq != eq1).all() and (eq > 0).all() and (gt1 > 0).all()
+
+
 def test_from_counts_conventions_and_argument_checks():
     from kanvit.metrics import metrics_from_counts
     # class 2 is never true and never predicted: F1 term 0 with weight 0, no recall term, AUC nan

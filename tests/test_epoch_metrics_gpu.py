@@ -145,6 +145,72 @@ def test_pair_counts_equal_the_brute_force_exactly(case):
         assert not counts[1::2].any() and counts[::2, 0].all()
 
 
+SCAN_THREADS = 256                  # metrics_scan_kernel: one work-group, ceil(C / 256) consecutive classes per thread
+
+
+@pytest.mark.parametrize("case", ["c257", "c300_every_third_empty"])
+def test_pair_counts_with_more_than_one_class_per_scan_thread(case):
+    """C = 257: two classes per thread, thread 128 owns class 256 alone and threads 129..255 own a range that starts past C.
+    C = 300: the same with every third class empty, so offsets repeat inside a thread's range."""
+    rng = np.random.default_rng(12)
+    if case == "c257":
+        C, n = 257, 1500
+        y = rng.integers(0, C, n)
+        y[[3, 700, 1499]] = 256
+    else:
+        C, n = 300, 2000
+        k = rng.integers(0, 200, n)
+        y = k + k // 2                                               # 0, 1, 3, 4, 6, 7, ...: classes 2, 5, 8, ... never occur
+    per = (C + SCAN_THREADS - 1) // SCAN_THREADS
+    assert per >= 2 and (C - 1) // per < SCAN_THREADS - 1              # some thread's range starts past C
+    p = _tied_probs(n, C, 13)
+    counts = _pairs(y, p, C)
+    gt, eq = mr.pair_counts(y, p, C)
+    assert np.array_equal(counts[:, 0], gt) and np.array_equal(counts[:, 1], eq)
+    assert eq.sum() > 0 and gt.sum() > 0
+    if case == "c257":
+        assert (y == 256).sum() >= 3 and counts[256, 0] > 0 and (C - 1) % per == 0 and C - 1 + per > C       # class 256: alone in its range
+    else:
+        assert not counts[2::3].any() and counts[0::3, 0].all() and counts[1::3, 0].all()
+
+
+def test_epoch_metrics_at_a_thousand_classes_equal_the_brute_force_tables():
+    """C = 1000 (four classes per scan thread), 3000 rows fed in batches of 128 as bfloat16: the update kernel and the pair kernel
+    together at an ImageNet-sized head.  The tables are exact integers; compute() is metrics_from_counts of the brute-force tables."""
+    from kanvit.metrics import EpochMetrics, metrics_from_counts
+    C, n, B = 1000, 3000, 128
+    assert (C + SCAN_THREADS - 1) // SCAN_THREADS >= 2
+    rng = np.random.default_rng(14)
+    t, z = _logits(n, C, 15, torch.bfloat16, True)
+    y = rng.permutation(np.arange(n) % C)                            # every class has positives: the AUC is a number
+    zt, yt = t.to(DEV), torch.from_numpy(y).to(DEV)
+    em = EpochMetrics(C, n, DEV)
+    for at in range(0, n, B):
+        em.update(zt[at:at + B], yt[at:at + B])
+    got = em.compute()
+    pred, p = em.preds().cpu().numpy(), em.probs().cpu().numpy()
+    assert np.array_equal(em.labels().cpu().numpy(), y) and np.array_equal(pred, mr.first_argmax(z))
+    cm = mr.confusion(y, pred, C)
+    gt, eq = mr.pair_counts(y, p, C)
+    counts = em.counts.cpu().numpy()
+    assert np.array_equal(em.confusion.cpu().numpy(), cm)
+    assert np.array_equal(counts[:, 0], gt) and np.array_equal(counts[:, 1], eq) and eq.sum() > 0 and gt.all()
+    assert got == metrics_from_counts(cm, gt, eq) and all(np.isfinite(got))
+
+
+def test_pair_counts_past_the_histogram_and_scatter_cap():
+    """n = 2048 * 256 + 700 samples, more than one lap of the histogram and the scatter, of which about 1600 are valid: 900 scattered
+    over the first lap and the 700 of the second (tests/_metrics_ref.past_cap_case; tests/test_epoch_metrics_cpu.py checks that the
+    first lap alone counts differently in every class)."""
+    y, p = mr.past_cap_case()
+    n, C = len(y), 3
+    assert n > mr.HIST_LAP == 2048 * 256 and (y[mr.HIST_LAP:] >= 0).all() and (y[:mr.HIST_LAP] >= 0).any()
+    counts = _pairs(y, p, C)
+    gt, eq = mr.pair_counts(y, p, C)
+    assert np.array_equal(counts[:, 0], gt) and np.array_equal(counts[:, 1], eq), (counts, gt, eq)
+    assert (eq > 0).all() and (gt > 0).all()
+
+
 @pytest.fixture(scope="module")
 def fed():
     """161 rows, 9 classes, with ties, fed to EpochMetrics in one batch and in batches of 7, 1, 120 and 33; computed once."""

@@ -131,6 +131,42 @@ def test_output_off_the_16_byte_grid_takes_the_scalar_form(cifar_case):
     assert torch.isnan(rest[0]) and torch.isnan(rest[n + 1:]).all()         # nothing written outside the view
 
 
+GRID_ITEMS = 2048 * 256             # BATCH_MAX_GROUPS work-groups of 256 threads: past that many work items a thread takes a second one
+# name -> ((H, W, C), B, pixels per work item, out= one element off the 16-byte grid)
+LAP_CASES = {"vec 8x8x3": ((8, 8, 3), 11000, 4, False), "vec 8x12x4": ((8, 12, 4), 5500, 4, False),
+             "scalar 6x6x1": ((6, 6, 1), 14600, 1, False), "scalar by alignment 8x8x3": ((8, 8, 3), 2750, 1, True)}
+
+
+@pytest.mark.parametrize("name", list(LAP_CASES))
+def test_batch_past_the_grid_cap_wraps_the_stride_loop(name):
+    """More work items than a full grid has threads: the end of the batch -- pixels, and the labels and parameters of its last samples,
+    which the thread of a sample's first item writes -- comes from a thread's second lap.  40 stored samples, repeated in a shuffled
+    order; the transform of a sample does not depend on its place, so the reference is the 40 transforms, gathered."""
+    (H, W, C), B, vec, off = LAP_CASES[name]
+    per_sample = H * C * (W // vec)
+    assert B * per_sample > GRID_ITEMS and (B - 1) * per_sample >= GRID_ITEMS           # the last sample lies in the second lap whole
+    assert (vec == 4) == (W % 4 == 0 and not off)
+    N, seed, epoch, pad = 40, 3, 2, (2, 2)
+    images, labels = _images((N, H, W, C) if C > 1 else (N, H, W), 8), (torch.arange(N) * 7) % 100
+    mean, std = [0.5, 0.4, 0.3, 0.2][:C], [0.2, 0.25, 0.3, 0.35][:C]
+    rng = np.random.default_rng(B)
+    idx = torch.from_numpy(np.concatenate([rng.permutation(N) for _ in range(-(-B // N))])[:B])
+    n = B * C * H * W
+    buf = torch.full((n + 5,), float("nan"), device=DEV)
+    view = buf[off:n + off].view(B, C, H, W)
+    assert view.data_ptr() % 16 == 4 * off and view.is_contiguous()
+    x, y, p = _run(images, labels, idx, mean, std, pad, True, seed, epoch, return_params=True, out=view)
+    assert x.data_ptr() == view.data_ptr()
+    got, rest = view.cpu(), buf.cpu()
+    assert not torch.isnan(got).any()
+    assert torch.isnan(rest[:off]).all() and torch.isnan(rest[n + off:]).all()           # nothing written outside the view
+    assert torch.equal(got, ar.augment(images, list(range(N)), mean, std, pad, True, seed, epoch)[idx])
+    assert torch.equal(y.cpu(), labels[idx])
+    par = torch.tensor(ar.params(seed, epoch, range(N), *pad), dtype=torch.int32)
+    assert p.dtype == torch.int32 and torch.equal(p.cpu(), par[idx])
+    assert len({tuple(q) for q in par.tolist()}) > 10                               # the parameters tell the samples apart
+
+
 def test_wrapper_checks_its_operands(cifar_case):
     from kanvit import KanvitError, data, ops
     images = cifar_case["images"][:4].to(DEV)

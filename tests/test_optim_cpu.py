@@ -114,16 +114,16 @@ def test_clip_coefficients_do_not_depend_on_the_order_of_the_sum(lib):
     to the same float32 norm and coefficient.  A case that fails here is replaced, not tolerated.  (The model cases check the same on
     their own gradients, inside the GPU test.)"""
     names = []
-    for name, numels, max_norm, none in R.clip_cases(lib.kanvit_optim_max_tensors()):
+    for name, numels, max_norm, none, steps in R.clip_cases(lib.kanvit_optim_max_tensors()):
         names.append(name)
-        for step in range(R.STEPS):
+        for step in range(steps):
             got = R.coefficient_in_three_orders(R.case_grads(numels, step, none=none), max_norm)
             assert got[0] == got[1] == got[2], (name, step, got)
             if max_norm == 0.5:
                 assert got[0][1] < 1.0, (name, step, got)                    # "clipping binds" means it
             else:
                 assert got[0][1] == 1.0, (name, step, got)
-    assert len(names) == len(set(names)) == sum(c[1] is not None for c in R.CONFIGS.values()) + 3
+    assert len(names) == len(set(names)) == sum(c[1] is not None for c in R.CONFIGS.values()) + 4
     n, value, max_norm = R.HUGE
     got = R.coefficient_in_three_orders([np.full(n, value, np.float32)], max_norm)
     assert got[0] == got[1] == got[2] and 0.0 < got[0][1] < 1.0, got

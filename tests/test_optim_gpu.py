@@ -141,6 +141,68 @@ def test_tensor_counts_on_both_sides_of_the_launch_boundary(extra):
     _assert_equals_host(run, f"{n} tensors")
 
 
+def _lap_partials(step):
+    return np.concatenate([R.sumsq_partials(g) for g in R.case_grads(R.LAP_NUMELS, step, none=())])
+
+
+def test_partials_past_the_begin_kernels_first_lap_over_two_launches():
+    """R.LAP_NUMELS: 343 partials, so threads 0..86 of the begin kernel add a second one; 83 tensors, so the 261-chunk tensor sits in
+    the second launch behind one tiny tensor and writes its partials from offset 80 of the workspace.  Misaligned, its gradient lies
+    4 bytes off the 16-byte grid (the 4-byte path over 261 chunks); aligned, it takes the 16-byte path.  Both equal the host bit for bit."""
+    from kanvit import ops
+    numels, big = tuple(R.LAP_NUMELS), len(R.LAP_NUMELS) - 2
+    assert len(numels) > ops.optim_max_tensors() and big >= ops.optim_max_tensors() and big % 4 == 1
+    assert numels[big] > 256 * R.CHUNK
+    mis = _run("ema_clip", numels=numels, steps=R.LAP_STEPS, none=())
+    ali = _run("ema_clip", numels=numels, misalign=False, steps=R.LAP_STEPS, none=())
+    _assert_equals_host(mis, "lap, misaligned")
+    _assert_equals_host(ali, "lap, aligned")
+    for s in range(R.LAP_STEPS):
+        parts = _lap_partials(s)
+        assert len(parts) == sum((n + R.CHUNK - 1) // R.CHUNK for n in numels) > R.THREADS
+        full, lap0 = R.norm_and_coef(R.total_sumsq(parts), 0.5), R.norm_and_coef(R.total_sumsq(parts[:R.THREADS]), 0.5)
+        assert full[0] != lap0[0] and full[1] != lap0[1], (s, full, lap0)      # a dropped second lap cannot hide
+        assert _same(mis[s][0]["norm"], np.asarray(full[0])) and _same(mis[s][0]["coef"], np.asarray(full[1])) and full[1] < 1.0
+        for key in ("p", "m", "v", "e"):
+            assert all(_same(a, b) for a, b in zip(mis[s][0][key], ali[s][0][key])), (s, key)
+        assert _same(mis[s][0]["norm"], ali[s][0]["norm"]) and _same(mis[s][0]["coef"], ali[s][0]["coef"])
+    assert not _same(mis[0][0]["p"][big], R.case_params(R.LAP_NUMELS)[big])
+
+
+def test_graph_replay_past_the_begin_kernels_first_lap_equals_the_eager_step():
+    numels = R.LAP_NUMELS
+    opt, params, _ = _make("ema_clip", numels)
+    eager = _run("ema_clip", numels=tuple(numels), steps=R.LAP_STEPS, none=())
+    assert len(_lap_partials(0)) > R.THREADS
+    static = []
+    for k, g in enumerate(R.case_grads(numels, 0, none=())):
+        buf = torch.zeros(g.size + k % 4, device=DEV)
+        static.append(buf[k % 4:])
+        params[k].grad = static[-1]
+    side = torch.cuda.Stream(device=DEV)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        opt.step()                                      # a throw-away step, as train.py's captured step takes one
+    torch.cuda.current_stream().wait_stream(side)
+    with torch.no_grad():
+        for p, v in zip(params, R.case_params(numels)):
+            p.copy_(torch.from_numpy(v).to(DEV))
+        for st in opt.state.values():                   # all zeros is a fresh optimizer
+            for t in st.values():
+                t.zero_()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        opt.step()
+    for buf, g in zip(static, R.case_grads(numels, 0, none=())):
+        buf.copy_(torch.from_numpy(g).to(DEV))
+    graph.replay()
+    got = _snapshot(opt, params)
+    for key in ("p", "m", "v", "e"):
+        assert all(_same(a, b) for a, b in zip(got[key], eager[0][0][key])), key
+    assert got["t"] == 1 and _same(got["norm"], eager[0][0]["norm"]) and _same(got["coef"], eager[0][0]["coef"])
+    _assert_equals_host([(got, eager[0][1])], "lap, replayed")       # and the host, whatever the eager run gave
+
+
 def test_huge_gradients_keep_a_finite_norm():
     """1e25 squared overflows float32; the float64 sum of squares does not, and the clipped step stays finite."""
     optim = _optim()

@@ -7,7 +7,7 @@ room for a different, equally valid order of the sums.
 
 e_t is taken per case (one shape, input kind, eps and target kind): the largest absolute error over the rows for `loss_rows` and over
 the entries for the gradient; the ulp term is that of each row's own value.  Every case prints its figures before it asserts; DESIGN.md
-section 4.20 has the measured table per shape and input (all 180 cases inside their bounds: at 130 x 1000 with standard-normal logits
+section 4.20 has the measured table per shape and input (all 252 cases inside their bounds: at 130 x 1000 with standard-normal logits
 the mean loss is off by 4.8e-7 against torch's 9.6e-7 and the gradient by 4.6e-10 against 4.2e-10)."""
 import numpy as np
 import pytest
@@ -18,7 +18,10 @@ from tests import _mix_ref as mr
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SHAPES = [(1, 2, 2), (5, 3, 3), (17, 100, 100), (130, 1000, 1000), (4, 1025, 1032)]
+# (257, 5, 5): one row in the mean kernel's second lap; (1000, 3, 4): four laps and a padded row stride
+SHAPES = [(1, 2, 2), (5, 3, 3), (17, 100, 100), (130, 1000, 1000), (4, 1025, 1032), (257, 5, 5), (1000, 3, 4)]
+MEAN_THREADS = 256                   # soft_ce_mean_kernel: one work-group, thread t adds rows t, t + 256, ...
+assert any(s[0] == MEAN_THREADS + 1 for s in SHAPES) and any(s[0] > 3 * MEAN_THREADS and s[2] > s[1] for s in SHAPES)
 INPUTS = ["normal", "pm80", "equal-row"]
 TARGETS = ["plain", "w0", "w1", "w037", "same-label", "bad-label"]
 
@@ -104,6 +107,29 @@ def test_loss_and_gradient_within_twice_torchs_own_error(shape, kind):
             assert k_dz <= 2 * e_dz + 2.0 ** -22, (eps, tk, k_dz, e_dz)
             if tk == "bad-label":
                 assert rows[B - 1] == 0.0 and not dz[B - 1].any()
+
+
+@pytest.mark.parametrize("B", [1, 130, 256, 257, 1000])
+def test_mean_equals_the_restatement_of_its_own_rows_bitwise(B):
+    """The second kernel given its input: `loss` is mr.mean_rows_f32 of the returned `loss_rows`, bit for bit, below, at and past one
+    lap of 256 rows.  With "bad-label" the last row has a bad label: it counts 0 and the divisor stays B (at B = 257 that row is the
+    whole second lap, so the same batch runs with every label good as well)."""
+    from kanvit import ops
+    C = 5
+    z, _ = _logits(B, C, C + 1, "normal", seed=11)
+    for tk in ("bad-label", "w037"):
+        y1, y2, w = _targets(B, C, tk, seed=11)
+        loss, rows, _ = ops.soft_ce(z, *_device_args(y1, y2, w), label_smoothing=0.1)
+        loss, rows = loss.cpu().numpy(), rows.cpu().numpy()
+        bad = tk == "bad-label"
+        assert rows.dtype == np.float32 and rows.shape == (B,) and (rows[:B - 1] > 0.0).all() and (rows[B - 1] == 0.0) == bad
+        want = mr.mean_rows_f32(rows)
+        assert np.array_equal(loss.view(np.uint32), want.view(np.uint32)), (B, tk, float(loss), float(want))
+        if B > MEAN_THREADS and (not bad or B > MEAN_THREADS + 1):       # what a walk that stops after its first lap would return
+            first_lap = mr.mean_rows_f32(rows[:MEAN_THREADS]) * np.float32(MEAN_THREADS) / np.float32(B)
+            assert rows[MEAN_THREADS:].sum() > 0.0 and first_lap != want, (B, tk)
+        if bad and B > 1:                                # the bad row is in the divisor: the mean of the good rows alone is another number
+            assert mr.mean_rows_f32(rows[:B - 1]) != want
 
 
 @pytest.fixture(scope="module")
