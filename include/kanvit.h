@@ -599,6 +599,38 @@ int kanvit_resample_u8(const uint8_t* images, const int64_t* labels, const int64
                        const int64_t* partner, const float* weight, const int32_t* box, float* out, int64_t* y_out, int64_t* y2_out,
                        float* w_out, int64_t N, int64_t B, int H, int W, int C, int OH, int OW, void* stream);
 
+/* ---- Random Erasing on the same pass (kanvit/data.py: erase_table, normal_table; csrc/batch_u8.hip) ----------------------
+ * kanvit_resample_u8 with a per-sample erase box applied BEFORE mixing (torchvision's RandomErasing / timm's, per sample, at the
+ * output resolution, after normalisation).  Every argument up to OW is kanvit_resample_u8's, with its meaning and its checks.
+ * erase [N][4] int32 = (y0, y1, x0, x1), half open, in OUTPUT coordinates, indexed by the DATASET index like the other tables.  With
+ * s = idx[b] and a(b,c,y,x) kanvit_resample_u8's value of s before mixing,
+ *   a'(b,c,y,x) = fill(s,c,y,x)   where erase[s] has y0 <= y < y1 and x0 <= x < x1
+ *               = a(b,c,y,x)      otherwise
+ * and p' is the same for the partner j = partner[s]: j's resampled value under j's OWN erase row and j's own fill.  The three mixing
+ * rules (unmixed / CutMix look-up / Mixup fadd(fmul(w, a'), fmul(1 - w, p'))) then run on a' and p'; labels and weights are not
+ * touched.  The test is a comparison on output coordinates and forms no sum of table entries: any int32 row is safe, one with
+ * y0 >= y1 or x0 >= x1 erases nothing, and one that reaches outside [0, OH) x [0, OW) is clipped by the comparison.  The erase row
+ * of an idx or partner outside [0, N) is never read (such a sample stays padding with label -1, such a partner leaves the row
+ * unmixed, but erased).
+ * The fill does no floating-point arithmetic:
+ *   noise == NULL (noise_len == 0):  fill = 0.0f  -- the dataset mean, normalised (torchvision's value=0, timm's "const");
+ *   otherwise (timm's "pixel"):      fill = noise[ h >> (64 - log2 noise_len) ],
+ *                                    h = mix( mix(noise_key + s) + ((c * OH + y) * OW + x) ),  all mod 2^64, mix() as above;
+ * noise [noise_len] fp32, noise_len a power of two in 2..65536 (data.normal_table: standard-normal quantiles), noise_key any value
+ * (data.erase_noise_key derives it from (seed, epoch)).  The fill depends on (noise_key, s, c, y, x) only -- not on B, the
+ * position in the batch, the rank, or whether s appears as a sample or as a partner -- and the same uint64 operations on the host
+ * give the same bits.  A row of a work item that lies wholly inside the box loads no source pixel.
+ * erase == NULL: the call is kanvit_resample_u8 (the same kernels, the same arguments); noise must then be NULL.  Stores, the
+ * launch (one, no atomics, no workspace, no synchronisation: capturable) and B = 0 as there.  KANVIT_EINVAL (named in
+ * kanvit_last_error, before any device call) for kanvit_resample_u8's cases and for noise_len not 0 or a power of two in 2..65536,
+ * noise without erase, noise without noise_len or noise_len without noise, a misaligned erase / noise.
+ * kanvit_erase_u8_supported is the shape check as a pure host function (1 / 0).  Additive: the ABI version stays 7. */
+int kanvit_erase_u8_supported(int64_t N, int H, int W, int C, int OH, int OW, int noise_len);
+int kanvit_erase_u8(const uint8_t* images, const int64_t* labels, const int64_t* idx, const float* lut, const int32_t* crop,
+                    const int64_t* partner, const float* weight, const int32_t* box, float* out, int64_t* y_out, int64_t* y2_out, float* w_out,
+                    int64_t N, int64_t B, int H, int W, int C, int OH, int OW, const int32_t* erase, const float* noise, int noise_len,
+                    uint64_t noise_key, void* stream);
+
 /* ---- soft-target cross-entropy, loss and gradient in one pass (ops.soft_cross_entropy; csrc/soft_ce.hip) -----------------
  * The training loss for Mixup / CutMix pairs and label smoothing.  logits [B][C] fp32, unit column stride, row stride ld >= C;
  * y1 [B] int64; y2 [B] int64 and w [B] fp32 together or both NULL (NULL: w = 1); eps in [0, 1).

@@ -14,8 +14,8 @@
 // W/VEC * C lanes of one image row read one contiguous W*C-byte stretch of the NHWC source between them, and every lane stores
 // VEC * 4 bytes (16 in the vector form) of a contiguous output row.
 //
-// mix_u8_kernel (Mixup / CutMix) and resample_u8_kernel (bilinear resize, RandomResizedCrop) are forms of the same pass, further down;
-// the three entry points share one host path (batch_check_shape, batch_check_operands, batch_vec_form, batch_grid), below the kernels.
+// mix_u8_kernel (Mixup / CutMix) and resample_u8_kernel (bilinear resize, RandomResizedCrop, Random Erasing) are forms of the same pass,
+// further down; the four entry points share one host path (batch_check_shape, batch_check_operands, batch_vec_form, batch_grid), below the kernels.
 #include "../../include/kanvit.h"
 #include "kanvit_common.h"
 
@@ -375,8 +375,54 @@ struct ResCols {
     }
 };
 
-template <int VEC, bool MIX>
-__global__ __launch_bounds__(256) void resample_u8_kernel(const ResArgs a) {
+// ---------------------------------------------------------------------------------------------------------------------------
+// Random Erasing on the same pass (kanvit/data.py: erase_table).  The epoch's erase table names, per DATASET index s, a box
+// (y0, y1, x0, x1), half open, in OUTPUT coordinates; inside it the resampled value of s is replaced by a fill BEFORE mixing, and the
+// partner is erased under ITS OWN row before it is pasted or blended in.  The fill is 0 (the dataset mean, normalised) or, with a noise
+// table of T = 2^k entries, noise[h >> (64 - k)], h = mix(mix(noise_key + s) + ((c OH + y) OW + x)): a look-up, no floating-point
+// arithmetic, a function of (noise_key, s, c, y, x) alone.  The box test is a comparison on output coordinates -- no sums of table
+// entries -- so any int32 row is safe, and an inverted or empty one erases nothing.
+// Erasing is a compile-time parameter of the one body (resample_u8_body); the erasing forms take their arguments as EraseArgs, the
+// others keep ResArgs, their kernel name and with them the registers they had before erasing existed.
+// The noise table is read through the caches, not staged in LDS: at the recipe's defaults 4 % of the pixels are erased, so most
+// work-groups never touch it, while staging would cost EVERY work-group a fill four times the look-up table's (16 KB at T = 4096)
+// and could not hold the 256 KB the ABI allows; the table is shared by all work-groups and stays in L2.
+struct EraseArgs : ResArgs {
+    const int* erase;           // [N][4]
+    const float* noise;         // [2^(64 - noise_shift)] or null: the fill is 0
+    unsigned long long noise_key;
+    int noise_shift;
+};
+
+// One sample's erase row against the columns x0 .. x0 + VEC - 1 of a work item.
+template <int VEC>
+struct ResErase {
+    int y0, y1;
+    unsigned cols;              // bit e: column x0 + e lies inside the box
+    unsigned long long base;    // mix(noise_key + s)
+
+    __device__ __forceinline__ void init(const EraseArgs& a, long long s, bool valid, int ox0) {
+        y0 = y1 = 0, cols = 0, base = 0;
+        if (!valid) return;     // no sample: no row is read
+        const int* q = a.erase + 4 * s;
+        y0 = q[0], y1 = q[1];
+        const int ex0 = q[2], ex1 = q[3];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) cols |= (ox0 + e >= ex0 && ox0 + e < ex1) ? 1u << e : 0u;
+        base = aug_mix(a.noise_key + (unsigned long long)s);
+    }
+    __device__ __forceinline__ bool hits(int oy) const { return cols != 0 && oy >= y0 && oy < y1; }     // some column of row oy is erased
+    __device__ __forceinline__ bool whole() const { return cols == (1u << VEC) - 1; }                    // ... then: all of them are
+    __device__ __forceinline__ void fill(const EraseArgs& a, int c, int oy, int ox0, float* v) const {
+        const unsigned long long at = ((unsigned long long)c * a.OH + oy) * a.OW + ox0;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e)
+            if (cols >> e & 1u) v[e] = a.noise ? a.noise[aug_mix(base + (at + e)) >> a.noise_shift] : 0.f;
+    }
+};
+
+template <int VEC, bool MIX, bool ERASE>
+__device__ __forceinline__ void resample_u8_body(const std::conditional_t<ERASE, EraseArgs, ResArgs> a) {
     __shared__ float lut[4 * 256];
     for (int i = threadIdx.x; i < a.C * 256; i += 256) lut[i] = a.lut[i];
     __syncthreads();
@@ -401,6 +447,8 @@ __global__ __launch_bounds__(256) void resample_u8_kernel(const ResArgs a) {
             if (sample_ok && a.labels) lab = a.labels[s];
             if (a.y_out) a.y_out[b] = lab;
         }
+        [[maybe_unused]] ResErase<VEC> own_er, par_er;    // ... and their erase rows
+        if constexpr (ERASE) own_er.init(a, s, sample_ok, x0);
         [[maybe_unused]] ResCols<VEC> par;                // the partner under ITS crop row
         [[maybe_unused]] bool mixed = false, cut = false;
         [[maybe_unused]] int by0 = 0, by1 = 0, bx0 = 0, bx1 = 0;
@@ -419,7 +467,10 @@ __global__ __launch_bounds__(256) void resample_u8_kernel(const ResArgs a) {
                 by0 = bx[0], by1 = bx[1], bx0 = bx[2], bx1 = bx[3];
                 cut = by0 < by1 && bx0 < bx1;
                 mixed = !cut || (x0 < bx1 && x0 + VEC > bx0);       // CutMix columns outside the box keep a
-                if (mixed) par.init(a, l, j, true, (int)c, x0);
+                if (mixed) {
+                    par.init(a, l, j, true, (int)c, x0);
+                    if constexpr (ERASE) par_er.init(a, j, true, x0);
+                }
             }
         }
         const int oy0 = (int)og * RES_ROWS, oy_end = min(oy0 + RES_ROWS, a.OH);
@@ -430,11 +481,23 @@ __global__ __launch_bounds__(256) void resample_u8_kernel(const ResArgs a) {
 #pragma unroll 1
             for (int oy = oy0; oy < oy_end; ++oy, o += a.OW) {
                 float v[VEC];
-                own.template row<WIN>(a, l, oy, v);
+                if constexpr (ERASE) {                   // a row of the item that lies wholly inside the box is not fetched
+                    const bool hit = own_er.hits(oy);
+                    if (!(hit && own_er.whole())) own.template row<WIN>(a, l, oy, v);
+                    if (hit) own_er.fill(a, (int)c, oy, x0, v);
+                } else {
+                    own.template row<WIN>(a, l, oy, v);
+                }
                 if constexpr (MIX) {
                     if (mixed && (!cut || (oy >= by0 && oy < by1))) {        // CutMix rows outside the box keep a
                         float p[VEC];
-                        par.template row<WIN>(a, l, oy, p);
+                        if constexpr (ERASE) {
+                            const bool hit = par_er.hits(oy);
+                            if (!(hit && par_er.whole())) par.template row<WIN>(a, l, oy, p);
+                            if (hit) par_er.fill(a, (int)c, oy, x0, p);
+                        } else {
+                            par.template row<WIN>(a, l, oy, p);
+                        }
 #pragma unroll
                         for (int e = 0; e < VEC; ++e) {
                             if (cut)
@@ -468,8 +531,21 @@ __global__ __launch_bounds__(256) void resample_u8_kernel(const ResArgs a) {
     }
 }
 
+// The one body under two kernel names: resample_u8_kernel<VEC, MIX> is the ERASE = false form and keeps the name, the argument type
+// and the registers it had before erasing existed; erase_u8_kernel<VEC, MIX> is the ERASE = true form.  The body takes the arguments
+// by value: by reference the <4, true> form needs one more VGPR and spills SGPRs.
+template <int VEC, bool MIX>
+__global__ __launch_bounds__(256) void resample_u8_kernel(const ResArgs a) {
+    resample_u8_body<VEC, MIX, false>(a);
+}
+
+template <int VEC, bool MIX>
+__global__ __launch_bounds__(256) void erase_u8_kernel(const EraseArgs a) {
+    resample_u8_body<VEC, MIX, true>(a);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
-// The host path the three entry points share: shape and operand checks, the AugArgs fill, the store form and the grid.
+// The host path the entry points share: shape and operand checks, the AugArgs fill, the store form and the grid.
 int batch_check_shape(const char* who, int64_t N, int H, int W, int C) {
     if (N < 1) return kv_fail(KANVIT_EINVAL, "%s: N=%lld: the dataset holds at least one image", who, (long long)N);
     if (C < 1 || C > 4) return kv_fail(KANVIT_EINVAL, "%s: C=%d must be in 1..4 (the look-up table is staged as C x 1 KB)", who, C);
@@ -490,7 +566,15 @@ int res_check_shape(const char* who, int64_t N, int H, int W, int C, int OH, int
     return 0;
 }
 
-// What the three launches check of their batch size and pointers.  Pointers an entry point does not have are passed null (flip: 0);
+// noise_len: 0 (no table: the fill is 0) or the table's length, a power of two so that the top bits of a hash index it
+int erase_check_shape(const char* who, int64_t N, int H, int W, int C, int OH, int OW, int noise_len) {
+    if (int rc = res_check_shape(who, N, H, W, C, OH, OW)) return rc;
+    if (noise_len != 0 && (noise_len < 2 || noise_len > 65536 || (noise_len & (noise_len - 1))))
+        return kv_fail(KANVIT_EINVAL, "%s: noise_len=%d must be a power of two in 2..65536 (or 0 with a null noise: the fill is 0)", who, noise_len);
+    return 0;
+}
+
+// What the launches check of their batch size and pointers.  Pointers an entry point does not have are passed null (flip: 0);
 // y_names is how it names its label outputs.  Returns KANVIT_EINVAL, 0 for the empty batch (B == 0: nothing to launch, whatever the
 // pointers) or BATCH_GO.
 constexpr int BATCH_GO = 1;
@@ -534,6 +618,77 @@ constexpr long long BATCH_MAX_GROUPS = 2048;
 dim3 batch_grid(long long total) {
     const long long blocks = (total + 255) / 256;
     return dim3((unsigned)(blocks > BATCH_MAX_GROUPS ? BATCH_MAX_GROUPS : blocks));
+}
+
+template <int VEC, bool MIX, bool ERASE>
+void res_dispatch(const EraseArgs& a, hipStream_t st) {
+    const dim3 grid = batch_grid(a.total), block(256);
+    if constexpr (ERASE)
+        hipLaunchKernelGGL((erase_u8_kernel<VEC, MIX>), grid, block, 0, st, a);
+    else
+        hipLaunchKernelGGL((resample_u8_kernel<VEC, MIX>), grid, block, 0, st, static_cast<const ResArgs&>(a));       // the ResArgs part alone
+}
+
+template <bool ERASE>
+void res_dispatch(const EraseArgs& a, bool vec, bool mix, hipStream_t st) {
+    if (vec && mix)
+        res_dispatch<4, true, ERASE>(a, st);
+    else if (vec)
+        res_dispatch<4, false, ERASE>(a, st);
+    else if (mix)
+        res_dispatch<1, true, ERASE>(a, st);
+    else
+        res_dispatch<1, false, ERASE>(a, st);
+}
+
+// kanvit_resample_u8 (erase, noise null; noise_len, noise_key 0) and kanvit_erase_u8: one set of checks, one launch.  Without an erase
+// table both launch the same kernels with the same arguments.
+int res_launch(const char* who, const uint8_t* images, const int64_t* labels, const int64_t* idx, const float* lut, const int32_t* crop,
+               const int64_t* partner, const float* weight, const int32_t* box, float* out, int64_t* y_out, int64_t* y2_out, float* w_out, int64_t N,
+               int64_t B, int H, int W, int C, int OH, int OW, const int32_t* erase, const float* noise, int noise_len, uint64_t noise_key,
+               void* stream) {
+    if (int rc = erase_check_shape(who, N, H, W, C, OH, OW, noise_len)) return rc;
+    if (B > (1ll << 62) / ((long long)C * OH * OW)) return kv_fail(KANVIT_EINVAL, "%s: B=%lld: too many output pixels for one launch", who, (long long)B);
+    const int rc = batch_check_operands(who, "y_out / y2_out", B, 0, images, labels, idx, lut, crop, partner, weight, box, out, y_out, y2_out, w_out,
+                                        nullptr);
+    if (rc != BATCH_GO) return rc;
+    const bool mix = partner || weight || box;
+    if (mix && (!partner || !weight || !box))
+        return kv_fail(KANVIT_EINVAL, "%s: null %s (the three mix tables partner/weight/box come together or not at all)", who,
+                       !partner ? "partner" : !weight ? "weight" : "box");
+    if ((y2_out || w_out) && !mix) return kv_fail(KANVIT_EINVAL, "%s: y2_out / w_out without the mix tables", who);
+    if (noise && !erase) return kv_fail(KANVIT_EINVAL, "%s: noise without erase (the noise fills the erase boxes)", who);
+    if ((noise != nullptr) != (noise_len != 0))
+        return kv_fail(KANVIT_EINVAL, "%s: noise_len=%d with %s noise (a table and its length come together; both absent: the fill is 0)", who,
+                       noise_len, noise ? "a" : "a null");
+    if ((uintptr_t)erase & 3 || (uintptr_t)noise & 3) return kv_fail(KANVIT_EINVAL, "%s: erase / noise is not aligned to its element size", who);
+    EraseArgs a;
+    a.erase = erase;
+    a.noise = noise;
+    a.noise_key = noise_key;
+    a.noise_shift = 64;
+    for (int t = noise_len; t > 1; t >>= 1) --a.noise_shift;       // 64 - log2(noise_len); not used without a table
+    a.images = images;
+    a.labels = (const long long*)labels;
+    a.idx = (const long long*)idx;
+    a.lut = lut;
+    a.crop = crop;
+    a.partner = (const long long*)partner;
+    a.weight = weight;
+    a.box = box;
+    a.out = out;
+    a.y_out = (long long*)y_out;
+    a.y2_out = (long long*)y2_out;
+    a.w_out = w_out;
+    a.N = N, a.B = B, a.H = H, a.W = W, a.C = C, a.OH = OH, a.OW = OW;
+    const bool vec = batch_vec_form(OW, out);
+    a.total = (long long)B * C * ((OH + RES_ROWS - 1) / RES_ROWS) * (vec ? OW / 4 : OW);       // items of RES_ROWS rows by 4 (or 1) columns
+    if (erase)
+        res_dispatch<true>(a, vec, mix, (hipStream_t)stream);
+    else
+        res_dispatch<false>(a, vec, mix, (hipStream_t)stream);
+    KV_LAUNCH_CHECK(erase ? "erase_u8_kernel" : "resample_u8_kernel");
+    return 0;
 }
 
 }  // namespace
@@ -597,46 +752,20 @@ int kanvit_resample_u8_supported(int64_t N, int H, int W, int C, int OH, int OW)
 int kanvit_resample_u8(const uint8_t* images, const int64_t* labels, const int64_t* idx, const float* lut, const int32_t* crop,
                        const int64_t* partner, const float* weight, const int32_t* box, float* out, int64_t* y_out, int64_t* y2_out,
                        float* w_out, int64_t N, int64_t B, int H, int W, int C, int OH, int OW, void* stream) {
-    const char* who = "kanvit_resample_u8";
-    if (int rc = res_check_shape(who, N, H, W, C, OH, OW)) return rc;
-    if (B > (1ll << 62) / ((long long)C * OH * OW)) return kv_fail(KANVIT_EINVAL, "kanvit_resample_u8: B=%lld: too many output pixels for one launch", (long long)B);
-    const int rc = batch_check_operands(who, "y_out / y2_out", B, 0, images, labels, idx, lut, crop, partner, weight, box, out, y_out, y2_out, w_out,
-                                        nullptr);
-    if (rc != BATCH_GO) return rc;
-    const bool mix = partner || weight || box;
-    if (mix && (!partner || !weight || !box))
-        return kv_fail(KANVIT_EINVAL, "kanvit_resample_u8: null %s (the three mix tables partner/weight/box come together or not at all)",
-                       !partner ? "partner" : !weight ? "weight" : "box");
-    if ((y2_out || w_out) && !mix) return kv_fail(KANVIT_EINVAL, "kanvit_resample_u8: y2_out / w_out without the mix tables");
-    ResArgs a;
-    a.images = images;
-    a.labels = (const long long*)labels;
-    a.idx = (const long long*)idx;
-    a.lut = lut;
-    a.crop = crop;
-    a.partner = (const long long*)partner;
-    a.weight = weight;
-    a.box = box;
-    a.out = out;
-    a.y_out = (long long*)y_out;
-    a.y2_out = (long long*)y2_out;
-    a.w_out = w_out;
-    a.N = N, a.B = B, a.H = H, a.W = W, a.C = C, a.OH = OH, a.OW = OW;
-    const bool vec = batch_vec_form(OW, out);
-    a.total = (long long)B * C * ((OH + RES_ROWS - 1) / RES_ROWS) * (vec ? OW / 4 : OW);       // items of RES_ROWS rows by 4 (or 1) columns
-    const dim3 grid = batch_grid(a.total), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (vec && mix)
-        hipLaunchKernelGGL((resample_u8_kernel<4, true>), grid, block, 0, st, a);
-    else if (vec)
-        hipLaunchKernelGGL((resample_u8_kernel<4, false>), grid, block, 0, st, a);
-    else if (mix)
-        hipLaunchKernelGGL((resample_u8_kernel<1, true>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((resample_u8_kernel<1, false>), grid, block, 0, st, a);
-    KV_LAUNCH_CHECK("resample_u8_kernel");
-    return 0;
+    return res_launch("kanvit_resample_u8", images, labels, idx, lut, crop, partner, weight, box, out, y_out, y2_out, w_out, N, B, H, W, C, OH, OW,
+                      nullptr, nullptr, 0, 0, stream);
+}
+
+int kanvit_erase_u8_supported(int64_t N, int H, int W, int C, int OH, int OW, int noise_len) {
+    return erase_check_shape("kanvit_erase_u8_supported", N, H, W, C, OH, OW, noise_len) == 0 ? 1 : 0;
+}
+
+int kanvit_erase_u8(const uint8_t* images, const int64_t* labels, const int64_t* idx, const float* lut, const int32_t* crop,
+                    const int64_t* partner, const float* weight, const int32_t* box, float* out, int64_t* y_out, int64_t* y2_out, float* w_out,
+                    int64_t N, int64_t B, int H, int W, int C, int OH, int OW, const int32_t* erase, const float* noise, int noise_len,
+                    uint64_t noise_key, void* stream) {
+    return res_launch("kanvit_erase_u8", images, labels, idx, lut, crop, partner, weight, box, out, y_out, y2_out, w_out, N, B, H, W, C, OH, OW, erase,
+                      noise, noise_len, noise_key, stream);
 }
 
 }  // extern "C"
-

@@ -134,6 +134,8 @@ SYMBOLS = {
     "kanvit_mix_u8": (C.c_int, [_P] * 11 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _P]),
     "kanvit_resample_u8_supported": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kanvit_resample_u8": (C.c_int, [_P] * 12 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "kanvit_erase_u8_supported": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "kanvit_erase_u8": (C.c_int, [_P] * 12 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_uint64, _P]),
     "kanvit_soft_ce": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int, C.c_float, _P, _P, _P, _P]),
     "kanvit_metrics_update": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int64, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
     "kanvit_metrics_auc_pairs_workspace": (C.c_size_t, [C.c_int64, C.c_int]),

@@ -18,6 +18,11 @@ Another output size and RandomResizedCrop ride on it too: GpuDataset(out_size=..
 ops.resample_u8, the bilinear resize of a per-sample box named by crop_table -- again one table per epoch drawn from (seed, epoch) and
 indexed by dataset index.  With the stored size and the padded crop nothing changes.
 
+Random Erasing rides on it as well: GpuDataset(erase=...) produces every batch with ops.erase_u8, which replaces a per-sample box
+named by erase_table -- one more table per epoch drawn from (seed, epoch) and indexed by dataset index -- by zeros or by
+standard-normal noise (normal_table, looked up through a hash of (seed, epoch, sample, channel, pixel)) before the sample is mixed,
+and erases the partner under the partner's own box.
+
 The file format is an .npz: x_train uint8 [N, H, W, C] (or [N, H, W] for one channel), y_train of any integer type, optionally
 x_test / y_test, optionally mean / std ([C], on the 0-1 scale; computed from x_train when absent).  tools/cifar_to_npz.py writes
 one from an unpacked CIFAR python-pickle directory.
@@ -200,6 +205,81 @@ def crop_table(n: int, epoch: int, seed: int, hw, mode: str, pad=(0, 0), flip: b
     return torch.from_numpy(rows.astype(np.int32))
 
 
+_ERASE_TABLE_KEY = 0x65726173655F7462   # "erase_tb": the erase table's generator, apart from the other tables'
+_ERASE_NOISE_KEY = 0x65726173655F6E7A   # "erase_nz": the key of the noise hash
+_ERASE_ATTEMPTS = 10                    # torchvision's RandomErasing.get_params tries ten boxes before it gives up
+
+
+def erase_table(n: int, epoch: int, seed: int, hw, prob: float = 0.25, scale=(0.02, 1.0 / 3.0), ratio=(0.3, 1.0 / 0.3)) -> torch.Tensor:
+    """The Random Erasing table of `epoch` for ops.erase_u8: int32 [n, 4] on the CPU, row s = (y0, y1, x0, x1), half open, for DATASET
+    index s, in the coordinates of the OUTPUT of size hw = (OH, OW) (torchvision's RandomErasing.get_params / timm's RandomErasing,
+    per sample).  Like mix_table and crop_table it is a function of its arguments alone: not of the batch size, the rank or the world
+    size.
+
+    The draws come from ONE NumPy PCG64 generator seeded by (seed, epoch) under a key of its own; every column is a g.random(n) in
+    float64 for all n rows in index order, whatever the flags: one u_p, ten area fractions a_k (area = OH OW (lo + (hi - lo) a_k) over
+    `scale`), ten ratios r_k = exp(log lo + (log hi - log lo) u_k) over `ratio`, one row position, one column position.  A row is
+    erased iff u_p < prob and an attempt fits: attempt k gives h = rint(sqrt(area r)), w = rint(sqrt(area / r)); the first with
+    1 <= h < OH and 1 <= w < OW is taken and placed at floor(u (OH - h + 1)), floor(u (OW - w + 1)).  Every other row is all zero
+    (nothing is erased: torchvision's no-op).  Bad arguments are a ValueError."""
+    OH, OW = int(hw[0]), int(hw[1])
+    if n < 1 or OH < 1 or OW < 1:
+        raise ValueError(f"erase_table: n={n}, hw={tuple(hw)}")
+    prob = float(prob)
+    s_lo, s_hi, r_lo, r_hi = float(scale[0]), float(scale[1]), float(ratio[0]), float(ratio[1])
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"erase_table: prob={prob} is not a probability")
+    if not 0 < s_lo <= s_hi <= 1 or not 0 < r_lo <= r_hi or not np.isfinite(r_hi):
+        raise ValueError(f"erase_table: scale={tuple(scale)} and ratio={tuple(ratio)} are (lo, hi) with 0 < lo <= hi, and scale's hi is at most 1")
+    base = _mix((_mix(int(seed) & _M64) + int(epoch)) & _M64)
+    g = np.random.Generator(np.random.PCG64(_mix(base ^ _ERASE_TABLE_KEY)))
+    chosen = g.random(n) < prob
+    area = [OH * OW * (s_lo + (s_hi - s_lo) * g.random(n)) for _ in range(_ERASE_ATTEMPTS)]
+    rat = [np.exp(np.log(r_lo) + (np.log(r_hi) - np.log(r_lo)) * g.random(n)) for _ in range(_ERASE_ATTEMPTS)]
+    uy, ux = g.random(n), g.random(n)
+    bh, bw = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    for a, r in zip(area, rat):
+        h, w = np.rint(np.sqrt(a * r)).astype(np.int64), np.rint(np.sqrt(a / r)).astype(np.int64)
+        take = (bh == 0) & (h >= 1) & (h < OH) & (w >= 1) & (w < OW)
+        bh, bw = np.where(take, h, bh), np.where(take, w, bw)
+    y0 = np.floor(uy * (OH - bh + 1)).astype(np.int64)
+    x0 = np.floor(ux * (OW - bw + 1)).astype(np.int64)
+    erased = chosen & (bh > 0)
+    rows = np.where(erased[:, None], np.stack([y0, y0 + bh, x0, x0 + bw], 1), 0)
+    return torch.from_numpy(rows.astype(np.int32))
+
+
+def normal_table(T: int = 4096) -> torch.Tensor:
+    """The noise table of ops.erase_u8's "pixel" fill: float32 [T] on the CPU, entry k the standard-normal quantile at (k + 0.5) / T
+    (statistics.NormalDist().inv_cdf in float64, rounded once).  A uniform index into it is a standard-normal draw quantised to T
+    levels: increasing, antisymmetric (t[k] == -t[T - 1 - k]), std 0.99984 and largest value 3.668 at T = 4096.  T is a power of two
+    in 2..65536, so that the top bits of a hash index it."""
+    from statistics import NormalDist
+    T = int(T)
+    if T < 2 or T > 65536 or T & (T - 1):
+        raise ValueError(f"normal_table: T={T} is a power of two in 2..65536")
+    inv = NormalDist().inv_cdf
+    return torch.from_numpy(np.array([inv((k + 0.5) / T) for k in range(T)], np.float64).astype(np.float32))
+
+
+def erase_noise_key(seed: int, epoch: int) -> int:
+    """The noise_key of ops.erase_u8 for (seed, epoch): the hash chain of the tables, under a key of its own."""
+    return _mix(_mix((_mix(int(seed) & _M64) + int(epoch)) & _M64) ^ _ERASE_NOISE_KEY)
+
+
+def _erase_config(erase) -> dict:
+    """GpuDataset's `erase` argument, checked: prob, scale, ratio as erase_table takes them and mode "pixel" or "const"."""
+    cfg = dict(prob=0.25, scale=(0.02, 1.0 / 3.0), ratio=(0.3, 1.0 / 0.3), mode="pixel")
+    if not isinstance(erase, dict) or not set(erase) <= set(cfg):
+        raise ValueError(f"GpuDataset: erase={erase!r} is a dict with keys out of {sorted(cfg)}")
+    cfg.update(erase)
+    if cfg["mode"] not in ("pixel", "const"):
+        raise ValueError(f"GpuDataset: erase mode '{cfg['mode']}' is 'pixel' or 'const'")
+    cfg["scale"], cfg["ratio"] = tuple(cfg["scale"]), tuple(cfg["ratio"])
+    erase_table(1, 0, 0, (2, 2), cfg["prob"], cfg["scale"], cfg["ratio"])        # its argument checks, once, before any epoch
+    return cfg
+
+
 def _fail(path, key, what):
     raise ValueError(f"{path}: '{key}' {what}")
 
@@ -267,10 +347,13 @@ class GpuDataset:
     """Images (uint8, NHWC) and labels (int64) resident on `device`; batches() yields normalised, augmented float32 NCHW batches."""
 
     def __init__(self, images, labels, mean, std, device, pad=0, flip=False, out_size=None, crop="pad", rrc_scale=(0.08, 1.0),
-                 rrc_ratio=(3.0 / 4.0, 4.0 / 3.0)):
+                 rrc_ratio=(3.0 / 4.0, 4.0 / 3.0), erase=None):
         """out_size (an int or (OH, OW)): the size of the batches, resized from the stored images by ops.resample_u8; None: the stored
         size.  crop: "pad" (the random crop out of the zero-padded image, `pad` and `flip`) or "rrc" (RandomResizedCrop over rrc_scale /
-        rrc_ratio, with `flip`; `pad` is then unused).  With the stored size and crop="pad" nothing changes: ops.augment_u8 / ops.mix_u8."""
+        rrc_ratio, with `flip`; `pad` is then unused).  With the stored size and crop="pad" nothing changes: ops.augment_u8 / ops.mix_u8.
+        erase: Random Erasing -- a dict of prob, scale, ratio (erase_table's; defaults 0.25, (0.02, 1/3), (0.3, 1/0.3)) and mode
+        ("pixel": standard-normal noise per value, the default; "const": zeros, the normalised mean).  Every batch then comes from
+        ops.erase_u8, at any size; None (default): nothing changes."""
         images = torch.as_tensor(images)
         labels = torch.as_tensor(labels)
         if images.dtype != torch.uint8 or images.dim() not in (3, 4):
@@ -290,11 +373,13 @@ class GpuDataset:
             (int(out_size), int(out_size)) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
         if min(self.out_hw) < 1:
             raise ValueError(f"GpuDataset: out_size={out_size} must be positive")
-        self.resample = crop != "pad" or self.out_hw != self.chw[1:]     # False: today's path, call for call
+        self.erase = None if erase is None else _erase_config(erase)
+        self.resample = crop != "pad" or self.out_hw != self.chw[1:] or self.erase is not None      # False: augment_u8 / mix_u8
         self.device = torch.device(device)
         self.images = images.contiguous().to(self.device)
         self.labels = labels.to(torch.int64).contiguous().to(self.device)
         self.lut = self.lut_cpu.to(self.device)
+        self.noise = normal_table().to(self.device) if self.erase is not None and self.erase["mode"] == "pixel" else None
 
     @classmethod
     def from_npz(cls, path, split, device, pad=0, flip=False, **resample):
@@ -305,7 +390,7 @@ class GpuDataset:
 
     @classmethod
     def from_arrays(cls, blob, path, split, device, pad=0, flip=False, **resample):
-        """`resample`: out_size, crop, rrc_scale, rrc_ratio, as the constructor takes them."""
+        """`resample`: out_size, crop, rrc_scale, rrc_ratio, erase, as the constructor takes them."""
         if f"x_{split}" not in blob:
             _fail(path, f"x_{split}", "is missing")
         mean, std = (blob["mean"], blob["std"]) if "mean" in blob else channel_stats(blob["x_train"])
@@ -332,7 +417,10 @@ class GpuDataset:
 
         A dataset with an out_size of its own or crop="rrc" yields x float32 [b, C, OH, OW] from one ops.resample_u8 launch per batch
         instead: the epoch's crop table (crop_table) is drawn, checked and uploaded once, like the mix table, which is then drawn
-        at hw = out_size; the evaluation transform (crop="pad", pad 0, no flip) passes no table at all."""
+        at hw = out_size; the evaluation transform (crop="pad", pad 0, no flip) passes no table at all.
+
+        A dataset with `erase` goes the same way through ops.erase_u8: the epoch's erase table (erase_table at hw = out_size) is drawn,
+        checked and uploaded once like the others; the noise table went to the device with the dataset."""
         if batch_size < 1:
             raise ValueError(f"GpuDataset.batches: batch_size={batch_size}")
         idx = epoch_indices(len(self), epoch, seed, rank, world, shuffle)
@@ -358,7 +446,7 @@ class GpuDataset:
         return tuple(t.contiguous().to(self.device) for t in table)
 
     def _resampled(self, idx, batch_size, epoch, seed, mix):
-        """batches() through ops.resample_u8: (x, y), or (x, y, y2, w) with `mix`."""
+        """batches() through ops.resample_u8, or ops.erase_u8 with `erase`: (x, y), or (x, y, y2, w) with `mix`."""
         n, crop = len(self), None
         if self.crop != "pad" or self.pad != (0, 0) or self.flip:
             crop = crop_table(n, epoch, seed, self.chw[1:], self.crop, pad=self.pad, flip=self.flip, scale=self.rrc_scale, ratio=self.rrc_ratio)
@@ -366,5 +454,14 @@ class GpuDataset:
                 raise ValueError(f"GpuDataset.batches: the crop table is not int32 [{n}, 5] or holds an empty box")
             crop = crop.contiguous().to(self.device)
         tables = self._mix_tables(epoch, seed, self.out_hw, mix) if mix is not None else ()
+        if self.erase is None:
+            for i in range(0, idx.numel(), batch_size):
+                yield ops.resample_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, self.out_hw, crop, *tables)
+            return
+        erase = erase_table(n, epoch, seed, self.out_hw, self.erase["prob"], self.erase["scale"], self.erase["ratio"])
+        if tuple(erase.shape) != (n, 4) or erase.dtype != torch.int32:
+            raise ValueError(f"GpuDataset.batches: the erase table is not int32 [{n}, 4]")
+        erase, key = erase.contiguous().to(self.device), erase_noise_key(seed, epoch)
         for i in range(0, idx.numel(), batch_size):
-            yield ops.resample_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, self.out_hw, crop, *tables)
+            yield ops.erase_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, self.out_hw, crop, *tables, erase=erase,
+                               noise=self.noise, noise_key=key)

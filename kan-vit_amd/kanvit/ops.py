@@ -1165,33 +1165,40 @@ def depth_keep(B: int, keep, seed: int, counter: int) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------------------------------------
 # the training loop's off-model kernels, from here to the end of the file: one operand check
 # ---------------------------------------------------------------------------------------------------------------------------
-def _require_tensor(who: str, name: str, t: torch.Tensor, dtype, shape=None, device=None, contiguous: bool = True, hint: str = ""):
+class KanvitOperandError(KanvitError, ValueError):
+    """A refused operand of erase_u8's own (erase, noise): a KanvitError like every refusal here, and the ValueError a caller of a
+    table-taking function expects."""
+
+
+def _require_tensor(who: str, name: str, t: torch.Tensor, dtype, shape=None, device=None, contiguous: bool = True, hint: str = "",
+                    error=KanvitError):
     """The one place the ops below test an operand: on a GPU (`device`: on that one; None: any), of `dtype` (one, or a tuple to choose
-    from; `hint` is added to that refusal), contiguous, and of `shape` where one is given."""
+    from; `hint` is added to that refusal), contiguous, and of `shape` where one is given.  A refusal raises `error`."""
     if not t.is_cuda:
-        raise KanvitError(f"{who}: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
+        raise error(f"{who}: {name} is on {t.device}: the kanvit ops run only on an AMD GPU (no CPU fallback)")
     if device is not None and t.device != device:
-        raise KanvitError(f"{who}: {name} is on {t.device}, expected {device}")
+        raise error(f"{who}: {name} is on {t.device}, expected {device}")
     dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
     if t.dtype not in dtypes:
-        raise KanvitError(f"{who}: {name} has dtype {t.dtype}, expected {' or '.join(str(d) for d in dtypes)}{hint}")
+        raise error(f"{who}: {name} has dtype {t.dtype}, expected {' or '.join(str(d) for d in dtypes)}{hint}")
     if contiguous and not t.is_contiguous():
-        raise KanvitError(f"{who}: {name} with shape {tuple(t.shape)} and strides {tuple(t.stride())} is not contiguous")
+        raise error(f"{who}: {name} with shape {tuple(t.shape)} and strides {tuple(t.stride())} is not contiguous")
     if shape is not None and tuple(t.shape) != tuple(shape):
-        raise KanvitError(f"{who}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+        raise error(f"{who}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # batches from a GPU-resident uint8 dataset (kanvit/data.py; csrc/batch_u8.hip)
 # ---------------------------------------------------------------------------------------------------------------------------
-_BATCH_TABLES = (("crop", torch.int32, (5,)), ("partner", torch.int64, ()), ("weight", torch.float32, ()), ("box", torch.int32, (4,)))
+_BATCH_TABLES = (("crop", torch.int32, (5,)), ("partner", torch.int64, ()), ("weight", torch.float32, ()), ("box", torch.int32, (4,)),
+                 ("erase", torch.int32, (4,)))
 
 
 def _batch_operands(who: str, images, labels, idx, lut, out, name: str, pair, **tables):
-    """What augment_u8 / mix_u8 / resample_u8 share, checked: the sizes (N, B, H, W, C), `pair` (an int or two; `name` is "pad", or
+    """What augment_u8 / mix_u8 / resample_u8 / erase_u8 share, checked: the sizes (N, B, H, W, C), `pair` (an int or two; `name` is "pad", or
     "out_size": the output then has that size instead of the images') as two ints, and the tensors the launch writes: `out` (the
-    caller's, or a new one), y where labels are given, y2 and w where the mix tables are.  tables: crop / partner / weight / box,
-    each or None."""
+    caller's, or a new one), y where labels are given, y2 and w where the mix tables are.  tables: crop / partner / weight / box /
+    erase, each or None."""
     _require_tensor(who, "images", images, torch.uint8)
     if images.dim() not in (3, 4):
         raise KanvitError(f"{who}: images has shape {tuple(images.shape)}, expected [N, H, W, C] or [N, H, W]")
@@ -1212,7 +1219,7 @@ def _batch_operands(who: str, images, labels, idx, lut, out, name: str, pair, **
     _require_tensor(who, "lut", lut, torch.float32, (Cn, 256), dev)
     for table, dt, tail in _BATCH_TABLES:
         if tables.get(table) is not None:
-            _require_tensor(who, table, tables[table], dt, (N,) + tail, dev)
+            _require_tensor(who, table, tables[table], dt, (N,) + tail, dev, error=KanvitOperandError if table == "erase" else KanvitError)
     if out is None:
         out = torch.empty((B, Cn, max(OH, 0), max(OW, 0)), device=dev, dtype=torch.float32)
     else:
@@ -1281,6 +1288,39 @@ def resample_u8(images: torch.Tensor, labels: Optional[torch.Tensor], idx: torch
     _launch(_lib.lib().kanvit_resample_u8, "kanvit_resample_u8", images.device, _ptr(images), _ptr(labels), _ptr(idx), _ptr(lut), _ptr(crop),
             _ptr(partner), _ptr(weight), _ptr(box), _ptr(out), _ptr(y), _ptr(y2), _ptr(w), *sizes, *size,
             tag="resample_u8", cost=(0, out.numel() * 4))
+    if mixing:
+        return out, y, y2, w
+    return (out, y) if labels is not None else out
+
+
+def erase_u8(images: torch.Tensor, labels: Optional[torch.Tensor], idx: torch.Tensor, lut: torch.Tensor, out_size, crop: Optional[torch.Tensor] = None,
+             partner: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None, box: Optional[torch.Tensor] = None,
+             erase: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, noise_key: int = 0, out: Optional[torch.Tensor] = None):
+    """resample_u8 with Random Erasing in the same launch (semantics: include/kanvit.h).  erase int32 [N, 4] = (y0, y1, x0, x1), half
+    open, in OUTPUT coordinates, is the epoch's table (data.erase_table) on the device, indexed by the DATASET index: inside its box
+    sample s = idx[b] is replaced by a fill before it is mixed, and its partner is erased under the partner's own row before it is
+    pasted or blended in.  noise float32 [T], T a power of two in 2..65536 (data.normal_table), makes the fill noise[top bits of a
+    hash of (noise_key, s, c, y, x)] (timm's "pixel"; noise_key: data.erase_noise_key); None makes it 0, the normalised mean
+    ("const").  Everything else, and what is returned, is resample_u8's; erase=None IS resample_u8 (noise must then be None)."""
+    tables = (partner, weight, box)
+    mixing = any(t is not None for t in tables)
+    if mixing and any(t is None for t in tables):
+        raise KanvitError("erase_u8: partner, weight and box come together (all three or none)")
+    if mixing and labels is None:
+        raise KanvitError("erase_u8: labels is None: the mix tables yield (x, y, y2, w)")
+    if noise is not None and erase is None:
+        raise KanvitOperandError("erase_u8: noise without erase: the noise fills the erase boxes")
+    sizes, size, (out, y, y2, w) = _batch_operands("erase_u8", images, labels, idx, lut, out, "out_size", out_size, crop=crop, partner=partner,
+                                                   weight=weight, box=box, erase=erase)
+    T = 0
+    if noise is not None:
+        _require_tensor("erase_u8", "noise", noise, torch.float32, None, images.device, error=KanvitOperandError)
+        T = int(noise.numel())
+        if noise.dim() != 1 or T < 2 or T > 65536 or T & (T - 1):
+            raise KanvitOperandError(f"erase_u8: noise has shape {tuple(noise.shape)}, expected [T], T a power of two in 2..65536")
+    _launch(_lib.lib().kanvit_erase_u8, "kanvit_erase_u8", images.device, _ptr(images), _ptr(labels), _ptr(idx), _ptr(lut), _ptr(crop),
+            _ptr(partner), _ptr(weight), _ptr(box), _ptr(out), _ptr(y), _ptr(y2), _ptr(w), *sizes, *size, _ptr(erase), _ptr(noise), T,
+            int(noise_key) & (2 ** 64 - 1), tag="erase_u8", cost=(0, out.numel() * 4))
     if mixing:
         return out, y, y2, w
     return (out, y) if labels is not None else out

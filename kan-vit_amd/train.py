@@ -25,7 +25,10 @@ batch kernel, from a per-epoch table that is a function of (seed, epoch) alone: 
 ops.soft_cross_entropy), --resize S / --random-resized-crop / --rrc-scale / --rrc-ratio (the batch kernel resamples: every batch
 comes out at S x S, bilinear, from the stored images -- `--data-npz cifar100.npz --resize 224 --n-patches 14` trains the ViT-B/16
 geometry on 32 x 32 images -- and RandomResizedCrop boxes come from a per-epoch table, a function of (seed, epoch) alone:
-kanvit/data.py crop_table, ops.resample_u8; --image-size stays the size of the stored images), --optimizer kanvit-adamw with --weight-decay /
+kanvit/data.py crop_table, ops.resample_u8; --image-size stays the size of the stored images), --random-erasing P / --erase-mode /
+--erase-scale / --erase-ratio (Random Erasing inside the batch kernel, before Mixup / CutMix and on the partner too: with probability
+P a per-sample box from a per-epoch table is replaced by standard-normal noise or zeros -- kanvit/data.py erase_table, ops.erase_u8;
+the train split only), --optimizer kanvit-adamw with --weight-decay /
 --clip-grad-norm / --warmup-steps / --lr-schedule / --min-lr / --ema-decay (AdamW with global-norm clipping, a schedule table and a weight
 EMA in the project's own fused step, kanvit/optim.py; the default --optimizer adam is the reference's step), --drop-path RATE /
 --drop-path-schedule (stochastic depth as a per-sample scale inside the fused residual add + LayerNorm passes, masks from a hash of
@@ -101,6 +104,20 @@ def check_data_args(args):
         lo, hi = (float(v) for v in getattr(args, name, default))
         if not 0 < lo <= hi or hi == float("inf"):
             raise SystemExit(f"{flag} {lo} {hi}: LO and HI are positive and LO is not above HI")
+    p_erase = float(getattr(args, "random_erasing", 0.0))
+    if not 0.0 <= p_erase <= 1.0:
+        raise SystemExit(f"--random-erasing {p_erase} is not a probability")
+    for flag, name, default in (("--erase-scale", "erase_scale", (0.02, 1.0 / 3.0)), ("--erase-ratio", "erase_ratio", (0.3, 1.0 / 0.3))):
+        lo, hi = (float(v) for v in getattr(args, name, default))
+        if not 0 < lo <= hi or hi == float("inf"):
+            raise SystemExit(f"{flag} {lo} {hi}: LO and HI are positive and LO is not above HI")
+        if name == "erase_scale" and hi > 1:
+            raise SystemExit(f"--erase-scale {lo} {hi}: HI is a fraction of the image, at most 1")
+    if p_erase > 0:
+        if not getattr(args, "data_npz", None):
+            raise SystemExit("--random-erasing erases inside the kernel that reads the GPU-resident dataset; give --data-npz")
+        if getattr(args, "no_augment", False):
+            raise SystemExit("--random-erasing is an augmentation; it is not combined with --no-augment")
 
 
 RECIPE_FLAGS = (("--weight-decay", "weight_decay", 0.0), ("--clip-grad-norm", "clip_grad_norm", 0.0), ("--warmup-steps", "warmup_steps", 0),
@@ -135,11 +152,21 @@ def mix_config(args):
                 switch_prob=float(getattr(args, "mix_switch_prob", 0.5)))
 
 
+def erase_config(args):
+    """The `erase` argument of GpuDataset from the flags, or None when --random-erasing is 0."""
+    p_erase = float(getattr(args, "random_erasing", 0.0))
+    if p_erase <= 0:
+        return None
+    return dict(prob=p_erase, scale=tuple(getattr(args, "erase_scale", (0.02, 1.0 / 3.0))), ratio=tuple(getattr(args, "erase_ratio", (0.3, 1.0 / 0.3))),
+                mode=getattr(args, "erase_mode", "pixel"))
+
+
 def npz_datasets(args, device, want_test=True):
     """--data-npz: (train, test or None) GpuDatasets.  --image-size / --in-chans left at their defaults follow the file (args is
     updated); given values that contradict it, labels that --out-d does not cover and non-square images are refused.  Only the rank
     that evaluates asks for the test split.  --resize S gives both splits out_size = (S, S) (--image-size stays the file's size) and
-    --random-resized-crop gives the train split crop="rrc": their batches then come from ops.resample_u8."""
+    --random-resized-crop gives the train split crop="rrc": their batches then come from ops.resample_u8.  --random-erasing gives the
+    train split -- never the test split -- erase=...: its batches come from ops.erase_u8."""
     from kanvit import data as kdata
     blob = kdata.load_npz(args.data_npz)
     x = blob["x_train"]
@@ -162,7 +189,7 @@ def npz_datasets(args, device, want_test=True):
     train = kdata.GpuDataset.from_arrays(blob, args.data_npz, "train", device, pad=args.crop_padding if augment else 0, flip=augment,
                                          out_size=out_size, crop="rrc" if rrc else "pad",
                                          rrc_scale=tuple(getattr(args, "rrc_scale", (0.08, 1.0))),
-                                         rrc_ratio=tuple(getattr(args, "rrc_ratio", (3.0 / 4.0, 4.0 / 3.0))))
+                                         rrc_ratio=tuple(getattr(args, "rrc_ratio", (3.0 / 4.0, 4.0 / 3.0))), erase=erase_config(args))
     test = kdata.GpuDataset.from_arrays(blob, args.data_npz, "test", device, out_size=out_size) if want_test and "x_test" in blob else None
     return train, test
 
@@ -610,6 +637,18 @@ def parse(argv=None):
                    help='--random-resized-crop: the range of the box area as a fraction of the image')
     p.add_argument('--rrc-ratio', type=float, nargs=2, default=(3.0 / 4.0, 4.0 / 3.0), metavar=('LO', 'HI'),
                    help='--random-resized-crop: the range of the box aspect ratio (log-uniform)')
+    p.add_argument('--random-erasing', type=float, default=0.0, metavar='P',
+                   help="with --data-npz: Random Erasing (torchvision's RandomErasing / timm's, per sample, at the output size, after "
+                        'normalisation, before Mixup / CutMix) inside the batch kernel -- with probability P a box from a per-epoch table, '
+                        'a function of (seed, epoch) alone, is replaced (kanvit/data.py erase_table, ops.erase_u8); the train split only.  '
+                        '0 (default): off')
+    p.add_argument('--erase-mode', choices=('pixel', 'const'), default='pixel',
+                   help="--random-erasing: 'pixel' fills the box with standard-normal noise per value (timm's pixel mode, DeiT's default), "
+                        "'const' with zeros, the normalised dataset mean")
+    p.add_argument('--erase-scale', type=float, nargs=2, default=(0.02, 1.0 / 3.0), metavar=('LO', 'HI'),
+                   help='--random-erasing: the range of the box area as a fraction of the image')
+    p.add_argument('--erase-ratio', type=float, nargs=2, default=(0.3, 1.0 / 0.3), metavar=('LO', 'HI'),
+                   help='--random-erasing: the range of the box aspect ratio (log-uniform)')
     p.add_argument('--mixup', type=float, default=0.0, metavar='ALPHA',
                    help='with --data-npz: Mixup -- blend every sample with a partner, lam ~ Beta(ALPHA, ALPHA), inside the batch kernel '
                         '(kanvit/data.py: mix_table, ops.mix_u8); the loss becomes the fused soft-target cross-entropy and the train '
