@@ -631,6 +631,59 @@ int kanvit_erase_u8(const uint8_t* images, const int64_t* labels, const int64_t*
                     int64_t N, int64_t B, int H, int W, int C, int OH, int OW, const int32_t* erase, const float* noise, int noise_len,
                     uint64_t noise_key, void* stream);
 
+/* ---- RandAugment: one uint8 -> uint8 pass over the dataset per epoch (kanvit/data.py: randaug_table; csrc/randaug.hip) --------
+ * dst[s] = src[s] passed through its K table rows in order, s = 0 .. N-1.  src and dst are [N][H][W][C] uint8 and do not overlap
+ * (several ops read more than the byte they write); table is [N][K][8] int32, row = (op, p0 .. p6), indexed by the DATASET index
+ * like the batch kernels' tables -- the batch kernels then read dst in place of the stored images, so crop, flip, resize, erase and
+ * mix work unchanged and a partner comes augmented under its own rows.  The ops run at the STORED resolution, before the crop
+ * (timm runs them after RandomResizedCrop).
+ * All arithmetic is integer; `>>` is an arithmetic shift, `/` divides non-negative integers, clamp is to [0, 255], Q16 means the
+ * host rounded value * 65536 to int32, and
+ *   blend(d, v, f) = clamp((d * 65536 + f * (v - d) + 32768) >> 16),   f in Q16, 0 <= f <= 2 * 65536,
+ *   L(pixel)       = (19595 R + 38470 G + 7471 B + 32768) >> 16        (PIL's conversion to "L"; channels 0, 1, 2).
+ * Per byte v of channel c of an H x W image:
+ *   IDENTITY      v
+ *   AUTOCONTRAST  lo, hi = min, max of channel c over the image; hi <= lo: v; else ((v - lo) * 255) / (hi - lo)
+ *   EQUALIZE      PIL's ImageOps.equalize per channel: h the histogram, step = (H W - h[last non-empty bin]) / 255; step == 0 or
+ *                 one non-empty bin: v; else min(255, (step / 2 + sum_{j < v} h[j]) / step)
+ *   INVERT        255 - v
+ *   POSTERIZE     p0 = bits kept, 0..8:                 v & ~(0xFF >> p0)
+ *   SOLARIZE      p0 = threshold, 0..256:               v < p0 ? v : 255 - v
+ *   SOLARIZE_ADD  p0 = add, 0..255, p1 = threshold, 0..256:   v < p1 ? min(v + p0, 255) : v
+ *   BRIGHTNESS    blend(0, v, p0)
+ *   COLOR         C >= 3: blend(L(pixel), v, p0) for c < 3, v for c = 3; C < 3: v
+ *   CONTRAST      blend(m, v, p0) for every channel, m = (sum of g over the pixels + H W / 2) / (H W), g = L(pixel) for C >= 3 and
+ *                 channel 0 for C < 3
+ *   SHARPNESS     blend(sm, v, p0), sm = (the 8 neighbours of the same channel + 5 v + 6) / 13 (PIL's SMOOTH); sm = v on the
+ *                 one-pixel border, so an image with H < 3 or W < 3 is unchanged
+ *   AFFINE        the byte of channel c at source pixel (xs, ys), nearest neighbour under an inverse map with half-pixel centres:
+ *                   xs = (p0 (2x + 1) + p1 (2y + 1) + 2 p2) >> 17,   ys = (p3 (2x + 1) + p4 (2y + 1) + 2 p5) >> 17   (64-bit)
+ *                 p0, p1, p3, p4 Q16 matrix entries, p2, p5 Q16 offsets in pixels, any int32; a source outside the image gives the
+ *                 fill byte (p6 >> 8 c) & 255.  Shear, translation and rotation are all AFFINE; the host builds the matrix.
+ * An unknown op code, or a parameter outside the range stated above, makes the row IDENTITY; parameters an op does not name are
+ * ignored.  Whatever a row holds, nothing outside image s of src and dst is read or written.
+ * One launch: one work-group per image, striding beyond 2048 work-groups, the image in LDS (two buffers, a C x 256 int32
+ * histogram / look-up area); integer sums and LDS integer atomics only, so the output does not depend on the launch shape and the
+ * same integer operations on the host give the same bytes.  No workspace, no synchronisation; capturable.  N = 0 returns 0 and
+ * touches nothing.  KANVIT_EINVAL (named in kanvit_last_error, before any device call) for N < 0, C outside 1..4, H or W < 1,
+ * H W C > KANVIT_RA_MAX_BYTES, K outside 1..KANVIT_RA_MAX_OPS, a null pointer, src == dst or overlapping arrays, a misaligned
+ * table.  `stream` is a hipStream_t.  Additive: the ABI version stays 7. */
+#define KANVIT_RA_IDENTITY 0
+#define KANVIT_RA_AUTOCONTRAST 1
+#define KANVIT_RA_EQUALIZE 2
+#define KANVIT_RA_INVERT 3
+#define KANVIT_RA_POSTERIZE 4
+#define KANVIT_RA_SOLARIZE 5
+#define KANVIT_RA_SOLARIZE_ADD 6
+#define KANVIT_RA_BRIGHTNESS 7
+#define KANVIT_RA_COLOR 8
+#define KANVIT_RA_CONTRAST 9
+#define KANVIT_RA_SHARPNESS 10
+#define KANVIT_RA_AFFINE 11
+#define KANVIT_RA_MAX_OPS 4          /* rows per sample */
+#define KANVIT_RA_MAX_BYTES 24576    /* H W C: two image buffers and the histograms stay under 64 KB of LDS */
+int kanvit_randaug_u8(const uint8_t* src, uint8_t* dst, const int32_t* table, long long N, int H, int W, int C, int K, void* stream);
+
 /* ---- soft-target cross-entropy, loss and gradient in one pass (ops.soft_cross_entropy; csrc/soft_ce.hip) -----------------
  * The training loss for Mixup / CutMix pairs and label smoothing.  logits [B][C] fp32, unit column stride, row stride ld >= C;
  * y1 [B] int64; y2 [B] int64 and w [B] fp32 together or both NULL (NULL: w = 1); eps in [0, 1).

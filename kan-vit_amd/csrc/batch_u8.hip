@@ -769,3 +769,7 @@ int kanvit_erase_u8(const uint8_t* images, const int64_t* labels, const int64_t*
 }
 
 }  // extern "C"
+
+// The other kernel of the data path, in a file of its own but in this translation unit (kanvit/build.py: one unit per family): the
+// per-epoch RandAugment pass that writes the uint8 copy of the dataset the kernels above then read.  It shares nothing but the unit.
+#include "randaug.hip"

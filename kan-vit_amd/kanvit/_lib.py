@@ -136,6 +136,7 @@ SYMBOLS = {
     "kanvit_resample_u8": (C.c_int, [_P] * 12 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "kanvit_erase_u8_supported": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kanvit_erase_u8": (C.c_int, [_P] * 12 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_uint64, _P]),
+    "kanvit_randaug_u8": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "kanvit_soft_ce": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int, C.c_float, _P, _P, _P, _P]),
     "kanvit_metrics_update": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int64, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
     "kanvit_metrics_auc_pairs_workspace": (C.c_size_t, [C.c_int64, C.c_int]),
@@ -148,6 +149,13 @@ SYMBOLS = {
 }
 OPTIM_CHUNK = 4096      # KANVIT_OPTIM_CHUNK: the elements one work-group of the optimizer kernels takes
 DEPTH_MAX_BRANCHES = 64      # KANVIT_DEPTH_MAX_BRANCHES: the residual branches one kanvit_depth_scales launch draws for
+# KANVIT_RA_*: the op codes of kanvit_randaug_u8's table, the rows per sample and the largest image (H W C bytes) it takes
+(RA_IDENTITY, RA_AUTOCONTRAST, RA_EQUALIZE, RA_INVERT, RA_POSTERIZE, RA_SOLARIZE, RA_SOLARIZE_ADD, RA_BRIGHTNESS, RA_COLOR, RA_CONTRAST,
+ RA_SHARPNESS, RA_AFFINE) = range(12)
+RA_OP_NAMES = ["identity", "autocontrast", "equalize", "invert", "posterize", "solarize", "solarize_add", "brightness", "color", "contrast",
+               "sharpness", "affine"]
+RA_MAX_OPS = 4
+RA_MAX_BYTES = 24576
 for _f in FAMILY_NAMES:
     SYMBOLS[f"kanvit_{_f}_fwd"] = (C.c_int, _LAYER_FWD)
     SYMBOLS[f"kanvit_{_f}_bwd_input"] = (C.c_int, _LAYER_BWD_IN)

@@ -23,6 +23,12 @@ named by erase_table -- one more table per epoch drawn from (seed, epoch) and in
 standard-normal noise (normal_table, looked up through a hash of (seed, epoch, sample, channel, pixel)) before the sample is mixed,
 and erases the partner under the partner's own box.
 
+RandAugment does not ride on the batch kernel: GpuDataset(randaug=...) keeps a second uint8 buffer of the dataset's size, and once
+per epoch ONE launch (ops.randaugment_u8, csrc/randaug.hip) writes every image into it through the two ops randaug_table names for
+it -- a table per epoch drawn from (seed, epoch), indexed by dataset index, integer parameters only.  Every batch kernel above then
+reads that buffer in place of the stored images and works unchanged; a Mixup / CutMix partner comes augmented under its own rows.
+The ops run at the stored resolution, BEFORE the crop, the flip and the resize (timm runs them after RandomResizedCrop).
+
 The file format is an .npz: x_train uint8 [N, H, W, C] (or [N, H, W] for one channel), y_train of any integer type, optionally
 x_test / y_test, optionally mean / std ([C], on the 0-1 scale; computed from x_train when absent).  tools/cifar_to_npz.py writes
 one from an unpacked CIFAR python-pickle directory.
@@ -280,6 +286,123 @@ def _erase_config(erase) -> dict:
     return cfg
 
 
+_RANDAUG_TABLE_KEY = 0x72616E646175675F  # "randaug_": the RandAugment table's counters, apart from the other tables' generators
+_RANDAUG_DRAWS = 4                      # hashed draws per slot: the op, whether it is kept, the magnitude, the sign
+# timm's "increasing" set (rand-...-inc1), in its order; Rotate .. TranslateY are AFFINE rows, the rest map to a code each
+RANDAUG_OPS = ("AutoContrast", "Equalize", "Invert", "Rotate", "Posterize", "Solarize", "SolarizeAdd", "Color", "Contrast", "Brightness",
+               "Sharpness", "ShearX", "ShearY", "TranslateX", "TranslateY")
+_RA_CODES = dict(Identity=0, AutoContrast=1, Equalize=2, Invert=3, Posterize=4, Solarize=5, SolarizeAdd=6, Brightness=7, Color=8, Contrast=9,
+                 Sharpness=10, Rotate=11, ShearX=11, ShearY=11, TranslateX=11, TranslateY=11)
+
+
+def _q16(v) -> np.ndarray:
+    """value * 65536 rounded to the nearest integer, inside int32."""
+    return np.clip(np.rint(np.asarray(v, np.float64) * 65536.0), -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int64)
+
+
+def _randaug_rows(name: str, level: np.ndarray, sign: np.ndarray, H: int, W: int, fill: int) -> np.ndarray:
+    """The rows (op, p0 .. p6) of op `name` at level = m / 10 in [0, 1] and sign = +-1, int64 [len(level), 8]: the magnitude rules of
+    randaug_table's docstring, in float64, rounded to integers here -- the kernel sees integers only."""
+    rows = np.zeros((len(level), 8), np.int64)
+    rows[:, 0] = _RA_CODES[name]
+    if name in ("Brightness", "Color", "Contrast", "Sharpness"):
+        rows[:, 1] = _q16(np.maximum(0.1, 1.0 + sign * 0.9 * level))
+    elif name == "Posterize":
+        rows[:, 1] = 4 - (4.0 * level).astype(np.int64)
+    elif name == "Solarize":
+        rows[:, 1] = 256 - (256.0 * level).astype(np.int64)
+    elif name == "SolarizeAdd":
+        rows[:, 1], rows[:, 2] = np.minimum(128, (110.0 * level).astype(np.int64)), 128
+    elif _RA_CODES[name] == 11:
+        # the inverse map source = A (output - centre) + centre + t, in half-pixel-centre coordinates: centre = (W / 2, H / 2)
+        one, zero = np.ones_like(level), np.zeros_like(level)
+        a, b, d, e, tx, ty = one, zero, zero, one, zero, zero
+        if name == "Rotate":                        # PIL's Image.rotate(angle): the matrix of -angle
+            t = -np.radians(sign * 30.0 * level)
+            a, b, d, e = np.cos(t), np.sin(t), -np.sin(t), np.cos(t)
+        elif name == "ShearX":
+            b = sign * 0.3 * level
+        elif name == "ShearY":
+            d = sign * 0.3 * level
+        elif name == "TranslateX":
+            tx = sign * 0.45 * level * W
+        else:
+            ty = sign * 0.45 * level * H
+        cx, cy = W / 2.0, H / 2.0
+        rows[:, 1], rows[:, 2], rows[:, 3] = _q16(a), _q16(b), _q16(cx - a * cx - b * cy + tx)
+        rows[:, 4], rows[:, 5], rows[:, 6] = _q16(d), _q16(e), _q16(cy - d * cx - e * cy + ty)
+        rows[:, 7] = fill
+    return rows
+
+
+def randaug_table(n: int, epoch: int, seed: int, hw, n_ops: int = 2, magnitude: float = 9.0, mstd: float = 0.5, prob: float = 0.5,
+                  fill=(128, 128, 128), ops=None) -> torch.Tensor:
+    """The RandAugment table of `epoch` for ops.randaugment_u8: int32 [n, n_ops, 8] on the CPU, rows (op, p0 .. p6) of include/kanvit.h
+    for DATASET index s, for stored images of size hw = (H, W) (timm's rand-m{magnitude}-mstd{mstd}-inc1 with n_ops ops per sample,
+    each applied with probability `prob`).  Like the other tables it is a function of its arguments alone -- not of the batch size,
+    the rank or the world size -- and it is drawn by counters, not by a generator: draw d of slot k of sample s is
+    mix(mix(base + s) + 4 k + d), base = mix(mix(mix(seed) + epoch) ^ key), all mod 2^64 (the vectorised splitmix64 of crop_table's "pad"
+    rows), so row s does not depend on n either: the table of n samples is the head of the table of any larger n.
+
+    Per slot: d = 0 picks the op, floor(u len(ops)) with u the top 53 bits as a fraction; d = 1 keeps it iff u < prob, otherwise the
+    row is IDENTITY (all zero); d = 2 draws the magnitude m = clip(magnitude + mstd z, 0, 10), z = normal_table(4096)[top 12 bits] (the
+    inverse normal CDF on a hashed uniform, quantised); d = 3 gives the sign (top bit set: -1) of the signed ops.  With level = m / 10:
+      Rotate                       +-30 degrees * level                        ShearX / ShearY   +-0.3 * level
+      TranslateX / TranslateY      +-0.45 * level of the width / height        AutoContrast, Equalize, Invert: no magnitude
+      Brightness / Color / Contrast / Sharpness     factor f = max(0.1, 1 +- 0.9 * level)
+      Posterize    bits = 4 - int(4 level)          Solarize   threshold = 256 - int(256 level)
+      SolarizeAdd  add = min(128, int(110 level)), threshold = 128
+    modelled on timm's _LEVEL functions; they are this project's definition.  Rotation, shear and translation are AFFINE rows: the
+    inverse matrix about the image centre in Q16, the fill byte of channel c is fill[c] (an int, or a sequence whose last entry serves
+    the channels beyond it).  All trigonometry and rounding happens here in float64.
+
+    ops: the names to pick from, default RANDAUG_OPS (timm's fifteen "increasing" ops; "Identity" may be listed too).  Bad arguments
+    are a ValueError."""
+    H, W = int(hw[0]), int(hw[1])
+    n_ops, magnitude, mstd, prob = int(n_ops), float(magnitude), float(mstd), float(prob)
+    if n < 1 or H < 1 or W < 1:
+        raise ValueError(f"randaug_table: n={n}, hw={tuple(hw)}")
+    if not 1 <= n_ops <= 4:
+        raise ValueError(f"randaug_table: n_ops={n_ops} is in 1..4")
+    if not 0.0 <= magnitude <= 10.0 or not 0.0 <= mstd < float("inf") or not 0.0 <= prob <= 1.0:
+        raise ValueError(f"randaug_table: magnitude={magnitude} is in [0, 10], mstd={mstd} is finite and not negative, prob={prob} is a probability")
+    names = RANDAUG_OPS if ops is None else tuple(ops)
+    if not names or any(name not in _RA_CODES for name in names):
+        raise ValueError(f"randaug_table: ops={names!r} is a non-empty list of names out of {sorted(_RA_CODES)}")
+    try:
+        fills = [int(fill)] if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
+    except (TypeError, ValueError):
+        fills = []
+    if not 1 <= len(fills) <= 4 or any(not 0 <= v <= 255 for v in fills):
+        raise ValueError(f"randaug_table: fill={fill!r} is a byte, or one to four bytes (one per channel)")
+    fills += [fills[-1]] * (4 - len(fills))
+    packed = int(np.array([fills[0] | fills[1] << 8 | fills[2] << 16 | fills[3] << 24], np.uint32).view(np.int32)[0])
+    base = _mix(_mix((_mix(int(seed) & _M64) + int(epoch)) & _M64) ^ _RANDAUG_TABLE_KEY)
+    sample = _mix_u64(np.uint64(base) + np.arange(n, dtype=np.uint64))
+    h = _mix_u64(sample[:, None] + np.arange(n_ops * _RANDAUG_DRAWS, dtype=np.uint64)[None, :]).reshape(n, n_ops, _RANDAUG_DRAWS)
+    u = (h >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    pick = np.minimum((u[..., 0] * len(names)).astype(np.int64), len(names) - 1)
+    keep = u[..., 1] < prob
+    z = normal_table(4096).numpy().astype(np.float64)[(h[..., 2] >> np.uint64(52)).astype(np.int64)]
+    level = np.clip(magnitude + mstd * z, 0.0, 10.0) / 10.0
+    sign = np.where((h[..., 3] >> np.uint64(63)).astype(bool), -1.0, 1.0)
+    rows = np.zeros((n, n_ops, 8), np.int64)
+    for j, name in enumerate(names):
+        m = keep & (pick == j)
+        rows[m] = _randaug_rows(name, level[m], sign[m], H, W, packed)
+    return torch.from_numpy(rows.astype(np.int32))
+
+
+def _randaug_config(randaug) -> dict:
+    """GpuDataset's `randaug` argument, checked: n_ops, magnitude, mstd, prob, fill and ops as randaug_table takes them."""
+    cfg = dict(n_ops=2, magnitude=9.0, mstd=0.5, prob=0.5, fill=(128, 128, 128), ops=None)
+    if not isinstance(randaug, dict) or not set(randaug) <= set(cfg):
+        raise ValueError(f"GpuDataset: randaug={randaug!r} is a dict with keys out of {sorted(cfg)}")
+    cfg.update(randaug)
+    randaug_table(1, 0, 0, (2, 2), **cfg)            # its argument checks, once, before any epoch
+    return cfg
+
+
 def _fail(path, key, what):
     raise ValueError(f"{path}: '{key}' {what}")
 
@@ -347,13 +470,18 @@ class GpuDataset:
     """Images (uint8, NHWC) and labels (int64) resident on `device`; batches() yields normalised, augmented float32 NCHW batches."""
 
     def __init__(self, images, labels, mean, std, device, pad=0, flip=False, out_size=None, crop="pad", rrc_scale=(0.08, 1.0),
-                 rrc_ratio=(3.0 / 4.0, 4.0 / 3.0), erase=None):
+                 rrc_ratio=(3.0 / 4.0, 4.0 / 3.0), erase=None, randaug=None):
         """out_size (an int or (OH, OW)): the size of the batches, resized from the stored images by ops.resample_u8; None: the stored
         size.  crop: "pad" (the random crop out of the zero-padded image, `pad` and `flip`) or "rrc" (RandomResizedCrop over rrc_scale /
         rrc_ratio, with `flip`; `pad` is then unused).  With the stored size and crop="pad" nothing changes: ops.augment_u8 / ops.mix_u8.
         erase: Random Erasing -- a dict of prob, scale, ratio (erase_table's; defaults 0.25, (0.02, 1/3), (0.3, 1/0.3)) and mode
         ("pixel": standard-normal noise per value, the default; "const": zeros, the normalised mean).  Every batch then comes from
-        ops.erase_u8, at any size; None (default): nothing changes."""
+        ops.erase_u8, at any size; None (default): nothing changes.
+        randaug: RandAugment -- a dict of n_ops, magnitude, mstd, prob, fill, ops (randaug_table's; defaults 2, 9, 0.5, 0.5, (128, 128,
+        128), timm's "increasing" ops).  The dataset then holds ONE second uint8 buffer of the images' size, allocated here;
+        batches() fills it once per epoch with ops.randaugment_u8 and every batch kernel reads it in place of the images (so two
+        epochs of one dataset are not iterated at the same time).  The images are at most 24 576 bytes each.  None (default): nothing
+        is allocated or launched and the batch kernels read the images themselves."""
         images = torch.as_tensor(images)
         labels = torch.as_tensor(labels)
         if images.dtype != torch.uint8 or images.dim() not in (3, 4):
@@ -374,12 +502,17 @@ class GpuDataset:
         if min(self.out_hw) < 1:
             raise ValueError(f"GpuDataset: out_size={out_size} must be positive")
         self.erase = None if erase is None else _erase_config(erase)
+        self.randaug = None if randaug is None else _randaug_config(randaug)
+        if self.randaug is not None and self.chw[0] * self.chw[1] * self.chw[2] > ops._lib.RA_MAX_BYTES:
+            raise ops.KanvitError(f"GpuDataset: randaug takes images of at most {ops._lib.RA_MAX_BYTES} bytes (they live in LDS); these are "
+                                  f"{self.chw[1]} x {self.chw[2]} x {self.chw[0]}")
         self.resample = crop != "pad" or self.out_hw != self.chw[1:] or self.erase is not None      # False: augment_u8 / mix_u8
         self.device = torch.device(device)
         self.images = images.contiguous().to(self.device)
         self.labels = labels.to(torch.int64).contiguous().to(self.device)
         self.lut = self.lut_cpu.to(self.device)
         self.noise = normal_table().to(self.device) if self.erase is not None and self.erase["mode"] == "pixel" else None
+        self.randaug_buffer = torch.empty_like(self.images) if self.randaug is not None else None
 
     @classmethod
     def from_npz(cls, path, split, device, pad=0, flip=False, **resample):
@@ -390,7 +523,7 @@ class GpuDataset:
 
     @classmethod
     def from_arrays(cls, blob, path, split, device, pad=0, flip=False, **resample):
-        """`resample`: out_size, crop, rrc_scale, rrc_ratio, erase, as the constructor takes them."""
+        """`resample`: out_size, crop, rrc_scale, rrc_ratio, erase, randaug, as the constructor takes them."""
         if f"x_{split}" not in blob:
             _fail(path, f"x_{split}", "is missing")
         mean, std = (blob["mean"], blob["std"]) if "mean" in blob else channel_stats(blob["x_train"])
@@ -420,23 +553,36 @@ class GpuDataset:
         at hw = out_size; the evaluation transform (crop="pad", pad 0, no flip) passes no table at all.
 
         A dataset with `erase` goes the same way through ops.erase_u8: the epoch's erase table (erase_table at hw = out_size) is drawn,
-        checked and uploaded once like the others; the noise table went to the device with the dataset."""
+        checked and uploaded once like the others; the noise table went to the device with the dataset.
+
+        A dataset with `randaug` first draws, checks and uploads the epoch's RandAugment table (randaug_table) and runs
+        ops.randaugment_u8 over the WHOLE dataset into its second buffer -- on every rank, because a partner can be any index -- and
+        the launches above read that buffer in place of the images."""
         if batch_size < 1:
             raise ValueError(f"GpuDataset.batches: batch_size={batch_size}")
         idx = epoch_indices(len(self), epoch, seed, rank, world, shuffle)
         if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= len(self)):
             raise IndexError(f"GpuDataset.batches: an index outside [0, {len(self)})")
         idx = idx.to(self.device)
+        images = self._epoch_images(epoch, seed)
         if self.resample:
-            yield from self._resampled(idx, batch_size, epoch, seed, mix)
+            yield from self._resampled(images, idx, batch_size, epoch, seed, mix)
             return
         if mix is None:
             for i in range(0, idx.numel(), batch_size):
-                yield ops.augment_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, self.pad, self.flip, seed, epoch)
+                yield ops.augment_u8(images, self.labels, idx[i:i + batch_size], self.lut, self.pad, self.flip, seed, epoch)
             return
         partner, weight, box = self._mix_tables(epoch, seed, self.chw[1:], mix)
         for i in range(0, idx.numel(), batch_size):
-            yield ops.mix_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, partner, weight, box, self.pad, self.flip, seed, epoch)
+            yield ops.mix_u8(images, self.labels, idx[i:i + batch_size], self.lut, partner, weight, box, self.pad, self.flip, seed, epoch)
+
+    def _epoch_images(self, epoch, seed):
+        """The images the epoch's batch kernels read: the stored ones, or with `randaug` the second buffer after this epoch's pass."""
+        if self.randaug is None:
+            return self.images
+        table = randaug_table(len(self), epoch, seed, self.chw[1:], **self.randaug)
+        table = ops.randaug_check_table(table, len(self)).contiguous().to(self.device)
+        return ops.randaugment_u8(self.images, table, out=self.randaug_buffer)
 
     def _mix_tables(self, epoch, seed, hw, mix):
         """The epoch's mix table at output size hw, checked on the CPU, on the device."""
@@ -445,7 +591,7 @@ class GpuDataset:
             raise IndexError(f"GpuDataset.batches: the mix table names a partner outside [-1, {len(self)}) or is not of length {len(self)}")
         return tuple(t.contiguous().to(self.device) for t in table)
 
-    def _resampled(self, idx, batch_size, epoch, seed, mix):
+    def _resampled(self, images, idx, batch_size, epoch, seed, mix):
         """batches() through ops.resample_u8, or ops.erase_u8 with `erase`: (x, y), or (x, y, y2, w) with `mix`."""
         n, crop = len(self), None
         if self.crop != "pad" or self.pad != (0, 0) or self.flip:
@@ -456,12 +602,12 @@ class GpuDataset:
         tables = self._mix_tables(epoch, seed, self.out_hw, mix) if mix is not None else ()
         if self.erase is None:
             for i in range(0, idx.numel(), batch_size):
-                yield ops.resample_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, self.out_hw, crop, *tables)
+                yield ops.resample_u8(images, self.labels, idx[i:i + batch_size], self.lut, self.out_hw, crop, *tables)
             return
         erase = erase_table(n, epoch, seed, self.out_hw, self.erase["prob"], self.erase["scale"], self.erase["ratio"])
         if tuple(erase.shape) != (n, 4) or erase.dtype != torch.int32:
             raise ValueError(f"GpuDataset.batches: the erase table is not int32 [{n}, 4]")
         erase, key = erase.contiguous().to(self.device), erase_noise_key(seed, epoch)
         for i in range(0, idx.numel(), batch_size):
-            yield ops.erase_u8(self.images, self.labels, idx[i:i + batch_size], self.lut, self.out_hw, crop, *tables, erase=erase,
+            yield ops.erase_u8(images, self.labels, idx[i:i + batch_size], self.lut, self.out_hw, crop, *tables, erase=erase,
                                noise=self.noise, noise_key=key)

@@ -1166,8 +1166,8 @@ def depth_keep(B: int, keep, seed: int, counter: int) -> torch.Tensor:
 # the training loop's off-model kernels, from here to the end of the file: one operand check
 # ---------------------------------------------------------------------------------------------------------------------------
 class KanvitOperandError(KanvitError, ValueError):
-    """A refused operand of erase_u8's own (erase, noise): a KanvitError like every refusal here, and the ValueError a caller of a
-    table-taking function expects."""
+    """A refused operand of erase_u8's own (erase, noise) or a refused RandAugment table: a KanvitError like every refusal here, and
+    the ValueError a caller of a table-taking function expects."""
 
 
 def _require_tensor(who: str, name: str, t: torch.Tensor, dtype, shape=None, device=None, contiguous: bool = True, hint: str = "",
@@ -1324,6 +1324,67 @@ def erase_u8(images: torch.Tensor, labels: Optional[torch.Tensor], idx: torch.Te
     if mixing:
         return out, y, y2, w
     return (out, y) if labels is not None else out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# RandAugment: one uint8 -> uint8 pass over the dataset per epoch (kanvit/data.py: randaug_table; csrc/randaug.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+_RA_FACTOR_OPS = (_lib.RA_BRIGHTNESS, _lib.RA_COLOR, _lib.RA_CONTRAST, _lib.RA_SHARPNESS)
+# (op, parameter, lowest, highest) of every parameter include/kanvit.h gives a range; AFFINE takes any int32
+_RA_RANGES = ((_lib.RA_POSTERIZE, 0, 0, 8), (_lib.RA_SOLARIZE, 0, 0, 256), (_lib.RA_SOLARIZE_ADD, 0, 0, 255), (_lib.RA_SOLARIZE_ADD, 1, 0, 256),
+              *((op, 0, 0, 2 * 65536) for op in _RA_FACTOR_OPS))
+
+
+def randaug_check_table(table: torch.Tensor, n: Optional[int] = None) -> torch.Tensor:
+    """The check of a RandAugment table on the CPU, BEFORE it is uploaded (data.GpuDataset.batches runs it once per epoch): int32
+    [N, K, 8] with 1 <= K <= 4 (and N == n where n is given), every op code one of the twelve of include/kanvit.h and every parameter
+    inside the range stated there.  The kernel would turn a row outside them into the identity; here it is a KanvitOperandError (a
+    ValueError) that names the first such row.  Returns the table."""
+    if not isinstance(table, torch.Tensor) or table.is_cuda or table.dtype != torch.int32 or table.dim() != 3 or table.shape[2] != 8 or \
+            not 1 <= table.shape[1] <= _lib.RA_MAX_OPS or (n is not None and table.shape[0] != n):
+        what = f"{table.dtype} {tuple(table.shape)} on {table.device}" if isinstance(table, torch.Tensor) else repr(type(table))
+        raise KanvitOperandError(f"randaug_check_table: the table is {what}, expected int32 [{'N' if n is None else n}, K, 8] on the CPU, "
+                                 f"1 <= K <= {_lib.RA_MAX_OPS}")
+    op, p = table[:, :, 0], table[:, :, 1:]
+    bad = (op < 0) | (op >= len(_lib.RA_OP_NAMES))
+    for code, j, lo, hi in _RA_RANGES:
+        bad |= (op == code) & ((p[:, :, j] < lo) | (p[:, :, j] > hi))
+    if bool(bad.any()):
+        s, k = (int(v) for v in bad.nonzero()[0])
+        raise KanvitOperandError(f"randaug_check_table: row [{s}, {k}] = {table[s, k].tolist()} has an unknown op code or a parameter outside its range")
+    return table
+
+
+def randaugment_u8(images: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """RandAugment over a whole uint8 dataset in one launch on the current stream (semantics, every op and its integer arithmetic:
+    include/kanvit.h, kanvit_randaug_u8): sample s is images[s] passed through the K rows table[s] in order.
+
+    images uint8 [N, H, W, C] or [N, H, W] (C = 1), 1 <= C <= 4 and H W C <= 24 576 bytes (the image lives in LDS; a larger one is
+    refused); table int32 [N, K, 8] on the device, 1 <= K <= 4, row = (op, p0 .. p6) -- data.randaug_table draws one per epoch,
+    randaug_check_table checks it before the upload; the kernel treats a row it does not know as the identity and never reaches outside
+    the image.  `out`: write into this contiguous uint8 tensor of the images' shape -- NOT the images themselves, nor memory that
+    overlaps them -- instead of allocating one.  Returns the augmented images; `images` is not changed."""
+    who = "randaugment_u8"
+    _require_tensor(who, "images", images, torch.uint8)
+    if images.dim() not in (3, 4):
+        raise KanvitError(f"{who}: images has shape {tuple(images.shape)}, expected [N, H, W, C] or [N, H, W]")
+    N, H, W = (int(v) for v in images.shape[:3])
+    Cn = int(images.shape[3]) if images.dim() == 4 else 1
+    if not 1 <= Cn <= 4 or H < 1 or W < 1 or H * W * Cn > _lib.RA_MAX_BYTES:
+        raise KanvitError(f"{who}: images of {H} x {W} x {Cn} = {H * W * Cn} bytes: 1 to 4 channels and at most {_lib.RA_MAX_BYTES} bytes "
+                          "(the image and its copy live in LDS)")
+    _require_tensor(who, "table", table, torch.int32, None, images.device)
+    if table.dim() != 3 or table.shape[0] != N or not 1 <= table.shape[1] <= _lib.RA_MAX_OPS or table.shape[2] != 8:
+        raise KanvitError(f"{who}: table has shape {tuple(table.shape)}, expected [{N}, K, 8], 1 <= K <= {_lib.RA_MAX_OPS}")
+    if out is None:
+        out = torch.empty_like(images)
+    else:
+        if out is images:
+            raise KanvitError(f"{who}: out is images: an op reads more than the byte it writes; give a second buffer")
+        _require_tensor(who, "out", out, torch.uint8, tuple(images.shape), images.device)
+    _launch(_lib.lib().kanvit_randaug_u8, "kanvit_randaug_u8", images.device, _ptr(images), _ptr(out), _ptr(table), N, H, W, Cn,
+            int(table.shape[1]), tag="randaug_u8", cost=(0, 2 * images.numel()))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

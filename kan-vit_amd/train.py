@@ -28,7 +28,10 @@ geometry on 32 x 32 images -- and RandomResizedCrop boxes come from a per-epoch 
 kanvit/data.py crop_table, ops.resample_u8; --image-size stays the size of the stored images), --random-erasing P / --erase-mode /
 --erase-scale / --erase-ratio (Random Erasing inside the batch kernel, before Mixup / CutMix and on the partner too: with probability
 P a per-sample box from a per-epoch table is replaced by standard-normal noise or zeros -- kanvit/data.py erase_table, ops.erase_u8;
-the train split only), --optimizer kanvit-adamw with --weight-decay /
+the train split only), --randaug [M] / --randaug-ops / --randaug-mstd / --randaug-prob (RandAugment, timm's rand-m9-mstd0.5-inc1, as
+ONE uint8 -> uint8 pass over the whole train split per epoch into a second GPU-resident copy that the batch kernels then read: two ops
+per sample from a per-epoch table that is a function of (seed, epoch) alone, integer arithmetic, at the stored size BEFORE crop, flip
+and resize where timm applies them after -- kanvit/data.py randaug_table, ops.randaugment_u8), --optimizer kanvit-adamw with --weight-decay /
 --clip-grad-norm / --warmup-steps / --lr-schedule / --min-lr / --ema-decay (AdamW with global-norm clipping, a schedule table and a weight
 EMA in the project's own fused step, kanvit/optim.py; the default --optimizer adam is the reference's step), --drop-path RATE /
 --drop-path-schedule (stochastic depth as a per-sample scale inside the fused residual add + LayerNorm passes, masks from a hash of
@@ -118,6 +121,20 @@ def check_data_args(args):
             raise SystemExit("--random-erasing erases inside the kernel that reads the GPU-resident dataset; give --data-npz")
         if getattr(args, "no_augment", False):
             raise SystemExit("--random-erasing is an augmentation; it is not combined with --no-augment")
+    randaug = getattr(args, "randaug", None)
+    if randaug is not None and not 0.0 <= float(randaug) <= 10.0:
+        raise SystemExit(f"--randaug {randaug}: the magnitude is in 0..10")
+    if not 1 <= int(getattr(args, "randaug_ops", 2)) <= 4:
+        raise SystemExit(f"--randaug-ops {args.randaug_ops} must be in 1..4")
+    if not 0.0 <= float(getattr(args, "randaug_mstd", 0.5)) < float("inf"):
+        raise SystemExit(f"--randaug-mstd {args.randaug_mstd} is negative or not finite")
+    if not 0.0 <= float(getattr(args, "randaug_prob", 0.5)) <= 1.0:
+        raise SystemExit(f"--randaug-prob {args.randaug_prob} is not a probability")
+    if randaug is not None:
+        if not getattr(args, "data_npz", None):
+            raise SystemExit("--randaug augments a second copy of the GPU-resident dataset once per epoch; give --data-npz")
+        if getattr(args, "no_augment", False):
+            raise SystemExit("--randaug is an augmentation; it is not combined with --no-augment")
 
 
 RECIPE_FLAGS = (("--weight-decay", "weight_decay", 0.0), ("--clip-grad-norm", "clip_grad_norm", 0.0), ("--warmup-steps", "warmup_steps", 0),
@@ -161,12 +178,25 @@ def erase_config(args):
                 mode=getattr(args, "erase_mode", "pixel"))
 
 
+def randaug_config(args, mean=None):
+    """The `randaug` argument of GpuDataset from the flags, or None without --randaug.  mean: the dataset's per-channel mean on the 0-1
+    scale; the geometric ops fill with round(255 mean) per channel."""
+    if getattr(args, "randaug", None) is None:
+        return None
+    cfg = dict(n_ops=int(getattr(args, "randaug_ops", 2)), magnitude=float(args.randaug), mstd=float(getattr(args, "randaug_mstd", 0.5)),
+               prob=float(getattr(args, "randaug_prob", 0.5)))
+    if mean is not None:
+        cfg["fill"] = tuple(min(max(int(round(255.0 * float(m))), 0), 255) for m in mean)
+    return cfg
+
+
 def npz_datasets(args, device, want_test=True):
     """--data-npz: (train, test or None) GpuDatasets.  --image-size / --in-chans left at their defaults follow the file (args is
     updated); given values that contradict it, labels that --out-d does not cover and non-square images are refused.  Only the rank
     that evaluates asks for the test split.  --resize S gives both splits out_size = (S, S) (--image-size stays the file's size) and
     --random-resized-crop gives the train split crop="rrc": their batches then come from ops.resample_u8.  --random-erasing gives the
-    train split -- never the test split -- erase=...: its batches come from ops.erase_u8."""
+    train split -- never the test split -- erase=...: its batches come from ops.erase_u8.  --randaug gives the train split -- never the
+    test split -- randaug=...: a second buffer that ops.randaugment_u8 fills once per epoch and the batch kernels read."""
     from kanvit import data as kdata
     blob = kdata.load_npz(args.data_npz)
     x = blob["x_train"]
@@ -186,10 +216,14 @@ def npz_datasets(args, device, want_test=True):
         raise SystemExit(f"--crop-padding {args.crop_padding} exceeds the image size {h}")
     resize, rrc = int(getattr(args, "resize", 0)), bool(getattr(args, "random_resized_crop", False))
     out_size = (resize, resize) if resize > 0 else None          # --resize: both splits come out at the model's size
+    mean = None
+    if getattr(args, "randaug", None) is not None:               # the fill of its geometric ops: the dataset mean, as the datasets use it
+        mean = blob["mean"] if "mean" in blob else kdata.channel_stats(x)[0]
     train = kdata.GpuDataset.from_arrays(blob, args.data_npz, "train", device, pad=args.crop_padding if augment else 0, flip=augment,
                                          out_size=out_size, crop="rrc" if rrc else "pad",
                                          rrc_scale=tuple(getattr(args, "rrc_scale", (0.08, 1.0))),
-                                         rrc_ratio=tuple(getattr(args, "rrc_ratio", (3.0 / 4.0, 4.0 / 3.0))), erase=erase_config(args))
+                                         rrc_ratio=tuple(getattr(args, "rrc_ratio", (3.0 / 4.0, 4.0 / 3.0))), erase=erase_config(args),
+                                         randaug=randaug_config(args, mean))
     test = kdata.GpuDataset.from_arrays(blob, args.data_npz, "test", device, out_size=out_size) if want_test and "x_test" in blob else None
     return train, test
 
@@ -649,6 +683,17 @@ def parse(argv=None):
                    help='--random-erasing: the range of the box area as a fraction of the image')
     p.add_argument('--erase-ratio', type=float, nargs=2, default=(0.3, 1.0 / 0.3), metavar=('LO', 'HI'),
                    help='--random-erasing: the range of the box aspect ratio (log-uniform)')
+    p.add_argument('--randaug', type=float, nargs='?', const=9.0, default=None, metavar='M',
+                   help="with --data-npz: RandAugment (timm's rand-mM-mstd0.5-inc1; M defaults to 9) as one uint8 -> uint8 pass over the "
+                        'whole train split per epoch, into a second GPU-resident copy that the batch kernel then reads (kanvit/data.py '
+                        'randaug_table, ops.randaugment_u8): --randaug-ops ops per sample out of fifteen, from a per-epoch table that is a '
+                        'function of (seed, epoch) alone, in integer arithmetic at the STORED size, before crop / flip / resize (timm '
+                        'applies them after RandomResizedCrop); geometric ops fill with the dataset mean.  The train split only; images '
+                        'of at most 24 576 bytes.  Default: off')
+    p.add_argument('--randaug-ops', type=int, default=2, metavar='N', help='--randaug: ops per sample, 1 to 4')
+    p.add_argument('--randaug-mstd', type=float, default=0.5, metavar='S',
+                   help='--randaug: standard deviation of the per-op magnitude around M (clipped to 0..10)')
+    p.add_argument('--randaug-prob', type=float, default=0.5, metavar='P', help='--randaug: probability that a drawn op is applied')
     p.add_argument('--mixup', type=float, default=0.0, metavar='ALPHA',
                    help='with --data-npz: Mixup -- blend every sample with a partner, lam ~ Beta(ALPHA, ALPHA), inside the batch kernel '
                         '(kanvit/data.py: mix_table, ops.mix_u8); the loss becomes the fused soft-target cross-entropy and the train '
