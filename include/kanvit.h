@@ -501,6 +501,49 @@ int kanvit_addln_sd_bwd(int64_t M, int D, const float* xsum, const float* gamma,
                         const void* dy, int dy_bf16, const float* dres, float* dx, void* ddelta, int ddelta_bf16, float* dgamma, float* dbeta,
                         const float* row_scale, int64_t rows_per_sample, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- PatchDropout: train on a hashed subset of every sample's patch tokens (csrc/patch_drop.hip) ------------------------------
+ * Liu et al. 2023, timm's patch_drop_rate, the masking of FLIP / MAE: in training every sample keeps K of its P patch tokens and the
+ * class token; everything behind the embedding runs on N = K + 1 tokens.  The reference model has no such option (model.py:144-152
+ * builds all P + 1 rows).  Stock PyTorch spends rand + argsort + gather on a full [B, P, I] patch matrix and needs a generator a
+ * captured graph does not step; here the keep set is a hash, the gather reads only the kept patches out of the NCHW batch, and the
+ * sequence is assembled with the position embedding of the ORIGINAL patch positions.
+ *
+ * kanvit_patch_keep: idx[B][K] (int32, device), the kept patch numbers of every sample in ascending order.  With mix() the splitmix64
+ * step stated at kanvit_augment_u8 and c the value of *counter when the launch starts,
+ *   base = mix(mix(seed ^ KANVIT_PATCH_KEEP_TAG) + c),          key(b, p) = mix(base + ((uint64)b << 32) + p),
+ * patch p of sample b is kept iff fewer than K pairs (key(b, p'), p') are lexicographically below (key(b, p), p): the K smallest
+ * keys, ties (which a 64-bit hash all but never has) going to the smaller p.  The tag keeps this stream apart from
+ * kanvit_depth_scales' under the same seed; a sample's row does not depend on B.  counter is a device uint64, 8-byte aligned, with a
+ * value below 2^48: every work-group reads it and the launch adds exactly 1 to it, with nothing from the host (one atomic per
+ * work-group is its read and its ticket in the top 16 bits; the last ticket puts c + 1 back -- DESIGN.md section 4.26), so consecutive
+ * launches and replays of a captured one draw new sets.  1 <= K <= P <= KANVIT_PATCH_KEEP_MAX_P (a sample's keys live in LDS), 0 <= B
+ * < 2^31; B = 0 returns KANVIT_OK without touching the counter.  KANVIT_EINVAL (named in kanvit_last_error, before the device is
+ * touched) outside that domain and for a null or misaligned pointer.
+ *
+ * kanvit_patch_gather: p as for kanvit_patch_embed_fwd (prepend_rows is ignored); ph = H / n_patches, pw = W / n_patches, I = C ph pw.
+ *   rows[(b*K + j)*ldr + i] = images[b][c][py*ph + iy][px*pw + ix],   idx[b][j] = py*n_patches + px,   i = (c*ph + iy)*pw + ix
+ * -- patchify restricted to the kept patches, a pure copy of B*K*I floats.  idx is any int32 [B][K] on the device with entries in
+ * [0, P): unsorted and repeated entries are fine, an entry outside is the caller's error (not checked on the device).  Any pw, any
+ * 4-byte aligned images / rows, ldr >= I; float4 moves where pw % 4 == 0, ldr % 4 == 0 and both addresses are 16-byte aligned.
+ * B*K < 2^31.  No gradient: the images are data.
+ *
+ * kanvit_tokens_assemble_fwd: out[B][K + 1][O] (contiguous) from the embedded rows tokens[B*K][ldt], cls[O] and pos[P + 1][O]:
+ *   out[b][0][:] = cls + pos[0],     out[b][1 + j][:] = tokens[(b*K + j)*ldt + :] + pos[1 + idx[b][j]]
+ * one fp32 add per element (bit for bit torch's cat + indexed add).  cls / pos may not be NULL.
+ * kanvit_tokens_assemble_bwd: dtokens[b*K + j][:] = dout[b][1 + j][:] (contiguous [B*K][O], a copy) and dcls[o] = sum_b dout[b][0][o];
+ * either may be NULL (not wanted), not both.  The sum has a fixed order and no atomics: slice s of eight adds samples s, s + 8, ...
+ * in that order, then the eight slices are added in order -- bitwise the same from run to run.
+ * All four return KANVIT_EINVAL before the device is touched for sizes below 1, ld below the row length, row counts of 2^31 and
+ * more, null and misaligned (4-byte) pointers.  Additive: the ABI version stays 7. */
+#define KANVIT_PATCH_KEEP_MAX_P 1024
+#define KANVIT_PATCH_KEEP_TAG 0x5061746368447270ull /* "PatchDrp" */
+int kanvit_patch_keep(int64_t B, int P, int K, uint64_t seed, uint64_t* counter, int32_t* idx, void* stream);
+int kanvit_patch_gather(const kanvit_patch_desc* p, int64_t B, int K, const int32_t* idx, const float* images, float* rows, int64_t ldr,
+                        void* stream);
+int kanvit_tokens_assemble_fwd(int64_t B, int K, int O, const float* tokens, int64_t ldt, const float* cls, const float* pos,
+                               const int32_t* idx, float* out, void* stream);
+int kanvit_tokens_assemble_bwd(int64_t B, int K, int O, const float* dout, float* dtokens, float* dcls, void* stream);
+
 /* ---- ReLU backward + bias gradient of the feed-forward's first Linear in one pass ----------------
  * The TransformerBlock's nn.Sequential(Linear, ReLU(inplace), Linear) (model.py:25-29): what autograd runs for the ReLU and
  * for the first Linear's bias -- threshold_backward on the saved activation y, then a column sum of the result --

@@ -747,3 +747,5 @@ int kanvit_layer_ln_bwd(const kanvit_layer_desc* d, const float* x, const float*
 }
 
 }  // extern "C"
+
+#include "patch_drop.hip"

@@ -124,6 +124,10 @@ SYMBOLS = {
     "kanvit_depth_scales": (C.c_int, [C.c_int64, C.c_int, _P, C.c_uint64, _P, _P, _P]),
     "kanvit_addln_sd_fwd": (C.c_int, [C.c_int64, C.c_int, C.c_float, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int64, _P]),
     "kanvit_addln_sd_bwd": (C.c_int, [C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_size_t, _P]),
+    "kanvit_patch_keep": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_uint64, _P, _P, _P]),
+    "kanvit_patch_gather": (C.c_int, [C.POINTER(PatchDesc), C.c_int64, C.c_int, _P, _P, _P, C.c_int64, _P]),
+    "kanvit_tokens_assemble_fwd": (C.c_int, [C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    "kanvit_tokens_assemble_bwd": (C.c_int, [C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "kanvit_relu_bwd_bias_workspace": (C.c_size_t, [C.c_int64, C.c_int]),
     "kanvit_relu_bwd_bias": (C.c_int, [C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_relu_bwd_bias_bf16": (C.c_int, [C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
@@ -149,6 +153,8 @@ SYMBOLS = {
 }
 OPTIM_CHUNK = 4096      # KANVIT_OPTIM_CHUNK: the elements one work-group of the optimizer kernels takes
 DEPTH_MAX_BRANCHES = 64      # KANVIT_DEPTH_MAX_BRANCHES: the residual branches one kanvit_depth_scales launch draws for
+PATCH_KEEP_MAX_P = 1024      # KANVIT_PATCH_KEEP_MAX_P: the patches per sample one kanvit_patch_keep launch ranks (its keys live in LDS)
+PATCH_KEEP_TAG = 0x5061746368447270      # KANVIT_PATCH_KEEP_TAG: xored into the seed, apart from kanvit_depth_scales' stream
 # KANVIT_RA_*: the op codes of kanvit_randaug_u8's table, the rows per sample and the largest image (H W C bytes) it takes
 (RA_IDENTITY, RA_AUTOCONTRAST, RA_EQUALIZE, RA_INVERT, RA_POSTERIZE, RA_SOLARIZE, RA_SOLARIZE_ADD, RA_BRIGHTNESS, RA_COLOR, RA_CONTRAST,
  RA_SHARPNESS, RA_AFFINE) = range(12)

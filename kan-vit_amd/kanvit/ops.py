@@ -1162,6 +1162,121 @@ def depth_keep(B: int, keep, seed: int, counter: int) -> torch.Tensor:
     return torch.from_numpy(out)
 
 
+def _patch_keep_domain(who: str, B: int, P: int, K: int):
+    if B < 0 or not 1 <= K <= P <= _lib.PATCH_KEEP_MAX_P:
+        raise KanvitOperandError(f"{who}: B={B}, P={P}, K={K}: B >= 0 and 1 <= K <= P <= {_lib.PATCH_KEEP_MAX_P} (one sample's keys live in LDS)")
+
+
+def patch_keep(B: int, P: int, K: int, seed: int, counter: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """PatchDropout's keep table of one forward: int32 [B, K], row b the K kept patch numbers of sample b out of P, ascending
+    (kanvit_patch_keep; the hash is stated in include/kanvit.h, patch_keep_ref below restates it on the CPU).  seed: any integer (taken
+    mod 2^64); counter: a one-element int64 tensor on the device with a value below 2^48, read by the launch and then incremented by
+    it, so consecutive calls -- and replays of a captured call -- draw different sets without RNG state and without anything from the
+    host.  One launch, capturable.  B = 0 gives an empty table and leaves the counter alone."""
+    B, P, K = int(B), int(P), int(K)
+    _patch_keep_domain("patch_keep", B, P, K)
+    if not torch.is_tensor(counter) or counter.numel() != 1:
+        raise KanvitOperandError("patch_keep: counter is a one-element int64 tensor on the GPU")
+    _require_tensor("patch_keep", "counter", counter, torch.int64)
+    if out is None:
+        out = torch.empty(B, K, device=counter.device, dtype=torch.int32)
+    else:
+        _require_tensor("patch_keep", "out", out, torch.int32, shape=(B, K), device=counter.device)
+    _launch(_lib.lib().kanvit_patch_keep, "kanvit_patch_keep", counter.device, B, P, K, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+            _ptr(counter), _ptr(out))
+    return out
+
+
+def patch_keep_ref(B: int, P: int, K: int, seed: int, counter: int) -> torch.Tensor:
+    """patch_keep restated in Python integers on the CPU (the tests compare the kernel with it bit for bit): base = mix(mix(seed ^
+    TAG) + counter), key(b, p) = mix(base + (b << 32) + p); row b is the K patches with the smallest (key, p), in ascending patch order."""
+    from .data import _mix
+    B, P, K = int(B), int(P), int(K)
+    _patch_keep_domain("patch_keep_ref", B, P, K)
+    m64 = 0xFFFFFFFFFFFFFFFF
+    base = _mix((_mix((int(seed) & m64) ^ _lib.PATCH_KEEP_TAG) + int(counter)) & m64)
+    out = torch.empty(B, K, dtype=torch.int32)
+    for b in range(B):
+        keys = [(_mix((base + (b << 32) + p) & m64), p) for p in range(P)]
+        out[b] = torch.tensor(sorted(p for _, p in sorted(keys)[:K]), dtype=torch.int32)
+    return out
+
+
+def patch_gather(images: torch.Tensor, idx: torch.Tensor, n_patches: int) -> torch.Tensor:
+    """patchify(images, n_patches) restricted to the patches idx names: float32 [B * K, C*ph*pw], row b*K + j = patch idx[b, j] of image b
+    flattened in (C, ph, pw) order (kanvit_patch_gather: a copy of the kept patches only, straight out of NCHW -- no [B, P, I] matrix).
+    images: float32 [B, C, H, W] on the GPU, contiguous, at any 4-byte address; idx: int32 [B, K] on the same GPU with entries in [0,
+    n_patches^2) -- in any order, repeats allowed, not checked on the device.  No gradient reaches the images: they are data."""
+    if not torch.is_tensor(images) or images.dim() != 4:
+        raise KanvitOperandError("patch_gather: images is a float32 [B, C, H, W] tensor on the GPU")
+    _require_tensor("patch_gather", "images", images, torch.float32)
+    B, Cc, H, W = images.shape
+    n = int(n_patches)
+    if n < 1 or H % n or W % n:
+        raise KanvitOperandError(f"patch_gather: n_patches={n} must divide H={H} and W={W}")
+    if not torch.is_tensor(idx) or idx.dim() != 2 or idx.shape[0] != B or not 1 <= idx.shape[1] <= n * n:
+        raise KanvitOperandError(f"patch_gather: idx is an int32 [B={B}, K] tensor with 1 <= K <= {n * n}")
+    _require_tensor("patch_gather", "idx", idx, torch.int32, device=images.device)
+    K, I = idx.shape[1], Cc * (H // n) * (W // n)
+    rows = torch.empty(B * K, I, device=images.device, dtype=torch.float32)
+    pd = _lib.PatchDesc(Cc, H, W, n, 0, 0)
+    _launch(_lib.lib().kanvit_patch_gather, "kanvit_patch_gather", images.device, C.byref(pd), B, K, _ptr(idx), _ptr(images), _ptr(rows), I)
+    return rows
+
+
+class _AssembleTokensFn(torch.autograd.Function):
+    """tokens [B*K, O] (or [B, K, O]), cls, pos, idx [B, K] -> [B, K + 1, O] = [cls + pos[0]; tokens[b, j] + pos[1 + idx[b, j]]] in one
+    launch; backward: d tokens = the gradient without its class rows (a copy), d cls = sum_b dout[b, 0] in a fixed order."""
+
+    @staticmethod
+    @_fwd_f32
+    def forward(ctx, tokens, cls, pos, idx):
+        who = "assemble_tokens"
+        for name, t in (("tokens", tokens), ("cls", cls), ("pos", pos), ("idx", idx)):
+            if not torch.is_tensor(t):
+                raise KanvitOperandError(f"{who}: {name} is a tensor on the GPU")
+        if idx.dim() != 2 or idx.shape[1] < 1:
+            raise KanvitOperandError(f"{who}: idx is an int32 [B, K] tensor with K >= 1, got shape {tuple(idx.shape)}")
+        B, K = idx.shape
+        _require_tensor(who, "tokens", tokens, torch.float32, contiguous=False)
+        O = tokens.shape[-1]
+        if tuple(tokens.shape) not in ((B * K, O), (B, K, O)):
+            raise KanvitOperandError(f"{who}: tokens has shape {tuple(tokens.shape)}, expected ({B * K}, O) or ({B}, {K}, O)")
+        _require_tensor(who, "idx", idx, torch.int32, device=tokens.device)
+        _require_tensor(who, "cls", cls, torch.float32, device=tokens.device, contiguous=False)
+        _require_tensor(who, "pos", pos, torch.float32, device=tokens.device, contiguous=False)
+        if cls.numel() != O or pos.dim() != 2 or pos.shape[1] != O:
+            raise KanvitOperandError(f"{who}: cls has {cls.numel()} elements and pos shape {tuple(pos.shape)}, expected {O} and (P + 1, {O})")
+        t2 = tokens.reshape(B * K, O)
+        if B * K and (t2.stride(1) != 1 or t2.stride(0) < O):      # a matrix with padded rows is read in place
+            t2 = t2.contiguous()
+        out = torch.empty(B, K + 1, O, device=tokens.device, dtype=torch.float32)
+        _launch(_lib.lib().kanvit_tokens_assemble_fwd, "kanvit_tokens_assemble_fwd", tokens.device, B, K, O, _ptr(t2), max(t2.stride(0), O),
+                _ptr(cls.reshape(-1).contiguous()), _ptr(pos.contiguous()), _ptr(idx), _ptr(out))
+        ctx.tokens_shape, ctx.cls_shape = tuple(tokens.shape), tuple(cls.shape)
+        return out
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, dout):
+        dout = dout.float().contiguous()
+        B, N, O = dout.shape
+        dtokens = torch.empty(B * (N - 1), O, device=dout.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        dcls = torch.empty(O, device=dout.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        if dtokens is not None or dcls is not None:
+            _launch(_lib.lib().kanvit_tokens_assemble_bwd, "kanvit_tokens_assemble_bwd", dout.device, B, N - 1, O, _ptr(dout), _ptr(dtokens),
+                    _ptr(dcls))
+        return (None if dtokens is None else dtokens.view(ctx.tokens_shape), None if dcls is None else dcls.view(ctx.cls_shape), None, None)
+
+
+def assemble_tokens(tokens: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """The token sequence of a PatchDropout forward: float32 [B, K + 1, O] with row 0 = cls + pos[0] and row 1 + j = tokens[b*K + j] +
+    pos[1 + idx[b, j]] -- the position embedding of the ORIGINAL patch positions, one fp32 add per element (bit for bit torch's cat +
+    indexed add).  tokens: float32 [B*K, O] (the row stride may exceed O) or [B, K, O]; cls: O elements; pos: [P + 1, O]; idx: int32
+    [B, K] as patch_keep writes it.  Gradients for tokens (a copy of the patch rows) and cls (a fixed-order sum: reproducible)."""
+    return _AssembleTokensFn.apply(tokens, cls, pos, idx)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # the training loop's off-model kernels, from here to the end of the file: one operand check
 # ---------------------------------------------------------------------------------------------------------------------------

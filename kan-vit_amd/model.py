@@ -197,6 +197,35 @@ class VisionTransformer(nn.Module):
         self._fused_embed = None       # None = not tried yet, else {bf16 autocast?: the fused patch-embedding kernel covers this model}
         self._drop_path = None         # set_drop_path: None = off, else (keep probabilities of the 2 * n_blocks branches, seed)
         self.drop_path_rates = []
+        self._patch_dropout = None     # set_patch_dropout: None = off, else (K kept patches per sample, seed)
+
+    def set_patch_dropout(self, rate, seed=0):
+        """PatchDropout (Liu et al. 2023; timm's patch_drop_rate): in train() mode on the GPU every sample keeps K = max(1, int(P *
+        (1 - rate))) of its P patch tokens (timm's rule) plus the class token, so every block runs on K + 1 tokens; eval() sees all
+        of them.  Set after construction, like set_drop_path; rate 0 (or a rate that keeps all P) removes it again.  The keep set
+        comes from one kanvit.ops.patch_keep launch per forward -- a hash of (seed, a device call counter, sample, patch), no RNG
+        state, so a captured step draws a new set at every replay; only the kept patches are gathered from the images and embedded
+        (_embed_kept).  The counter is a non-persistent buffer: state_dict() is unchanged.  update_grid, extend_grid and the attention
+        maps always use the full sequence.  Returns K."""
+        rate = float(rate)
+        if not 0.0 <= rate < 1.0:
+            raise ValueError(f"set_patch_dropout: rate {rate} must be in [0, 1)")
+        P = self.n_patches ** 2
+        K = max(1, int(P * (1.0 - rate)))
+        if rate == 0.0 or K == P:
+            self._patch_dropout = None
+            if "patch_dropout_counter" in self._buffers:
+                del self._buffers["patch_dropout_counter"]
+                self._non_persistent_buffers_set.discard("patch_dropout_counter")
+            return P
+        if P > _lib.PATCH_KEEP_MAX_P:
+            raise NotImplementedError(f"set_patch_dropout: {P} patches per image; one patch_keep launch ranks {_lib.PATCH_KEEP_MAX_P}")
+        self._patch_dropout = (K, int(seed))
+        if "patch_dropout_counter" not in self._buffers:
+            self.register_buffer("patch_dropout_counter", torch.zeros(1, dtype=torch.int64, device=self.v_class.device), persistent=False)
+        else:
+            self.patch_dropout_counter.zero_()
+        return K
 
     def set_drop_path(self, rate, seed=0, schedule="linear"):
         """Stochastic depth (DropPath, Huang et al. 2016, as the DeiT recipe uses it): in train() mode every residual branch of
@@ -298,6 +327,38 @@ class VisionTransformer(nn.Module):
             cls = self.v_class.unsqueeze(0).expand(b, -1, -1)
             out = torch.cat((cls, tokens), dim=1) + self.pos_embeddings[: p + 1]
         return out
+
+    def _keeps_patches(self, images):
+        """PatchDropout applies: set, train() mode, a batch on the GPU (a CPU model, eval() and rate 0 run what they always ran)."""
+        return self._patch_dropout is not None and self.training and images.is_cuda
+
+    def _embed_kept_torch(self, images, idx):
+        """_embed_kept in stock torch ops, for images that want a gradient (and what the tests compare _embed_kept with): the full
+        patch matrix, the rows idx ([B, K], any integer dtype) names, the embedding, cat and the position rows of the original
+        patch numbers.  Returns (tokens [B, K + 1, d], the kept patch rows [B * K, I])."""
+        b, k = idx.shape
+        take = idx.to(device=images.device, dtype=torch.int64)
+        patches = self.patchify(images, self.n_patches)
+        rows = torch.gather(patches, 1, take.unsqueeze(-1).expand(b, k, patches.shape[-1])).reshape(b * k, self.input_d)
+        tokens = self.linear_mapper(rows).float().reshape(b, k, self.d_hidden)
+        cls = self.v_class.unsqueeze(0).expand(b, -1, -1)
+        pos = self.pos_embeddings[: self.n_patches ** 2 + 1]
+        return torch.cat((cls + pos[:1], tokens + pos[1 + take]), dim=1), rows
+
+    def _embed_kept(self, images):
+        """The token sequence of a PatchDropout forward, [B, K + 1, d]: the keep table (ops.patch_keep bumps the device counter), the
+        kept patches gathered out of the NCHW batch, the patch-embedding module on those B * K rows, whatever its type, and the
+        sequence with the class token and the position embedding of the original positions (ops.assemble_tokens).  Also returns the
+        gathered rows -- the rows the layer saw, which is what the regulariser is taken on."""
+        K, seed = self._patch_dropout
+        idx = ops.patch_keep(images.shape[0], self.n_patches ** 2, K, seed, self.patch_dropout_counter)
+        if images.requires_grad or images.dtype != torch.float32:
+            return self._embed_kept_torch(images, idx)
+        rows = ops.patch_gather(images.contiguous(), idx, self.n_patches)
+        tokens = self.linear_mapper(rows)
+        if tokens.dtype != torch.float32:               # nn.Linear under autocast: torch's cat with the fp32 class token promotes it too
+            tokens = tokens.float()
+        return ops.assemble_tokens(tokens, self.v_class, self.pos_embeddings[: self.n_patches ** 2 + 1], idx), rows
 
     @torch.no_grad()
     def update_grid(self, images, margin=0.01):
@@ -430,6 +491,10 @@ class VisionTransformer(nn.Module):
         every block's per-head q|k|v layers, on norm1(x) -- computed on the tensors this forward holds anyway, by the fused
         edge-activation kernel (no second forward, no (rows, in, out) tensor).  Model types efficientkan, cheby and fast."""
         reg, reg_kw, patches = None, None, None
+        # PatchDropout (set_patch_dropout), train() mode on the GPU only: the sequence is built from the kept patches
+        out = None
+        if self._keeps_patches(images):
+            out, rows = self._embed_kept(images)
         if return_regularization:
             kinds = self.layer_types()
             if not kinds <= set(self.REGULARIZED_TYPES):
@@ -437,13 +502,16 @@ class VisionTransformer(nn.Module):
                                           f"edge-activation regulariser; supported: {', '.join(self.REGULARIZED_TYPES)}")
             reg_kw = dict(regularize_activation=regularize_activation, regularize_entropy=regularize_entropy)
             # the fused patch embedding gathers from NCHW and never holds the patch matrix: build it once for the regulariser
-            patches = self.patchify(images, self.n_patches)
-            rows = patches.reshape(-1, self.input_d)
+            # (under PatchDropout the regulariser is taken on the kept rows, the rows the layer saw)
+            if out is None:
+                patches = self.patchify(images, self.n_patches)
+                rows = patches.reshape(-1, self.input_d)
             if isinstance(self.linear_mapper, KANLinear):
                 reg = self.linear_mapper.regularization_loss(x=rows, **reg_kw)
             else:
                 reg = self.linear_mapper.regularization_loss(rows, **reg_kw)
-        out = self._embed(images, patches)
+        if out is None:
+            out = self._embed(images, patches)
         pending = None
         # the head reads the class token only: the last block computes that row alone (TransformerBlock.run_cls), except for the
         # small geometries (launch-bound: they keep the one-launch LN2 + feed-forward) and when the regulariser is asked for

@@ -35,7 +35,8 @@ and resize where timm applies them after -- kanvit/data.py randaug_table, ops.ra
 --clip-grad-norm / --warmup-steps / --lr-schedule / --min-lr / --ema-decay (AdamW with global-norm clipping, a schedule table and a weight
 EMA in the project's own fused step, kanvit/optim.py; the default --optimizer adam is the reference's step), --drop-path RATE /
 --drop-path-schedule (stochastic depth as a per-sample scale inside the fused residual add + LayerNorm passes, masks from a hash of
---seed and a device step counter: VisionTransformer.set_drop_path; the test pass runs without it).
+--seed and a device step counter: VisionTransformer.set_drop_path; the test pass runs without it), --patch-dropout RATE (PatchDropout:
+every sample trains on a hashed subset of its patch tokens, VisionTransformer.set_patch_dropout; the test pass sees all of them).
 
 `main(args, batches=None, init_state=None)` also serves the parity tests: `batches` (a list of (x, y) tensors) replaces
 the data stream, `init_state` (a reference-layout state dict) replaces the random initialisation, and the returned dict
@@ -235,15 +236,17 @@ class _GraphedStep:
 
     Capturing needs lazily created state (optimizer moments, library workspaces) to exist, so one throw-away step runs on a
     side stream first; parameters are then restored, the Adam moments / step counters zeroed, which is exactly the state
-    of a fresh optimizer, and the model's drop-path counter (--drop-path) put back -- the replayed trajectory equals the eager one."""
+    of a fresh optimizer, and the model's drop-path and patch-dropout counters (--drop-path, --patch-dropout) put back -- the
+    replayed trajectory equals the eager one."""
 
     def __init__(self, eager_step, model, optimizer, x, y, y2=None, w=None):
         self.eager = eager_step
         self.sx, self.sy = x.clone(), y.clone()
         self.pair = () if y2 is None else (y2.clone(), w.clone())      # Mixup / CutMix: static buffers like x and y
         saved = [p.detach().clone() for p in model.parameters()]
-        counter = getattr(model, "drop_path_counter", None)          # --drop-path: the throw-away step must not use up a mask
-        count = None if counter is None else counter.clone()
+        # --drop-path / --patch-dropout: the throw-away step must not use up a mask or a keep set
+        counters = [c for c in (getattr(model, "drop_path_counter", None), getattr(model, "patch_dropout_counter", None)) if c is not None]
+        counts = [c.clone() for c in counters]
         side = torch.cuda.Stream(device=x.device)
         side.wait_stream(torch.cuda.current_stream(x.device))
         with torch.cuda.stream(side):
@@ -257,8 +260,8 @@ class _GraphedStep:
                 for v in st.values():
                     if torch.is_tensor(v):
                         v.zero_()
-            if counter is not None:
-                counter.copy_(count)
+            for c, count in zip(counters, counts):
+                c.copy_(count)
         optimizer.zero_grad(set_to_none=True)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
@@ -399,6 +402,16 @@ def main(args, batches=None, init_state=None):
                                 schedule=getattr(args, "drop_path_schedule", "linear"))
         except NotImplementedError as e:
             raise SystemExit(f"--drop-path: {e}")
+    patch_dropout = float(getattr(args, "patch_dropout", 0.0))
+    if not 0.0 <= patch_dropout < 1.0:
+        raise SystemExit(f"--patch-dropout {patch_dropout} must be in [0, 1)")
+    if patch_dropout > 0:
+        # --patch-dropout: the keep sets are a hash of (seed, step counter, position in the rank's batch, patch); the rank is mixed in as above
+        from kanvit.data import _mix
+        try:
+            model.set_patch_dropout(patch_dropout, seed=args.seed if world == 1 else _mix(_mix(args.seed) + rank))
+        except NotImplementedError as e:
+            raise SystemExit(f"--patch-dropout: {e}")
     if init_state is not None:
         model.load_state_dict(init_state)
     model = model.to(device)
@@ -734,9 +747,15 @@ def parse(argv=None):
                         "works); not for 'flash-attn'; the test pass runs without it.  0 (default): off")
     p.add_argument('--drop-path-schedule', choices=['linear', 'constant'], default='linear',
                    help='--drop-path: the rate of block l of L is RATE * l / (L - 1) (linear, the DeiT / timm rule) or RATE in every block')
+    p.add_argument('--patch-dropout', type=float, default=0.0, metavar='RATE',
+                   help='PatchDropout: in training every sample keeps max(1, int(P * (1 - RATE))) of its P patch tokens (timm\'s rule) and '
+                        'the class token, so a step costs roughly the kept fraction (VisionTransformer.set_patch_dropout; keep sets from a '
+                        'hash of --seed and a device step counter, so --graph works); the test pass sees every patch.  0 (default): off')
     args = p.parse_args(argv)
     if not 0.0 <= args.drop_path < 1.0:
         raise SystemExit(f"--drop-path {args.drop_path} must be in [0, 1)")
+    if not 0.0 <= args.patch_dropout < 1.0:
+        raise SystemExit(f"--patch-dropout {args.patch_dropout} must be in [0, 1)")
     check_data_args(args)
     check_optimizer_args(args)
     return args
