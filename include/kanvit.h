@@ -823,6 +823,47 @@ int kanvit_optim_adamw(int n, void* const* params, const void* const* grads, con
                        int64_t table_rows, const int64_t* step, const float* norm_coef, int has_wd, float b1, float ob1, float b2, float ob2,
                        float eps, float d, float od, void* stream);
 
+/* ---- KAN edge pruning: ranked edge masks, held at zero (csrc/edge_prune.hip) ----------------------------------
+ * kanvit_edge_select: scores A[groups][E] (float32, device; the [out, in] activation table of kanvit_edge_l1_fwd, flat index
+ * e = i O + o) -> mask[groups][E] (uint8, 1 = keep, any alignment) and kept[groups] (int64: the ones of the group's mask).
+ * The order of the entries of a group is exact and total: key(a) = bits(a) & 0x7fffffff compared as uint32, ties broken by
+ * ascending e.  A is finite and non-negative by construction; the key order defines the behaviour for every other input (a
+ * negative entry ranks as its magnitude, a NaN above every number) and the kernel does not special-case them.
+ *   KANVIT_PRUNE_COUNT  exactly the n_prune smallest entries of every group in that order get 0; 0 <= n_prune <= E - 1, so a
+ *                       group always keeps its strongest edge.  Where the cut falls inside a run of equal keys the lower flat
+ *                       indices are the pruned ones.  threshold is ignored.
+ *   KANVIT_PRUNE_ABS    mask = key(a) >= key(threshold); threshold finite and >= 0.  n_prune is ignored.
+ *   KANVIT_PRUNE_REL    mask = key(a) >= key(t_g), t_g = fmul(threshold, max_g): ONE fp32 rounding, denormals kept, max_g the
+ *                       float whose bits are the group's largest key; 0 <= threshold <= 1, so the maximum always stays.
+ * One work-group per group: a group's result does not depend on the other groups of the launch.  An exact radix select on the
+ * keys (integer LDS histograms) and one index-ordered pass that walks laps of KANVIT_EDGE_SELECT_LAP entries; no atomics on
+ * floats, no global atomics, no workspace, no host synchronisation: capturable, and the same bits on every run.  groups = 0
+ * launches nothing.  KANVIT_EINVAL (named in kanvit_last_error, checked before any launch) for an unknown mode, groups outside
+ * 0..2^31-1, E outside 1..2^31-1, n_prune outside 0..E-1 (COUNT), a NaN, negative or infinite threshold, or one above 1 in REL
+ * mode, a null pointer, A off 4-byte or kept off 8-byte alignment.
+ *
+ * kanvit_mask_rows: a multi-tensor launch in the style of kanvit_optim_adamw -- up to KANVIT_MASK_MAX_TENSORS tensors (the host
+ * query returns it) passed BY VALUE in the kernel arguments, so a captured graph keeps the tensors' own pointers; tensors / numel /
+ * run / masks are HOST arrays of n entries.  Tensor k is fp32 with numel[k] elements seen as rows of run[k] contiguous ones:
+ *   x[e] = masks[k][e / run[k]] ? x[e] : +0.0f
+ * a select, not a multiply: a kept element keeps its bits (the kernel neither reads nor writes it), a masked NaN, infinity or
+ * -0 becomes +0.  Tensors need 4-byte alignment only; a 16-byte-aligned one may take 16-byte stores, with identical results;
+ * masks are uint8 (0 = masked) at any alignment, and one mask may serve several tensors.  A work-group takes one chunk of
+ * KANVIT_MASK_CHUNK elements of one tensor; a tensor with numel = 0 may have null pointers and gets none; n = 0 launches nothing.
+ * No host synchronisation; capturable.  KANVIT_EINVAL (named in kanvit_last_error, checked before any launch) for n outside
+ * 0..KANVIT_MASK_MAX_TENSORS, a null array or pointer, a negative numel, run[k] < 1 or numel[k] % run[k] != 0, a tensor off
+ * 4-byte alignment.  Additive: the ABI version stays 7. */
+#define KANVIT_PRUNE_COUNT 0
+#define KANVIT_PRUNE_ABS 1
+#define KANVIT_PRUNE_REL 2
+#define KANVIT_EDGE_SELECT_LAP 4096
+#define KANVIT_MASK_MAX_TENSORS 80
+#define KANVIT_MASK_CHUNK 4096
+int kanvit_edge_select(const float* A, int64_t groups, int64_t E, int mode, float threshold, int64_t n_prune, uint8_t* mask, int64_t* kept,
+                       void* stream);
+int kanvit_mask_max_tensors(void);
+int kanvit_mask_rows(int n, void* const* tensors, const int64_t* numel, const int64_t* run, const uint8_t* const* masks, void* stream);
+
 /* ---- per-family named entry points (SURVEY.md section 8b naming) ----------------------------
  * kanvit_<family>_{fwd,bwd_input,bwd_weight} are kanvit_layer_* with d->family checked;
  * kanvit_<family>_qkv_* additionally require groups == 3 * x_group_mod (one launch for all

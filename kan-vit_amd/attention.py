@@ -155,6 +155,32 @@ class MSA(torch.nn.Module):
         return ops.l1_entropy_loss(self.edge_activation_l1(x, include_base), regularize_activation, regularize_entropy)
 
     @torch.no_grad()
+    def prune_edges(self, x, fraction=None, threshold=None, relative=True):
+        """prune_edges (kanvit/prune.py) for all 3*H per-head q, k and v layers on the rows of x [..., d]: ONE grouped
+        edge_activation_l1 launch scores the whole edge functions (the base term included where the layers have one) and ONE
+        ops.edge_select launch (groups = 3*H: every layer is ranked on its own) chooses; `fraction` / `threshold` apply per layer.
+        Every layer ends bit for bit as its own prune_edges on its head's slice would leave it.  Types 'efficientkan', 'cheby' and
+        'fast'; others, and mixed base activations, raise edge_activation_l1's NotImplementedError.  Returns the number of kept
+        edges of the 3*H layers (0-d device tensor)."""
+        from kanvit import prune
+        layers, _ = self._qkv_layers()
+        H, dh = self.n_heads, self.d_head
+        A = self.edge_activation_l1(x, include_base=True)             # [3, H, out, in], a transposed view of edge_l1's [3*H, in, out]
+        mode, value = prune.select_args(dh * dh, fraction, threshold, relative)
+        sel, _ = ops.edge_select(A.transpose(-1, -2).reshape(3 * H, dh * dh), mode, value)
+        triples = []
+        for g, m in enumerate(layers):
+            m._take_selection(sel[g].view(dh, dh))
+            triples += m.edge_masked()
+        prune.zero_masked(triples)
+        return torch.stack([m.edge_mask for m in layers]).sum()
+
+    def edge_masked(self):
+        """The (parameter, mask, run) triples of the 3*H per-head layers (kanvit/prune.py); [] for types that are not pruned."""
+        layers, l0 = self._qkv_layers()
+        return [t for m in layers for t in m.edge_masked()] if hasattr(l0, "edge_masked") else []
+
+    @torch.no_grad()
     def update_grid(self, x, margin=0.01):
         """KANLinear.update_grid for all 3*H per-head q, k and v layers on the rows of x [..., d], from ONE grouped refit launch
         (groups = 3*H, x_group_mod = H, packing as edge_activation_l1).  The q, k and v layers of a head read the same columns

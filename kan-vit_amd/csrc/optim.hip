@@ -313,3 +313,6 @@ int kanvit_optim_adamw(int n, void* const* params, const void* const* grads, con
 }
 
 }  // extern "C"
+
+// KAN edge pruning (kanvit_edge_select, kanvit_mask_rows) compiles as part of this unit: its multi-tensor launch follows the one above
+#include "edge_prune.hip"

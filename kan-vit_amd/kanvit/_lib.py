@@ -150,8 +150,15 @@ SYMBOLS = {
     "kanvit_optim_sumsq": (C.c_int, [C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "kanvit_optim_begin": (C.c_int, [_P, C.c_int64, C.c_double, _P, _P, _P]),
     "kanvit_optim_adamw": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int] + [C.c_float] * 7 + [_P]),
+    "kanvit_edge_select": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_int64, _P, _P, _P]),
+    "kanvit_mask_max_tensors": (C.c_int, []),
+    "kanvit_mask_rows": (C.c_int, [C.c_int, _P, _P, _P, _P, _P]),
 }
-OPTIM_CHUNK = 4096      # KANVIT_OPTIM_CHUNK: the elements one work-group of the optimizer kernels takes
+PRUNE_COUNT, PRUNE_ABS, PRUNE_REL = range(3)      # KANVIT_PRUNE_*: the modes of kanvit_edge_select
+PRUNE_MODES = {"count": PRUNE_COUNT, "abs": PRUNE_ABS, "rel": PRUNE_REL}
+EDGE_SELECT_LAP = 4096      # KANVIT_EDGE_SELECT_LAP: the entries one lap of kanvit_edge_select's index-ordered pass covers
+MASK_CHUNK = 4096      # KANVIT_MASK_CHUNK: the elements one work-group of kanvit_mask_rows takes
+OPTIM_CHUNK = 4096     # KANVIT_OPTIM_CHUNK: the elements one work-group of the optimizer kernels takes
 DEPTH_MAX_BRANCHES = 64      # KANVIT_DEPTH_MAX_BRANCHES: the residual branches one kanvit_depth_scales launch draws for
 PATCH_KEEP_MAX_P = 1024      # KANVIT_PATCH_KEEP_MAX_P: the patches per sample one kanvit_patch_keep launch ranks (its keys live in LDS)
 PATCH_KEEP_TAG = 0x5061746368447270      # KANVIT_PATCH_KEEP_TAG: xored into the seed, apart from kanvit_depth_scales' stream

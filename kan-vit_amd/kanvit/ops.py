@@ -1701,3 +1701,113 @@ def optim_adamw(params, grads, offsets, decay, exp_avg: torch.Tensor, exp_avg_sq
                 (C.c_int64 * n)(*[p.numel() for p in ps]), (C.c_int32 * n)(*[int(bool(f)) for f in decay[lo:lo + cap]]), _ptr(exp_avg),
                 _ptr(exp_avg_sq), _ptr(ema), S, _ptr(table), int(table.shape[0]), _ptr(step), _ptr(norm_coef), int(bool(has_wd)),
                 *[C.c_float(float(c)) for c in consts], tag="optim_adamw", cost=(0, moved * (36 if ema is not None else 28)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# KAN edge pruning: ranked edge masks, held at zero (csrc/edge_prune.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _prune_mode(who: str, mode) -> int:
+    if isinstance(mode, str):
+        if mode not in _lib.PRUNE_MODES:
+            raise KanvitError(f"{who}: mode {mode!r} is none of {', '.join(_lib.PRUNE_MODES)}")
+        return _lib.PRUNE_MODES[mode]
+    return int(mode)
+
+
+def edge_select(A: torch.Tensor, mode, value) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mask, kept) of the score table A (float32 [groups, ...]: every group's E entries in edge_l1's flat order, e = i * O + o):
+    mask is uint8 of A's shape, 1 = keep, and kept int64 [groups] counts its ones (kanvit_edge_select; the exact total order --
+    key = bits & 0x7fffffff, ties by ascending e -- is stated in include/kanvit.h and restated by edge_select_ref below).  mode
+    'count': `value` = n_prune, exactly the n_prune smallest entries of every group go (0 <= n_prune <= E - 1); 'abs': the entries
+    below the threshold `value` go; 'rel': those below fmul(value, the group's maximum), 0 <= value <= 1.  One launch, one
+    work-group per group, no host synchronisation; capturable; bitwise reproducible."""
+    who = "edge_select"
+    if A.dim() < 1:
+        raise KanvitError(f"{who}: A is a float32 [groups, ...] tensor, got a 0-d one")
+    _require_tensor(who, "A", A, torch.float32)
+    m = _prune_mode(who, mode)
+    groups = A.shape[0]
+    mask = torch.empty(A.shape, dtype=torch.uint8, device=A.device)
+    kept = torch.empty(groups, dtype=torch.int64, device=A.device)
+    if groups == 0:
+        return mask, kept
+    E = A.numel() // groups
+    count = m == _lib.PRUNE_COUNT
+    _launch(_lib.lib().kanvit_edge_select, "kanvit_edge_select", A.device, _ptr(A), groups, E, m, C.c_float(0.0 if count else float(value)),
+            int(value) if count else 0, _ptr(mask), _ptr(kept), tag="edge_select", cost=(0, groups * E * 5))
+    return mask, kept
+
+
+def _edge_keys(a):
+    import numpy as np
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32) & np.uint32(0x7FFFFFFF)
+
+
+def edge_select_ref(A, mode, value):
+    """edge_select restated in NumPy on the CPU (the tests compare the kernel with it bit for bit): A is an array-like
+    [groups, ...]; 'count' is a STABLE argsort of the uint32 keys, whose first n_prune indices go."""
+    import numpy as np
+    a = np.ascontiguousarray(A.detach().cpu().numpy() if torch.is_tensor(A) else A, dtype=np.float32)
+    groups = a.shape[0]
+    keys = _edge_keys(a).reshape(groups, -1)
+    E = keys.shape[1] if groups else 0
+    m = _prune_mode("edge_select_ref", mode)
+    mask = np.ones((groups, E), dtype=np.uint8)
+    if m == _lib.PRUNE_COUNT:
+        n = int(value)
+        if not 0 <= n <= E - 1:
+            raise KanvitError(f"edge_select_ref: n_prune={n} must be in 0..E-1={E - 1}")
+        for g in range(groups):
+            mask[g, np.argsort(keys[g], kind="stable")[:n]] = 0
+    else:
+        t = np.float32(value)
+        if not (t >= 0 and np.isfinite(t)) or (m == _lib.PRUNE_REL and t > 1):
+            raise KanvitError(f"edge_select_ref: threshold={value} out of range")
+        for g in range(groups):
+            if m == _lib.PRUNE_REL:
+                tg = np.float32(t * keys[g].max().reshape(1).view(np.float32)[0])       # ONE fp32 rounding
+            else:
+                tg = t
+            mask[g] = keys[g] >= _edge_keys(np.array([tg], dtype=np.float32))[0]
+    return mask.reshape(a.shape), mask.sum(axis=1, dtype=np.int64)
+
+
+def mask_max_tensors() -> int:
+    """Tensors one kanvit_mask_rows launch takes in its kernel arguments (KANVIT_MASK_MAX_TENSORS)."""
+    return int(_lib.lib().kanvit_mask_max_tensors())
+
+
+def mask_rows(tensors, masks, runs) -> None:
+    """In place, for every k: tensors[k] (float32, contiguous, numel = rows * runs[k]) keeps row r of runs[k] consecutive elements
+    where masks[k].flatten()[r] != 0 and becomes +0.0 elsewhere (kanvit_mask_rows: a select -- kept elements keep their bits, a
+    masked NaN, infinity or -0 becomes +0; mask_rows_ref restates it).  masks[k] is uint8 with rows entries; one mask may serve
+    several tensors.  ceil(len(tensors) / mask_max_tensors()) launches; no host synchronisation; capturable."""
+    who = "mask_rows"
+    tensors, masks, runs = list(tensors), list(masks), [int(r) for r in runs]
+    if not (len(tensors) == len(masks) == len(runs)):
+        raise KanvitError(f"{who}: {len(tensors)} tensors, {len(masks)} masks, {len(runs)} runs")
+    if not tensors:
+        return
+    dev = tensors[0].device
+    for k, (x, m, r) in enumerate(zip(tensors, masks, runs)):
+        _require_tensor(who, f"tensors[{k}]", x, torch.float32, None, dev)
+        _require_tensor(who, f"masks[{k}]", m, torch.uint8, None, dev)
+        if r < 1 or x.numel() != m.numel() * r:
+            raise KanvitError(f"{who}: tensors[{k}] has {x.numel()} elements, masks[{k}] {m.numel()} rows of run {r}")
+    L, cap = _lib.lib(), mask_max_tensors()
+    for lo in range(0, len(tensors), cap):
+        xs, ms, rs = tensors[lo:lo + cap], masks[lo:lo + cap], runs[lo:lo + cap]
+        n = len(xs)
+        moved = sum(m.numel() for m in ms) + 4 * sum(x.numel() for x in xs)
+        _launch(L.kanvit_mask_rows, "kanvit_mask_rows", dev, n, _optim_ptrs(xs), (C.c_int64 * n)(*[x.numel() for x in xs]),
+                (C.c_int64 * n)(*rs), _optim_ptrs(ms), tag="mask_rows", cost=(0, moved))
+
+
+def mask_rows_ref(x, mask, run: int):
+    """mask_rows restated in NumPy for ONE tensor: a new float32 array of x's shape (x array-like or a tensor), bit for bit."""
+    import numpy as np
+    a = np.array(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=np.float32, copy=True)
+    m = np.asarray(mask.detach().cpu().numpy() if torch.is_tensor(mask) else mask).reshape(-1)
+    rows = a.reshape(-1, int(run)) if a.size else a.reshape(0, int(run))
+    rows.view(np.uint32)[m == 0] = 0
+    return rows.reshape(a.shape)

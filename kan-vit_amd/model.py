@@ -415,6 +415,56 @@ class VisionTransformer(nn.Module):
         self._fused_embed = None
         return fell_back
 
+    def _prunable(self, who):
+        """The modules edge pruning covers, in the walk's order (the patch embedding, then every block's MSA), or NotImplementedError
+        naming the model types that have no edge statistic to prune by."""
+        kinds = self.layer_types()
+        if not kinds <= set(self.REGULARIZED_TYPES):
+            raise NotImplementedError(f"{who}: model type(s) {sorted(kinds - set(self.REGULARIZED_TYPES))} have no edge-activation "
+                                      f"statistic to prune by; supported: {', '.join(self.REGULARIZED_TYPES)}")
+        return [self.linear_mapper] + [blk.attn for blk in self.blocks]
+
+    @torch.no_grad()
+    def prune_edges(self, images, fraction=None, threshold=None, relative=True):
+        """prune_edges (kanvit/prune.py) for every KAN layer of the model on one image batch; `fraction` / `threshold` apply to
+        every layer on its own.  The walk is update_grid's: the patch embedding on the patch rows, then block by block the
+        per-head q|k|v layers on norm1 of the block's input (MSA.prune_edges: one scoring and one selection launch per block); a
+        block runs after its own pruning, so later blocks are scored on the activations the pruned earlier ones produce.  The
+        walk runs the plain blocks on the full sequence, whatever the mode: drop path (set_drop_path) drops no branch and
+        PatchDropout (set_patch_dropout) no patch, and neither counter moves.  Model types efficientkan, cheby and fast.
+        Returns [(kept, total)], 0-d device tensors, per pruned layer group: the patch embedding, then every block's 3*H layers."""
+        self._prunable("prune_edges")
+        kw = dict(fraction=fraction, threshold=threshold, relative=relative)
+
+        def pair(kept, total):
+            return kept, torch.full((), total, dtype=torch.int64, device=images.device)
+        out = [pair(self.linear_mapper.prune_edges(self.patchify(images, self.n_patches).reshape(-1, self.input_d), **kw),
+                    self.input_d * self.d_hidden)]
+        x = self._embed(images)
+        for blk in self.blocks:
+            out.append(pair(blk.attn.prune_edges(blk.norm1(x), **kw), 3 * blk.attn.n_heads * blk.attn.d_head ** 2))
+            if blk is not self.blocks[-1]:
+                x = blk(x)
+        return out
+
+    def edge_masked(self):
+        """The (parameter, mask, run) triples of every prunable layer (kanvit/prune.py); creates the all-ones masks on first use."""
+        return [t for m in self._prunable("edge_masked") for t in m.edge_masked()]
+
+    @torch.no_grad()
+    def restore_edge_masks(self):
+        """restore_edge_mask on every prunable layer: the masks of a pruned checkpoint, rebuilt from its exact zeros after
+        load_state_dict.  Returns the number of kept edges (0-d device tensor)."""
+        self._prunable("restore_edge_masks")
+        return torch.stack([m.restore_edge_mask() for m in self.modules() if hasattr(m, "restore_edge_mask")]).sum()
+
+    def edge_sparsity(self):
+        """(kept, total) edges over every prunable layer, 0-d device tensors; a layer never pruned counts as whole.  No host
+        synchronisation."""
+        masks = {id(m): m for _, m, _ in self.edge_masked()}.values()
+        kept = torch.stack([m.sum() for m in masks]).sum()
+        return kept, torch.full((), sum(m.numel() for m in masks), dtype=torch.int64, device=kept.device)
+
     def _walk_attention_maps(self, images, rows):
         """One block's map at a time, update_grid's walk: the map of block l is taken on the block's real input, then the block
         runs (the last one does not have to).  'flash-attn' models stack bare FlashAttention modules."""

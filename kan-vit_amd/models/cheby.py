@@ -4,9 +4,10 @@ import torch
 import torch.nn as nn
 
 from kanvit import grouped, ops
+from kanvit.prune import EdgePruning
 
 
-class ChebyKANLayer(nn.Module):
+class ChebyKANLayer(EdgePruning, nn.Module):
     """y[b, o] = sum_i sum_{d=0..degree} T_d(tanh x[b, i]) * cheby_coeffs[i, o, d].
 
     Same constructor, parameter / buffer names and shapes as the reference (models/cheby.py:11-34):
@@ -45,6 +46,18 @@ class ChebyKANLayer(nn.Module):
         w, _, _ = self.kan_pack()
         x2d = x if x.dim() == 2 else x.reshape(-1, self.inputdim)
         return ops.edge_l1(x2d, w.unsqueeze(0), self.kan_cfg())[0].t()
+
+    # ---- edge pruning (kanvit/prune.py: prune_edges, edge_masked, restore_edge_mask) ----
+    _edge_mask_out_in = False       # cheby_coeffs leads with [in, out]
+
+    def _edge_dims(self):
+        return self.inputdim, self.outdim
+
+    def _edge_tensors(self):
+        return [(self.cheby_coeffs, self.degree + 1)]
+
+    def _edge_scores(self, x):
+        return self.edge_activation_l1(x)
 
     def regularization_loss(self, x, regularize_activation=1.0, regularize_entropy=1.0):
         """The L1 and entropy terms of models/effkan.py:258-264 on edge_activation_l1(x)."""

@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 from kanvit import _lib, grouped, ops
+from kanvit.prune import EdgePruning
 
 
 _GRID_FACTS = {}      # (ids, versions, data_ptrs of the knot buffers) -> (uniform, all_equal, the knot buffers)
@@ -50,7 +51,7 @@ def _grid_facts(layers):
     return hit[:2]
 
 
-class KANLinear(torch.nn.Module):
+class KANLinear(EdgePruning, torch.nn.Module):
     def __init__(self, in_features, out_features, grid_size=5, spline_order=3, scale_noise=0.1, scale_base=1.0,
                  scale_spline=1.0, enable_standalone_scale_spline=True, base_activation=torch.nn.SiLU, grid_eps=0.02,
                  grid_range=[-1, 1]):
@@ -290,6 +291,17 @@ class KANLinear(torch.nn.Module):
             cfg = replace(cfg, has_base=0, base_act=0)
             w, bp = self.scaled_spline_weight.permute(1, 2, 0).reshape(-1, self.out_features), self.grid.reshape(-1)
         return ops.edge_l1(x2d, w.unsqueeze(0), cfg, bp.unsqueeze(0))[0].t()
+
+    # ---- edge pruning (kanvit/prune.py: prune_edges, edge_masked, restore_edge_mask) ----
+    def _edge_dims(self):
+        return self.in_features, self.out_features
+
+    def _edge_tensors(self):
+        # spline_scaler stays as it is: its gradient through a zero spline_weight is zero
+        return [(self.spline_weight, self.spline_weight.shape[2]), (self.base_weight, 1)]
+
+    def _edge_scores(self, x):
+        return self.edge_activation_l1(x, include_base=True)
 
     def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0, x=None, include_base=False):
         """Without x: the L1 / entropy surrogate on the spline weights (models/effkan.py:244-264); parameter-only math.

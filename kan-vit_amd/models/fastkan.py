@@ -7,6 +7,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from kanvit import grouped, ops
+from kanvit.prune import EdgePruning
 
 
 _RBF_FACTS = {}
@@ -62,7 +63,7 @@ class RadialBasisFunction(nn.Module):
         return y.reshape(*x.shape, n)
 
 
-class FastKANLayer(nn.Module):
+class FastKANLayer(EdgePruning, nn.Module):
     """y = spline_linear(rbf(layernorm(x))) + base_linear(base_activation(x)) (models/fastkan.py:66-76); base_activation is
     F.silu by default or one of ops.SUPPORTED_BASE_ACTIVATIONS, read on every forward.
 
@@ -149,6 +150,19 @@ class FastKANLayer(nn.Module):
             cfg = replace(cfg, has_base=0, base_act=0)
             w, bp, xin = self.spline_linear.weight.view(o, i, g).permute(1, 2, 0).reshape(-1, o), self.rbf.grid.detach(), u
         return ops.edge_l1(xin, w.unsqueeze(0), cfg, bp.unsqueeze(0))[0].t()
+
+    # ---- edge pruning (kanvit/prune.py: prune_edges, edge_masked, restore_edge_mask) ----
+    def _edge_dims(self):
+        return self.input_dim, self.output_dim
+
+    def _edge_tensors(self):
+        tensors = [(self.spline_linear.weight, self.num_grids)]         # [O, I*G]: edge (o, i) owns columns i*G .. i*G + G - 1
+        if self.use_base_update:
+            tensors.append((self.base_linear.weight, 1))
+        return tensors
+
+    def _edge_scores(self, x):
+        return self.edge_activation_l1(x, include_base=self.use_base_update)
 
     def regularization_loss(self, x, regularize_activation=1.0, regularize_entropy=1.0, include_base=False):
         """The L1 and entropy terms of models/effkan.py:258-264 on edge_activation_l1(x, include_base)."""

@@ -36,7 +36,10 @@ and resize where timm applies them after -- kanvit/data.py randaug_table, ops.ra
 EMA in the project's own fused step, kanvit/optim.py; the default --optimizer adam is the reference's step), --drop-path RATE /
 --drop-path-schedule (stochastic depth as a per-sample scale inside the fused residual add + LayerNorm passes, masks from a hash of
 --seed and a device step counter: VisionTransformer.set_drop_path; the test pass runs without it), --patch-dropout RATE (PatchDropout:
-every sample trains on a hashed subset of its patch tokens, VisionTransformer.set_patch_dropout; the test pass sees all of them).
+every sample trains on a hashed subset of its patch tokens, VisionTransformer.set_patch_dropout; the test pass sees all of them),
+--prune STEP:VALUE[,...] / --prune-mode (KAN edge pruning: at the start of step STEP the weakest edges of every KAN layer, ranked by
+their mean absolute activation on the step's batch, become exact zeros -- VisionTransformer.prune_edges -- with their optimizer
+moments and weight EMA, and one masking launch per step between backward and the optimizer step holds them there: prune_and_mask).
 
 `main(args, batches=None, init_state=None)` also serves the parity tests: `batches` (a list of (x, y) tensors) replaces
 the data stream, `init_state` (a reference-layout state dict) replaces the random initialisation, and the returned dict
@@ -329,10 +332,81 @@ def extend_grid_and_swap(model, optimizer, x, grid_size):
     return len(swap)
 
 
+PRUNE_MODES = ("fraction", "relative", "absolute")
+
+
+def parse_prune(text):
+    """'3:0.5,6:0.75' -> {3: 0.5, 6: 0.75}: at the start of step 3 prune with VALUE 0.5, at step 6 with 0.75 (--prune-mode says
+    what VALUE is)."""
+    plan = {}
+    for item in filter(None, (t.strip() for t in (text or "").split(","))):
+        try:
+            step, value = item.split(":")
+            step, value = int(step), float(value)
+        except ValueError:
+            raise SystemExit(f"--prune: '{item}' is not STEP:VALUE")
+        if step < 1 or not 0.0 <= value < float("inf") or step in plan:
+            raise SystemExit(f"--prune: '{item}': STEP is positive, VALUE is finite and not negative, and a step is named once")
+        plan[step] = value
+    return plan
+
+
+def check_prune_args(args):
+    """--prune against --prune-mode and --dp; parse() and main() both call it."""
+    plan = getattr(args, "prune", None) or {}
+    mode = getattr(args, "prune_mode", "fraction")
+    if mode not in PRUNE_MODES:
+        raise SystemExit(f"--prune-mode {mode} is none of {', '.join(PRUNE_MODES)}")
+    if not plan:
+        return
+    if mode != "absolute" and any(v > 1.0 for v in plan.values()):
+        raise SystemExit(f"--prune: with --prune-mode {mode} VALUE is a share, at most 1")
+    if getattr(args, "dp", False):
+        raise SystemExit("--prune is not combined with --dp: every rank would score its own shard and the replicas "
+                         "would diverge (a gathered scoring is not implemented)")
+
+
+def prune_and_mask(model, optimizer, x, value, mode="fraction"):
+    """model.prune_edges on the batch x (mode 'fraction': value is the share of every layer's edges that ends up pruned; 'relative' /
+    'absolute': a threshold on the edge scores), then the masked runs of the optimizer's state become +0 as the parameters' just
+    did (ops.mask_rows): KanvitAdamW's views moments(p) and ema(p), stock Adam's state[p]['exp_avg'] / ['exp_avg_sq'] where they
+    exist.  With weight, moments and EMA at +0 and the gradient masked before every step, both optimizers leave a pruned entry at
+    exactly 0.  Returns model.prune_edges' [(kept, total)]."""
+    from kanvit import prune
+    from kanvit.optim import KanvitAdamW
+    if mode == "fraction":
+        counts = model.prune_edges(x, fraction=value)
+    else:
+        counts = model.prune_edges(x, threshold=value, relative=mode == "relative")
+    if isinstance(optimizer, KanvitAdamW):
+        mine = {id(p) for p in optimizer._params}
+        has_ema = "ema" in optimizer.flat
+
+        def state_of(p):
+            if id(p) not in mine:
+                return ()
+            return optimizer.moments(p) + ((optimizer.ema(p),) if has_ema else ())
+    else:
+        def state_of(p):
+            st = optimizer.state.get(p, {})
+            return tuple(st.get(k) for k in ("exp_avg", "exp_avg_sq"))
+    prune.zero_masked(model.edge_masked(), of=state_of)
+    return counts
+
+
 def main(args, batches=None, init_state=None):
     rank, world, local = 0, 1, 0
     check_data_args(args)
     check_optimizer_args(args)
+    check_prune_args(args)
+    prune_plan = getattr(args, "prune", None) or {}
+    prune_mode = getattr(args, "prune_mode", "fraction")
+    if prune_plan:
+        from model import split_types
+        bad = sorted(set(split_types(args.model_type)) - set(VisionTransformer.REGULARIZED_TYPES))
+        if bad:
+            raise SystemExit(f"--prune: model type(s) {', '.join(bad)} have no edge-activation statistic to prune by; "
+                             f"supported: {', '.join(VisionTransformer.REGULARIZED_TYPES)}")
     grid_extend = getattr(args, "grid_extend", None) or {}
     if grid_extend:
         from model import split_types
@@ -463,6 +537,16 @@ def main(args, batches=None, init_state=None):
     if reg_lambda > 0 and not model.layer_types() <= set(VisionTransformer.REGULARIZED_TYPES):
         raise SystemExit(f"--reg-lambda: the edge-activation regulariser covers the model types {', '.join(VisionTransformer.REGULARIZED_TYPES)}")
 
+    if prune_plan:
+        # --prune: the masks exist from the first step, all ones, and are rewritten in place -- a captured step keeps its one launch
+        from kanvit import prune as kprune
+        model.edge_masked()
+
+    def mask_gradients():
+        """--prune: the gradients of pruned edges become +0 between backward and the step (one ops.mask_rows call), so the optimizer
+        keeps those entries at 0 and the clip norm is the norm of the gradients that are used."""
+        kprune.zero_masked(model.edge_masked(), of=lambda p: (p.grad,))
+
     def eager_step(x, y, y2=None, w=None):
         if reg_lambda > 0:
             return regularized_step(x, y, y2, w)
@@ -476,6 +560,8 @@ def main(args, batches=None, init_state=None):
         else:
             optimizer.zero_grad()
             loss.backward()
+        if prune_plan:
+            mask_gradients()
         optimizer.step()
         return loss.detach(), y_hat.detach()
 
@@ -494,6 +580,8 @@ def main(args, batches=None, init_state=None):
         else:
             optimizer.zero_grad()
             total.backward()
+        if prune_plan:
+            mask_gradients()
         optimizer.step()
         return loss.detach(), y_hat.detach()
 
@@ -541,6 +629,8 @@ def main(args, batches=None, init_state=None):
                 extend_grid_and_swap(model, optimizer, x, grid_extend[n_steps])
             elif grid_every > 0 and n_steps % grid_every == 0:
                 model.update_grid(x)            # before the step, on the step's own batch; Adam's moments stay as they are
+            if n_steps in prune_plan:           # before the step, on the step's own batch; parameters, moments and EMA of pruned edges -> 0
+                prune_and_mask(model, optimizer, x, prune_plan[n_steps], prune_mode)
             loss, y_hat = step(x, y, *pair)
             if pair:                            # the metrics count a mixed sample against its majority label
                 y = torch.where(pair[1] >= 0.5, y, pair[0])
@@ -555,13 +645,20 @@ def main(args, batches=None, init_state=None):
         if world > 1:                           # every rank's step loss is the mean over ITS shard; equal shards -> the mean
             torch.distributed.all_reduce(losses)        # of rank means is the global-batch mean the reference would log
             losses /= world
+        if prune_plan:                          # --prune: the kept and total edge counts ride on the epoch's host sync
+            edges = torch.stack(model.edge_sparsity())
         losses = losses.cpu()                   # the epoch's one host sync
         history["epoch_seconds"].append(time.perf_counter() - t_epoch)     # host clock around work that ends in that sync
         history["losses"] += [float(v) for v in losses]
         train_loss = float(losses.sum() / max(n_batches, 1))
         history["epoch_loss"].append(train_loss)
+        if prune_plan:                          # two integers the device finished before the losses left it
+            kept, total = (int(v) for v in edges.cpu())
+            history.setdefault("edges", []).append((kept, total))
         if rank == 0:
             logging.info(f"Epoch {epoch + 1}/{args.epochs}\n  Train Loss: {train_loss:.4f}")
+            if prune_plan:
+                logging.info(f"  Edges kept: {kept} of {total}")
             if ys or (device_metrics and epoch_metrics.n):
                 t_metrics = time.perf_counter()             # host clock around work that ends with the four numbers on the host
                 if device_metrics:
@@ -663,6 +760,15 @@ def parse(argv=None):
                         "every edge keeps its function (VisionTransformer.extend_grid; 'efficientkan' model types; not with --graph "
                         "or --dp).  The replaced spline_weight parameters start with fresh Adam state, every other parameter keeps "
                         "its own; a --grid-update-every update due on the same step is skipped.  Default: never")
+    p.add_argument('--prune', type=parse_prune, default={}, metavar='STEP:VALUE[,STEP:VALUE...]',
+                   help="KAN edge pruning -- at the start of step STEP (counted from 1 over the whole run), on that step's batch, prune "
+                        "the weakest edges of every KAN layer by their mean absolute activation (VisionTransformer.prune_edges; "
+                        "'efficientkan', 'cheby' and 'fast' model types; not with --dp) and zero their optimizer state; from the first "
+                        "step on, one masking launch between backward and the optimizer step keeps pruned edges at exactly 0, with "
+                        "--graph too.  VALUE is what --prune-mode says.  Default: never")
+    p.add_argument('--prune-mode', choices=list(PRUNE_MODES), default='fraction',
+                   help="--prune: VALUE is the share of every layer's edges that ends up pruned (fraction, cumulative over the named "
+                        "steps), or a threshold on the edge scores relative to the layer's largest (relative, 0..1), or absolute")
     p.add_argument('--no-tuned-gemms', action='store_true', help='library-default kernel selection for the stock GEMMs')
     p.add_argument('--data-npz', type=str, default=None, metavar='PATH',
                    help='train on this .npz (x_train uint8 [N,H,W,C] or [N,H,W], y_train; optional x_test, y_test, mean, std: '
@@ -758,6 +864,7 @@ def parse(argv=None):
         raise SystemExit(f"--patch-dropout {args.patch_dropout} must be in [0, 1)")
     check_data_args(args)
     check_optimizer_args(args)
+    check_prune_args(args)
     return args
 
 
