@@ -53,6 +53,12 @@ def _mix(z: int) -> int:
     return z ^ (z >> 31)
 
 
+def rank_seed(seed: int, rank: int = 0, world: int = 1) -> int:
+    """The seed of a rank's own hashes (drop-path masks, patch-dropout keep sets): `seed` itself on one rank; with more, the rank
+    is mixed in, or every rank would draw the same positions of its shard."""
+    return seed if world == 1 else _mix(_mix(seed) + rank)
+
+
 def make_lut(mean, std) -> torch.Tensor:
     """[C, 256] float32 on the CPU: the normalised value of every byte per channel, with the reference's own operations (ToTensor's
     byte / 255, then Normalize's (v - mean) / std, all in fp32: train.py:100-118).  Built on the CPU on purpose: a device divide by a

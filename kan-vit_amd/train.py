@@ -9,52 +9,33 @@ train.py:31-40), running on the MI355X kernels, with optional pure data parallel
     python train.py --model-type cheby --data-npz cifar100.npz         # real images from a GPU-resident uint8 dataset, no torchvision
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py --dp --synthetic ...
 
-Additions over the reference (none change a default): --synthetic / --image-size / --in-chans /
---n-patches / --out-d (geometry), --seed, --dp, --steps-per-epoch, --amp, --graph, --no-tuned-gemms, --reg-lambda /
---reg-activation / --reg-entropy (the sample-based KAN regulariser added to the step's loss), --grid-update-every
-(KANLinear.update_grid on the step's batch every N-th step), --grid-extend STEP:SIZE[,...] (grid extension: at the start of
-step STEP every KANLinear moves to SIZE grid intervals with its function kept),
---data-npz / --no-augment / --crop-padding (the dataset lives on the GPU as uint8 and one kernel per batch gathers, crops, flips and
-normalises it: kanvit/data.py; the reference's transforms, train.py:100-118, without torchvision, workers or a copy per batch),
---no-step-metrics (the per-step metrics stay on the device either way: one host sync per epoch instead of the
-reference's three per step, train.py:37,42-44), --device-metrics (the epoch's four metrics from integer tables counted on the GPU,
-kanvit/metrics.py: one kernel per step, one pair-counting pass per epoch, C*C + 2*C integers to the host -- instead of three lists,
-an [N, C] copy and scikit-learn on one CPU thread), --mixup / --cutmix / --mix-prob / --mix-switch-prob (Mixup and CutMix inside the
-batch kernel, from a per-epoch table that is a function of (seed, epoch) alone: kanvit/data.py mix_table, ops.mix_u8),
---label-smoothing and --fused-loss (the training loss and its gradient from one fused soft-target cross-entropy launch:
-ops.soft_cross_entropy), --resize S / --random-resized-crop / --rrc-scale / --rrc-ratio (the batch kernel resamples: every batch
-comes out at S x S, bilinear, from the stored images -- `--data-npz cifar100.npz --resize 224 --n-patches 14` trains the ViT-B/16
-geometry on 32 x 32 images -- and RandomResizedCrop boxes come from a per-epoch table, a function of (seed, epoch) alone:
-kanvit/data.py crop_table, ops.resample_u8; --image-size stays the size of the stored images), --random-erasing P / --erase-mode /
---erase-scale / --erase-ratio (Random Erasing inside the batch kernel, before Mixup / CutMix and on the partner too: with probability
-P a per-sample box from a per-epoch table is replaced by standard-normal noise or zeros -- kanvit/data.py erase_table, ops.erase_u8;
-the train split only), --randaug [M] / --randaug-ops / --randaug-mstd / --randaug-prob (RandAugment, timm's rand-m9-mstd0.5-inc1, as
-ONE uint8 -> uint8 pass over the whole train split per epoch into a second GPU-resident copy that the batch kernels then read: two ops
-per sample from a per-epoch table that is a function of (seed, epoch) alone, integer arithmetic, at the stored size BEFORE crop, flip
-and resize where timm applies them after -- kanvit/data.py randaug_table, ops.randaugment_u8), --optimizer kanvit-adamw with --weight-decay /
---clip-grad-norm / --warmup-steps / --lr-schedule / --min-lr / --ema-decay (AdamW with global-norm clipping, a schedule table and a weight
-EMA in the project's own fused step, kanvit/optim.py; the default --optimizer adam is the reference's step), --drop-path RATE /
---drop-path-schedule (stochastic depth as a per-sample scale inside the fused residual add + LayerNorm passes, masks from a hash of
---seed and a device step counter: VisionTransformer.set_drop_path; the test pass runs without it), --patch-dropout RATE (PatchDropout:
-every sample trains on a hashed subset of its patch tokens, VisionTransformer.set_patch_dropout; the test pass sees all of them),
---prune STEP:VALUE[,...] / --prune-mode (KAN edge pruning: at the start of step STEP the weakest edges of every KAN layer, ranked by
-their mean absolute activation on the step's batch, become exact zeros -- VisionTransformer.prune_edges -- with their optimizer
-moments and weight EMA, and one masking launch per step between backward and the optimizer step holds them there: prune_and_mask).
+Additions over the reference (none changes a default; each flag's help text has the details, DESIGN.md the design):
+    stream, geometry      --synthetic --steps-per-epoch --image-size --in-chans --n-patches --out-d --seed
+    step and metrics      --dp --amp --graph --no-tuned-gemms --base-activation --no-step-metrics --device-metrics
+    KAN layers            --reg-lambda --reg-activation --reg-entropy --grid-update-every --grid-extend STEP:SIZE[,...] --prune STEP:VALUE[,...] --prune-mode
+    GPU-resident dataset  --data-npz --no-augment --crop-padding --resize S --random-resized-crop --rrc-scale --rrc-ratio --mixup --cutmix --mix-prob
+                          --mix-switch-prob --random-erasing P --erase-mode --erase-scale --erase-ratio --randaug [M] --randaug-ops --randaug-mstd --randaug-prob
+    loss, optimizer       --label-smoothing --fused-loss --optimizer kanvit-adamw --weight-decay --clip-grad-norm --warmup-steps --lr-schedule --min-lr --ema-decay
+    regularisation        --drop-path RATE --drop-path-schedule --patch-dropout RATE
 
 `main(args, batches=None, init_state=None)` also serves the parity tests: `batches` (a list of (x, y) tensors) replaces
 the data stream, `init_state` (a reference-layout state dict) replaces the random initialisation, and the returned dict
 carries the per-step loss trajectory."""
 import argparse
 import contextlib
+import functools
 import logging
 import os
 import time
+import types
 
 import torch
 from torch.optim import Adam
 
-from kanvit import dp as kdp
-from model import VisionTransformer
+from kanvit import data as kdata, dp as kdp, ops as kops, prune as kprune, tuned
+from kanvit.metrics import EpochMetrics
+from kanvit.optim import KanvitAdamW
+from model import VisionTransformer, split_types
 from utils import calculate_metrics, save_metrics, setup_logging
 
 
@@ -81,114 +62,144 @@ def cifar_loaders(batch, rank, world):
             mk(test, batch_size=batch, shuffle=False, num_workers=8, pin_memory=True), sampler)
 
 
+@functools.lru_cache(maxsize=None)
+def defaults():
+    """Every flag's default by attribute name, read from build_parser(): the one place where a default is written down."""
+    return vars(build_parser().parse_args([]))
+
+
+def complete(args):
+    """Give `args` every attribute it lacks, at the parser's default: in place, so that a namespace built by hand (the tests build
+    them) reads like one from parse().  It validates nothing.  main() and every helper that takes `args` call it first."""
+    for name, default in defaults().items():
+        vars(args).setdefault(name, default)
+    return args
+
+
+def check_args(args):
+    """Everything parse() refuses.  main() calls it too, for namespaces that did not come through parse()."""
+    complete(args)
+    for flag, name in (("--drop-path", "drop_path"), ("--patch-dropout", "patch_dropout")):
+        if not 0.0 <= float(getattr(args, name)) < 1.0:
+            raise SystemExit(f"{flag} {float(getattr(args, name))} must be in [0, 1)")
+    check_data_args(args)
+    check_optimizer_args(args)
+    check_prune_args(args)
+
+
+def lo_hi(flag, pair):
+    """(LO, HI) of a range flag as floats; refused unless 0 < LO <= HI < inf."""
+    lo, hi = (float(v) for v in pair)
+    if not 0 < lo <= hi or hi == float("inf"):
+        raise SystemExit(f"{flag} {lo} {hi}: LO and HI are positive and LO is not above HI")
+    return lo, hi
+
+
 def check_data_args(args):
-    """Contradictions among the data-source flags; parse() and main() both call it."""
-    if getattr(args, "data_npz", None) and args.synthetic:
+    """Contradictions among the data-source flags."""
+    complete(args)
+    if args.data_npz and args.synthetic:
         raise SystemExit("--synthetic and --data-npz name two data sources; give one")
-    if getattr(args, "crop_padding", 4) < 0:
+    if args.crop_padding < 0:
         raise SystemExit(f"--crop-padding {args.crop_padding} is negative")
-    mixup, cutmix = float(getattr(args, "mixup", 0.0)), float(getattr(args, "cutmix", 0.0))
+    mixup, cutmix = float(args.mixup), float(args.cutmix)
     if mixup < 0 or cutmix < 0:
         raise SystemExit(f"--mixup {mixup} / --cutmix {cutmix}: a Beta parameter is not negative")
     for flag, name in (("--mix-prob", "mix_prob"), ("--mix-switch-prob", "mix_switch_prob")):
-        if not 0.0 <= float(getattr(args, name, 1.0)) <= 1.0:
+        if not 0.0 <= float(getattr(args, name)) <= 1.0:
             raise SystemExit(f"{flag} {getattr(args, name)} is not a probability")
-    if not 0.0 <= float(getattr(args, "label_smoothing", 0.0)) < 1.0:
+    if not 0.0 <= float(args.label_smoothing) < 1.0:
         raise SystemExit(f"--label-smoothing {args.label_smoothing} must be in [0, 1)")
     if mixup > 0 or cutmix > 0:
-        if not getattr(args, "data_npz", None):
+        if not args.data_npz:
             raise SystemExit("--mixup / --cutmix mix inside the kernel that reads the GPU-resident dataset; give --data-npz")
-        if getattr(args, "no_augment", False):
+        if args.no_augment:
             raise SystemExit("--mixup / --cutmix are augmentations; they are not combined with --no-augment")
-    resize, rrc = int(getattr(args, "resize", 0)), bool(getattr(args, "random_resized_crop", False))
+    resize, rrc = int(args.resize), bool(args.random_resized_crop)
     if resize < 0:
         raise SystemExit(f"--resize {resize} is negative (0: off)")
-    if (resize > 0 or rrc) and not getattr(args, "data_npz", None):
+    if (resize > 0 or rrc) and not args.data_npz:
         raise SystemExit("--resize / --random-resized-crop resample inside the kernel that reads the GPU-resident dataset; give --data-npz")
-    if rrc and getattr(args, "no_augment", False):
+    if rrc and args.no_augment:
         raise SystemExit("--random-resized-crop is an augmentation; it is not combined with --no-augment")
-    for flag, name, default in (("--rrc-scale", "rrc_scale", (0.08, 1.0)), ("--rrc-ratio", "rrc_ratio", (3.0 / 4.0, 4.0 / 3.0))):
-        lo, hi = (float(v) for v in getattr(args, name, default))
-        if not 0 < lo <= hi or hi == float("inf"):
-            raise SystemExit(f"{flag} {lo} {hi}: LO and HI are positive and LO is not above HI")
-    p_erase = float(getattr(args, "random_erasing", 0.0))
+    lo_hi("--rrc-scale", args.rrc_scale)
+    lo_hi("--rrc-ratio", args.rrc_ratio)
+    p_erase = float(args.random_erasing)
     if not 0.0 <= p_erase <= 1.0:
         raise SystemExit(f"--random-erasing {p_erase} is not a probability")
-    for flag, name, default in (("--erase-scale", "erase_scale", (0.02, 1.0 / 3.0)), ("--erase-ratio", "erase_ratio", (0.3, 1.0 / 0.3))):
-        lo, hi = (float(v) for v in getattr(args, name, default))
-        if not 0 < lo <= hi or hi == float("inf"):
-            raise SystemExit(f"{flag} {lo} {hi}: LO and HI are positive and LO is not above HI")
-        if name == "erase_scale" and hi > 1:
-            raise SystemExit(f"--erase-scale {lo} {hi}: HI is a fraction of the image, at most 1")
+    lo, hi = lo_hi("--erase-scale", args.erase_scale)
+    if hi > 1:
+        raise SystemExit(f"--erase-scale {lo} {hi}: HI is a fraction of the image, at most 1")
+    lo_hi("--erase-ratio", args.erase_ratio)
     if p_erase > 0:
-        if not getattr(args, "data_npz", None):
+        if not args.data_npz:
             raise SystemExit("--random-erasing erases inside the kernel that reads the GPU-resident dataset; give --data-npz")
-        if getattr(args, "no_augment", False):
+        if args.no_augment:
             raise SystemExit("--random-erasing is an augmentation; it is not combined with --no-augment")
-    randaug = getattr(args, "randaug", None)
-    if randaug is not None and not 0.0 <= float(randaug) <= 10.0:
-        raise SystemExit(f"--randaug {randaug}: the magnitude is in 0..10")
-    if not 1 <= int(getattr(args, "randaug_ops", 2)) <= 4:
+    if args.randaug is not None and not 0.0 <= float(args.randaug) <= 10.0:
+        raise SystemExit(f"--randaug {args.randaug}: the magnitude is in 0..10")
+    if not 1 <= int(args.randaug_ops) <= 4:
         raise SystemExit(f"--randaug-ops {args.randaug_ops} must be in 1..4")
-    if not 0.0 <= float(getattr(args, "randaug_mstd", 0.5)) < float("inf"):
+    if not 0.0 <= float(args.randaug_mstd) < float("inf"):
         raise SystemExit(f"--randaug-mstd {args.randaug_mstd} is negative or not finite")
-    if not 0.0 <= float(getattr(args, "randaug_prob", 0.5)) <= 1.0:
+    if not 0.0 <= float(args.randaug_prob) <= 1.0:
         raise SystemExit(f"--randaug-prob {args.randaug_prob} is not a probability")
-    if randaug is not None:
-        if not getattr(args, "data_npz", None):
+    if args.randaug is not None:
+        if not args.data_npz:
             raise SystemExit("--randaug augments a second copy of the GPU-resident dataset once per epoch; give --data-npz")
-        if getattr(args, "no_augment", False):
+        if args.no_augment:
             raise SystemExit("--randaug is an augmentation; it is not combined with --no-augment")
 
 
-RECIPE_FLAGS = (("--weight-decay", "weight_decay", 0.0), ("--clip-grad-norm", "clip_grad_norm", 0.0), ("--warmup-steps", "warmup_steps", 0),
-                ("--lr-schedule", "lr_schedule", "constant"), ("--min-lr", "min_lr", 0.0), ("--ema-decay", "ema_decay", 0.0))
+RECIPE_FLAGS = (("--weight-decay", "weight_decay"), ("--clip-grad-norm", "clip_grad_norm"), ("--warmup-steps", "warmup_steps"),
+                ("--lr-schedule", "lr_schedule"), ("--min-lr", "min_lr"), ("--ema-decay", "ema_decay"))
 
 
 def check_optimizer_args(args):
-    """Contradictions among the optimizer flags; parse() and main() both call it.  The recipe flags belong to --optimizer kanvit-adamw:
-    given without it they are refused, not ignored."""
-    fused = getattr(args, "optimizer", "adam") == "kanvit-adamw"
-    given = [flag for flag, name, default in RECIPE_FLAGS if getattr(args, name, default) != default]
+    """Contradictions among the optimizer flags.  The recipe flags belong to --optimizer kanvit-adamw: given without it (away from
+    their defaults) they are refused, not ignored."""
+    complete(args)
+    fused = args.optimizer == "kanvit-adamw"
+    given = [flag for flag, name in RECIPE_FLAGS if getattr(args, name) != defaults()[name]]
     if given and not fused:
         raise SystemExit(f"{' / '.join(given)}: the recipe flags are implemented by --optimizer kanvit-adamw; the default Adam has none of them")
     if not fused:
         return
-    if getattr(args, "grid_extend", None):
+    if args.grid_extend:
         raise SystemExit("--grid-extend is not combined with --optimizer kanvit-adamw: its flat moment buffers cannot take the "
                          "parameters of a new shape that an extension creates")
-    for flag, name, default in RECIPE_FLAGS:
-        if name != "lr_schedule" and float(getattr(args, name, default)) < 0:
+    for flag, name in RECIPE_FLAGS:
+        if name != "lr_schedule" and float(getattr(args, name)) < 0:
             raise SystemExit(f"{flag} {getattr(args, name)} is negative")
-    if not float(getattr(args, "ema_decay", 0.0)) < 1.0:
+    if not float(args.ema_decay) < 1.0:
         raise SystemExit(f"--ema-decay {args.ema_decay} must be in [0, 1)")
 
 
 def mix_config(args):
     """The `mix` argument of GpuDataset.batches from the flags, or None when neither --mixup nor --cutmix is given."""
-    mixup, cutmix = float(getattr(args, "mixup", 0.0)), float(getattr(args, "cutmix", 0.0))
+    complete(args)
+    mixup, cutmix = float(args.mixup), float(args.cutmix)
     if mixup <= 0 and cutmix <= 0:
         return None
-    return dict(mixup_alpha=mixup, cutmix_alpha=cutmix, prob=float(getattr(args, "mix_prob", 1.0)),
-                switch_prob=float(getattr(args, "mix_switch_prob", 0.5)))
+    return dict(mixup_alpha=mixup, cutmix_alpha=cutmix, prob=float(args.mix_prob), switch_prob=float(args.mix_switch_prob))
 
 
 def erase_config(args):
     """The `erase` argument of GpuDataset from the flags, or None when --random-erasing is 0."""
-    p_erase = float(getattr(args, "random_erasing", 0.0))
+    complete(args)
+    p_erase = float(args.random_erasing)
     if p_erase <= 0:
         return None
-    return dict(prob=p_erase, scale=tuple(getattr(args, "erase_scale", (0.02, 1.0 / 3.0))), ratio=tuple(getattr(args, "erase_ratio", (0.3, 1.0 / 0.3))),
-                mode=getattr(args, "erase_mode", "pixel"))
+    return dict(prob=p_erase, scale=tuple(args.erase_scale), ratio=tuple(args.erase_ratio), mode=args.erase_mode)
 
 
 def randaug_config(args, mean=None):
     """The `randaug` argument of GpuDataset from the flags, or None without --randaug.  mean: the dataset's per-channel mean on the 0-1
     scale; the geometric ops fill with round(255 mean) per channel."""
-    if getattr(args, "randaug", None) is None:
+    complete(args)
+    if args.randaug is None:
         return None
-    cfg = dict(n_ops=int(getattr(args, "randaug_ops", 2)), magnitude=float(args.randaug), mstd=float(getattr(args, "randaug_mstd", 0.5)),
-               prob=float(getattr(args, "randaug_prob", 0.5)))
+    cfg = dict(n_ops=int(args.randaug_ops), magnitude=float(args.randaug), mstd=float(args.randaug_mstd), prob=float(args.randaug_prob))
     if mean is not None:
         cfg["fill"] = tuple(min(max(int(round(255.0 * float(m))), 0), 255) for m in mean)
     return cfg
@@ -201,14 +212,14 @@ def npz_datasets(args, device, want_test=True):
     --random-resized-crop gives the train split crop="rrc": their batches then come from ops.resample_u8.  --random-erasing gives the
     train split -- never the test split -- erase=...: its batches come from ops.erase_u8.  --randaug gives the train split -- never the
     test split -- randaug=...: a second buffer that ops.randaugment_u8 fills once per epoch and the batch kernels read."""
-    from kanvit import data as kdata
+    complete(args)
     blob = kdata.load_npz(args.data_npz)
     x = blob["x_train"]
     c, h, w = (x.shape[3] if x.ndim == 4 else 1), x.shape[1], x.shape[2]
     if h != w:
         raise SystemExit(f"--data-npz {args.data_npz}: images are {h}x{w}; the model takes square images (--image-size)")
-    for flag, name, default, have in (("--image-size", "image_size", 32, h), ("--in-chans", "in_chans", 3, c)):
-        if getattr(args, name) == default:
+    for flag, name, have in (("--image-size", "image_size", h), ("--in-chans", "in_chans", c)):
+        if getattr(args, name) == defaults()[name]:
             setattr(args, name, int(have))
         elif getattr(args, name) != have:
             raise SystemExit(f"{flag} {getattr(args, name)} contradicts --data-npz {args.data_npz}, whose images have {have}")
@@ -218,15 +229,14 @@ def npz_datasets(args, device, want_test=True):
     augment = not args.no_augment
     if augment and args.crop_padding > h:
         raise SystemExit(f"--crop-padding {args.crop_padding} exceeds the image size {h}")
-    resize, rrc = int(getattr(args, "resize", 0)), bool(getattr(args, "random_resized_crop", False))
+    resize = int(args.resize)
     out_size = (resize, resize) if resize > 0 else None          # --resize: both splits come out at the model's size
     mean = None
-    if getattr(args, "randaug", None) is not None:               # the fill of its geometric ops: the dataset mean, as the datasets use it
+    if args.randaug is not None:                                 # the fill of its geometric ops: the dataset mean, as the datasets use it
         mean = blob["mean"] if "mean" in blob else kdata.channel_stats(x)[0]
     train = kdata.GpuDataset.from_arrays(blob, args.data_npz, "train", device, pad=args.crop_padding if augment else 0, flip=augment,
-                                         out_size=out_size, crop="rrc" if rrc else "pad",
-                                         rrc_scale=tuple(getattr(args, "rrc_scale", (0.08, 1.0))),
-                                         rrc_ratio=tuple(getattr(args, "rrc_ratio", (3.0 / 4.0, 4.0 / 3.0))), erase=erase_config(args),
+                                         out_size=out_size, crop="rrc" if args.random_resized_crop else "pad",
+                                         rrc_scale=tuple(args.rrc_scale), rrc_ratio=tuple(args.rrc_ratio), erase=erase_config(args),
                                          randaug=randaug_config(args, mean))
     test = kdata.GpuDataset.from_arrays(blob, args.data_npz, "test", device, out_size=out_size) if want_test and "x_test" in blob else None
     return train, test
@@ -286,7 +296,6 @@ def set_base_activation(model, model_type, name):
     """--base-activation: the base activation of every KANLinear ('efficientkan') or FastKANLayer ('fast') of the model, set
     after construction as the reference's layers allow (they read `base_activation` on every forward).  The constructors of
     VisionTransformer / MSA take no such argument, so their signatures stay the reference's."""
-    import functools
     import torch.nn.functional as F
     from models.effkan import KANLinear
     from models.fastkan import FastKANLayer
@@ -352,16 +361,15 @@ def parse_prune(text):
 
 
 def check_prune_args(args):
-    """--prune against --prune-mode and --dp; parse() and main() both call it."""
-    plan = getattr(args, "prune", None) or {}
-    mode = getattr(args, "prune_mode", "fraction")
-    if mode not in PRUNE_MODES:
-        raise SystemExit(f"--prune-mode {mode} is none of {', '.join(PRUNE_MODES)}")
-    if not plan:
+    """--prune against --prune-mode and --dp."""
+    complete(args)
+    if args.prune_mode not in PRUNE_MODES:
+        raise SystemExit(f"--prune-mode {args.prune_mode} is none of {', '.join(PRUNE_MODES)}")
+    if not args.prune:
         return
-    if mode != "absolute" and any(v > 1.0 for v in plan.values()):
-        raise SystemExit(f"--prune: with --prune-mode {mode} VALUE is a share, at most 1")
-    if getattr(args, "dp", False):
+    if args.prune_mode != "absolute" and any(v > 1.0 for v in args.prune.values()):
+        raise SystemExit(f"--prune: with --prune-mode {args.prune_mode} VALUE is a share, at most 1")
+    if args.dp:
         raise SystemExit("--prune is not combined with --dp: every rank would score its own shard and the replicas "
                          "would diverge (a gathered scoring is not implemented)")
 
@@ -372,8 +380,6 @@ def prune_and_mask(model, optimizer, x, value, mode="fraction"):
     did (ops.mask_rows): KanvitAdamW's views moments(p) and ema(p), stock Adam's state[p]['exp_avg'] / ['exp_avg_sq'] where they
     exist.  With weight, moments and EMA at +0 and the gradient masked before every step, both optimizers leave a pruned entry at
     exactly 0.  Returns model.prune_edges' [(kept, total)]."""
-    from kanvit import prune
-    from kanvit.optim import KanvitAdamW
     if mode == "fraction":
         counts = model.prune_edges(x, fraction=value)
     else:
@@ -390,47 +396,50 @@ def prune_and_mask(model, optimizer, x, value, mode="fraction"):
         def state_of(p):
             st = optimizer.state.get(p, {})
             return tuple(st.get(k) for k in ("exp_avg", "exp_avg_sq"))
-    prune.zero_masked(model.edge_masked(), of=state_of)
+    kprune.zero_masked(model.edge_masked(), of=state_of)
     return counts
 
 
-def main(args, batches=None, init_state=None):
+def check_run_args(args):
+    """What only a run refuses, not parse(): main() calls it after check_args, before anything touches the GPU or the process group."""
+    regularized = VisionTransformer.REGULARIZED_TYPES
+    kinds = split_types(args.model_type)
+    bad = sorted(set(kinds) - set(regularized))
+    if args.prune and bad:
+        raise SystemExit(f"--prune: model type(s) {', '.join(bad)} have no edge-activation statistic to prune by; "
+                         f"supported: {', '.join(regularized)}")
+    for flag, on, verb, noun, baked in (
+            ("--grid-extend", bool(args.grid_extend), "extend", "extension",
+             "the parameters, the grid sizes and the kernel forms the grids' flags selected, and an extension replaces all three"),
+            ("--grid-update-every", int(args.grid_update_every) > 0, "update", "update",
+             "the kernel forms the grids' flags selected, and a grid update changes them")):
+        if not on:
+            continue
+        if args.graph:
+            raise SystemExit(f"{flag} is not combined with --graph: the captured step bakes in {baked}")
+        if args.dp:
+            raise SystemExit(f"{flag} is not combined with --dp: every rank would fit its own shard and the replicas "
+                             f"would diverge (a gathered {noun} is not implemented)")
+        if "efficientkan" not in kinds:
+            raise SystemExit(f"{flag}: model type '{args.model_type}' has no KANLinear, the only layer with a B-spline "
+                             f"grid to {verb} ('efficientkan')")
+    if args.dp:
+        world = int(os.environ["WORLD_SIZE"])
+        if args.batch_size % world:
+            raise SystemExit(f"--batch-size {args.batch_size} is not divisible by the {world} ranks (equal shards keep the "
+                             "all-reduced mean equal to the global-batch mean)")
+        if args.graph:
+            raise SystemExit("--graph captures a single-GPU step; it is not combined with --dp")
+    elif torch.device(args.device).type != "cuda":
+        raise SystemExit("this build runs the hot path on the MI355X only; --device must be a cuda device")
+    # the model's layer types (VisionTransformer.layer_types): block l has kinds[l % len(kinds)], the patch embedding kinds[0]
+    if float(args.reg_lambda) > 0 and not set(kinds[:max(args.n_blocks, 1)]) <= set(regularized):
+        raise SystemExit(f"--reg-lambda: the edge-activation regulariser covers the model types {', '.join(regularized)}")
+
+
+def setup_distributed(args):
+    """(rank, world, device); with --dp the process group comes up here.  The kernels launch on the current device: it becomes `device`."""
     rank, world, local = 0, 1, 0
-    check_data_args(args)
-    check_optimizer_args(args)
-    check_prune_args(args)
-    prune_plan = getattr(args, "prune", None) or {}
-    prune_mode = getattr(args, "prune_mode", "fraction")
-    if prune_plan:
-        from model import split_types
-        bad = sorted(set(split_types(args.model_type)) - set(VisionTransformer.REGULARIZED_TYPES))
-        if bad:
-            raise SystemExit(f"--prune: model type(s) {', '.join(bad)} have no edge-activation statistic to prune by; "
-                             f"supported: {', '.join(VisionTransformer.REGULARIZED_TYPES)}")
-    grid_extend = getattr(args, "grid_extend", None) or {}
-    if grid_extend:
-        from model import split_types
-        if args.graph:
-            raise SystemExit("--grid-extend is not combined with --graph: the captured step bakes in the parameters, the grid sizes and "
-                             "the kernel forms the grids' flags selected, and an extension replaces all three")
-        if args.dp:
-            raise SystemExit("--grid-extend is not combined with --dp: every rank would fit its own shard and the replicas "
-                             "would diverge (a gathered extension is not implemented)")
-        if "efficientkan" not in split_types(args.model_type):
-            raise SystemExit(f"--grid-extend: model type '{args.model_type}' has no KANLinear, the only layer with a B-spline "
-                             "grid to extend ('efficientkan')")
-    grid_every = int(getattr(args, "grid_update_every", 0))
-    if grid_every > 0:
-        from model import split_types
-        if args.graph:
-            raise SystemExit("--grid-update-every is not combined with --graph: the captured step bakes in the kernel forms the "
-                             "grids' flags selected, and a grid update changes them")
-        if args.dp:
-            raise SystemExit("--grid-update-every is not combined with --dp: every rank would fit its own shard and the replicas "
-                             "would diverge (a gathered update is not implemented)")
-        if "efficientkan" not in split_types(args.model_type):
-            raise SystemExit(f"--grid-update-every: model type '{args.model_type}' has no KANLinear, the only layer with a B-spline "
-                             "grid to update ('efficientkan')")
     if args.dp:
         import torch.distributed as dist
         rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
@@ -444,275 +453,267 @@ def main(args, batches=None, init_state=None):
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
         else:
             dist.init_process_group(backend)
-        if args.batch_size % world:
-            raise SystemExit(f"--batch-size {args.batch_size} is not divisible by the {world} ranks (equal shards keep the "
-                             "all-reduced mean equal to the global-batch mean)")
-        if args.graph:
-            raise SystemExit("--graph captures a single-GPU step; it is not combined with --dp")
     device = torch.device(args.device if not args.dp else f"cuda:{local}")
-    if device.type != "cuda":
-        raise SystemExit("this build runs the hot path on the MI355X only; --device must be a cuda device")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    torch.cuda.set_device(device)           # the kernels launch on the model's device also with --device cuda:N
-    torch.manual_seed(args.seed)
-    train_set = test_set = None
-    if batches is None and getattr(args, "data_npz", None):
-        train_set, test_set = npz_datasets(args, device, want_test=rank == 0)     # before the model: the geometry may come from the file
-    size = int(getattr(args, "resize", 0)) or args.image_size       # --resize S: --image-size stays the file's, the model sees S x S
-    chw = (args.in_chans, size, size)
+    torch.cuda.set_device(device)
+    return rank, world, device
+
+
+def build_model(args, chw, rank, world, device, init_state=None):
+    """The VisionTransformer of the flags on `device`, the same on every rank.  --drop-path's masks and --patch-dropout's keep sets are
+    hashes of (seed, a device step counter, position in the rank's batch, ...), so under --dp each rank has a seed of its own."""
     model = VisionTransformer(chw, n_patches=args.n_patches, n_blocks=args.n_blocks, d_hidden=args.d_hidden,
                               n_heads=args.n_heads, out_d=args.out_d, type=args.model_type)
-    set_base_activation(model, args.model_type, getattr(args, "base_activation", "silu"))
-    drop_path = float(getattr(args, "drop_path", 0.0))
-    if not 0.0 <= drop_path < 1.0:
-        raise SystemExit(f"--drop-path {drop_path} must be in [0, 1)")
-    if drop_path > 0:
-        # --drop-path: the masks are a hash of (seed, step counter, branch, position in the rank's batch); under --dp the rank is mixed
-        # into the seed, or every rank would drop the same positions of its shard
-        from kanvit.data import _mix
+    set_base_activation(model, args.model_type, args.base_activation)
+    for flag, rate, switch_on, more in (("--drop-path", args.drop_path, model.set_drop_path, dict(schedule=args.drop_path_schedule)),
+                                        ("--patch-dropout", args.patch_dropout, model.set_patch_dropout, {})):
         try:
-            model.set_drop_path(drop_path, seed=args.seed if world == 1 else _mix(_mix(args.seed) + rank),
-                                schedule=getattr(args, "drop_path_schedule", "linear"))
+            if float(rate) > 0:
+                switch_on(float(rate), seed=kdata.rank_seed(args.seed, rank, world), **more)
         except NotImplementedError as e:
-            raise SystemExit(f"--drop-path: {e}")
-    patch_dropout = float(getattr(args, "patch_dropout", 0.0))
-    if not 0.0 <= patch_dropout < 1.0:
-        raise SystemExit(f"--patch-dropout {patch_dropout} must be in [0, 1)")
-    if patch_dropout > 0:
-        # --patch-dropout: the keep sets are a hash of (seed, step counter, position in the rank's batch, patch); the rank is mixed in as above
-        from kanvit.data import _mix
-        try:
-            model.set_patch_dropout(patch_dropout, seed=args.seed if world == 1 else _mix(_mix(args.seed) + rank))
-        except NotImplementedError as e:
-            raise SystemExit(f"--patch-dropout: {e}")
+            raise SystemExit(f"{flag}: {e}")
     if init_state is not None:
         model.load_state_dict(init_state)
     model = model.to(device)
     kdp.broadcast_parameters(model)
-    criterion = torch.nn.CrossEntropyLoss()
-    mix = mix_config(args) if train_set is not None else None
-    label_smoothing = float(getattr(args, "label_smoothing", 0.0))
-    soft_loss = mix is not None or label_smoothing > 0 or bool(getattr(args, "fused_loss", False))
-    if soft_loss:
-        from kanvit import ops as kops
+    return model
 
-    def step_loss(logits, y, y2, w):
-        """The training loss: the reference's criterion, or with any of --mixup / --cutmix / --label-smoothing / --fused-loss the
-        fused soft-target cross-entropy (ops.soft_cross_entropy: loss and gradient in one launch).  The test loop keeps the criterion."""
-        if not soft_loss:
-            return criterion(logits, y)
-        return kops.soft_cross_entropy(logits, y, y2, w, label_smoothing)
-    if not args.no_tuned_gemms:
-        from kanvit import tuned
-        tuned.enable_tuned_gemms()          # recorded kernel selections for the stock FF GEMMs (no run-time tuning)
-    recipe = getattr(args, "optimizer", "adam") == "kanvit-adamw"
-    ema_decay = float(getattr(args, "ema_decay", 0.0)) if recipe else 0.0
-    if not recipe:
+
+def steps_per_epoch(args, batches, train_set, per_rank, world):
+    """Steps every rank takes per epoch: the loop's count and, times --epochs, the length of kanvit-adamw's schedule."""
+    if batches is not None:
+        return len(batches)
+    if train_set is not None:
+        return train_set.n_batches(per_rank, world)
+    if args.synthetic:
+        return args.steps_per_epoch
+    return -(-50000 // args.batch_size)         # CIFAR-100's train split as cifar_loaders serves it: len() of its train loader on every rank
+
+
+def build_optimizer(args, model, per_epoch):
+    if args.optimizer != "kanvit-adamw":
         # fused=True: same update rule as the reference's Adam, one multi-tensor kernel per parameter chunk instead of ~8 per step
-        optimizer = Adam(model.parameters(), lr=args.learning_rate, fused=True, capturable=bool(args.graph))
-    else:
-        # --optimizer kanvit-adamw: clipping, decay, schedule and weight EMA in the project's own step (kanvit/optim.py); the schedule
-        # spans the run, epochs x batches per epoch, and a step past it keeps the last row
-        from kanvit.optim import KanvitAdamW
-        if batches is not None:
-            per_epoch = len(batches)
-        elif train_set is not None:
-            per_epoch = train_set.n_batches(args.batch_size // world if args.dp else args.batch_size, world)
-        elif args.synthetic:
-            per_epoch = args.steps_per_epoch
-        else:
-            per_epoch = -(-50000 // args.batch_size)            # CIFAR-100's train split, as cifar_loaders serves it
-        total = max(args.epochs * per_epoch, 1)
-        optimizer = KanvitAdamW(model.parameters(), lr=args.learning_rate, weight_decay=float(getattr(args, "weight_decay", 0.0)),
-                                max_grad_norm=float(getattr(args, "clip_grad_norm", 0.0)) or None, ema_decay=ema_decay, total_steps=total,
-                                warmup_steps=min(int(getattr(args, "warmup_steps", 0)), total),
-                                schedule=getattr(args, "lr_schedule", "constant"), min_lr=float(getattr(args, "min_lr", 0.0)))
-    reducer = kdp.GradReducer(model.parameters()) if world > 1 else None
-    metrics_file = setup_logging(args.log_dir) if rank == 0 else None
-    logging.info(f"Using device: {device} ({torch.cuda.get_device_name(device)}), world {world}, amp {args.amp}, "
-                 f"graph {bool(args.graph)}")
+        return Adam(model.parameters(), lr=args.learning_rate, fused=True, capturable=bool(args.graph))
+    # --optimizer kanvit-adamw: clipping, decay, schedule and weight EMA in the project's own step (kanvit/optim.py); the schedule
+    # spans the run, epochs x batches per epoch, and a step past it keeps the last row
+    total = max(args.epochs * per_epoch, 1)
+    return KanvitAdamW(model.parameters(), lr=args.learning_rate, weight_decay=float(args.weight_decay),
+                       max_grad_norm=float(args.clip_grad_norm) or None, ema_decay=float(args.ema_decay), total_steps=total,
+                       warmup_steps=min(int(args.warmup_steps), total), schedule=args.lr_schedule, min_lr=float(args.min_lr))
+
+
+def build_step(args, model, optimizer, reducer, mixed):
+    """The step that _GraphedStep captures: eager_step(x, y, y2=None, w=None) -> (CE loss, logits), both detached.  The loss is the
+    reference's criterion, or with any of --mixup / --cutmix (`mixed`) / --label-smoothing / --fused-loss the fused soft-target
+    cross-entropy (ops.soft_cross_entropy: loss and gradient in one launch).  --reg-lambda adds the KAN paper's sample-based
+    regulariser of the same forward (exact fp32 also under --amp bf16) to what is differentiated; the returned (logged) loss stays
+    the CE term, so trajectories with and without it compare.  --prune makes the gradients of pruned edges +0 between backward and
+    the step (one ops.mask_rows call), so the optimizer keeps those entries at 0 and the clip norm is that of the gradients in use."""
     amp = args.amp == "bf16"
-    reg_lambda = float(getattr(args, "reg_lambda", 0.0))
-    if reg_lambda > 0 and not model.layer_types() <= set(VisionTransformer.REGULARIZED_TYPES):
-        raise SystemExit(f"--reg-lambda: the edge-activation regulariser covers the model types {', '.join(VisionTransformer.REGULARIZED_TYPES)}")
-
-    if prune_plan:
-        # --prune: the masks exist from the first step, all ones, and are rewritten in place -- a captured step keeps its one launch
-        from kanvit import prune as kprune
-        model.edge_masked()
-
-    def mask_gradients():
-        """--prune: the gradients of pruned edges become +0 between backward and the step (one ops.mask_rows call), so the optimizer
-        keeps those entries at 0 and the clip norm is the norm of the gradients that are used."""
-        kprune.zero_masked(model.edge_masked(), of=lambda p: (p.grad,))
+    label_smoothing = float(args.label_smoothing)
+    soft_loss = mixed or label_smoothing > 0 or bool(args.fused_loss)
+    reg_lambda = float(args.reg_lambda)
+    reg_kw = dict(return_regularization=True, regularize_activation=float(args.reg_activation), regularize_entropy=float(args.reg_entropy))
+    masking = bool(args.prune)
+    criterion = torch.nn.CrossEntropyLoss()
 
     def eager_step(x, y, y2=None, w=None):
-        if reg_lambda > 0:
-            return regularized_step(x, y, y2, w)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
-            y_hat = model(x)
-            loss = step_loss(y_hat.float(), y, y2, w)
+            if reg_lambda > 0:
+                y_hat, reg = model(x, **reg_kw)
+            else:
+                y_hat = model(x)
+            loss = kops.soft_cross_entropy(y_hat.float(), y, y2, w, label_smoothing) if soft_loss else criterion(y_hat.float(), y)
+        total = loss + reg_lambda * reg.float() if reg_lambda > 0 else loss
         if reducer is not None:
             reducer.zero_grad()
-            reducer.scale_loss(loss).backward()     # mean over ranks inside the collective (RCCL AVG) or the loss: kanvit/dp.py
-            reducer.finish()
-        else:
-            optimizer.zero_grad()
-            loss.backward()
-        if prune_plan:
-            mask_gradients()
-        optimizer.step()
-        return loss.detach(), y_hat.detach()
-
-    def regularized_step(x, y, y2=None, w=None):
-        """The step with the KAN paper's sample-based regulariser: loss = CE + lambda * reg, reg from the same forward (exact fp32
-        also under --amp bf16).  The returned (logged) loss stays the CE term, so trajectories with and without it compare."""
-        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
-            y_hat, reg = model(x, return_regularization=True, regularize_activation=float(getattr(args, "reg_activation", 1.0)),
-                               regularize_entropy=float(getattr(args, "reg_entropy", 1.0)))
-            loss = step_loss(y_hat.float(), y, y2, w)
-        total = loss + reg_lambda * reg.float()
-        if reducer is not None:
-            reducer.zero_grad()
-            reducer.scale_loss(total).backward()
+            reducer.scale_loss(total).backward()    # mean over ranks inside the collective (RCCL AVG) or the loss: kanvit/dp.py
             reducer.finish()
         else:
             optimizer.zero_grad()
             total.backward()
-        if prune_plan:
-            mask_gradients()
+        if masking:
+            kprune.zero_masked(model.edge_masked(), of=lambda p: (p.grad,))
         optimizer.step()
         return loss.detach(), y_hat.detach()
+    return eager_step
 
-    step = eager_step
+
+class Metrics:
+    """(accuracy, balanced accuracy, F1, ROC AUC) of the (logits, labels) that update() saw since reset(): from host lists through
+    utils.calculate_metrics, or, given `rows` (the most it will see), from the integer tables kanvit.metrics.EpochMetrics counts on the
+    device (--device-metrics).  True once it saw anything."""
+
+    def __init__(self, num_classes, device=None, rows=None):
+        self.num_classes, self.seen = num_classes, []
+        self.table = EpochMetrics(num_classes, max(rows, 1), device) if rows is not None else None
+
+    def reset(self):
+        self.seen = []
+        if self.table is not None:
+            self.table.reset()
+
+    def update(self, logits, y):
+        if self.table is not None:
+            return self.table.update(logits, y)
+        self.seen.append((y, logits.argmax(dim=1), torch.softmax(logits.float(), dim=1)))
+
+    def __bool__(self):
+        return bool(self.seen or (self.table is not None and self.table.n))
+
+    def compute(self):
+        if self.table is not None:
+            return self.table.compute()
+        ys, preds, probs = (torch.cat(column).cpu().numpy() for column in zip(*self.seen))
+        return calculate_metrics(ys, preds, probs, num_classes=self.num_classes)
+
+
+def run_epoch(run, epoch, loader, n_batches):
+    """One epoch over `loader` with ONE host sync, the step losses' way to the host; rank 0's train metrics follow it.  run.step becomes a
+    _GraphedStep at the first batch under --graph; run.n_steps counts the run's steps from 1, as --grid-extend and --prune name them."""
+    args, model, optimizer, history, device = run.args, run.model, run.optimizer, run.history, run.device
+    grid_extend, grid_every, prune_plan = args.grid_extend or {}, int(args.grid_update_every), args.prune or {}
+    metrics = run.train_metrics
+    step_losses = []
+    if metrics is not None:
+        metrics.reset()
+    t_epoch = time.perf_counter()
+    for x, y, *pair in loader:
+        x, y = x.to(device, non_blocking=True), y.to(device, non_blocking=True)
+        if args.graph and not isinstance(run.step, _GraphedStep):
+            run.step = _GraphedStep(run.step, model, optimizer, x, y, *pair)
+        run.n_steps = n_steps = run.n_steps + 1
+        if n_steps in grid_extend:              # the extension refits on this batch too: an update due on the same step is skipped
+            extend_grid_and_swap(model, optimizer, x, grid_extend[n_steps])
+        elif grid_every > 0 and n_steps % grid_every == 0:
+            model.update_grid(x)                # before the step, on the step's own batch; Adam's moments stay as they are
+        if n_steps in prune_plan:               # before the step, on the step's own batch; parameters, moments and EMA of pruned edges -> 0
+            prune_and_mask(model, optimizer, x, prune_plan[n_steps], args.prune_mode)
+        loss, y_hat = run.step(x, y, *pair)
+        if pair:                                # the metrics count a mixed sample against its majority label
+            y = torch.where(pair[1] >= 0.5, y, pair[0])
+        step_losses.append(loss.clone() if args.graph else loss)
+        if metrics is not None:
+            metrics.update(y_hat, y)            # eagerly after the step, also under --graph (y_hat is then the graph's output buffer)
+    losses = torch.stack(step_losses) if step_losses else torch.zeros(0, device=device)
+    if run.world > 1:                           # every rank's step loss is the mean over ITS shard; equal shards -> the mean
+        torch.distributed.all_reduce(losses)            # of rank means is the global-batch mean the reference would log
+        losses /= run.world
+    if prune_plan:                              # --prune: the kept and total edge counts ride on the epoch's host sync
+        edges = torch.stack(model.edge_sparsity())
+    losses = losses.cpu()                       # the epoch's one host sync
+    history["epoch_seconds"].append(time.perf_counter() - t_epoch)     # host clock around work that ends in that sync
+    history["losses"] += [float(v) for v in losses]
+    train_loss = float(losses.sum() / max(n_batches, 1))
+    history["epoch_loss"].append(train_loss)
+    if prune_plan:                              # two integers the device finished before the losses left it
+        kept, total = (int(v) for v in edges.cpu())
+        history.setdefault("edges", []).append((kept, total))
+    if run.rank != 0:
+        return
+    logging.info(f"Epoch {epoch + 1}/{args.epochs}\n  Train Loss: {train_loss:.4f}")
+    if prune_plan:
+        logging.info(f"  Edges kept: {kept} of {total}")
+    if metrics:
+        t_metrics = time.perf_counter()         # host clock around work that ends with the four numbers on the host
+        acc, bal, f1, auc = metrics.compute()
+        history["train_metrics"].append((acc, bal, f1, auc))
+        history["metrics_seconds"].append(time.perf_counter() - t_metrics)
+        logging.info(f"  Train Accuracy: {acc:.4f}\n  Train Balanced Accuracy: {bal:.4f}\n"
+                     f"  Train F1 Score: {f1:.4f}\n  Train ROC AUC: {auc:.4f}")
+        if epoch == args.epochs - 1:
+            save_metrics(run.metrics_file, epoch + 1, "Train", train_loss, acc, bal, f1, auc, flag=0)
+            history["metrics_file"] = run.metrics_file
+
+
+def evaluate(run, test_loader, per_rank):
+    """The test pass (rank 0): the plain criterion, no drop-path, every patch, and with --ema-decay the averaged weights."""
+    args, model, device, history = run.args, run.model, run.device, run.history
+    ema = float(args.ema_decay) > 0             # --ema-decay (kanvit-adamw's alone): the test pass runs on the averaged weights
+    criterion = torch.nn.CrossEntropyLoss()
+    model.eval()
+    if args.optimizer == "kanvit-adamw":
+        history["ema_eval"] = ema
+    with torch.no_grad(), (run.optimizer.ema_weights(model) if ema else contextlib.nullcontext()):
+        tl = []
+        metrics = Metrics(args.out_d, device, len(test_loader) * per_rank if args.device_metrics else None)
+        for x, y in test_loader:
+            x, y = x.to(device), y.to(device)
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=args.amp == "bf16"):
+                y_hat = model(x)
+            tl.append(criterion(y_hat.float(), y))
+            metrics.update(y_hat, y)
+        test_loss = float(torch.stack(tl).sum() / len(test_loader))
+        acc, bal, f1, auc = metrics.compute()
+        history["test_metrics"] = (acc, bal, f1, auc)
+        logging.info(f"Test Results:\n  Test Loss: {test_loss:.4f}\n  Test Accuracy: {acc:.4f}")
+        save_metrics(run.metrics_file, args.epochs, "Test", test_loss, acc, bal, f1, auc, flag=1)
+
+
+def main(args, batches=None, init_state=None):
+    check_args(args)
+    check_run_args(args)
+    rank, world, device = setup_distributed(args)
     per_rank = args.batch_size // world if args.dp else args.batch_size
+    torch.manual_seed(args.seed)
+    train_set = test_set = None
+    if batches is None and args.data_npz:
+        train_set, test_set = npz_datasets(args, device, want_test=rank == 0)     # before the model: the geometry may come from the file
+    size = int(args.resize) or args.image_size          # --resize S: --image-size stays the file's, the model sees S x S
+    chw = (args.in_chans, size, size)
+    model = build_model(args, chw, rank, world, device, init_state)
+    mix = mix_config(args) if train_set is not None else None
+    if not args.no_tuned_gemms:
+        tuned.enable_tuned_gemms()          # recorded kernel selections for the stock FF GEMMs (no run-time tuning)
+    n_batches = steps_per_epoch(args, batches, train_set, per_rank, world)
+    optimizer = build_optimizer(args, model, n_batches)
+    reducer = kdp.GradReducer(model.parameters()) if world > 1 else None
+    metrics_file = setup_logging(args.log_dir) if rank == 0 else None
+    logging.info(f"Using device: {device} ({torch.cuda.get_device_name(device)}), world {world}, amp {args.amp}, graph {bool(args.graph)}")
+    if args.prune:
+        model.edge_masked()     # --prune: the masks exist from the first step, all ones, and are rewritten in place -- a captured step keeps its one launch
+    history = {"losses": [], "epoch_loss": [], "epoch_seconds": [], "train_metrics": [], "metrics_seconds": []}
+    run = types.SimpleNamespace(args=args, rank=rank, world=world, device=device, model=model, optimizer=optimizer, history=history,
+                                metrics_file=metrics_file, step=build_step(args, model, optimizer, reducer, mix is not None),
+                                n_steps=0, train_metrics=None)          # what run_epoch and evaluate share
     train_loader = test_loader = sampler = None
     if train_set is not None:
         if test_set is not None:                # the evaluation transform: normalise only, in the file's order
             test_loader = test_set.loader(per_rank, shuffle=False)
     elif batches is None and not args.synthetic:
         train_loader, test_loader, sampler = cifar_loaders(per_rank, rank, world)
-    history = {"losses": [], "epoch_loss": [], "epoch_seconds": [], "train_metrics": [], "metrics_seconds": []}
-    device_metrics = bool(getattr(args, "device_metrics", False)) and not args.no_step_metrics and rank == 0
-    epoch_metrics = None            # --device-metrics: rank 0's shard, as the lists below are; sized at the first epoch, reset per epoch
-    n_steps = 0
     model.train()
     for epoch in range(args.epochs):
         if batches is not None:
-            loader, n_batches = batches, len(batches)
+            loader = batches
         elif train_set is not None:             # order and augmentation are functions of (seed, epoch): the same on every rank
-            loader = train_set.batches(per_rank, epoch, args.seed, rank, world) if mix is None else \
-                train_set.batches(per_rank, epoch, args.seed, rank, world, mix=mix)     # yields (x, y, y2, w): one table per epoch
-            n_batches = train_set.n_batches(per_rank, world)
+            loader = train_set.batches(per_rank, epoch, args.seed, rank, world, mix=mix)    # with mix: (x, y, y2, w), one table per epoch
         elif args.synthetic:
             loader = synthetic_loader(args.steps_per_epoch, per_rank, chw, args.out_d, device, args.seed + 1000 * epoch + rank)
-            n_batches = args.steps_per_epoch
         else:
             if sampler is not None:
                 sampler.set_epoch(epoch)            # a different shuffle per epoch, the same on every rank
-            loader, n_batches = train_loader, len(train_loader)
-        step_losses, ys, preds, probs = [], [], [], []
-        if device_metrics:
-            if epoch_metrics is None:
-                from kanvit.metrics import EpochMetrics
-                rows = sum(int(b[1].shape[0]) for b in batches) if batches is not None else n_batches * per_rank
-                epoch_metrics = history["epoch_metrics"] = EpochMetrics(args.out_d, max(rows, 1), device)
-            epoch_metrics.reset()
-        t_epoch = time.perf_counter()
-        for x, y, *pair in loader:
-            x, y = x.to(device, non_blocking=True), y.to(device, non_blocking=True)
-            if args.graph and step is eager_step:
-                step = _GraphedStep(eager_step, model, optimizer, x, y, *pair)
-            n_steps += 1
-            if n_steps in grid_extend:             # the extension refits on this batch too: an update due on the same step is skipped
-                extend_grid_and_swap(model, optimizer, x, grid_extend[n_steps])
-            elif grid_every > 0 and n_steps % grid_every == 0:
-                model.update_grid(x)            # before the step, on the step's own batch; Adam's moments stay as they are
-            if n_steps in prune_plan:           # before the step, on the step's own batch; parameters, moments and EMA of pruned edges -> 0
-                prune_and_mask(model, optimizer, x, prune_plan[n_steps], prune_mode)
-            loss, y_hat = step(x, y, *pair)
-            if pair:                            # the metrics count a mixed sample against its majority label
-                y = torch.where(pair[1] >= 0.5, y, pair[0])
-            step_losses.append(loss.clone() if args.graph else loss)
-            if device_metrics:
-                epoch_metrics.update(y_hat, y)      # eagerly after the step, also under --graph (y_hat is then the graph's output buffer)
-            elif not args.no_step_metrics:
-                ys.append(y)
-                preds.append(y_hat.argmax(dim=1))
-                probs.append(torch.softmax(y_hat.float(), dim=1))
-        losses = torch.stack(step_losses) if step_losses else torch.zeros(0, device=device)
-        if world > 1:                           # every rank's step loss is the mean over ITS shard; equal shards -> the mean
-            torch.distributed.all_reduce(losses)        # of rank means is the global-batch mean the reference would log
-            losses /= world
-        if prune_plan:                          # --prune: the kept and total edge counts ride on the epoch's host sync
-            edges = torch.stack(model.edge_sparsity())
-        losses = losses.cpu()                   # the epoch's one host sync
-        history["epoch_seconds"].append(time.perf_counter() - t_epoch)     # host clock around work that ends in that sync
-        history["losses"] += [float(v) for v in losses]
-        train_loss = float(losses.sum() / max(n_batches, 1))
-        history["epoch_loss"].append(train_loss)
-        if prune_plan:                          # two integers the device finished before the losses left it
-            kept, total = (int(v) for v in edges.cpu())
-            history.setdefault("edges", []).append((kept, total))
-        if rank == 0:
-            logging.info(f"Epoch {epoch + 1}/{args.epochs}\n  Train Loss: {train_loss:.4f}")
-            if prune_plan:
-                logging.info(f"  Edges kept: {kept} of {total}")
-            if ys or (device_metrics and epoch_metrics.n):
-                t_metrics = time.perf_counter()             # host clock around work that ends with the four numbers on the host
-                if device_metrics:
-                    acc, bal, f1, auc = epoch_metrics.compute()
-                else:
-                    acc, bal, f1, auc = calculate_metrics(torch.cat(ys).cpu().numpy(), torch.cat(preds).cpu().numpy(),
-                                                          torch.cat(probs).cpu().numpy(), num_classes=args.out_d)
-                history["train_metrics"].append((acc, bal, f1, auc))
-                history["metrics_seconds"].append(time.perf_counter() - t_metrics)
-                logging.info(f"  Train Accuracy: {acc:.4f}\n  Train Balanced Accuracy: {bal:.4f}\n"
-                             f"  Train F1 Score: {f1:.4f}\n  Train ROC AUC: {auc:.4f}")
-                if epoch == args.epochs - 1:
-                    save_metrics(metrics_file, epoch + 1, "Train", train_loss, acc, bal, f1, auc, flag=0)
-                    history["metrics_file"] = metrics_file
+            loader = train_loader
+        if epoch == 0 and rank == 0 and not args.no_step_metrics:      # rank 0's shard; --device-metrics: sized here, once, reset per epoch
+            rows =sum(int(b[1].shape[0]) for b in batches) if batches is not None else n_batches * per_rank
+            run.train_metrics = Metrics(args.out_d, device, rows if args.device_metrics else None)
+            if args.device_metrics:
+                history["epoch_metrics"] = run.train_metrics.table
+        run_epoch(run, epoch, loader, n_batches)
 
-    if recipe:
+    if args.optimizer == "kanvit-adamw":
         history["grad_norm"] = float(optimizer.grad_norm)       # the last step's global norm (NaN without --clip-grad-norm: not taken)
     if test_loader is not None and rank == 0:
-        model.eval()
-        if recipe:
-            history["ema_eval"] = ema_decay > 0                 # --ema-decay: the test pass runs on the averaged weights
-        with torch.no_grad(), (optimizer.ema_weights(model) if ema_decay > 0 else contextlib.nullcontext()):
-            tl, ys, preds, probs = [], [], [], []
-            test_metrics = None
-            if bool(getattr(args, "device_metrics", False)):
-                from kanvit.metrics import EpochMetrics
-                test_metrics = EpochMetrics(args.out_d, max(len(test_loader) * per_rank, 1), device)
-            for x, y in test_loader:
-                x, y = x.to(device), y.to(device)
-                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
-                    y_hat = model(x)
-                tl.append(criterion(y_hat.float(), y))
-                if test_metrics is not None:
-                    test_metrics.update(y_hat, y)
-                else:
-                    ys.append(y), preds.append(y_hat.argmax(dim=1)), probs.append(torch.softmax(y_hat.float(), dim=1))
-            test_loss = float(torch.stack(tl).sum() / len(test_loader))
-            if test_metrics is not None:
-                acc, bal, f1, auc = test_metrics.compute()
-            else:
-                acc, bal, f1, auc = calculate_metrics(torch.cat(ys).cpu().numpy(), torch.cat(preds).cpu().numpy(),
-                                                      torch.cat(probs).cpu().numpy(), num_classes=args.out_d)
-            history["test_metrics"] = (acc, bal, f1, auc)
-            logging.info(f"Test Results:\n  Test Loss: {test_loss:.4f}\n  Test Accuracy: {acc:.4f}")
-            save_metrics(metrics_file, args.epochs, "Test", test_loss, acc, bal, f1, auc, flag=1)
+        evaluate(run, test_loader, per_rank)
     if args.dp:
         torch.distributed.barrier()             # the other ranks wait for rank 0's evaluation before the group goes away
         torch.distributed.destroy_process_group()
-    history["model"] = model
-    history["optimizer"] = optimizer
+    history.update(model=model, optimizer=optimizer)
     return history
 
 
-def parse(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(description='Benchmark Vision Transformer on CIFAR-100')
     # the reference's flags, verbatim (train.py:87-97)
     p.add_argument('--epochs', type=int, default=20, help='number of epochs to train')
@@ -857,14 +858,12 @@ def parse(argv=None):
                    help='PatchDropout: in training every sample keeps max(1, int(P * (1 - RATE))) of its P patch tokens (timm\'s rule) and '
                         'the class token, so a step costs roughly the kept fraction (VisionTransformer.set_patch_dropout; keep sets from a '
                         'hash of --seed and a device step counter, so --graph works); the test pass sees every patch.  0 (default): off')
-    args = p.parse_args(argv)
-    if not 0.0 <= args.drop_path < 1.0:
-        raise SystemExit(f"--drop-path {args.drop_path} must be in [0, 1)")
-    if not 0.0 <= args.patch_dropout < 1.0:
-        raise SystemExit(f"--patch-dropout {args.patch_dropout} must be in [0, 1)")
-    check_data_args(args)
-    check_optimizer_args(args)
-    check_prune_args(args)
+    return p
+
+
+def parse(argv=None):
+    args = build_parser().parse_args(argv)
+    check_args(args)
     return args
 
 

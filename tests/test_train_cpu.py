@@ -31,6 +31,34 @@ def test_train_refuses_to_run_the_hot_path_on_the_cpu():
         train.main(train.parse(["--device", "cpu", "--synthetic", "--epochs", "1"]))
 
 
+def test_complete_fills_a_hand_built_namespace_from_the_parser():
+    """train.complete: a namespace built by hand reads like one from parse(); given values stay; a second call changes nothing; and
+    every flag has a default to fill in."""
+    import argparse
+    import train
+    by_hand = train.complete(argparse.Namespace(synthetic=True))
+    assert vars(by_hand) == vars(train.parse(["--synthetic"]))
+    before = dict(vars(by_hand))
+    assert train.complete(by_hand) is by_hand and vars(by_hand) == before
+    kept = train.complete(argparse.Namespace(weight_decay=0.1, rrc_scale=(0.5, 0.75)))
+    assert kept.weight_decay == 0.1 and kept.rrc_scale == (0.5, 0.75) and kept.synthetic is False
+    dests = {a.dest: a.default for a in train.build_parser()._actions if a.dest != "help"}       # -h stores nothing
+    assert dests.keys() == vars(train.parse([])).keys() and len(dests) > 50
+    assert all(default is not argparse.SUPPRESS for default in dests.values())
+
+
+@pytest.mark.parametrize("argv, word", [
+    (["--model-type", "efficientkan", "--grid-extend", "3:10", "--graph"], "--grid-extend is not combined with --graph"),
+    (["--model-type", "cheby", "--grid-update-every", "2"], "--grid-update-every: model type 'cheby' has no KANLinear"),
+    (["--model-type", "sine", "--prune", "3:0.5"], "--prune: model type\\(s\\) sine have no edge-activation statistic"),
+    (["--device", "cpu"], "--device must be a cuda device")])
+def test_what_only_a_run_refuses_passes_parse_and_stops_main_before_the_gpu(argv, word):
+    import train
+    args = train.parse(["--synthetic", "--device", "cuda", *argv])      # parse() takes it ...
+    with pytest.raises(SystemExit, match=word):
+        train.main(args)                                                # ... main() refuses it, with no GPU in sight
+
+
 def test_save_metrics_is_byte_identical_to_the_reference(tmp_path):
     from utils import save_metrics
     fn = str(tmp_path / "logs" / "m.txt")
