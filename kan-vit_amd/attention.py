@@ -10,6 +10,7 @@ import torch
 from torch import nn
 
 from kanvit import grouped, ops
+from kanvit.prune import EdgePruning
 from models.cheby import ChebyKANLayer
 from models.effkan import KANLinear
 from models.fastkan import FastKANLayer
@@ -125,27 +126,27 @@ class MSA(torch.nn.Module):
         the rows of x [..., d] (the quantity the KAN paper regularises), from ONE grouped launch of kanvit.ops.edge_l1 with the
         packing of grouped.run_qkv.  `include_base` adds the base term of the efficient-KAN / FastKAN edge functions."""
         layers, l0 = self._qkv_layers()
-        if not isinstance(l0, (KANLinear, ChebyKANLayer, FastKANLayer)):
+        if not isinstance(l0, EdgePruning):
             raise NotImplementedError(f"edge_activation_l1: per-head layers of type {type(l0).__name__} have no edge-activation "
                                       f"statistic; supported MSA types: {', '.join(self.REGULARIZED_TYPES)}")
         H, dh = self.n_heads, self.d_head
         x2d = x.reshape(-1, self.d)
-        cfg = l0.kan_cfg() if isinstance(l0, ChebyKANLayer) else l0.kan_cfg(layers)
+        cfg = l0.kan_cfg(layers)
         w, bp, _ = type(l0).kan_pack_grouped(layers)
         base = bool(include_base) and cfg.has_base
-        if base and len({ops.base_activation_code(m.base_activation) for m in layers}) > 1:
+        if base and len({m.kan_base_act() for m in layers}) > 1:
             raise NotImplementedError("edge_activation_l1(include_base=True): one grouped launch has one base activation")
         if cfg.has_base and not base:        # spline path only: drop the base column of the packed weights
             w = w.reshape(3 * H, dh, cfg.GP, dh)[:, :, :cfg.G].reshape(3 * H, dh * cfg.G, dh)
             cfg = replace(cfg, has_base=0, base_act=0)
-        if isinstance(l0, FastKANLayer):     # every layer has its own LayerNorm: u[M, 3*H*dh], one column block per group
-            xin = FastKANLayer.kan_u_grouped(layers, x2d, H)
+        xin = type(l0).kan_u_grouped(layers, x2d, H)
+        if xin is None:                      # the basis reads x: every group its head's columns
+            xin = x2d
+            cfg = replace(cfg, groups=3 * H, x_group_mod=H)
+        else:                                # every layer has its own u (FastKAN's LayerNorm): u[M, 3*H*dh], one column block per group
             if base:
                 xin = torch.cat([xin, x2d.to(xin.dtype).repeat(1, 3)], dim=1)
             cfg = replace(cfg, groups=3 * H, x_group_mod=3 * H)
-        else:
-            xin = x2d
-            cfg = replace(cfg, groups=3 * H, x_group_mod=H)
         A = ops.edge_l1(xin, w, cfg, bp)                       # [3*H, in, out]
         return A.view(3, H, dh, dh).transpose(-1, -2)
 
@@ -178,7 +179,7 @@ class MSA(torch.nn.Module):
     def edge_masked(self):
         """The (parameter, mask, run) triples of the 3*H per-head layers (kanvit/prune.py); [] for types that are not pruned."""
         layers, l0 = self._qkv_layers()
-        return [t for m in layers for t in m.edge_masked()] if hasattr(l0, "edge_masked") else []
+        return [t for m in layers for t in m.edge_masked()] if isinstance(l0, EdgePruning) else []
 
     @torch.no_grad()
     def update_grid(self, x, margin=0.01):

@@ -1,13 +1,25 @@
 """Launch helpers: one fused kernel per KAN layer, or ONE kernel for every head's q, k and v
-mapping of an MSA block (3*H independent layers that share the rows of x).
+mapping of an MSA block (3*H independent layers that share the rows of x) -- and the protocol a layer
+module speaks to take part, `KanLayer`.  Every layer class of models/*.py inherits it; `as_kan` presents an
+nn.Linear through it.  The packing is O(|W|) plumbing; every flop of the layer itself runs in the HIP kernel.
 
-A layer module takes part by exposing
-    kan_cfg()  -> ops.LayerCfg (groups = 1)
-    kan_pack() -> (w[K, O], bparams[stride] | None, bias[O] | None)   built with differentiable
-                  torch ops from the module's reference-layout parameters, so autograd scatters
-                  the packed-weight gradient back to cheby_coeffs / spline_weight / ... itself
-    kan_u(x2d) -> u | None  (FastKAN: the LayerNorm'ed input of the spline path)
-The packing is O(|W|) plumbing; every flop of the layer itself runs in the HIP kernel.
+    kan_cfg(layers=None) -> ops.LayerCfg (groups = 1).  `layers`: the sibling layers of a grouped launch, for the families
+                  whose flags depend on all of them (the efficient-KAN knot tables, the FastKAN centres); others ignore it.
+    kan_pack()    -> (w[K, O], bparams[stride] | None, bias[O] | None), built with differentiable torch ops from the
+                  module's reference-layout parameters, so autograd scatters the packed-weight gradient back to
+                  cheby_coeffs / spline_weight / ... itself.  Row k = i*GP + j, a base column last (include/kanvit.h).
+                  bparams None: the family has no basis parameters; bias None: no bias.
+    kan_pack_grouped(layers)  (static) -> (w[g, K, O], bparams[g, stride] | None, bias[g, O] | None): kan_pack() of every
+                  layer, stacked with a handful of launches (stack_params).  A family that is never grouped (FourierKAN:
+                  patch embedding only) keeps the default, NotImplementedError.
+    kan_u(x2d)    -> u[M, I], the separate input of the spline path (FastKAN: LayerNorm(x)), or None: the basis reads x.
+    kan_u_grouped(layers, x2d, n_heads)  (static) -> u[M, g*I], column block g = proj*H + head, or None as above.
+    kan_ln()      -> the nn.LayerNorm the kernels may form u with themselves (ops.kan_layer_ln), or None: no such LayerNorm
+                  (or it is switched off: FastKANLayer.forward(time_benchmark=True)).
+    kan_base_act() -> the kernels' code of the layer's base activation (ops.base_act_of), or None: no live base path.
+                  One grouped launch has ONE base activation.
+
+Adding a family: DESIGN.md section 2, "Adding a KAN family".
 """
 from __future__ import annotations
 
@@ -64,29 +76,66 @@ def stack_params(tensors: Sequence[torch.Tensor], perm: Sequence[int] = None) ->
     return torch.stack(tensors)
 
 
-def linear_cfg(lin: torch.nn.Linear) -> ops.LayerCfg:
-    return ops.LayerCfg(family=ops.LINEAR, I=lin.in_features, O=lin.out_features, G=1)
+class KanLayer:
+    """The layer-to-kernel protocol (module docstring).  A family states kan_cfg and kan_pack, kan_pack_grouped where it serves as
+    per-head q|k|v mapping; the defaults below are a layer that reads x alone, has no LayerNorm to fuse and no base path."""
+
+    def kan_cfg(self, layers=None) -> ops.LayerCfg:
+        raise NotImplementedError
+
+    def kan_pack(self):
+        raise NotImplementedError
+
+    @staticmethod
+    def kan_pack_grouped(layers):
+        raise NotImplementedError(f"{type(layers[0]).__name__} has no grouped packing: it is not a per-head q|k|v mapping")
+
+    def kan_u(self, x2d):
+        return None
+
+    @staticmethod
+    def kan_u_grouped(layers, x2d, n_heads):
+        return None
+
+    def kan_ln(self):
+        return None
+
+    def kan_base_act(self):
+        return None
 
 
-def linear_pack(lin: torch.nn.Linear):
-    return lin.weight.t(), None, lin.bias
+class LinearKan(KanLayer):
+    """An nn.Linear (the vanilla q|k|v mapping) seen through the protocol: family LINEAR, nn.Linear keeps its weight as [O, I]."""
+
+    def __init__(self, lin: torch.nn.Linear):
+        self.lin = lin
+
+    def kan_cfg(self, layers=None):
+        return ops.LayerCfg(family=ops.LINEAR, I=self.lin.in_features, O=self.lin.out_features, G=1)
+
+    def kan_pack(self):
+        return self.lin.weight.t(), None, self.lin.bias
+
+    @staticmethod
+    def kan_pack_grouped(layers):
+        w = stack_params([m.lin.weight for m in layers], perm=(1, 0))      # [g, I, O]
+        return w, None, None if layers[0].lin.bias is None else stack_params([m.lin.bias for m in layers])
 
 
-def _cfg_pack(m):
-    if isinstance(m, torch.nn.Linear):
-        return linear_cfg(m), linear_pack(m)
-    return m.kan_cfg(), m.kan_pack()
+def as_kan(m) -> KanLayer:
+    """m itself, or the adapter of an nn.Linear."""
+    return LinearKan(m) if isinstance(m, torch.nn.Linear) else m
 
 
 def run_single(layer, x2d: torch.Tensor) -> torch.Tensor:
     """y[M, O] for one layer on a 2-D input."""
-    cfg, (w, bp, bias) = _cfg_pack(layer)
-    if hasattr(layer, "kan_ln") and layer.kan_ln() is not None and ops.ln_fusable(cfg, x2d.shape[0]):
-        ln = layer.kan_ln()           # FastKAN: the LayerNorm of the spline path is formed inside the kernels
+    layer = as_kan(layer)
+    cfg, (w, bp, bias) = layer.kan_cfg(), layer.kan_pack()
+    ln = layer.kan_ln()
+    if ln is not None and ops.ln_fusable(cfg, x2d.shape[0]):      # FastKAN: the LayerNorm of the spline path is formed inside the kernels
         return ops.kan_layer_ln(x2d, w.unsqueeze(0), cfg, torch.cat([bp, ln.weight, ln.bias]).unsqueeze(0),
                                 None if bias is None else bias.reshape(1, -1), ln.eps)
-    u = layer.kan_u(x2d) if hasattr(layer, "kan_u") else None
-    return ops.kan_layer(x2d, w.unsqueeze(0), cfg, u=u,
+    return ops.kan_layer(x2d, w.unsqueeze(0), cfg, u=layer.kan_u(x2d),
                          bparams=None if bp is None else bp.unsqueeze(0),
                          bias=None if bias is None else bias.reshape(1, -1))
 
@@ -104,23 +153,14 @@ def pack_projections(projections: Sequence[Sequence]):
     group g = proj*H + head.  Pure packing (differentiable torch ops on the layers' parameters), no launch."""
     H = len(projections[0])
     assert all(len(p) == H for p in projections), "every projection has one layer per head"
-    layers = [m for p in projections for m in p]
-    if isinstance(layers[0], torch.nn.Linear):
-        cfg0 = linear_cfg(layers[0])
-    elif hasattr(type(layers[0]), "kan_pack_grouped") and "layers" in layers[0].kan_cfg.__code__.co_varnames:
-        cfg0 = layers[0].kan_cfg(layers)          # family whose flags depend on all the layers (efficient-KAN knot tables)
-    else:
-        cfg0 = layers[0].kan_cfg()
-    cfg = replace(cfg0, groups=len(layers), x_group_mod=H)
-    # Pack ALL P*H layers with one stack + one layout transform (a handful of launches) instead of a
+    return _pack_layers([as_kan(m) for p in projections for m in p], H)
+
+
+def _pack_layers(layers: Sequence[KanLayer], H: int):
+    cfg = replace(layers[0].kan_cfg(layers), groups=len(layers), x_group_mod=H)
+    # kan_pack_grouped packs ALL P*H layers with one stack + one layout transform (a handful of launches) instead of a
     # permute-copy per head (3*H launches forward and again backward: 880 tiny kernels per ViT-B step).
-    if isinstance(layers[0], torch.nn.Linear):
-        w = stack_params([m.weight for m in layers], perm=(1, 0))      # [g, I, O]: nn.Linear keeps [O, I]
-        bp = None
-        bias = None if layers[0].bias is None else stack_params([m.bias for m in layers])
-    else:
-        w, bp, bias = type(layers[0]).kan_pack_grouped(layers)
-    return cfg, w, bp, bias
+    return (cfg,) + tuple(type(layers[0]).kan_pack_grouped(layers))
 
 
 def run_projections(projections: Sequence[Sequence], x2d: torch.Tensor, tag: str = None) -> torch.Tensor:
@@ -128,20 +168,18 @@ def run_projections(projections: Sequence[Sequence], x2d: torch.Tensor, tag: str
     launch; column block g = proj*H + head holds layer g's output.  `tag` names the launch for the kernel timer (kanvit.ops.kan_layer);
     the q|k|v launch of run_qkv keeps the default "qkv"."""
     H = len(projections[0])
-    layers = [m for p in projections for m in p]
+    assert all(len(p) == H for p in projections), "every projection has one layer per head"
+    layers = [as_kan(m) for p in projections for m in p]
     # one grouped launch has ONE base activation (kanvit_layer_desc.base_act): layers whose activations differ (swapped after
     # construction) run one launch each, on their own head's columns
-    acts = {ops.base_activation_code(m.base_activation) for m in layers
-            if hasattr(m, "base_activation") and getattr(m, "use_base_update", True)}
-    if len(acts) > 1:
+    if len({m.kan_base_act() for m in layers} - {None}) > 1:
         dh = x2d.shape[1] // H
         return torch.cat([run_single(m, x2d[:, (g % H) * dh:(g % H + 1) * dh]) for g, m in enumerate(layers)], dim=1)
-    cfg, w, bp, bias = pack_projections(projections)
-    if hasattr(layers[0], "kan_ln") and layers[0].kan_ln() is not None and ops.ln_fusable(cfg, x2d.shape[0]):
-        gamma = stack_params([l.kan_ln().weight for l in layers])
-        beta = stack_params([l.kan_ln().bias for l in layers])
-        return ops.kan_layer_ln(x2d, w, cfg, torch.cat([bp, gamma, beta], dim=1), bias, layers[0].kan_ln().eps, tag=tag)
-    u = None
-    if hasattr(layers[0], "kan_u_grouped"):
-        u = type(layers[0]).kan_u_grouped(layers, x2d, H)
+    cfg, w, bp, bias = _pack_layers(layers, H)
+    lns = [m.kan_ln() for m in layers]
+    if lns[0] is not None and ops.ln_fusable(cfg, x2d.shape[0]):
+        gamma = stack_params([ln.weight for ln in lns])
+        beta = stack_params([ln.bias for ln in lns])
+        return ops.kan_layer_ln(x2d, w, cfg, torch.cat([bp, gamma, beta], dim=1), bias, lns[0].eps, tag=tag)
+    u = type(layers[0]).kan_u_grouped(layers, x2d, H)
     return ops.kan_layer(x2d, w, cfg, u=u, bparams=bp, bias=bias, tag=tag)

@@ -54,6 +54,10 @@ class EdgePruning:
         """[out, in]: edge_activation_l1 of the WHOLE edge function (the base term included where the layer has one)."""
         raise NotImplementedError
 
+    def regularization_loss(self, x, regularize_activation=1.0, regularize_entropy=1.0, include_base=False):
+        """The L1 and entropy terms of models/effkan.py:258-264 on edge_activation_l1(x, include_base)."""
+        return ops.l1_entropy_loss(self.edge_activation_l1(x, include_base), regularize_activation, regularize_entropy)
+
     def _edge_mask_buffer(self):
         if getattr(self, "edge_mask", None) is None:
             i, o = self._edge_dims()

@@ -11,11 +11,15 @@ from attention import MSA, FlashAttention
 from kanvit import _lib, ops
 from kanvit.dense import feed_forward, ff_mode, ff_small_supported, ln_feed_forward
 from kanvit.ops import add_layernorm
+from kanvit.prune import EdgePruning
 from models.cheby import ChebyKANLayer
 from models.effkan import KANLinear
 from models.fastkan import FastKANLayer
 from models.nfkan import NaiveFourierKANLayer
 from models.sinekan import SineKANLayer
+
+
+_NO_DROP = (None, None, None)      # TransformerBlock.run / run_cls: the scale rows of stochastic depth, off
 
 
 class TransformerBlock(nn.Module):
@@ -39,7 +43,7 @@ class TransformerBlock(nn.Module):
         (MSA.attention_map of norm1(x))."""
         return self.attn.attention_map(self.norm1(x), rows)
 
-    def run(self, x, pending, reg=None, drop=None):
+    def run(self, x, pending, reg=None, drop=_NO_DROP):
         """The block with its residual adds fused into the LayerNorms (kanvit.ops.add_layernorm: one pass instead of an
         add kernel + a LayerNorm kernel forward, one pass instead of three + an add backward).  `pending` is the previous
         block's feed-forward output that has not been added to the stream yet (None for the first block); returns
@@ -47,29 +51,24 @@ class TransformerBlock(nn.Module):
             x = x + MSA(LN1(x));  x = x + FF(LN2(x)).
         reg (a dict of MSA.regularization_loss keywords, or None): also return, as a third value, the sample-based KAN
         regulariser of the per-head q|k|v layers on the rows they read, LN1(x) -- the tensor this forward already holds.
-        drop (stochastic depth, VisionTransformer.set_drop_path; None = off): (the [B] scale row of the branch `pending` is -- the
-        previous block's feed-forward -- or None, the [B] scale row of this block's attention branch).  Each fused add takes the row
-        of the branch it adds; the returned feed-forward output is unscaled, like `pending`."""
-        if drop is None:
-            x, h1 = add_layernorm(x, pending, self.norm1)
-        else:
-            x, h1 = add_layernorm(x, pending, self.norm1, row_scale=None if pending is None else drop[0])
+        drop (stochastic depth, VisionTransformer.set_drop_path; all None = off): (the [B] scale row of the branch `pending` is --
+        the previous block's feed-forward -- or None, the [B] scale row of this block's attention branch, ...).  Each fused add takes
+        the row of the branch it adds; the returned feed-forward output is unscaled, like `pending`."""
+        x, h1 = add_layernorm(x, pending, self.norm1, row_scale=None if pending is None else drop[0])
         if reg is not None:
-            return self._rest(x, h1, drop) + (self.attn.regularization_loss(h1, **reg),)
-        return self._rest(x, h1, drop)
+            return self._rest(x, h1, drop[1]) + (self.attn.regularization_loss(h1, **reg),)
+        return self._rest(x, h1, drop[1])
 
-    def _rest(self, x, h1, drop=None):
-        if drop is None and x.dim() == 3 and ff_small_supported(self.ff[0].in_features, self.ff[0].out_features):
+    def _rest(self, x, h1, attn_scale):
+        if attn_scale is None and x.dim() == 3 and ff_small_supported(self.ff[0].in_features, self.ff[0].out_features):
             # small geometries: residual add + LN2 + feed-forward in one launch (SURVEY 8(f)1); ln_feed_forward itself falls
             # back to add_layernorm + feed_forward for inputs the fused kernel refuses (dtype, autocast, row count)
             return ln_feed_forward(x, self.attn(h1), self.norm2, self.ff[0], self.ff[2])
         # under bf16 autocast the stock feed-forward GEMMs take bf16 operands: LN2 writes its output as bf16 directly, and the bf16
         # feed-forward output comes back into the next block's add_layernorm as it is (no cast passes in either direction)
         ybf = (x.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16 and ff_mode() != "bf16x3")
-        if drop is None:
-            x, h2 = add_layernorm(x, self.attn(h1), self.norm2, y_bf16=ybf)
-        else:             # also the small geometries: the one-launch LN2 + feed-forward has no scaled form (DESIGN 4.23)
-            x, h2 = add_layernorm(x, self.attn(h1), self.norm2, y_bf16=ybf, row_scale=drop[1])
+        # a scaled attention branch comes here also at the small geometries: the one-launch LN2 + feed-forward has no scaled form (DESIGN 4.23)
+        x, h2 = add_layernorm(x, self.attn(h1), self.norm2, y_bf16=ybf, row_scale=attn_scale)
         # Same three ops as self.ff (Linear -> ReLU(inplace) -> Linear, model.py:25-29), applied to the 2-D
         # (B*N, d) tensor: nn.Linear on 3-D input returns a VIEW, and an in-place ReLU on a view makes autograd
         # insert CopySlices (two full [B*N, 4d] copies per block in backward: 12 ms/step at ViT-B, B=128).
@@ -79,25 +78,22 @@ class TransformerBlock(nn.Module):
         return x, feed_forward(h2.reshape(b * n, d), self.ff[0], self.ff[2]).view(b, n, d)   # bias + ReLU in the GEMM epilogue
 
 
-    def run_cls(self, x, pending, drop=None):
+    def run_cls(self, x, pending, drop=_NO_DROP):
         """The class-token row [B, d] of x + MSA(LN1(x)) + FF(LN2(.)) after the pending add, i.e. forward(x + pending)[:, 0]:
         all the head of a ViT reads of its last block (model.py:166-169).  LN1 still runs on all rows (k and v need them); the
         q layers, the attention, the residual, LN2 and the feed-forward run on the B class rows only (MSA.forward_cls).  Under
         bf16 autocast the grouped q|k|v launch and the attention stay what they are in run() -- all rows, on the bf16 matrix
         cores, the rounding points the bf16 results are specified with -- and LN2 + feed-forward take the class rows.
-        drop (stochastic depth; None = off): run()'s pair and, third, the scale row of this block's feed-forward branch.  The pending
-        add takes its row inside the fused pass; the two [B, d] class-row branches are scaled by a plain multiply."""
-        if drop is None:
-            x, h1 = add_layernorm(x, pending, self.norm1)
-        else:
-            x, h1 = add_layernorm(x, pending, self.norm1, row_scale=None if pending is None else drop[0])
+        drop (stochastic depth; all None = off): run()'s pair and, third, the scale row of this block's feed-forward branch.  The
+        pending add takes its row inside the fused pass; the two [B, d] class-row branches are scaled by a plain multiply."""
+        x, h1 = add_layernorm(x, pending, self.norm1, row_scale=None if pending is None else drop[0])
         ybf = (x.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16)
         a0 = _FirstRow.apply(self.attn(h1)) if ybf else self.attn.forward_cls(h1)
-        if drop is not None:
+        if drop[1] is not None:
             a0 = a0 * drop[1].unsqueeze(1)
         s, h2 = add_layernorm(_FirstRow.apply(x), a0, self.norm2, y_bf16=ybf and ff_mode() != "bf16x3")
         f = feed_forward(h2, self.ff[0], self.ff[2])
-        return s + (f if drop is None else f * drop[2].unsqueeze(1))
+        return s + (f if drop[2] is None else f * drop[2].unsqueeze(1))
 
 
 class _FirstRow(torch.autograd.Function):
@@ -199,6 +195,18 @@ class VisionTransformer(nn.Module):
         self.drop_path_rates = []
         self._patch_dropout = None     # set_patch_dropout: None = off, else (K kept patches per sample, seed)
 
+    def _set_counter(self, name, on):
+        """The device call counter `name` of a hashed draw (set_drop_path, set_patch_dropout): a non-persistent int64 buffer, so
+        state_dict() is unchanged.  on: create it, or zero the one there is; off: remove it."""
+        if not on:
+            if name in self._buffers:
+                del self._buffers[name]
+                self._non_persistent_buffers_set.discard(name)
+        elif name not in self._buffers:
+            self.register_buffer(name, torch.zeros(1, dtype=torch.int64, device=self.v_class.device), persistent=False)
+        else:
+            self._buffers[name].zero_()
+
     def set_patch_dropout(self, rate, seed=0):
         """PatchDropout (Liu et al. 2023; timm's patch_drop_rate): in train() mode on the GPU every sample keeps K = max(1, int(P *
         (1 - rate))) of its P patch tokens (timm's rule) plus the class token, so every block runs on K + 1 tokens; eval() sees all
@@ -214,17 +222,12 @@ class VisionTransformer(nn.Module):
         K = max(1, int(P * (1.0 - rate)))
         if rate == 0.0 or K == P:
             self._patch_dropout = None
-            if "patch_dropout_counter" in self._buffers:
-                del self._buffers["patch_dropout_counter"]
-                self._non_persistent_buffers_set.discard("patch_dropout_counter")
+            self._set_counter("patch_dropout_counter", False)
             return P
         if P > _lib.PATCH_KEEP_MAX_P:
             raise NotImplementedError(f"set_patch_dropout: {P} patches per image; one patch_keep launch ranks {_lib.PATCH_KEEP_MAX_P}")
         self._patch_dropout = (K, int(seed))
-        if "patch_dropout_counter" not in self._buffers:
-            self.register_buffer("patch_dropout_counter", torch.zeros(1, dtype=torch.int64, device=self.v_class.device), persistent=False)
-        else:
-            self.patch_dropout_counter.zero_()
+        self._set_counter("patch_dropout_counter", True)
         return K
 
     def set_drop_path(self, rate, seed=0, schedule="linear"):
@@ -243,9 +246,7 @@ class VisionTransformer(nn.Module):
         if rate == 0.0:
             self._drop_path = None
             self.drop_path_rates = []
-            if "drop_path_counter" in self._buffers:
-                del self._buffers["drop_path_counter"]
-                self._non_persistent_buffers_set.discard("drop_path_counter")
+            self._set_counter("drop_path_counter", False)
             return self.drop_path_rates
         if not all(isinstance(blk, TransformerBlock) for blk in self.blocks):
             raise NotImplementedError("set_drop_path: 'flash-attn' models stack bare FlashAttention modules (model.py:113-117), which "
@@ -255,10 +256,7 @@ class VisionTransformer(nn.Module):
             raise NotImplementedError(f"set_drop_path: {n} blocks have {2 * n} branches; one depth_scales launch takes {_lib.DEPTH_MAX_BRANCHES}")
         self.drop_path_rates = [rate if schedule == "constant" or n == 1 else rate * l / (n - 1) for l in range(n)]
         self._drop_path = ([1.0 - r for r in self.drop_path_rates for _ in range(2)], int(seed))      # branch 2l: attention, 2l + 1: feed-forward
-        if "drop_path_counter" not in self._buffers:
-            self.register_buffer("drop_path_counter", torch.zeros(1, dtype=torch.int64, device=self.v_class.device), persistent=False)
-        else:
-            self.drop_path_counter.zero_()
+        self._set_counter("drop_path_counter", True)
         return self.drop_path_rates
 
     def patchify(self, images, n_patches):
@@ -284,7 +282,7 @@ class VisionTransformer(nn.Module):
         8(f)2; kanvit.ops.patch_embed), or None when the fused kernel does not cover this layer / geometry (then the
         three-step path below runs: same arithmetic).  Under bf16 autocast the same launch runs on the bf16 matrix cores."""
         lm = self.linear_mapper
-        if isinstance(lm, nn.Linear) or not hasattr(lm, "kan_pack") or hasattr(lm, "kan_u"):
+        if isinstance(lm, nn.Linear) or lm.kan_ln() is not None:      # the kernel forms no LayerNorm: a layer whose basis reads u is not covered
             return None
         # the cached per-model decision is per arithmetic mode: the fp32 and the bf16 kernels tile the patch width differently
         mode = bool(torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16)
@@ -360,6 +358,36 @@ class VisionTransformer(nn.Module):
             tokens = tokens.float()
         return ops.assemble_tokens(tokens, self.v_class, self.pos_embeddings[: self.n_patches ** 2 + 1], idx), rows
 
+    def _walk(self, images):
+        """(block, the block's real input) for every block, on the full sequence: embed, hand a block and its input to the consumer,
+        run the block after the consumer returns -- so a consumer that changes the block is seen by its run, and later blocks read
+        the activations of the already-changed earlier ones.  The last block is not run: nothing reads its output."""
+        out = self._embed(images)
+        for blk in self.blocks:
+            yield blk, out
+            if blk is not self.blocks[-1]:
+                out = blk(out)
+
+    def _refit_grids(self, who, images, refit):
+        """The body of update_grid and extend_grid (`who`): refit(module, rows) -- the method of that name of a KANLinear or an MSA --
+        on the patch embedding with the patch rows, then on every efficient-KAN block's MSA with norm1 of the block's input.  Returns
+        the sum of what refit returns."""
+        def has_grid(blk):
+            return isinstance(blk, TransformerBlock) and isinstance(blk.attn.q_mappings[0], KANLinear)
+        if not isinstance(self.linear_mapper, KANLinear) and not any(has_grid(blk) for blk in self.blocks):
+            raise NotImplementedError(f"{who}: model type(s) {sorted(self.layer_types())} have no KANLinear, the only layer "
+                                      f"with a B-spline grid to {who.split('_')[0]} ('efficientkan')")
+        count = torch.zeros((), dtype=torch.int64, device=images.device)
+        if isinstance(self.linear_mapper, KANLinear):
+            count = count + refit(self.linear_mapper, self.patchify(images, self.n_patches).reshape(-1, self.input_d))
+        # whether the fused patch embedding covers this model was decided for the old grid's flags and size
+        self._fused_embed = None
+        for blk, x in self._walk(images):
+            if has_grid(blk):
+                count = count + refit(blk.attn, blk.norm1(x))
+        self._fused_embed = None
+        return count
+
     @torch.no_grad()
     def update_grid(self, images, margin=0.01):
         """KANLinear.update_grid (models/effkan.py:189-242) for every efficient-KAN layer of the model on one image batch: the
@@ -368,23 +396,7 @@ class VisionTransformer(nn.Module):
         activations of the already-updated earlier ones.  Blocks of other types in a mixed model just run.  Afterwards the
         updated layers evaluate the general Cox-de Boor kernels instead of the uniform closed form.  Returns the number of
         features kept unchanged (0-d device tensor)."""
-        kan_blocks = [isinstance(blk, TransformerBlock) and isinstance(blk.attn.q_mappings[0], KANLinear) for blk in self.blocks]
-        if not isinstance(self.linear_mapper, KANLinear) and not any(kan_blocks):
-            raise NotImplementedError(f"update_grid: model type(s) {sorted(self.layer_types())} have no KANLinear, the only layer "
-                                      "with a B-spline grid to update ('efficientkan')")
-        kept = torch.zeros((), dtype=torch.int64, device=images.device)
-        if isinstance(self.linear_mapper, KANLinear):
-            kept = kept + self.linear_mapper.update_grid(self.patchify(images, self.n_patches).reshape(-1, self.input_d), margin)
-        # whether the fused patch embedding covers this model was decided for the old grid's flags
-        self._fused_embed = None
-        out = self._embed(images)
-        for blk, is_kan in zip(self.blocks, kan_blocks):
-            if is_kan:
-                kept = kept + blk.attn.update_grid(blk.norm1(out), margin)
-            if blk is not self.blocks[-1]:
-                out = blk(out)
-        self._fused_embed = None
-        return kept
+        return self._refit_grids("update_grid", images, lambda m, rows: m.update_grid(rows, margin))
 
     @torch.no_grad()
     def extend_grid(self, images, grid_size, margin=0.01):
@@ -394,26 +406,10 @@ class VisionTransformer(nn.Module):
         (MSA.extend_grid); a block runs after its own extension; blocks of other types in a mixed model just run.  Every
         spline_weight of an extended layer is a NEW Parameter: an optimizer holding the old ones must be told (train.py
         --grid-extend does).  Returns the number of features that took the fallback fit (0-d device tensor)."""
-        kan_blocks = [isinstance(blk, TransformerBlock) and isinstance(blk.attn.q_mappings[0], KANLinear) for blk in self.blocks]
-        if not isinstance(self.linear_mapper, KANLinear) and not any(kan_blocks):
-            raise NotImplementedError(f"extend_grid: model type(s) {sorted(self.layer_types())} have no KANLinear, the only layer "
-                                      "with a B-spline grid to extend ('efficientkan')")
         for m in self.modules():                             # refuse a size a layer cannot take before any of them moves
             if isinstance(m, KANLinear):
                 KANLinear.check_extension(grid_size, m.spline_order)
-        fell_back = torch.zeros((), dtype=torch.int64, device=images.device)
-        if isinstance(self.linear_mapper, KANLinear):
-            fell_back = fell_back + self.linear_mapper.extend_grid(self.patchify(images, self.n_patches).reshape(-1, self.input_d),
-                                                                   grid_size, margin)
-        self._fused_embed = None                             # decided for the old grid's flags and size
-        out = self._embed(images)
-        for blk, is_kan in zip(self.blocks, kan_blocks):
-            if is_kan:
-                fell_back = fell_back + blk.attn.extend_grid(blk.norm1(out), grid_size, margin)
-            if blk is not self.blocks[-1]:
-                out = blk(out)
-        self._fused_embed = None
-        return fell_back
+        return self._refit_grids("extend_grid", images, lambda m, rows: m.extend_grid(rows, grid_size, margin))
 
     def _prunable(self, who):
         """The modules edge pruning covers, in the walk's order (the patch embedding, then every block's MSA), or NotImplementedError
@@ -440,11 +436,8 @@ class VisionTransformer(nn.Module):
             return kept, torch.full((), total, dtype=torch.int64, device=images.device)
         out = [pair(self.linear_mapper.prune_edges(self.patchify(images, self.n_patches).reshape(-1, self.input_d), **kw),
                     self.input_d * self.d_hidden)]
-        x = self._embed(images)
-        for blk in self.blocks:
+        for blk, x in self._walk(images):
             out.append(pair(blk.attn.prune_edges(blk.norm1(x), **kw), 3 * blk.attn.n_heads * blk.attn.d_head ** 2))
-            if blk is not self.blocks[-1]:
-                x = blk(x)
         return out
 
     def edge_masked(self):
@@ -456,7 +449,7 @@ class VisionTransformer(nn.Module):
         """restore_edge_mask on every prunable layer: the masks of a pruned checkpoint, rebuilt from its exact zeros after
         load_state_dict.  Returns the number of kept edges (0-d device tensor)."""
         self._prunable("restore_edge_masks")
-        return torch.stack([m.restore_edge_mask() for m in self.modules() if hasattr(m, "restore_edge_mask")]).sum()
+        return torch.stack([m.restore_edge_mask() for m in self.modules() if isinstance(m, EdgePruning)]).sum()
 
     def edge_sparsity(self):
         """(kept, total) edges over every prunable layer, 0-d device tensors; a layer never pruned counts as whole.  No host
@@ -465,15 +458,6 @@ class VisionTransformer(nn.Module):
         kept = torch.stack([m.sum() for m in masks]).sum()
         return kept, torch.full((), sum(m.numel() for m in masks), dtype=torch.int64, device=kept.device)
 
-    def _walk_attention_maps(self, images, rows):
-        """One block's map at a time, update_grid's walk: the map of block l is taken on the block's real input, then the block
-        runs (the last one does not have to).  'flash-attn' models stack bare FlashAttention modules."""
-        out = self._embed(images)
-        for blk in self.blocks:
-            yield blk.attention_map(out, rows=rows)
-            if blk is not self.blocks[-1]:
-                out = blk(out)
-
     @torch.no_grad()
     def attention_maps(self, images, rows=None):
         """[n_blocks, B, H, R, N] float32 (N = n_patches^2 + 1 tokens, the class token first): every head's attention
@@ -481,7 +465,7 @@ class VisionTransformer(nn.Module):
         'flash-attn' model) on each block's real input.  `rows` = R keeps the first R query rows (default N; 1 = the class-token
         row).  Runs without gradients and leaves the training / eval mode as it finds it.  The stacked result grows with
         n_blocks * B * H * N^2 (ViT-B at batch 128: 2.9 GB); attention_rollout holds one block's map at a time."""
-        return torch.stack(list(self._walk_attention_maps(images, rows)))
+        return torch.stack([blk.attention_map(x, rows=rows) for blk, x in self._walk(images)])
 
     @staticmethod
     def _rollout_factor(block_map, head_fusion):
@@ -519,7 +503,8 @@ class VisionTransformer(nn.Module):
         """rollout(attention_maps(images), head_fusion) -> [B, N, N] without the stacked maps: the same walk, carrying the running
         product and one block's map.  [:, 0, 1:] is the class token's saliency over the patches (cls_saliency)."""
         out = None
-        for block_map in self._walk_attention_maps(images, None):
+        for blk, x in self._walk(images):
+            block_map = blk.attention_map(x)
             with torch.autocast(block_map.device.type, enabled=False):
                 f = self._rollout_factor(block_map, head_fusion)
                 out = f if out is None else f @ out
@@ -556,10 +541,7 @@ class VisionTransformer(nn.Module):
             if out is None:
                 patches = self.patchify(images, self.n_patches)
                 rows = patches.reshape(-1, self.input_d)
-            if isinstance(self.linear_mapper, KANLinear):
-                reg = self.linear_mapper.regularization_loss(x=rows, **reg_kw)
-            else:
-                reg = self.linear_mapper.regularization_loss(rows, **reg_kw)
+            reg = self.linear_mapper.regularization_loss(x=rows, **reg_kw)
         if out is None:
             out = self._embed(images, patches)
         pending = None
@@ -574,15 +556,14 @@ class VisionTransformer(nn.Module):
         if self._drop_path is not None and self.training:
             scales = ops.depth_scales(out.shape[0], self._drop_path[0], self._drop_path[1], self.drop_path_counter)
         for l, blk in enumerate(self.blocks):
-            drop = None if scales is None else (scales[2 * l - 1] if l else None, scales[2 * l], scales[2 * l + 1])
+            drop = _NO_DROP if scales is None else (scales[2 * l - 1] if l else None, scales[2 * l], scales[2 * l + 1])
             if cls_tail and blk is last:
-                out = blk.run_cls(out, pending) if drop is None else blk.run_cls(out, pending, drop)
-                return self.mlp_head(out)
+                return self.mlp_head(blk.run_cls(out, pending, drop))
             if isinstance(blk, TransformerBlock) and reg_kw is not None:
-                out, pending, r = blk.run(out, pending, reg_kw) if drop is None else blk.run(out, pending, reg_kw, drop)
+                out, pending, r = blk.run(out, pending, reg_kw, drop)
                 reg = reg + r
             elif isinstance(blk, TransformerBlock):
-                out, pending = blk.run(out, pending) if drop is None else blk.run(out, pending, drop=drop)
+                out, pending = blk.run(out, pending, drop=drop)
             else:                                     # 'flash-attn' models stack bare FlashAttention modules (model.py:113-117)
                 out = blk(out)
         if pending is not None and scales is not None:    # the class rows of the stream and of the last, still pending branch

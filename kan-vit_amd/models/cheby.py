@@ -7,7 +7,7 @@ from kanvit import grouped, ops
 from kanvit.prune import EdgePruning
 
 
-class ChebyKANLayer(EdgePruning, nn.Module):
+class ChebyKANLayer(EdgePruning, grouped.KanLayer, nn.Module):
     """y[b, o] = sum_i sum_{d=0..degree} T_d(tanh x[b, i]) * cheby_coeffs[i, o, d].
 
     Same constructor, parameter / buffer names and shapes as the reference (models/cheby.py:11-34):
@@ -26,7 +26,7 @@ class ChebyKANLayer(EdgePruning, nn.Module):
         self.register_buffer("arange", torch.arange(0, degree + 1, 1))
 
     # ---- fused-kernel protocol (kanvit/grouped.py) ----
-    def kan_cfg(self):
+    def kan_cfg(self, layers=None):
         return ops.LayerCfg(family=ops.CHEBY, I=self.inputdim, O=self.outdim, G=self.degree + 1)
 
     def kan_pack(self):
@@ -40,9 +40,9 @@ class ChebyKANLayer(EdgePruning, nn.Module):
         g, i, d1, o = c.shape
         return c.view(g, i * d1, o), None, None
 
-    def edge_activation_l1(self, x):
+    def edge_activation_l1(self, x, include_base=False):
         """[out, in]: mean over the samples of |sum_d T_d(tanh x_i) cheby_coeffs[i, o, d]|, the per-edge activation magnitude
-        of the KAN paper's regulariser, reduced over the samples inside the fused kernel (kanvit.ops.edge_l1)."""
+        of the KAN paper's regulariser, reduced over the samples inside the fused kernel (kanvit.ops.edge_l1).  The family has no base term: include_base is ignored."""
         w, _, _ = self.kan_pack()
         x2d = x if x.dim() == 2 else x.reshape(-1, self.inputdim)
         return ops.edge_l1(x2d, w.unsqueeze(0), self.kan_cfg())[0].t()
@@ -58,10 +58,6 @@ class ChebyKANLayer(EdgePruning, nn.Module):
 
     def _edge_scores(self, x):
         return self.edge_activation_l1(x)
-
-    def regularization_loss(self, x, regularize_activation=1.0, regularize_entropy=1.0):
-        """The L1 and entropy terms of models/effkan.py:258-264 on edge_activation_l1(x)."""
-        return ops.l1_entropy_loss(self.edge_activation_l1(x), regularize_activation, regularize_entropy)
 
     def forward(self, x):
         return grouped.run_single(self, x.reshape(-1, self.inputdim))

@@ -51,7 +51,7 @@ def _grid_facts(layers):
     return hit[:2]
 
 
-class KANLinear(EdgePruning, torch.nn.Module):
+class KANLinear(EdgePruning, grouped.KanLayer, torch.nn.Module):
     def __init__(self, in_features, out_features, grid_size=5, spline_order=3, scale_noise=0.1, scale_base=1.0,
                  scale_spline=1.0, enable_standalone_scale_spline=True, base_activation=torch.nn.SiLU, grid_eps=0.02,
                  grid_range=[-1, 1]):
@@ -149,6 +149,9 @@ class KANLinear(EdgePruning, torch.nn.Module):
         w = torch.cat([sw.permute(0, 2, 3, 1), bw.permute(0, 2, 1).unsqueeze(2)], dim=2)   # [g, I, nb+1, O]
         g, i, nb1, o = w.shape
         return w.reshape(g, i * nb1, o), torch.stack([m.grid.reshape(-1) for m in layers]), None
+
+    def kan_base_act(self):
+        return ops.base_act_of(self.base_activation)
 
     def forward(self, x: torch.Tensor):
         assert x.size(-1) == self.in_features

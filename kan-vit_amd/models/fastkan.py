@@ -63,7 +63,7 @@ class RadialBasisFunction(nn.Module):
         return y.reshape(*x.shape, n)
 
 
-class FastKANLayer(EdgePruning, nn.Module):
+class FastKANLayer(EdgePruning, grouped.KanLayer, nn.Module):
     """y = spline_linear(rbf(layernorm(x))) + base_linear(base_activation(x)) (models/fastkan.py:66-76); base_activation is
     F.silu by default or one of ops.SUPPORTED_BASE_ACTIVATIONS, read on every forward.
 
@@ -114,12 +114,17 @@ class FastKANLayer(EdgePruning, nn.Module):
             bias = grouped.stack_params([m.base_linear.bias for m in layers])
         return w.reshape(g, -1, o), torch.stack([m.rbf.grid.detach() for m in layers]), bias
 
+    _use_ln = True          # False inside forward(time_benchmark=True)
+
     def kan_u(self, x2d):
-        return self.layernorm(x2d) if getattr(self, "_use_ln", True) else None
+        return self.layernorm(x2d) if self._use_ln else None
 
     def kan_ln(self):
         """The LayerNorm to fuse into the kernels, or None (time_benchmark skips it, models/fastkan.py:67-70)."""
-        return self.layernorm if getattr(self, "_use_ln", True) else None
+        return self.layernorm if self._use_ln else None
+
+    def kan_base_act(self):
+        return ops.base_act_of(self.base_activation) if self.use_base_update else None
 
     @staticmethod
     def kan_u_grouped(layers, x2d, n_heads):
@@ -163,10 +168,6 @@ class FastKANLayer(EdgePruning, nn.Module):
 
     def _edge_scores(self, x):
         return self.edge_activation_l1(x, include_base=self.use_base_update)
-
-    def regularization_loss(self, x, regularize_activation=1.0, regularize_entropy=1.0, include_base=False):
-        """The L1 and entropy terms of models/effkan.py:258-264 on edge_activation_l1(x, include_base)."""
-        return ops.l1_entropy_loss(self.edge_activation_l1(x, include_base), regularize_activation, regularize_entropy)
 
     def forward(self, x, time_benchmark=False):
         self._use_ln = not time_benchmark        # time_benchmark skips the LayerNorm (models/fastkan.py:67-70)

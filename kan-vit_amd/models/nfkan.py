@@ -9,7 +9,7 @@ import torch
 from kanvit import grouped, ops
 
 
-class NaiveFourierKANLayer(torch.nn.Module):
+class NaiveFourierKANLayer(grouped.KanLayer, torch.nn.Module):
     """y[m, o] = sum_i sum_{k=1..G} cos(k x_mi) F[0,o,i,k-1] + sin(k x_mi) F[1,o,i,k-1] (+ bias).
 
     Signature as the reference (models/nfkan.py:6, including the ``smootorch_initialization``
@@ -31,7 +31,7 @@ class NaiveFourierKANLayer(torch.nn.Module):
         if addbias:
             self.bias = torch.nn.Parameter(torch.zeros(1, outdim))
 
-    def kan_cfg(self):
+    def kan_cfg(self, layers=None):
         return ops.LayerCfg(family=ops.FOURIER, I=self.inputdim, O=self.outdim, G=self.gridsize)
 
     def kan_pack(self):

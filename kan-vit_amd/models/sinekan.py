@@ -11,7 +11,7 @@ def forward_step(i_n, grid_size, A, K, C):
     return (A * grid_size ** (-K) + C) * i_n
 
 
-class SineKANLayer(torch.nn.Module):
+class SineKANLayer(grouped.KanLayer, torch.nn.Module):
     """y[m, o] = sum_i sum_g sin(x_mi * freq_g + phase_ig) * amplitudes[o, i, g] (+ bias).
 
     Parameters / buffers exactly as the reference: ``amplitudes[O, I, G]``, trainable
@@ -50,7 +50,7 @@ class SineKANLayer(torch.nn.Module):
         if add_bias:
             self.bias = torch.nn.Parameter(torch.ones(1, output_dim) / output_dim)
 
-    def kan_cfg(self):
+    def kan_cfg(self, layers=None):
         return ops.LayerCfg(family=ops.SINE, I=self.input_dim, O=self.output_dim, G=self.grid_size)
 
     def kan_pack(self):

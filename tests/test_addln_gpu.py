@@ -117,7 +117,7 @@ def test_block_under_autocast_feeds_bf16_through_the_layernorms(monkeypatch):
     outs = []
     for force_f32 in (False, True):
         if force_f32:
-            monkeypatch.setattr(model, "add_layernorm", lambda x_, d_, n_, y_bf16=False: ops.add_layernorm(x_, None if d_ is None else d_.float(), n_, False))
+            monkeypatch.setattr(model, "add_layernorm", lambda x_, d_, n_, y_bf16=False, **kw: ops.add_layernorm(x_, None if d_ is None else d_.float(), n_, False, **kw))
         x.grad = None
         pend.grad = None
         blk.zero_grad()

@@ -182,7 +182,7 @@ def test_state_dict_is_unchanged_and_rate_zero_restores():
 
 
 def test_rate_zero_takes_the_old_path(monkeypatch):
-    """With the rate back at 0 the forward asks for no scales and calls add_layernorm with the arguments it always did."""
+    """With the rate back at 0 the forward asks for no scales and hands add_layernorm no scale row."""
     import model
     seen = []
 
@@ -222,12 +222,12 @@ def test_rate_zero_takes_the_old_path(monkeypatch):
     del seen[:]
     m.eval()
     want = m(x)
-    assert len(seen) == 4 and all(kw == {} for kw in seen)             # eval(): the calls the model always made
+    assert len(seen) == 4 and all(kw == {"row_scale": None} for kw in seen)             # eval(): the unscaled calls
     del seen[:]
     m.train()
     m.set_drop_path(0.0)
     got = m(x)
-    assert len(seen) == 4 and all(kw == {} for kw in seen)
+    assert len(seen) == 4 and all(kw == {"row_scale": None} for kw in seen)
     assert torch.equal(got, want)
 
 

@@ -121,7 +121,7 @@ def test_packed_formula_equals_the_oracle_single_layer(name):
     go = torch.autograd.grad((yo * dy).sum(), [x] + [p for _, p in params], allow_unused=True)
     # the ABI formula on the packed operands
     w, bp, bias = m64.kan_pack()
-    u = m64.kan_u(x) if hasattr(m64, "kan_u") else None
+    u = m64.kan_u(x)
     y = ref.forward(cfg, x, u, w.unsqueeze(0), None if bp is None else bp.reshape(1, -1), None if bias is None else bias.reshape(1, -1))
     assert y.shape == (M, cfg.O)
     assert _rel(y, yo) < RTOL, _rel(y, yo)
@@ -156,14 +156,7 @@ def test_packed_formula_equals_the_oracle_qkv(kind):
     H, dh, M = 2, 8, 29
     msa = MSA(H * dh, H, type=kind)
     layers = list(msa.q_mappings) + list(msa.k_mappings) + list(msa.v_mappings)
-    l0 = layers[0]
-    if kind == "vanilla":
-        cfg0 = grouped.linear_cfg(l0)
-    elif kind in ("efficientkan", "fast"):
-        cfg0 = l0.kan_cfg(layers)
-    else:
-        cfg0 = l0.kan_cfg()
-    cfg = replace(cfg0, groups=3 * H, x_group_mod=H)
+    cfg = replace(grouped.as_kan(layers[0]).kan_cfg(layers), groups=3 * H, x_group_mod=H)
     m64, sd = _double(msa)
     l64 = list(m64.q_mappings) + list(m64.k_mappings) + list(m64.v_mappings)
     x = (torch.randn(M, H * dh, dtype=torch.float64) * 0.8).requires_grad_(True)
@@ -177,7 +170,7 @@ def test_packed_formula_equals_the_oracle_qkv(kind):
         bp, bias = None, torch.stack([m.bias for m in l64])
     else:
         w, bp, bias = type(l64[0]).kan_pack_grouped(l64)
-    u = type(l64[0]).kan_u_grouped(l64, x, H) if hasattr(l64[0], "kan_u_grouped") else None
+    u = type(grouped.as_kan(l64[0])).kan_u_grouped(l64, x, H)
     y = ref.forward(cfg, x, u, w, bp, bias)
     assert _rel(y, yo) < RTOL, _rel(y, yo)
     g = torch.autograd.grad((y * dy).sum(), [x] + [p for _, p in params], allow_unused=True)

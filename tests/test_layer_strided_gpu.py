@@ -134,21 +134,23 @@ def problem(key, bf16):
             layers = list(mod.q_mappings) + list(mod.k_mappings) + list(mod.v_mappings)
             cfg = replace(layers[0].kan_cfg(), groups=3 * mod.n_heads, x_group_mod=mod.n_heads)
             w, bp, bias = type(layers[0]).kan_pack_grouped(layers)
+            kan_u, ln = (lambda x_: type(layers[0]).kan_u_grouped(layers, x_, mod.n_heads)), None
         else:
             cfg = mod.kan_cfg()
             w, bp, bias = mod.kan_pack()
             w, bp, bias = w.unsqueeze(0), None if bp is None else bp.reshape(1, -1), None if bias is None else bias.reshape(1, -1)
+            kan_u, ln = mod.kan_u, mod.kan_ln()
         if bf16:
             cfg = replace(cfg, flags=cfg.flags | _lib.FLAG_BF16_MFMA)
         x = torch.randn(m, cfg.x_group_mod * cfg.I)
-        u = mod.kan_u(x) if hasattr(mod, "kan_u") else None
+        u = kan_u(x)
         if bias is None:
             bias = 0.5 * torch.randn(cfg.groups, cfg.O)
         dy = torch.randn(m, cfg.groups * cfg.O)
         ops_ = {"x": x, "u": u, "w": w.contiguous().float(), "bparams": None if bp is None else bp.contiguous().float(),
                 "bias": bias.contiguous().float(), "dy": dy}
-        if hasattr(mod, "kan_ln"):                 # FastKAN: (gamma, beta, eps) of the LayerNorm that produced u, for the fused route
-            ops_["ln"] = (mod.layernorm.weight.detach().clone(), mod.layernorm.bias.detach().clone(), mod.layernorm.eps)
+        if ln is not None:                         # FastKAN: (gamma, beta, eps) of the LayerNorm that produced u, for the fused route
+            ops_["ln"] = (ln.weight.detach().clone(), ln.bias.detach().clone(), ln.eps)
     refs = {}
     for nb in (True, False):                       # with the bias, and for the `nobias` layout without
         b_ = ops_["bias"] if nb else None
