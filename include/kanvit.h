@@ -743,6 +743,43 @@ int kanvit_randaug_u8(const uint8_t* src, uint8_t* dst, const int32_t* table, lo
 int kanvit_soft_ce(const float* logits, int64_t ld, const int64_t* y1, const int64_t* y2, const float* w, int64_t B, int C, float eps,
                    float* loss_rows, float* dlogits, float* loss, void* stream);
 
+/* ---- masked-autoencoder pretraining: token restore and the masked-patch loss (mae.py; csrc/mae.hip) ------------------------
+ * He et al. 2022 on top of kanvit_patch_keep: the encoder runs on the K kept patches and the class token; a light decoder then
+ * reconstructs the P - K dropped patches from the full sequence.  The reference has no such mode.  idx is int32 [B][K] exactly as
+ * kanvit_patch_keep writes it -- every row strictly ascending with entries in [0, P): a precondition, not checked on the device.
+ *
+ * kanvit_tokens_restore_fwd: out[B][P + 1][O] (contiguous) from y[B][K + 1][O] (contiguous: the encoder output after the decoder's
+ * input projection), mask_token[O] and pos[P + 1][O]:
+ *   out[b][0][:] = y[b][0] + pos[0],    out[b][1 + p][:] = (y[b][1 + j] if p == idx[b][j] else mask_token) + pos[1 + p]
+ * one fp32 add per element (bit for bit torch's repeat + cat + gather + add); the rank of p is a binary search of the sample's row.
+ * kanvit_tokens_restore_bwd: dy[b][0] = dout[b][0], dy[b][1 + j] = dout[b][1 + idx[b][j]] (contiguous [B][K + 1][O], copies) and
+ * dmask[o] = the sum of dout[b][1 + p][o] over every dropped (b, p); either may be NULL (not wanted), not both.  No atomics; the
+ * addition tree depends on (B, P, K) alone: with the n = B (P - K) dropped rows numbered in (sample, ascending patch) order and L =
+ * ceil(n / 128), slice s of 128 adds rows s L .. min(n, (s + 1) L) - 1 in that order, then slice s += slice s + h for h = 64, 32, ..,
+ * 1 -- bitwise the same from run to run.  Both: 1 <= K < P <= KANVIT_PATCH_KEEP_MAX_P, O >= 1, 0 <= B, B (P + 1) < 2^31; any 4-byte
+ * aligned pointers, float4 moves where O % 4 == 0 and every address is 16-byte aligned.
+ *
+ * kanvit_mae_loss: p as for kanvit_patch_gather (I = C ph pw, a patch flattened in patchify's (C, ph, pw) order); images fp32 NCHW
+ * contiguous; pred and dpred [B][P + 1][I] fp32 contiguous -- the decoder head's output with its class row in place, which the kernel
+ * skips.  For every dropped (b, p) with target t = the patch of the image:
+ *   norm_pix != 0: mu = sum(t) / I, var = sum((t - mu)^2) / (I - 1) (unbiased, as Tensor.var), that = (t - mu) / sqrt(var + 1e-6);
+ *   norm_pix == 0: that = t;
+ *   rows[b][p] = sum_i (pred - that)^2 / I,      dpred[b][1 + p][i] = 2 (pred - that) / (I B (P - K)),
+ * kept entries of rows, and the kept rows and the class row of dpred, are written as +0; loss[0] = (the ordered sum of the B P entries
+ * of rows, kanvit_soft_ce's tree: thread t of 256 adds entries t, t + 256, ... in order, then a fixed tree) / float(B (P - K)).  One
+ * wave per row holds the patch in registers: read once for mean, variance and error; a row's bits depend on the row alone; the factor
+ * 2 / (I B (P - K)) is rounded once on the host.  Two launches, no host synchronisation, capturable.  1 <= K < P, 1 <= I <=
+ * KANVIT_MAE_MAX_I (I = 1 only without norm_pix: one value has no variance), B >= 1, B (P + 1) < 2^31; any 4-byte aligned pointers,
+ * float4 moves where pw % 4 == 0 and images, pred and dpred are 16-byte aligned.  No gradient reaches the images: they are data.
+ * All three return KANVIT_EINVAL (named in kanvit_last_error, before the device is touched) outside their domain and for a null or
+ * misaligned pointer.  Additive: the ABI version stays 7. */
+#define KANVIT_MAE_MAX_I 4096
+int kanvit_tokens_restore_fwd(int64_t B, int P, int K, int O, const float* y, const float* mask_token, const float* pos, const int32_t* idx,
+                              float* out, void* stream);
+int kanvit_tokens_restore_bwd(int64_t B, int P, int K, int O, const float* dout, const int32_t* idx, float* dy, float* dmask, void* stream);
+int kanvit_mae_loss(const kanvit_patch_desc* p, int64_t B, int K, const int32_t* idx, const float* images, const float* pred, int norm_pix,
+                    float* rows, float* loss, float* dpred, void* stream);
+
 /* ---- epoch metrics on the device (kanvit/metrics.py; csrc/metrics.hip) ---------------------------------------------------
  * The reference appends labels, argmax and softmax of every step to host lists and runs scikit-learn on them per epoch
  * (train.py:42-44, utils.py:13-47).  Accuracy, balanced accuracy and weighted F1 are functions of the C x C confusion matrix; the

@@ -65,17 +65,24 @@ __global__ __launch_bounds__(SC_THREADS) void soft_ce_kernel(const SoftCeArgs a)
     }
 }
 
-__global__ __launch_bounds__(256) void soft_ce_mean_kernel(const SoftCeArgs a) {
+// The ordered sum of rows[0 .. n) by one work-group of 256 threads (valid in thread 0): thread t adds rows t, t + 256, ... in order,
+// then a fixed LDS tree.  soft_ce_mean_kernel's sum, and mae_mean_kernel's (mae.hip).
+__device__ __forceinline__ float sc_ordered_sum(const float* rows, long long n) {
     __shared__ float part[256];
     float s = 0.f;
-    for (long long r = threadIdx.x; r < a.B; r += 256) s += a.loss_rows[r];
+    for (long long r = threadIdx.x; r < n; r += 256) s += rows[r];
     part[threadIdx.x] = s;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) a.loss[0] = part[0] / (float)a.B;
+    return part[0];
+}
+
+__global__ __launch_bounds__(256) void soft_ce_mean_kernel(const SoftCeArgs a) {
+    const float s = sc_ordered_sum(a.loss_rows, a.B);
+    if (threadIdx.x == 0) a.loss[0] = s / (float)a.B;
 }
 
 }  // namespace
@@ -112,3 +119,6 @@ int kanvit_soft_ce(const float* logits, int64_t ld, const int64_t* y1, const int
 }
 
 }  // extern "C"
+
+// masked-autoencoder pretraining: token restore and the masked-patch loss share this unit (and sc_ordered_sum)
+#include "mae.hip"

@@ -142,6 +142,9 @@ SYMBOLS = {
     "kanvit_erase_u8": (C.c_int, [_P] * 12 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_uint64, _P]),
     "kanvit_randaug_u8": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "kanvit_soft_ce": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int, C.c_float, _P, _P, _P, _P]),
+    "kanvit_tokens_restore_fwd": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "kanvit_tokens_restore_bwd": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "kanvit_mae_loss": (C.c_int, [C.POINTER(PatchDesc), C.c_int64, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "kanvit_metrics_update": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int64, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
     "kanvit_metrics_auc_pairs_workspace": (C.c_size_t, [C.c_int64, C.c_int]),
     "kanvit_metrics_auc_pairs": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int64, _P, _P, C.c_size_t, _P]),
@@ -162,6 +165,7 @@ OPTIM_CHUNK = 4096     # KANVIT_OPTIM_CHUNK: the elements one work-group of the 
 DEPTH_MAX_BRANCHES = 64      # KANVIT_DEPTH_MAX_BRANCHES: the residual branches one kanvit_depth_scales launch draws for
 PATCH_KEEP_MAX_P = 1024      # KANVIT_PATCH_KEEP_MAX_P: the patches per sample one kanvit_patch_keep launch ranks (its keys live in LDS)
 PATCH_KEEP_TAG = 0x5061746368447270      # KANVIT_PATCH_KEEP_TAG: xored into the seed, apart from kanvit_depth_scales' stream
+MAE_MAX_I = 4096             # KANVIT_MAE_MAX_I: the values per patch one wave of kanvit_mae_loss holds in registers
 # KANVIT_RA_*: the op codes of kanvit_randaug_u8's table, the rows per sample and the largest image (H W C bytes) it takes
 (RA_IDENTITY, RA_AUTOCONTRAST, RA_EQUALIZE, RA_INVERT, RA_POSTERIZE, RA_SOLARIZE, RA_SOLARIZE_ADD, RA_BRIGHTNESS, RA_COLOR, RA_CONTRAST,
  RA_SHARPNESS, RA_AFFINE) = range(12)

@@ -20,11 +20,12 @@ LIB = os.path.join(HERE, "libkanvit.so")
 # unit per family (batch_u8, soft_ce, metrics, optim).  The data family has two files: batch_u8.hip includes randaug.hip (the
 # per-epoch RandAugment pass) at its end, so the two compile as one unit and randaug.hip is a dependency below, not a source.
 # In the same way addln.hip includes patch_drop.hip (PatchDropout: the keep table shares kanvit_depth_scales' hash step), and
-# optim.hip includes edge_prune.hip (KAN edge pruning: kanvit_mask_rows follows the optimizer's multi-tensor chunking).
+# optim.hip includes edge_prune.hip (KAN edge pruning: kanvit_mask_rows follows the optimizer's multi-tensor chunking), and
+# soft_ce.hip includes mae.hip (MAE pretraining: the masked-patch loss shares the ordered row sum of the cross-entropy's mean).
 SOURCES = ["kan_tile.hip", "kan_fwd_reg.hip", "kan_fwd_reg_bf16.hip", "kan_bwd_input_reg.hip", "kan_bwd_input_reg_bf16.hip",
            "kan_bwd_weight_reg.hip", "kan_bwd_weight_dma.hip", "kan_layer.hip", "attention.hip", "attention16.hip", "attention_x.hip", "attention_probs.hip", "addln.hip", "ff_small.hip", "ff_epilogue.hip", "kan_tiny.hip", "kan_edge_l1.hip",
            "kan_bspline_refit.hip", "batch_u8.hip", "soft_ce.hip", "metrics.hip", "optim.hip"]
-HEADERS = ["kan_basis.h", "kanvit_common.h", "kan_layer_common.h", "attention_common.h", "randaug.hip", "patch_drop.hip", "edge_prune.hip", os.path.join(INCLUDE, "kanvit.h")]
+HEADERS = ["kan_basis.h", "kanvit_common.h", "kan_layer_common.h", "attention_common.h", "randaug.hip", "patch_drop.hip", "edge_prune.hip", "mae.hip", os.path.join(INCLUDE, "kanvit.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=on", "-fno-finite-math-only", "-fvisibility=hidden"]
 
 

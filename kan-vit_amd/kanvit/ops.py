@@ -1277,6 +1277,63 @@ def assemble_tokens(tokens: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, 
     return _AssembleTokensFn.apply(tokens, cls, pos, idx)
 
 
+class _RestoreTokensFn(torch.autograd.Function):
+    """y [B, K + 1, O], mask_token, pos [P + 1, O], idx [B, K] -> [B, P + 1, O]: the kept tokens back at their patch positions, the mask
+    token at the dropped ones, the position rows of all positions, in one launch; backward: d y = the rows the kept tokens went to (a
+    copy), d mask_token = the sum of the dropped rows in a fixed tree."""
+
+    @staticmethod
+    @_fwd_f32
+    def forward(ctx, y, mask_token, pos, idx):
+        who = "restore_tokens"
+        for name, t in (("y", y), ("mask_token", mask_token), ("pos", pos), ("idx", idx)):
+            if not torch.is_tensor(t):
+                raise KanvitOperandError(f"{who}: {name} is a tensor on the GPU")
+        if idx.dim() != 2 or y.dim() != 3 or pos.dim() != 2:
+            raise KanvitOperandError(f"{who}: y is [B, K + 1, O], pos [P + 1, O] and idx [B, K]; got shapes {tuple(y.shape)}, {tuple(pos.shape)}, "
+                                     f"{tuple(idx.shape)}")
+        B, K = idx.shape
+        O, P = y.shape[-1], pos.shape[0] - 1
+        if not 1 <= K < P <= _lib.PATCH_KEEP_MAX_P:
+            raise KanvitOperandError(f"{who}: K={K} kept of P={P} patches: 1 <= K < P <= {_lib.PATCH_KEEP_MAX_P} (idx is patch_keep's table)")
+        _require_tensor(who, "y", y, torch.float32, shape=(B, K + 1, O), contiguous=False, error=KanvitOperandError)
+        _require_tensor(who, "idx", idx, torch.int32, device=y.device, error=KanvitOperandError)
+        _require_tensor(who, "mask_token", mask_token, torch.float32, device=y.device, contiguous=False, error=KanvitOperandError)
+        _require_tensor(who, "pos", pos, torch.float32, shape=(P + 1, O), device=y.device, contiguous=False, error=KanvitOperandError)
+        if mask_token.numel() != O:
+            raise KanvitOperandError(f"{who}: mask_token has {mask_token.numel()} elements, expected O = {O}")
+        out = torch.empty(B, P + 1, O, device=y.device, dtype=torch.float32)
+        _launch(_lib.lib().kanvit_tokens_restore_fwd, "kanvit_tokens_restore_fwd", y.device, B, P, K, O, _ptr(y.contiguous()),
+                _ptr(mask_token.reshape(-1).contiguous()), _ptr(pos.contiguous()), _ptr(idx), _ptr(out), tag="restore_tokens",
+                cost=(0, 4 * O * (B * (2 * P + K + 3) + P + 2)))
+        ctx.save_for_backward(idx)
+        ctx.mask_shape = tuple(mask_token.shape)
+        return out
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, dout):
+        idx, = ctx.saved_tensors
+        dout = dout.float().contiguous()
+        (B, N, O), K = dout.shape, idx.shape[1]
+        dy = torch.empty(B, K + 1, O, device=dout.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        dmask = torch.empty(O, device=dout.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        if dy is not None or dmask is not None:
+            _launch(_lib.lib().kanvit_tokens_restore_bwd, "kanvit_tokens_restore_bwd", dout.device, B, N - 1, K, O, _ptr(dout), _ptr(idx),
+                    _ptr(dy), _ptr(dmask), tag="restore_tokens_bwd", cost=(0, 4 * O * (B * (N + K + 1) + 1)))
+        return dy, None if dmask is None else dmask.view(ctx.mask_shape), None, None
+
+
+def restore_tokens(y: torch.Tensor, mask_token: torch.Tensor, pos: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """The decoder's sequence of a masked autoencoder: float32 [B, P + 1, O] with row 0 = y[b, 0] + pos[0] and row 1 + p = y[b, 1 + j] +
+    pos[1 + p] where p = idx[b, j], mask_token + pos[1 + p] at every dropped p -- one fp32 add per element (bit for bit torch's repeat
+    + cat + gather + add).  y: float32 [B, K + 1, O], the encoder's K + 1 rows after the decoder's input projection; mask_token: O
+    elements; pos: [P + 1, O]; idx: int32 [B, K] as patch_keep writes it (rows strictly ascending: a precondition, not checked on the
+    device), 1 <= K < P.  Gradients for y (a copy of its rows) and mask_token (a sum over the B (P - K) dropped rows in a tree that (B,
+    P, K) fix: reproducible)."""
+    return _RestoreTokensFn.apply(y, mask_token, pos, idx)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # the training loop's off-model kernels, from here to the end of the file: one operand check
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -1562,6 +1619,69 @@ def soft_cross_entropy(logits: torch.Tensor, y: torch.Tensor, y2: Optional[torch
     upstream gradient, with no second pass over the logits.  A row with a label outside [0, C) contributes 0 to the sum (the divisor
     stays B) and gets a zero gradient."""
     return _SoftCeFn.apply(logits, y, y2, w, float(label_smoothing))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# masked-patch reconstruction loss of a masked autoencoder: targets out of NCHW, loss and gradient in one pass (csrc/mae.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+def mae_loss_rows(pred: torch.Tensor, images: torch.Tensor, idx: torch.Tensor, n_patches: int, norm_pix: bool = True):
+    """The kernel call behind mae_loss, without autograd: (loss float32 [], rows float32 [B, P], dpred float32 [B, P + 1, I]) for pred
+    float32 [B, P + 1, I] contiguous (the class row in place: skipped), images float32 [B, C, H, W] contiguous at any 4-byte address
+    and idx int32 [B, K] as patch_keep writes it (semantics: include/kanvit.h).  One launch plus the one-work-group mean; no host
+    synchronisation."""
+    who = "mae_loss"
+    for name, t in (("pred", pred), ("images", images), ("idx", idx)):
+        if not torch.is_tensor(t):
+            raise KanvitOperandError(f"{who}: {name} is a tensor on the GPU")
+    if images.dim() != 4 or pred.dim() != 3 or idx.dim() != 2:
+        raise KanvitOperandError(f"{who}: pred is [B, P + 1, I], images [B, C, H, W] and idx [B, K]; got shapes {tuple(pred.shape)}, "
+                                 f"{tuple(images.shape)}, {tuple(idx.shape)}")
+    B, Cc, H, W = images.shape
+    n = int(n_patches)
+    if n < 1 or H % n or W % n:
+        raise KanvitOperandError(f"{who}: n_patches={n} must divide H={H} and W={W}")
+    P, I, K = n * n, Cc * (H // n) * (W // n), idx.shape[1]
+    if B < 1 or not 1 <= K < P:
+        raise KanvitOperandError(f"{who}: B={B}, K={K} kept of P={P} patches: B >= 1 and 1 <= K < P (at least one masked patch)")
+    if I > _lib.MAE_MAX_I or (norm_pix and I < 2):
+        raise KanvitOperandError(f"{who}: I={I} values per patch: {2 if norm_pix else 1}..{_lib.MAE_MAX_I} (a wave holds one patch in registers)")
+    _require_tensor(who, "pred", pred, torch.float32, shape=(B, P + 1, I), hint=" (the caller hands the loss pred.float())", error=KanvitOperandError)
+    _require_tensor(who, "images", images, torch.float32, device=pred.device, error=KanvitOperandError)
+    _require_tensor(who, "idx", idx, torch.int32, shape=(B, K), device=pred.device, error=KanvitOperandError)
+    out = torch.empty((B * (P + 1) * I + B * P + 1,), device=pred.device, dtype=torch.float32)
+    dpred, rows, loss = out[:B * (P + 1) * I].view(B, P + 1, I), out[B * (P + 1) * I:-1].view(B, P), out[-1:].view(())
+    pd = _lib.PatchDesc(Cc, H, W, n, 0, 0)
+    _launch(_lib.lib().kanvit_mae_loss, "kanvit_mae_loss", pred.device, C.byref(pd), B, K, _ptr(idx), _ptr(images), _ptr(pred),
+            1 if norm_pix else 0, _ptr(rows), _ptr(loss), _ptr(dpred), tag="mae_loss", cost=(0, 4 * I * B * (3 * P - 2 * K + 1)))
+    return loss, rows, dpred
+
+
+class _MaeLossFn(torch.autograd.Function):
+    @staticmethod
+    @_fwd_f32
+    def forward(ctx, pred, images, idx, n_patches, norm_pix):
+        loss, _, dpred = mae_loss_rows(pred, images, idx, n_patches, norm_pix)
+        ctx.save_for_backward(dpred)
+        return loss
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad_output):
+        dpred, = ctx.saved_tensors
+        return dpred * grad_output, None, None, None, None
+
+
+def mae_loss(pred: torch.Tensor, images: torch.Tensor, idx: torch.Tensor, n_patches: int, norm_pix: bool = True) -> torch.Tensor:
+    """The masked autoencoder's reconstruction loss (He et al. 2022): the mean over the dropped patches of the mean squared error between
+    pred[b, 1 + p] and the patch p of images[b], flattened in patchify's (C, ph, pw) order and, with norm_pix, normalised by its own mean
+    and unbiased variance ((t - mean) / sqrt(var + 1e-6), MAE's norm_pix_loss).  pred: float32 [B, P + 1, I] contiguous, the decoder
+    head's output with its class row still in place (skipped: no slice copy); images: float32 [B, C, H, W] contiguous -- data, no
+    gradient; idx: int32 [B, K] as patch_keep writes it, the KEPT patches.  The forward launch reads every dropped patch once, straight
+    from the images, computes the gradient 2 (pred - target) / (I B (P - K)) as well (+0 in the kept rows and the class row) and keeps
+    it: backward is one element-wise multiply by the upstream gradient.  Returns the 0-d loss."""
+    if torch.is_tensor(images) and images.requires_grad:
+        raise KanvitOperandError("mae_loss: images that want a gradient are not supported: the targets are data")
+    return _MaeLossFn.apply(pred, images, idx, int(n_patches), bool(norm_pix))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

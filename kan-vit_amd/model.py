@@ -343,13 +343,15 @@ class VisionTransformer(nn.Module):
         pos = self.pos_embeddings[: self.n_patches ** 2 + 1]
         return torch.cat((cls + pos[:1], tokens + pos[1 + take]), dim=1), rows
 
-    def _embed_kept(self, images):
+    def _embed_kept(self, images, idx=None):
         """The token sequence of a PatchDropout forward, [B, K + 1, d]: the keep table (ops.patch_keep bumps the device counter), the
         kept patches gathered out of the NCHW batch, the patch-embedding module on those B * K rows, whatever its type, and the
         sequence with the class token and the position embedding of the original positions (ops.assemble_tokens).  Also returns the
-        gathered rows -- the rows the layer saw, which is what the regulariser is taken on."""
-        K, seed = self._patch_dropout
-        idx = ops.patch_keep(images.shape[0], self.n_patches ** 2, K, seed, self.patch_dropout_counter)
+        gathered rows -- the rows the layer saw, which is what the regulariser is taken on.  idx (int32 [B, K], a keep table the caller
+        drew: MaskedAutoencoder's) replaces the draw; set_patch_dropout need not be set then."""
+        if idx is None:
+            K, seed = self._patch_dropout
+            idx = ops.patch_keep(images.shape[0], self.n_patches ** 2, K, seed, self.patch_dropout_counter)
         if images.requires_grad or images.dtype != torch.float32:
             return self._embed_kept_torch(images, idx)
         rows = ops.patch_gather(images.contiguous(), idx, self.n_patches)

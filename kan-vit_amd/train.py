@@ -17,6 +17,8 @@ Additions over the reference (none changes a default; each flag's help text has 
                           --mix-switch-prob --random-erasing P --erase-mode --erase-scale --erase-ratio --randaug [M] --randaug-ops --randaug-mstd --randaug-prob
     loss, optimizer       --label-smoothing --fused-loss --optimizer kanvit-adamw --weight-decay --clip-grad-norm --warmup-steps --lr-schedule --min-lr --ema-decay
     regularisation        --drop-path RATE --drop-path-schedule --patch-dropout RATE
+    pretraining           --pretrain mae --mask-ratio --decoder-dim --decoder-blocks --decoder-heads --decoder-type --no-norm-pix-loss
+                          --save-encoder PATH --init-encoder PATH
 
 `main(args, batches=None, init_state=None)` also serves the parity tests: `batches` (a list of (x, y) tensors) replaces
 the data stream, `init_state` (a reference-layout state dict) replaces the random initialisation, and the returned dict
@@ -35,6 +37,7 @@ from torch.optim import Adam
 from kanvit import data as kdata, dp as kdp, ops as kops, prune as kprune, tuned
 from kanvit.metrics import EpochMetrics
 from kanvit.optim import KanvitAdamW
+from mae import MaskedAutoencoder
 from model import VisionTransformer, split_types
 from utils import calculate_metrics, save_metrics, setup_logging
 
@@ -82,6 +85,11 @@ def check_args(args):
     for flag, name in (("--drop-path", "drop_path"), ("--patch-dropout", "patch_dropout")):
         if not 0.0 <= float(getattr(args, name)) < 1.0:
             raise SystemExit(f"{flag} {float(getattr(args, name))} must be in [0, 1)")
+    if not 0.0 < float(args.mask_ratio) < 1.0:
+        raise SystemExit(f"--mask-ratio {float(args.mask_ratio)} must be in (0, 1)")
+    for flag, name, least in (("--decoder-dim", "decoder_dim", 0), ("--decoder-blocks", "decoder_blocks", 1), ("--decoder-heads", "decoder_heads", 0)):
+        if int(getattr(args, name)) < least:
+            raise SystemExit(f"{flag} {getattr(args, name)} is below {least}")
     check_data_args(args)
     check_optimizer_args(args)
     check_prune_args(args)
@@ -242,6 +250,12 @@ def npz_datasets(args, device, want_test=True):
     return train, test
 
 
+def hash_counters(model):
+    """The device call counters of the model's hashed draws (drop_path_counter, patch_dropout_counter, a MaskedAutoencoder's
+    mask_counter), wherever in the module tree they live."""
+    return [b for name, b in model.named_buffers() if name.rsplit(".", 1)[-1].endswith("_counter")]
+
+
 class _GraphedStep:
     """The whole train step (forward, loss, zero_grad, backward, Adam) captured once in a HIP graph and replayed per batch:
     the launch-bound geometries (train.py's own defaults: 64-wide model, 17 tokens) spend their time in ~1000 launches of
@@ -249,16 +263,16 @@ class _GraphedStep:
 
     Capturing needs lazily created state (optimizer moments, library workspaces) to exist, so one throw-away step runs on a
     side stream first; parameters are then restored, the Adam moments / step counters zeroed, which is exactly the state
-    of a fresh optimizer, and the model's drop-path and patch-dropout counters (--drop-path, --patch-dropout) put back -- the
-    replayed trajectory equals the eager one."""
+    of a fresh optimizer, and the model's drop-path, patch-dropout and mask counters (--drop-path, --patch-dropout, --pretrain mae)
+    put back -- the replayed trajectory equals the eager one."""
 
     def __init__(self, eager_step, model, optimizer, x, y, y2=None, w=None):
         self.eager = eager_step
         self.sx, self.sy = x.clone(), y.clone()
         self.pair = () if y2 is None else (y2.clone(), w.clone())      # Mixup / CutMix: static buffers like x and y
         saved = [p.detach().clone() for p in model.parameters()]
-        # --drop-path / --patch-dropout: the throw-away step must not use up a mask or a keep set
-        counters = [c for c in (getattr(model, "drop_path_counter", None), getattr(model, "patch_dropout_counter", None)) if c is not None]
+        # --drop-path / --patch-dropout / --pretrain mae: the throw-away step must not use up a mask or a keep set
+        counters = hash_counters(model)
         counts = [c.clone() for c in counters]
         side = torch.cuda.Stream(device=x.device)
         side.wait_stream(torch.cuda.current_stream(x.device))
@@ -400,10 +414,41 @@ def prune_and_mask(model, optimizer, x, value, mode="fraction"):
     return counts
 
 
+PRETRAIN_REFUSED = (("--mixup", "mixup", "there are no labels to mix"), ("--cutmix", "cutmix", "there are no labels to mix"),
+                    ("--label-smoothing", "label_smoothing", "there are no labels to smooth"),
+                    ("--fused-loss", "fused_loss", "the loss is the reconstruction error, not a cross-entropy"),
+                    ("--reg-lambda", "reg_lambda", "the kept-token walk takes no regulariser"),
+                    ("--prune", "prune", "edge scoring walks the supervised model"),
+                    ("--grid-update-every", "grid_update_every", "the grid refit walks the supervised model"),
+                    ("--grid-extend", "grid_extend", "the grid refit walks the supervised model"),
+                    ("--patch-dropout", "patch_dropout", "the mask is the patch dropout: --mask-ratio sets it"),
+                    ("--device-metrics", "device_metrics", "there are no class metrics to count"))
+
+
+def check_pretrain_args(args, kinds):
+    """--pretrain mae against the flags of the supervised step, and --init-encoder against the file system."""
+    if args.pretrain is not None:
+        for flag, name, why in PRETRAIN_REFUSED:
+            if getattr(args, name) != defaults()[name]:
+                raise SystemExit(f"{flag} is not combined with --pretrain {args.pretrain}: {why}")
+        if "flash-attn" in kinds:
+            raise SystemExit(f"--pretrain {args.pretrain}: model type 'flash-attn' stacks bare attention modules, which the kept-token "
+                             "walk does not cover")
+        try:
+            split_types(args.decoder_type)
+        except ValueError as e:
+            raise SystemExit(f"--decoder-type: {e}")
+        if "flash-attn" in split_types(args.decoder_type) or len(split_types(args.decoder_type)) != 1:
+            raise SystemExit(f"--decoder-type {args.decoder_type}: one attention type of a TransformerBlock, not 'flash-attn'")
+    if args.init_encoder and not os.path.isfile(args.init_encoder):
+        raise SystemExit(f"--init-encoder {args.init_encoder}: no such file")
+
+
 def check_run_args(args):
     """What only a run refuses, not parse(): main() calls it after check_args, before anything touches the GPU or the process group."""
     regularized = VisionTransformer.REGULARIZED_TYPES
     kinds = split_types(args.model_type)
+    check_pretrain_args(args, kinds)
     bad = sorted(set(kinds) - set(regularized))
     if args.prune and bad:
         raise SystemExit(f"--prune: model type(s) {', '.join(bad)} have no edge-activation statistic to prune by; "
@@ -475,9 +520,56 @@ def build_model(args, chw, rank, world, device, init_state=None):
             raise SystemExit(f"{flag}: {e}")
     if init_state is not None:
         model.load_state_dict(init_state)
+    if args.init_encoder:
+        load_encoder(model, args.init_encoder)
+    if args.pretrain == "mae":
+        try:
+            model = MaskedAutoencoder(model, mask_ratio=float(args.mask_ratio), decoder_dim=int(args.decoder_dim) or None,
+                                      decoder_blocks=int(args.decoder_blocks), decoder_heads=int(args.decoder_heads) or None,
+                                      decoder_type=args.decoder_type, norm_pix_loss=not args.no_norm_pix_loss,
+                                      seed=kdata.rank_seed(args.seed, rank, world))
+        except (NotImplementedError, ValueError) as e:
+            raise SystemExit(f"--pretrain mae: {e}")
+        # the reconstruction loss never reaches the classifier head: frozen, the optimizers and the gradient reducer leave it out (a
+        # trainable parameter without a gradient would read as zeros in kanvit-adamw's weight EMA and never fill its bucket under --dp)
+        for p in model.encoder.mlp_head.parameters():
+            p.requires_grad_(False)
     model = model.to(device)
     kdp.broadcast_parameters(model)
     return model
+
+
+def encoder_of(model):
+    """The VisionTransformer of a run's model: the model itself, or a MaskedAutoencoder's encoder."""
+    return model.encoder if isinstance(model, MaskedAutoencoder) else model
+
+
+def load_encoder(model, path):
+    """--init-encoder: load a --save-encoder file (a VisionTransformer state_dict) into `model`.  mlp_head.* is skipped -- the head of a
+    pretraining run never saw a gradient -- and everything else is strict: a key the file lacks, a key the model lacks or a shape that
+    differs ends the run naming it.  The edge masks of a pruned file are rebuilt from its exact zeros, as for any loaded checkpoint."""
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(state, dict) or not all(torch.is_tensor(v) for v in state.values()):
+        raise SystemExit(f"--init-encoder {path}: not a state_dict (a mapping of names to tensors)")
+    own = model.state_dict()
+    is_head = lambda k: k.startswith("mlp_head.")
+    missing = sorted(k for k in own if not is_head(k) and k not in state)
+    foreign = sorted(k for k in state if not is_head(k) and k not in own)
+    shapes = sorted(k for k in state if not is_head(k) and k in own and tuple(state[k].shape) != tuple(own[k].shape))
+    if missing or foreign or shapes:
+        raise SystemExit(f"--init-encoder {path} does not fit the model: missing keys {missing}, unexpected keys {foreign}, "
+                         f"shapes that differ {shapes}")
+    model.load_state_dict({k: v for k, v in state.items() if not is_head(k)}, strict=False)
+    if model.layer_types() <= set(model.REGULARIZED_TYPES):
+        model.restore_edge_masks()
+
+
+def save_encoder(model, optimizer, path, ema):
+    """--save-encoder: the VisionTransformer's state_dict() to `path` (torch.save); with `ema` the averaged weights, the ones evaluate()
+    would use."""
+    with torch.no_grad(), (optimizer.ema_weights(model) if ema else contextlib.nullcontext()):
+        state = {k: v.detach().to("cpu", copy=True) for k, v in encoder_of(model).state_dict().items()}
+    torch.save(state, path)
 
 
 def steps_per_epoch(args, batches, train_set, per_rank, world):
@@ -517,6 +609,23 @@ def build_step(args, model, optimizer, reducer, mixed):
     reg_kw = dict(return_regularization=True, regularize_activation=float(args.reg_activation), regularize_entropy=float(args.reg_entropy))
     masking = bool(args.prune)
     criterion = torch.nn.CrossEntropyLoss()
+
+    def pretrain_step(x, y, y2=None, w=None):
+        """--pretrain mae: the same step around the reconstruction loss; the labels are ignored, and with no logits the second output is
+        the loss again."""
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+            loss = model(x)
+        if reducer is not None:
+            reducer.zero_grad()
+            reducer.scale_loss(loss).backward()
+            reducer.finish()
+        else:
+            optimizer.zero_grad()
+            loss.backward()
+        optimizer.step()
+        return loss.detach(), loss.detach()
+    if args.pretrain == "mae":
+        return pretrain_step
 
     def eager_step(x, y, y2=None, w=None):
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
@@ -695,7 +804,7 @@ def main(args, batches=None, init_state=None):
             if sampler is not None:
                 sampler.set_epoch(epoch)            # a different shuffle per epoch, the same on every rank
             loader = train_loader
-        if epoch == 0 and rank == 0 and not args.no_step_metrics:      # rank 0's shard; --device-metrics: sized here, once, reset per epoch
+        if epoch == 0 and rank == 0 and not args.no_step_metrics and args.pretrain is None:      # rank 0's shard; --device-metrics: sized here, once, reset per epoch
             rows =sum(int(b[1].shape[0]) for b in batches) if batches is not None else n_batches * per_rank
             run.train_metrics = Metrics(args.out_d, device, rows if args.device_metrics else None)
             if args.device_metrics:
@@ -704,8 +813,10 @@ def main(args, batches=None, init_state=None):
 
     if args.optimizer == "kanvit-adamw":
         history["grad_norm"] = float(optimizer.grad_norm)       # the last step's global norm (NaN without --clip-grad-norm: not taken)
-    if test_loader is not None and rank == 0:
+    if test_loader is not None and rank == 0 and args.pretrain is None:      # --pretrain: no classifier to test
         evaluate(run, test_loader, per_rank)
+    if args.save_encoder and rank == 0:
+        save_encoder(model, optimizer, args.save_encoder, ema=float(args.ema_decay) > 0)
     if args.dp:
         torch.distributed.barrier()             # the other ranks wait for rank 0's evaluation before the group goes away
         torch.distributed.destroy_process_group()
@@ -858,6 +969,25 @@ def build_parser():
                    help='PatchDropout: in training every sample keeps max(1, int(P * (1 - RATE))) of its P patch tokens (timm\'s rule) and '
                         'the class token, so a step costs roughly the kept fraction (VisionTransformer.set_patch_dropout; keep sets from a '
                         'hash of --seed and a device step counter, so --graph works); the test pass sees every patch.  0 (default): off')
+    p.add_argument('--pretrain', choices=['mae'], default=None,
+                   help='mae: masked-autoencoder pretraining (He et al. 2022; mae.py) -- the model of the flags becomes the encoder of a '
+                        'MaskedAutoencoder, every sample keeps 1 - --mask-ratio of its patches (the kept-token path of --patch-dropout), a '
+                        'light decoder reconstructs the dropped ones and the step differentiates the masked-patch loss (ops.restore_tokens, '
+                        'ops.mae_loss); labels are ignored, train metrics and the test pass are off.  Works with --graph, --dp, --amp bf16 '
+                        'and both optimizers; not with the label, regulariser, grid, pruning and --patch-dropout flags.  Default: off')
+    p.add_argument('--mask-ratio', type=float, default=0.75, help='--pretrain mae: the share of patches dropped per sample')
+    p.add_argument('--decoder-dim', type=int, default=0, help='--pretrain mae: width of the decoder; 0 (default): max(32, d_hidden / 2)')
+    p.add_argument('--decoder-blocks', type=int, default=2, help='--pretrain mae: transformer blocks of the decoder')
+    p.add_argument('--decoder-heads', type=int, default=0, help="--pretrain mae: heads of the decoder; 0 (default): the encoder's")
+    p.add_argument('--decoder-type', type=str, default='vanilla', help='--pretrain mae: attention type of the decoder blocks (any --model-type but flash-attn)')
+    p.add_argument('--no-norm-pix-loss', action='store_true',
+                   help='--pretrain mae: compare with the raw pixels instead of every patch normalised by its own mean and variance')
+    p.add_argument('--save-encoder', type=str, default=None, metavar='PATH',
+                   help="after the last epoch, rank 0 writes the VisionTransformer's state_dict() to PATH (torch.save; under --pretrain the "
+                        'encoder alone); with --ema-decay the averaged weights.  Not a resume facility: no optimizer state')
+    p.add_argument('--init-encoder', type=str, default=None, metavar='PATH',
+                   help='start from the weights of a --save-encoder file: everything but mlp_head.* (a pretrained head is untrained), strict; '
+                        'then training runs as usual')
     return p
 
 
